@@ -4,8 +4,13 @@ sketches (L3K10, ~1,220 hashes each, clades of 10 strains), distance kernel only
 resident in HBM (BASELINE.json metric; config "10,000 synthetic 5 Mb bacteria, L3K10,
 alldist from precomputed .sketch/.dict").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it generates the collection, builds the index once, warms up, times the K
+steps and prints a short result line.  --full adds every other leg and field listed below (and the --no-* switches act on
+those legs only).  --dump-outputs DIR writes the hit records of the last timed step, every rank's, ordered by (row, col), as
+DIR/hits_<field>.npy (float64) plus DIR/hit_count.npy.
 
 One "step" = one pass of the hot path (intersection counting through the inverted index +
 Jaccard->Mash epilogue + hit compaction, ONE kernel launch per rank) over this rank's query rows.
@@ -15,7 +20,7 @@ timed region); there is no data-path collective and no reduction.  Scaling is ST
 the metric is "10k bacteria at 1/2/4/8 GPUs", so the dataset stays 10,000 genomes at every N
 (--scaling weak grows it to round(10000*sqrt(N)) genomes instead, constant pairs per GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Besides the headline fields:
+Prints ONE JSON line on rank 0.  With --full, besides the headline fields:
   roofline      distance kernel: achieved / frac = HBM bytes really moved per second (counters of profiles/pmc_traffic.json,
                 else the kernel's own stream) over 8 TB/s; contract_* = SURVEY 8d's byte model (kept for continuity, exceeds 1);
                 issue_frac = share of the kernel's duration the SIMDs issue vector instructions
@@ -81,6 +86,9 @@ def parse_args():
                          "genomes) + alldist; without it the figure of BASELINE.md (8-vCPU container) stands in, labelled as such")
     ap.add_argument("--no-scale", action="store_true", help="skip the large-collection leg (scale)")
     ap.add_argument("--scale-genomes", type=int, default=500000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (baselines, other collections and sizes, rooflines, checks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the hit records of the last timed step as DIR/*.npy")
     return ap.parse_args()
 
 
@@ -124,7 +132,7 @@ class Env:
         self.ctx = capi.Context(self.local_rank)
         # the device's stream-read rate, measured in this very run, stated next to the nominal 8 TB/s (a 2 GiB buffer:
         # eight times the 256 MB Infinity Cache, 16 bytes per lane, HIP events around five launches)
-        self.peak_measured = self.ctx.stream_read_gbs(2048, 5) if self.rank == 0 else None
+        self.peak_measured = self.ctx.stream_read_gbs(2048, 5) if self.rank == 0 and args.full else None
         self.ctx.trim()
         self.dev = torch.device("cuda", self.local_rank)
         # a stream of our own: torch.cuda.Event measures the stream it is recorded on
@@ -200,19 +208,24 @@ class Env:
         first, then one gather of equal-sized padded buffers; returns milliseconds, barrier to barrier"""
         if self.world == 1:
             return 0.0
-        torch = self.torch
         self.fence()
         t0 = time.time()
+        self.gather_hits(hits_tensor, n_hits, itemsize)
+        self.fence()
+        return (time.time() - t0) * 1e3
+
+    def gather_hits(self, hits_tensor, n_hits, itemsize):
+        """the gather of gather_hits_ms, unclocked: rank 0 returns (every rank's count, every rank's padded buffer), the others None"""
+        torch = self.torch
         on = self.dev if self.args.backend == "nccl" else torch.device("cpu")   # (gloo gathers host tensors: rehearsals only)
         cnt = torch.tensor([n_hits], dtype=torch.int64, device=on)
         all_cnt = [torch.zeros_like(cnt) for _ in range(self.world)]
         self.dist.all_gather(all_cnt, cnt)
-        most = int(max(int(c.item()) for c in all_cnt))
-        mine = hits_tensor[: most * itemsize].to(on)
+        counts = [int(c.item()) for c in all_cnt]
+        mine = hits_tensor[: max(counts) * itemsize].to(on)
         got = [torch.empty_like(mine) for _ in range(self.world)] if self.rank == 0 else None
         self.dist.gather(mine, got, dst=0)
-        self.fence()
-        return (time.time() - t0) * 1e3
+        return (counts, got) if self.rank == 0 else None
 
     def share_sketches(self, hashes, off):
         """rank 0's host sketches to every rank (queries of the dist path are scattered by the host)"""
@@ -287,11 +300,11 @@ def counter_slots(steps, warmup):
     return warmup + steps + spread_steps(steps) + 1
 
 
-def timed_steps(env, launch, steps, warmup):
+def timed_steps(env, launch, steps, warmup, spread=True):
     """W untimed + K timed launches on env.stream, barrier + synchronize on both sides; returns
     (wall seconds max over ranks, mean kernel ms by HIP events on the launch stream, per-step ms [min, median, max]).
-    The timed region holds nothing but the K launches between two events; the per-step spread comes from a second,
-    untimed stretch of up to 50 launches with an event after each (an event costs ~1-2 us on the stream)."""
+    The timed region holds nothing but the K launches between two events; the per-step spread (None with spread=False) comes
+    from step_spread, after it."""
     torch = env.torch
     with torch.cuda.stream(env.stream):
         for i in range(warmup):
@@ -305,16 +318,23 @@ def timed_steps(env, launch, steps, warmup):
         ev1.record(env.stream)
         env.fence()
         elapsed = time.perf_counter() - t0
-        n = spread_steps(steps)
+    per_step = step_spread(env, launch, warmup + steps, spread_steps(steps)) if spread else None
+    return env.max_over_ranks(elapsed), ev0.elapsed_time(ev1) / steps, per_step
+
+
+def step_spread(env, launch, first, n):
+    """per-step ms [min, median, max] of a second, untimed stretch of n launches (launch(first) .. launch(first + n - 1)) with an
+    event after each (an event costs ~1-2 us on the stream)"""
+    torch = env.torch
+    with torch.cuda.stream(env.stream):
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
         evs[0].record(env.stream)
         for i in range(n):
-            launch(warmup + steps + i)   # (slots of their own: a launch ADDS its hits to its counter slot)
+            launch(first + i)   # (slots of their own: a launch ADDS its hits to its counter slot)
             evs[i + 1].record(env.stream)
         env.fence()
     per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n))
-    spread = [per[0], per[len(per) // 2], per[-1]]
-    return env.max_over_ranks(elapsed), ev0.elapsed_time(ev1) / steps, spread
+    return [per[0], per[len(per) // 2], per[-1]]
 
 
 def canonical_pairs(hits_tensor, n, capi, order=None):
@@ -328,6 +348,39 @@ def canonical_pairs(hits_tensor, n, capi, order=None):
     lo, hi = np.minimum(r, c), np.maximum(r, c)
     key = np.lexsort((h["common"], hi, lo))
     return np.stack([lo[key], hi[key], h["common"][key].astype(np.int64)])
+
+
+def hit_records(env, hits_tensor, n):
+    """the first n device hit records of every rank (HIT_DTYPE) on rank 0, None on the others"""
+    from rabbitkssd_amd import capi
+    size = capi.HIT_DTYPE.itemsize
+    if env.world == 1:
+        raw = hits_tensor[: n * size].cpu().numpy().tobytes()
+    else:
+        got = env.gather_hits(hits_tensor, n, size)
+        if got is None:
+            return None
+        raw = b"".join(t[: c * size].cpu().numpy().tobytes() for c, t in zip(*got))
+    return np.frombuffer(raw, dtype=capi.HIT_DTYPE)
+
+
+DUMP_FIELDS = ("row", "col", "common", "size0", "size1", "jorc", "dist")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, recs):
+    """what a caller of rk_dist_rows_dev receives from one step -- its hit records -- one float64 array per field, ordered by
+    (row, col): the kernel writes the records in completion order.  Beyond 64 MiB a fixed, seeded sample of the ordered records
+    is written; hit_count holds the number of them all"""
+    os.makedirs(path, exist_ok=True)
+    recs = recs[np.lexsort((recs["col"], recs["row"]))]
+    n = len(recs)
+    most = (DUMP_MAX_BYTES - 4096) // (8 * len(DUMP_FIELDS))   # (4 KiB: the .npy headers)
+    if n > most:
+        recs = recs[np.sort(np.random.default_rng(20261003).choice(n, most, replace=False))]
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(path, "hits_%s.npy" % f), recs[f].astype(np.float64))
+    np.save(os.path.join(path, "hit_count.npy"), np.array([n], dtype=np.float64))
 
 
 def threshold_legs(env, index, n_pairs, steps=20):
@@ -354,11 +407,14 @@ def threshold_legs(env, index, n_pairs, steps=20):
     return out
 
 
-def alldist_block(env, n_genomes, steps, warmup, keep=None, order_mode="sorted", build_reps=0, strains=10, tiny=0, skew=0):
+def alldist_block(env, n_genomes, steps, warmup, keep=None, order_mode="sorted", build_reps=0, strains=10, tiny=0, skew=0,
+                  full=True, dump=False):
     """alldist over n_genomes synthetic sketches, this rank's block-cyclic row shard; rank 0 returns the report.
     order_mode: the order the collection is listed in ("sorted" as generated, "shuffled", "jitter": synth.genome_order);
     strains: genomes per clade (> 10: a species tree, synth.strain_rates); tiny: extra 40-hash sketches; skew: the hashes fill the
-    hash space as a canonical k-mer's leading bases do (synth.canonical_skew, levels = skew)"""
+    hash space as a canonical k-mer's leading bases do (synth.canonical_skew, levels = skew).
+    full=False: one index build, the first call, warm-up and the timed steps only -- no build times, spread, cold steps or
+    checks, and a short report.  dump: the report's "last_hits" holds the hit records of the last timed step, every rank's"""
     from rabbitkssd_amd import capi, shard, synth
     torch, ctx, rank, world = env.torch, env.ctx, env.rank, env.world
     n_pairs = n_genomes * (n_genomes - 1) // 2
@@ -380,15 +436,16 @@ def alldist_block(env, n_genomes, steps, warmup, keep=None, order_mode="sorted",
         t0 = time.time()
         index = ctx.index_build(sk, HASH_BITS)      # first call: the context's pool is cold (hipMalloc)
         t_cold = time.time() - t0
-        del index
-        ts = []
-        for _ in range(5):
-            t0 = time.time()
-            index = ctx.index_build(sk, HASH_BITS)  # steady state: no allocation, one read-back
-            ts.append(time.time() - t0)
-            if _ < 4:
-                del index
-        t_steady = sorted(ts)[len(ts) // 2]
+        if full:
+            del index
+            ts = []
+            for _ in range(5):
+                t0 = time.time()
+                index = ctx.index_build(sk, HASH_BITS)  # steady state: no allocation, one read-back
+                ts.append(time.time() - t0)
+                if _ < 4:
+                    del index
+            t_steady = sorted(ts)[len(ts) // 2]
     fast = bool(index.built_fast) if rank == 0 else False
     stats = index.self_stats if rank == 0 else (0, 0, 0)
     index, nbytes, t_bcast, repl_mode = env.share_index(index, hashes, off)
@@ -410,7 +467,21 @@ def alldist_block(env, n_genomes, steps, warmup, keep=None, order_mode="sorted",
     env.stream.synchronize()
     t_first = time.perf_counter() - t0
     products = index.products   # 1 slice records, 2 tile records, 4 the tile records came with the build (rk_index_products)
-    elapsed, kernel_ms, spread = timed_steps(env, launch, steps, warmup)
+    elapsed, kernel_ms, _ = timed_steps(env, launch, steps, warmup, spread=False)
+    last_hits = None
+    if dump:
+        n_last = int(counters[warmup + steps - 1].item())
+        if env.max_over_ranks(n_last) > hits_cap:   # (every rank takes the same way: the gather below is collective)
+            sys.exit("bench.py: --dump-outputs: a rank's %d hits of the last step do not fit the buffer of %d" % (n_last, hits_cap))
+        last_hits = hit_records(env, hits, n_last)
+    kernel = ctx.dist_kernel_name(index, None, 1, 0, KMER, MAX_DIST, row_first=rank, row_step=world, row_block=shard.ROW_BLOCK)
+    if not full:
+        tot_hits = env.sum_over_ranks(int(counters[warmup + steps - 1].item()))
+        if rank != 0:
+            return None
+        return {"value": n_pairs * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "genomes": n_genomes, "pairs": n_pairs,
+                "hits": tot_hits, "kernel": kernel, "last_hits": last_hits}
+    spread = step_spread(env, launch, warmup + steps, spread_steps(steps))
     # cold steps: other options in between make the library forget what it learned about this (index, options) pair -- here
     # that rk_near_kernel's fallback list is empty --, so every launch of this stretch is a first one (two option sets taking turns)
     n_cold = min(steps, 20)
@@ -432,7 +503,6 @@ def alldist_block(env, n_genomes, steps, warmup, keep=None, order_mode="sorted",
         sys.exit("bench.py: launches of the same shard reported different hit counts: %s" % sorted(set(per_launch.tolist())))
     tot_hits = env.sum_over_ranks(my_hits)
     gather_ms = env.max_over_ranks(env.gather_hits_ms(hits, min(my_hits, hits_cap), capi.HIT_DTYPE.itemsize))
-    kernel = ctx.dist_kernel_name(index, None, 1, 0, KMER, MAX_DIST, row_first=rank, row_step=world, row_block=shard.ROW_BLOCK)
     pairs = None
     if rank == 0 and world == 1 and my_hits <= hits_cap:
         pairs = canonical_pairs(hits, my_hits, capi, order)   # the last launch's records (every launch writes the same set)
@@ -482,7 +552,7 @@ def alldist_block(env, n_genomes, steps, warmup, keep=None, order_mode="sorted",
         "e2e_ms": t_bcast * 1e3 + elapsed / steps * 1e3 + gather_ms,
         "slice_records": stats[0], "compact_share": (stats[1] / stats[0]) if stats[0] else None, "records_walked": stats[2],
         "build_plus_dist_ms": t_bd * 1e3 if t_bd else None, "pairs_canonical": pairs, "order": order_mode,
-        "first_call_ms": t_first * 1e3, "kernel_ms_cold": kernel_ms_cold,
+        "first_call_ms": t_first * 1e3, "kernel_ms_cold": kernel_ms_cold, "last_hits": last_hits,
     }
 
 
@@ -1327,6 +1397,34 @@ def build_roofline(block, peak_measured=None):
                           "the two-pass partition 120 us, the tile sort 100 us (profiles/r05_index_build_kernels.txt)"}
 
 
+def headline(head, args, world):
+    """the fields of the result line that a plain run prints, for the report of alldist_block over the headline collection"""
+    u16 = head["kernel"].startswith("rk_dist_kernel<true")
+    near = head["kernel"].startswith("rk_near_kernel")
+    tile = head["kernel"].startswith("rk_tile_kernel")
+    return {
+        "metric": "genome-pairs/sec alldist (10k bacteria, L3K10)",
+        "value": head["value"],
+        "unit": "genome-pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": head["ms_per_step"],
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": ("bit-sliced counters of 32 x 32 tiles in registers, 16 planes (exact), u32 counts after extraction" if tile else
+                  "u32 window counts in registers, accumulated bit-sliced per lane (exact)" if near else
+                  "u16 intersection counters in LDS (exact: a count is bounded by the sketch size, < 65536)" if u16 else
+                  "u32 intersection counters in LDS") + " / f64 jaccard + distance",
+        "data": "synthetic",
+        "config": {"workload": "alldist over %d synthetic bacterial sketches (sketch-level clade generator, seed 20261003, "
+                               "L3K10: 28-bit hashes, ~%d per genome, clades of 10), -D %g, distance kernel only from an "
+                               "HBM-resident index (BASELINE configs[2]: precomputed .sketch/.dict)" % (head["genomes"], HASHES_PER_GENOME, MAX_DIST),
+                   "genomes": head["genomes"], "pairs": head["pairs"], "hits": head["hits"], "max_dist": MAX_DIST, "kernel": head["kernel"]},
+    }
+
+
 def main():
     args = parse_args()
     env = Env(args)
@@ -1334,8 +1432,19 @@ def main():
     rank, world, ctx = env.rank, env.world, env.ctx
 
     n_genomes = args.genomes if args.scaling == "strong" else shard.weak_scaling_genomes(args.genomes, world)
-    keep = {}
-    head = alldist_block(env, n_genomes, args.steps, args.warmup, keep, build_reps=(15 if world == 1 else 0))
+    keep = {} if args.full else None
+    head = alldist_block(env, n_genomes, args.steps, args.warmup, keep, build_reps=(15 if world == 1 and args.full else 0),
+                         full=args.full, dump=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["last_hits"])
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(head, args, world)), flush=True)
+        if world > 1:
+            env.dist.destroy_process_group()
+        return
+    if rank == 0:
+        head.pop("last_hits")
 
     # the same collection listed in other orders (random permutation of the ids; completion-order jitter): the index
     # renumbers the genomes internally, so kernel variant, time and hits must not depend on the order
@@ -1413,33 +1522,13 @@ def main():
 
     head["distinct"] = distinct
     n_pairs = head["pairs"]
-    u16 = head["kernel"].startswith("rk_dist_kernel<true")
-    near = head["kernel"].startswith("rk_near_kernel")
     tile = head["kernel"].startswith("rk_tile_kernel")
-    out = {
-        "metric": "genome-pairs/sec alldist (10k bacteria, L3K10)",
-        "hbm_peak": {"nominal_gbs": HBM_PEAK_GBS, "measured_gbs": env.peak_measured,
-                     "how": "k_calib_read: a streaming read of a 2 GiB buffer (8 x the Infinity Cache), 16 B per lane, HIP events around 5 "
-                            "launches, at the start of this run (SURVEY 8d's measured denominator)"},
-        "value": head["value"],
-        "unit": "genome-pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": head["ms_per_step"],
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": ("bit-sliced counters of 32 x 32 tiles in registers, 16 planes (exact), u32 counts after extraction" if tile else
-                  "u32 window counts in registers, accumulated bit-sliced per lane (exact)" if near else
-                  "u16 intersection counters in LDS (exact: a count is bounded by the sketch size, < 65536)" if u16 else
-                  "u32 intersection counters in LDS") + " / f64 jaccard + distance",
-        "data": "synthetic",
-        "config": {"workload": "alldist over %d synthetic bacterial sketches (sketch-level clade generator, seed 20261003, "
-                               "L3K10: 28-bit hashes, ~%d per genome, clades of 10), -D %g, distance kernel only from an "
-                               "HBM-resident index (BASELINE configs[2]: precomputed .sketch/.dict)" % (n_genomes, HASHES_PER_GENOME, MAX_DIST),
-                   "genomes": n_genomes, "pairs": n_pairs, "hashes": head["hashes"],
-                   "postings_streamed_T": head["postings_streamed_T"], "hits": head["hits"], "max_dist": MAX_DIST,
+    out = headline(head, args, world)
+    out["hbm_peak"] = {"nominal_gbs": HBM_PEAK_GBS, "measured_gbs": env.peak_measured,
+                       "how": "k_calib_read: a streaming read of a 2 GiB buffer (8 x the Infinity Cache), 16 B per lane, HIP events around 5 "
+                              "launches, at the start of this run (SURVEY 8d's measured denominator)"}
+    out["config"].update({
+                   "hashes": head["hashes"], "postings_streamed_T": head["postings_streamed_T"],
                    "slice_records": head["slice_records"], "compact_share": head["compact_share"],
                    "records_walked_per_launch": head["records_walked"],
                    "sharding": "query rows in blocks of %d dealt round-robin to %d rank(s); sketches broadcast once (RCCL on GPUs), index built per rank" % (shard.ROW_BLOCK, world),
@@ -1457,7 +1546,8 @@ def main():
                            ("one rk_dist_rows_dev call: rk_near_kernel counts and evaluates every pair of the launch; its exact "
                             "fallback pass (rows whose far cells could be reportable) is launched until a completed launch with "
                             "the same options has shown that list to be empty -- here after the warm-up -- and skipped from then on "
-                            "(RK_DIST_FB_SKIP=0 launches it always: +3 us per step)")},
+                            "(RK_DIST_FB_SKIP=0 launches it always: +3 us per step)")})
+    out.update({
         "roofline": dist_roofline(head, "pmc_traffic.json" if world == 1 else None, env.peak_measured),
         # second headline: what an alldist costs when the index is NOT there yet -- sketches resident in HBM -> hits in HBM
         "build_plus_dist": {
@@ -1476,7 +1566,7 @@ def main():
                   "host_inclusive_ms": t_host_inclusive * 1e3,
                   "host_inclusive_note": "host sketches -> H2D -> rk_index_build -> rk_dist_rows -> %d hits on the host "
                                          "(PCIe-inclusive, whole dataset, one pass, steady state; not `value`)" % n_host_hits},
-    }
+    })
     if config3:
         out["config3"] = {
             "workload": "alldist over %d synthetic bacterial sketches (BASELINE configs[3]), -D %g, strong scaling: the same "

@@ -61,7 +61,7 @@ def main(tag, traffic_only=False):
         json.dump(d, open(os.path.join(PROF, tag + "_bench.json"), "w"))
         f = glob.glob(os.path.join(OUT, "prof_final", "**", "*kernel_stats.csv"), recursive=True)[0]
         with open(os.path.join(PROF, tag + "_bench_kernel_stats.csv"), "w") as o:
-            o.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline "
+            o.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline "
                     "(MI355X, tools/measure_round.sh)\nName,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs\n")
             for r in csv.DictReader(open(f)):
                 o.write('"%s",%s,%s,%s,%s,%s,%s\n' % (short_name(r["Name"]), r["Calls"], r["TotalDurationNs"], r["AverageNs"],

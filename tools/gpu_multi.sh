@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 for mode in sketches blob; do
-timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 3 \
+timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full --steps 10 --warmup 3 \
    --backend gloo --same-device --replicate $mode --no-cpu-baseline --no-sketch > gpurun_out/bench_2ranks_$mode.json 2> gpurun_out/bench_2ranks_$mode.err || { tail -30 gpurun_out/bench_2ranks_$mode.err; exit 1; }
 python3 - <<PY
 import json

@@ -7,6 +7,8 @@ tag=${1:-r05}
 phase=${2:-all}   # pmc: the counter passes + kernel trace of the index build; bench: bench.py and its kernel trace; all: both (two gpurun calls fit their limits better)
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
+root=$PWD
+out=$(python3 -c 'import runpy; print(runpy.run_path("tools/collect_profiles.py")["OUT"])')   # the tools' output directory
 if [ "$phase" != bench ]; then
 for w in 4 8 16; do
   printf 'FETCH_SIZE\n' | tools/pmc_pass.sh pmcC$w k_calib_read calib 1024 $w || exit 1
@@ -35,8 +37,8 @@ fi
 # (phase all: the counter records of this very call feed bench.py; phase bench: run `python3 tools/collect_profiles.py <tag>
 # --traffic-only` in the build container after the pmc phase -- gpurun_out/ does not travel, profiles/ does)
 [ "$phase" = all ] && { python3 tools/collect_profiles.py $tag --traffic-only || exit 1; }
-python3 bench.py > gpurun_out/bench_round.json 2> gpurun_out/bench_round.err || { tail -20 gpurun_out/bench_round.err; exit 1; }
+python3 bench.py --full > "$out/bench_round.json" 2> "$out/bench_round.err" || { tail -20 "$out/bench_round.err"; exit 1; }
 tail -c 300 gpurun_out/bench_round.json; echo
 rm -rf gpurun_out/prof_final
-( cd /tmp && timeout -k 10 700 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_final -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/prof_final.json 2> $GRAFT_REPO_ROOT/gpurun_out/prof_final.err ) || { tail -5 gpurun_out/prof_final.err; exit 1; }
+( cd /tmp && timeout -k 10 700 rocprofv3 --kernel-trace --stats -d "$out/prof_final" -o run --output-format csv -- python3 "$root/bench.py" --full --steps 100 --warmup 10 --no-cpu-baseline > "$out/prof_final.json" 2> "$out/prof_final.err" ) || { tail -5 "$out/prof_final.err"; exit 1; }
 echo "kernel trace done"
