@@ -15,6 +15,8 @@
  *   rk_dist_rows           <- row loop of index_tridist  src/dist.cpp:174-258
  *                             row loop of index_dist     src/dist.cpp:560-692 (without -N)
  *   rk_topn_rows           <- -N max-heap of index_dist  src/dist.cpp:599,625-640,683-689
+ *   rk_dist_topn           <- row loop of index_dist with -N (counting, epilogue and heap per
+ *                             query row)             src/dist.cpp:560-692
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -89,6 +91,14 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
  * rk_ctx_last_ms(ctx, RK_MS_SKETCH_KERNEL) then returns that kernel's duration in milliseconds for the last
  * rk_sketch_* call.  (The distance entry points launch one kernel per call or band: bracket rk_dist_rows_dev yourself.) */
 #define RK_MS_SKETCH_KERNEL 0
+/* rk_dist_topn with timing on, summed over its batches: the counting kernel, the selection kernel (its retries included), the
+ * candidates' sort + download, the host finish (exact distances + heap); RK_MS_TOPN_CANDIDATES is no time but the number of
+ * candidate records the selection kept (0 when the call took the plain path). */
+#define RK_MS_TOPN_COUNTS 1
+#define RK_MS_TOPN_SELECT 2
+#define RK_MS_TOPN_DOWNLOAD 3
+#define RK_MS_TOPN_HOST 4
+#define RK_MS_TOPN_CANDIDATES 5
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -353,6 +363,21 @@ int rk_dist_kernel_name(rk_ctx *ctx, const rk_index *idx, const rk_sketches *que
  * order (emitted largest distance first).  hits must be sorted by (row, col); the
  * result is written in place and its length returned through n_hits. */
 int rk_topn_rows(rk_hit *hits, uint64_t *n_hits, uint64_t max_neighbor);
+
+/* -N on the device: per selected query row, the max_neighbor nearest references under opts (triangle must be 0;
+ * row_first/row_step/row_block as in rk_dist_rows).  Returns exactly the records, values and order of
+ * rk_dist_rows(...) followed by rk_topn_rows(..., max_neighbor): rows ascending, within a row the reference heap's
+ * pop order (largest distance first).  Device and host memory are O(batch + Q * max_neighbor), never O(Q * R): a batch
+ * of query rows is counted into int32 counter rows, a selection kernel keeps per row only the cells that can reach the
+ * reference's heap (room for min(R, 1024 + 16 * max_neighbor) per row), and the host replays that heap over them.  Counter
+ * rows and candidate buffers of a batch fit RK_TOPN_BATCH_BYTES (default 1 GiB; at least one row); a row with more
+ * candidates than its room grows the buffer to the exact count, never beyond the batch's rows x R.
+ * Thresholds that exclude distance 1.0 (their output is bounded by the hits anyway), max_neighbor above 1,024 and
+ * RK_DIST_TOPN=0 run as rk_dist_rows + rk_topn_rows inside the call.  max_neighbor == 0 returns no record and runs nothing
+ * on the device.  RK_ERR_ARG for triangle == 1 (the reference has no -N for alldist) and null pointers.
+ * hits_out: library-allocated (rk_free_host). */
+int rk_dist_topn(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_dist_opts *opts,
+                 uint64_t max_neighbor, rk_hit **hits_out, uint64_t *n_hits);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

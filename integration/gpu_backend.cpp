@@ -121,8 +121,10 @@ void index_dist_gpu(vector<sketch_t> &ref_sketches, sketchInfo_t &ref_info, stri
     o.max_dist = maxDist;
     rk_hit *hits = nullptr;
     uint64_t n = 0;
-    gpu_check(rk_dist_rows(g_ctx, idx, qs, &o, &hits, &n, nullptr), "rk_dist_rows");
-    if (isNeighbor) gpu_check(rk_topn_rows(hits, &n, maxNeighbor), "rk_topn_rows");  // -N, src/dist.cpp:599,625-640
+    if (isNeighbor)  // -N, src/dist.cpp:599,625-640: the nearest references per query, never all Q x R pairs
+        gpu_check(rk_dist_topn(g_ctx, idx, qs, &o, maxNeighbor, &hits, &n), "rk_dist_topn");
+    else
+        gpu_check(rk_dist_rows(g_ctx, idx, qs, &o, &hits, &n, nullptr), "rk_dist_rows");
     write_text(outputFile, hits, n, query_sketches, ref_sketches, false);
     rk_free_host(hits);
     rk_index_free(idx);

@@ -24,7 +24,7 @@ EXPORTS = [
     "rk_sketches_download", "rk_sketches_hashes_dev", "rk_sketches_off_dev", "rk_sketches_free",
     "rk_index_build", "rk_index_import", "rk_index_export", "rk_index_export_lists", "rk_index_import64", "rk_index_export64", "rk_index_total",
     "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
-    "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_format_hit",
+    "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
 ]
 
 
@@ -305,6 +305,20 @@ class Context:
         buf = C.string_at(hits.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
         lib().rk_free_host(hits)
         return np.frombuffer(buf, dtype=HIT_DTYPE).copy(), dense
+
+    def dist_topn(self, index, queries, metric, kmer_size, max_dist, max_neighbor, row_first=0, row_step=1,
+                  row_block=0, triangle=0):
+        """-N on the device: per query row the max_neighbor nearest references, in the reference heap's pop order
+        (the records of dist_rows + topn_rows), as HIT_DTYPE."""
+        opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
+                        int(row_first), int(row_step))
+        hits = C.c_void_p()
+        n = C.c_uint64()
+        self.check(lib().rk_dist_topn(self._h, index._h, queries._h if queries is not None else None,
+                                      C.byref(opts), C.c_uint64(max_neighbor), C.byref(hits), C.byref(n)))
+        buf = C.string_at(hits.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
+        lib().rk_free_host(hits)
+        return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
 
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):

@@ -300,6 +300,9 @@ int rk_ctx_create(int device, rk_ctx **out)
     if (getenv("RK_INDEX_TILES")) ctx->sw_index_tiles = atoi(getenv("RK_INDEX_TILES"));
     if (getenv("RK_INDEX_NO_HEAVY")) ctx->sw_index_heavy = atoi(getenv("RK_INDEX_NO_HEAVY")) == 0;
     if (getenv("RK_TILE_REC_CAP")) ctx->sw_tile_rec_cap = strtoull(getenv("RK_TILE_REC_CAP"), nullptr, 10);
+    ctx->sw_topn = getenv("RK_DIST_TOPN") ? atoi(getenv("RK_DIST_TOPN")) != 0 : 1;
+    if (getenv("RK_TOPN_BATCH_BYTES")) ctx->sw_topn_batch_bytes = std::max(1ULL, strtoull(getenv("RK_TOPN_BATCH_BYTES"), nullptr, 10));
+    if (getenv("RK_TOPN_CAND_CAP")) ctx->sw_topn_cand_cap = strtoull(getenv("RK_TOPN_CAND_CAP"), nullptr, 10);
     *out = ctx;
     return RK_OK;
 }
@@ -327,7 +330,7 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4])
     out[3] = ctx->driver_frees;
 }
 
-double rk_ctx_last_ms(const rk_ctx *ctx, int which) { return ctx && which >= 0 && which < 4 ? ctx->last_ms[which] : 0.0; }
+double rk_ctx_last_ms(const rk_ctx *ctx, int which) { return ctx && which >= 0 && which < 8 ? ctx->last_ms[which] : 0.0; }
 
 void rk_ctx_trim(rk_ctx *ctx)
 {

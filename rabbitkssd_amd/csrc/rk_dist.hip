@@ -1346,6 +1346,8 @@ uint64_t host_exact_distances(rk_hit *h, uint64_t n, const rk_dist_opts *o)
 
 }  // namespace
 
+uint64_t rk_host_exact_distances(rk_hit *h, uint64_t n, const rk_dist_opts *o) { return host_exact_distances(h, n, o); }
+
 #ifdef RK_DIST_PROFILE
 extern "C" int rk_debug_dist_prof_raw(unsigned long long *out, unsigned long long n_waves)
 {

@@ -63,6 +63,8 @@ struct DistQArgs {
     int32_t hash_bits, dir_shift;
     uint32_t n_query, n_ref;
     uint32_t row_first, row_step, row_block, n_units;   // block-cyclic row shard (rk_dist_opts)
+    uint32_t slot_base;          // first row slot of the shard this launch covers (a batch of rk_dist_topn; else 0)
+    int32_t counts_only;         // stage A of rk_dist_topn: common_dense rows by slot - slot_base, no hit epilogue
     uint32_t tile_cols, n_tiles, cnt_words;
     uint32_t cand_cap, stage_hits;
     int32_t triangle, metric, kmer_size, dense_mode;
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(kMaxThreads) void rk_distq_kernel(DistQArgs a)
         const uint32_t x = it & 7, p = it >> 3;
         const uint32_t u = ((p / a.n_tiles) * 8 + x) * a.n_tiles + p % a.n_tiles;
         if (u >= total) continue;
-        const uint32_t slot = u / a.n_tiles, tile = u % a.n_tiles;
+        const uint32_t slot = a.slot_base + u / a.n_tiles, tile = u % a.n_tiles;
         // block-cyclic rows: this shard owns blocks row_first, row_first + row_step, ... of row_block rows
         const uint32_t blk = slot / a.row_block;
         const uint64_t row64 = ((uint64_t)a.row_first + (uint64_t)blk * a.row_step) * a.row_block + slot % a.row_block;
@@ -429,7 +431,7 @@ __global__ __launch_bounds__(kMaxThreads) void rk_distq_kernel(DistQArgs a)
 
         // ---- epilogue (src/dist.cpp:600-682; :207-255 in triangle mode) -------------------------------------
         if (a.common_dense) {
-            int32_t *dst = a.common_dense + (size_t)row * a.n_ref;
+            int32_t *dst = a.common_dense + (size_t)(a.counts_only ? slot - a.slot_base : row) * a.n_ref;
             for (uint32_t i = tid; i < ncol; i += nthreads) dst[a.orig ? a.orig[col0 + i] : col0 + i] = (int32_t)cell(i);
         }
         const int qsize = (int)(qe - qb);
@@ -470,7 +472,9 @@ __global__ __launch_bounds__(kMaxThreads) void rk_distq_kernel(DistQArgs a)
                 if (at < a.cap) a.hits[at] = hrec;
             }
         };
-        if (!a.dense_mode) {
+        if (a.counts_only) {
+            // the counter row is all rk_dist_topn needs (its selection kernel reads it)
+        } else if (!a.dense_mode) {
             // the threshold excludes distance 1.0 (== common 0): scan the row 16 B per lane skipping all-zero
             // quads, compact the non-zero cells into an LDS list, evaluate the list one cell per lane
             const uint4 *c4 = reinterpret_cast<const uint4 *>(cnt);
@@ -850,8 +854,9 @@ int rk_distq_kernel_name(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs
     return RK_OK;
 }
 
-int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_dist_opts *o, bool dense_mode,
-                    rk_hit *hits_dev, uint64_t cap, unsigned long long *n_hits_dev, int32_t *dense_dev, hipStream_t stream)
+static int distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_dist_opts *o, bool dense_mode,
+                        rk_hit *hits_dev, uint64_t cap, unsigned long long *n_hits_dev, int32_t *dense_dev, hipStream_t stream,
+                        uint32_t slot_base, uint32_t n_slots, bool counts_only)
 {
     if (o->kmer_size <= 0) return rk_fail(ctx, RK_ERR_ARG, "kmer_size must be positive");
     if (o->row_block < 0) return rk_fail(ctx, RK_ERR_ARG, "row_block must be >= 0");
@@ -907,6 +912,7 @@ int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, con
     const uint64_t n_blocks = ((uint64_t)qs->n + p.row_block - 1) / p.row_block;
     const uint64_t my_blocks = p.row_first < n_blocks ? (n_blocks - p.row_first + p.row_step - 1) / p.row_step : 0;
     p.n_units = (uint32_t)std::min<uint64_t>(my_blocks * p.row_block, 0xFFFFFFF0u / p.n_tiles);
+    p.n_units = slot_base < p.n_units ? std::min(n_slots, p.n_units - slot_base) : 0u;
     if (!p.n_units) return RK_OK;
 
     DistQArgs a;
@@ -929,6 +935,8 @@ int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, con
     a.row_step = p.row_step;
     a.row_block = p.row_block;
     a.n_units = p.n_units;
+    a.slot_base = slot_base;
+    a.counts_only = counts_only ? 1 : 0;
     a.tile_cols = p.tile_cols;
     a.n_tiles = p.n_tiles;
     a.cnt_words = p.cnt_words;
@@ -995,9 +1003,13 @@ int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, con
         m.rec = q->d_member_rec;
         m.seg_start = q->d_member_seg;
         m.seg_cnt = q->d_member_seg + (size_t)kSegStride * qs->n;
-        RK_HIP(ctx, hipMemsetAsync(q->d_member_seg, 0, (size_t)2 * kSegStride * qs->n * 4, stream));   // (ranges a launch does not use count zero)
-        hipLaunchKernelGGL(k_member_sliced, dim3(batches, ranges), dim3(kMemberWaves * 64), 0, stream, m);
-        RK_HIP(ctx, hipGetLastError());
+        // the pass covers every query: the later batches of one rk_dist_topn call (counts-only, slot_base > 0, same index and
+        // queries, same stream) read what its first batch left
+        if (!(counts_only && slot_base > 0)) {
+            RK_HIP(ctx, hipMemsetAsync(q->d_member_seg, 0, (size_t)2 * kSegStride * qs->n * 4, stream));   // (ranges a launch does not use count zero)
+            hipLaunchKernelGGL(k_member_sliced, dim3(batches, ranges), dim3(kMemberWaves * 64), 0, stream, m);
+            RK_HIP(ctx, hipGetLastError());
+        }
         a.rec = m.rec;
         a.seg_start = m.seg_start;
         a.seg_cnt = m.seg_cnt;
@@ -1005,4 +1017,17 @@ int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, con
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds_bytes, stream, a);
     RK_HIP(ctx, hipGetLastError());
     return RK_OK;
+}
+
+int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_dist_opts *o, bool dense_mode,
+                    rk_hit *hits_dev, uint64_t cap, unsigned long long *n_hits_dev, int32_t *dense_dev, hipStream_t stream)
+{
+    return distq_launch(ctx, idx, qs, o, dense_mode, hits_dev, cap, n_hits_dev, dense_dev, stream, 0, 0xFFFFFFFFu, false);
+}
+
+int rk_distq_counts(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_dist_opts *o, uint32_t slot_base,
+                    uint32_t n_slots, int32_t *counts_dev, hipStream_t stream)
+{
+    if (!counts_dev) return rk_fail(ctx, RK_ERR_ARG, "rk_distq_counts needs a counter scratch");
+    return distq_launch(ctx, idx, qs, o, true, nullptr, 0, nullptr, counts_dev, stream, slot_base, n_slots, true);
 }

@@ -48,7 +48,7 @@ struct rk_ctx {
                                // object load) costs more than they save on one call
     bool timing = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double last_ms[4] = {0, 0, 0, 0};
+    double last_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // RK_MS_* (include/rabbitkssd.h)
     // developer switches (environment), read once at context creation
     uint32_t sw_dist_threads = 0, sw_dist_rows = 0, sw_dist_pair = 1, sw_dist_pair_minwg = 3, sw_dist_persist = 1;
     uint32_t sw_dist_cand_cap = 0, sw_dist_stage_hits = 0, sw_dist_xcd_rows = 0;
@@ -74,6 +74,9 @@ struct rk_ctx {
     int sw_index_heavy = 1;    // RK_INDEX_NO_HEAVY=1: a bucket beyond the LDS sort refuses the bucket-sort build (as until round 5) instead of going to k_bucket_heavy
     int sw_index_tiles = 2;    // RK_INDEX_TILES: 0 the fast build always emits slice records, 1 tile records whenever it can, 2 from RK_DIST_TILES_MIN_GENOMES genomes on
     unsigned long long sw_tile_rec_cap = 0;   // RK_TILE_REC_CAP: capacity of the build's unsorted tile records (default H / 2 + 64 K; tests force the overflow)
+    int sw_topn = 1;           // RK_DIST_TOPN=0: rk_dist_topn always as rk_dist_rows + rk_topn_rows (A/B runs)
+    unsigned long long sw_topn_batch_bytes = 1ULL << 30;   // RK_TOPN_BATCH_BYTES: counter rows of one batch of rk_dist_topn (tests: several batches)
+    unsigned long long sw_topn_cand_cap = 0;   // RK_TOPN_CAND_CAP: first capacity of the candidate buffer (default by rows and N; tests force the retry)
 };
 constexpr size_t kPinnedBytes = 1 << 16;
 
@@ -272,6 +275,15 @@ int rk_index_ensure_dir(rk_ctx *ctx, rk_index *idx, hipStream_t stream);
 int rk_distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_dist_opts *opts, bool dense_mode,
                     rk_hit *hits_dev, uint64_t cap, unsigned long long *n_hits_dev, int32_t *dense_dev,
                     hipStream_t stream);
+// stage A of rk_dist_topn (rk_topn.hip): the counter rows of row slots [slot_base, slot_base + n_slots) of the shard of `opts`
+// (rk_dist_opts.row_first/row_step/row_block, triangle 0) into counts_dev[slot - slot_base][n_ref], columns in the CALLER's
+// reference order; no hit is evaluated.  Enqueues on `stream`.  The batches of one call come in order on one stream, slot_base
+// 0 first: the sliced membership pass (RK_DISTQ_SLICED=1, over every query) runs with the first only.
+int rk_distq_counts(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_dist_opts *opts, uint32_t slot_base,
+                    uint32_t n_slots, int32_t *counts_dev, hipStream_t stream);
+// the host's last word on reported pairs (rk_dist.hip): jorc / dist of every record recomputed with the C library's log,
+// records beyond the exact threshold of `opts` dropped (order kept); returns the records left
+uint64_t rk_host_exact_distances(rk_hit *h, uint64_t n, const rk_dist_opts *opts);
 // the kernel variant rk_distq_launch would pick, as a profiler prints it
 int rk_distq_kernel_name(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, char *buf, size_t cap);
 // true when every posting is reportable regardless of its count (the threshold admits distance 1.0)

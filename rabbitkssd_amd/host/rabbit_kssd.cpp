@@ -5,7 +5,7 @@
 //   sketch   -i list -o out [-L shuf] [-q] [-Q q -n c]   (GPU: rk_sketch_batch_ex [+ rk_index_build];
 //                                             FASTA or FASTQ lists, plain or .gz)
 //   alldist  -i sketch|list -o out [-D -M -L]            (GPU: rk_index_build, rk_dist_rows)
-//   dist     -r ref -q qry -o out [-D -M -N -L]          (GPU: rk_dist_rows [+ rk_topn_rows])
+//   dist     -r ref -q qry -o out [-D -M -N -L]          (GPU: rk_dist_rows; -N: rk_dist_topn)
 //   info     -i sketch -o out [-F]           (host only, src/subCommand.cpp:70-147)
 //   merge    -i list -o out                  (host only, src/subCommand.cpp:796-892)
 //   union / sub                              (host only, src/subCommand.cpp:307-794)
@@ -1382,9 +1382,11 @@ static int cmd_dist(const Args &a)
         o.metric = metric;
         o.kmer_size = 2 * ref.info.half_k;
         o.max_dist = max_dist;
-        dev.check(rk_dist_rows(dev.ctx, idx[g], qs, &o, &hits[g], &n_hits[g], nullptr), "rk_dist_rows");
+        if (is_neighbor)   // -N: the nearest references per query row (src/dist.cpp:599,625-640), never all Q x R pairs
+            dev.check(rk_dist_topn(dev.ctx, idx[g], qs, &o, (uint64_t)max_neighbor, &hits[g], &n_hits[g]), "rk_dist_topn");
+        else
+            dev.check(rk_dist_rows(dev.ctx, idx[g], qs, &o, &hits[g], &n_hits[g], nullptr), "rk_dist_rows");
         for (uint64_t i = 0; i < n_hits[g]; i++) hits[g][i].row += q0[g];
-        if (is_neighbor) rk_topn_rows(hits[g], &n_hits[g], (uint64_t)max_neighbor);
         rk_sketches_free(qs);
     };
     {
