@@ -281,6 +281,40 @@ int rk_index_join_shard(rk_ctx *ctx, const rk_index *part, const void *recv_dev,
  * context; recv_dev[d] (free with rk_dev_free) and n_recv[d] are what rk_index_join_shard takes on GPU d.
  * Called from one host thread; the shard builds before it and the joins behind it may run one thread per GPU. */
 int rk_index_shard_exchange(rk_index *const *parts, uint32_t n, void **recv_dev, uint64_t *n_recv);
+/* The same sharded build from PER-RANK sketches.  A collection sketched on N ranks (the reference's per-genome loop shards by
+ * genome with no communication, src/sketch.cpp:455) is not replicated: rank r holds the genomes genome_base .. genome_base +
+ * rk_sketches_count(local) - 1 of a collection of n_genomes (contiguous ranges in rank order; every rank holds at least one genome).
+ * Instead of broadcasting the collection, every rank cuts its sketches into keys by destination shard, ONE all-to-all moves them,
+ * and every shard builds its posting lists from the keys that arrived:
+ *   every rank:   rk_sketches_signature(local, sig_dev)           68 bytes per genome, all-gathered (the renumbering reads them)
+ *                 rk_sketches_shard_keys(local, ..., counts)       keys for every destination shard
+ *                 rk_sketches_shard_pack(local, ..., send_dev)     ... contiguous by destination (8 bytes each)
+ *   (the caller's all-to-all of the keys)
+ *   every shard:  rk_index_build_shard_keys(keys, n, sig, ...)     a shard index like rk_index_build_shard's: the same rk_index_order,
+ *                 rk_index_total and rk_index_shard_records; rk_index_shard_pack / rk_index_join_shard / rk_dist_rows as above.
+ * Signature: sig_dev[g * RK_SIG_WORDS] = size of local genome g, then its min(16, size) smallest hashes ascending (64-bit hashes folded
+ * to 32 bits as hash ^ hash >> 32, the fold of the renumbering), zero-padded.  Asynchronous on `stream`.
+ * Wire format of a key (u64): (hash & (2^(hash_bits - shard_bits) - 1)) << gb | global genome id, where shard_bits = log2(n_shards),
+ * gb = the smallest gb >= 1 with 2^gb >= n_genomes, and the destination shard of the key is hash >> (hash_bits - shard_bits).
+ * RK_ERR_ARG: n_shards not a power of two up to 64, genome_base + rk_sketches_count(local) > n_genomes, an empty `local`, a hash
+ * beyond hash_bits (rk_sketches_shard_keys; the pack leaves such hashes out).  RK_ERR_UNSUPPORTED: local sketches that are not sets
+ * (a genome lists a hash twice), a key that does not fit 64 bits (hash_bits - shard_bits + gb > 64).
+ * rk_sketches_shard_pack enqueues on `stream` and returns without waiting.
+ * rk_index_build_shard_keys takes the keys that arrived (any order, any source; the buffer is read, never written) and the
+ * all-gathered signatures of all n_genomes (n_genomes * RK_SIG_WORDS u32, in global genome order); 2 .. 64 shards.  Its arrays that
+ * scale with postings are sized by the keys of the shard, not by the collection.  RK_ERR_ARG for a key outside the wire format (hash
+ * bits beyond hash_bits - shard_bits, a genome id >= n_genomes): the build is refused, no key is dropped or cut down.
+ * RK_ERR_UNSUPPORTED, besides rk_index_build_shard's own limits, when fewer than 7 hash bits remain inside a shard (hash_bits -
+ * shard_bits < 7, or fewer inside one of its passes): the keys are partitioned by the two-pass bucket sort, which needs >= 128
+ * buckets (rk_index_build_shard builds such tiny hash spaces another way, from the sketches). */
+#define RK_SIG_WORDS 17
+int rk_sketches_signature(rk_ctx *ctx, const rk_sketches *local, void *sig_dev, void *stream);
+int rk_sketches_shard_keys(rk_ctx *ctx, const rk_sketches *local, uint32_t genome_base, uint32_t n_genomes, int hash_bits,
+                           uint32_t n_shards, uint64_t *counts_out);
+int rk_sketches_shard_pack(rk_ctx *ctx, const rk_sketches *local, uint32_t genome_base, uint32_t n_genomes, int hash_bits,
+                           uint32_t n_shards, void *send_dev, void *stream);
+int rk_index_build_shard_keys(rk_ctx *ctx, const void *keys_dev, uint64_t n_keys, const void *sig_dev, uint32_t n_genomes,
+                              int hash_bits, uint32_t shard, uint32_t n_shards, rk_index **out);
 /* Multi-GPU: the whole index as ONE contiguous device blob, so that the owner can hand it
  * to an RCCL broadcast (one collective, no reduction: query rows are independent) and every
  * peer rebuilds an identical rk_index from the received bytes.  pack/unpack only enqueue

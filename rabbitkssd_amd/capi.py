@@ -12,6 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librabbitkssd.so")
 _LIB = None
 
+SIG_WORDS = 17   # RK_SIG_WORDS: u32 per genome of a signature (size, then its <= 16 smallest hashes)
+KEY_BYTES = 8    # one key of a sharded build from per-rank sketches
+
 HIT_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("common", "<i4"), ("size0", "<i4"),
                       ("size1", "<i4"), ("pad", "<i4"), ("jorc", "<f8"), ("dist", "<f8")])
 
@@ -24,6 +27,7 @@ EXPORTS = [
     "rk_sketches_download", "rk_sketches_hashes_dev", "rk_sketches_off_dev", "rk_sketches_free",
     "rk_index_build", "rk_index_import", "rk_index_export", "rk_index_export_lists", "rk_index_import64", "rk_index_export64", "rk_index_total",
     "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
+    "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
 ]
 
@@ -268,6 +272,39 @@ class Context:
         L = lib()
         L.rk_index_build_shard.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         self.check(L.rk_index_build_shard(self._h, sketches._h, int(hash_bits_), int(shard), int(n_shards), C.byref(h)))
+        return Index(self, h)
+
+    # ---- sharded build from per-rank sketches: this rank holds genomes genome_base .. genome_base + local.count - 1 of n_genomes
+    def sketches_signature(self, local, sig_dev_ptr, stream=0):
+        """local.count * SIG_WORDS u32 at sig_dev_ptr: per genome its size and <= 16 smallest hashes (rk_sketches_signature;
+        asynchronous on `stream`)"""
+        L = lib()
+        L.rk_sketches_signature.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.check(L.rk_sketches_signature(self._h, local._h, C.c_void_p(sig_dev_ptr), C.c_void_p(stream)))
+
+    def sketches_shard_keys(self, local, genome_base, n_genomes, hash_bits_, n_shards):
+        """keys this rank sends to every destination shard (rk_sketches_shard_keys)"""
+        out = (C.c_uint64 * int(n_shards))()
+        L = lib()
+        L.rk_sketches_shard_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
+        self.check(L.rk_sketches_shard_keys(self._h, local._h, int(genome_base), int(n_genomes), int(hash_bits_), int(n_shards), out))
+        return [int(x) for x in out]
+
+    def sketches_shard_pack(self, local, genome_base, n_genomes, hash_bits_, n_shards, send_dev_ptr, stream=0):
+        """the keys themselves, contiguous by destination shard, KEY_BYTES each (rk_sketches_shard_pack; asynchronous on `stream`)"""
+        L = lib()
+        L.rk_sketches_shard_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        self.check(L.rk_sketches_shard_pack(self._h, local._h, int(genome_base), int(n_genomes), int(hash_bits_), int(n_shards),
+                                            C.c_void_p(send_dev_ptr), C.c_void_p(stream)))
+
+    def index_build_shard_keys(self, keys_dev_ptr, n_keys, sig_dev_ptr, n_genomes, hash_bits_, shard, n_shards):
+        """shard `shard` of `n_shards` from the keys that arrived and the all-gathered signatures (rk_index_build_shard_keys)"""
+        h = C.c_void_p()
+        L = lib()
+        L.rk_index_build_shard_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_void_p)]
+        self.check(L.rk_index_build_shard_keys(self._h, C.c_void_p(keys_dev_ptr), C.c_uint64(n_keys), C.c_void_p(sig_dev_ptr), int(n_genomes),
+                                               int(hash_bits_), int(shard), int(n_shards), C.byref(h)))
         return Index(self, h)
 
     def index_join_shard(self, part, recv_dev_ptr, n_records):

@@ -352,6 +352,20 @@ template <class K> __device__ inline uint32_t fold_hash(K h)
     else return (uint32_t)h;
 }
 
+// What the renumbering reads of genome g: the count and the values of its first min(size, kMinK) hashes, folded to 32 bits -- from the
+// sketches' CSR, or from the all-gathered signatures of a build from keys (rk_index_keys.inc: size, then those hashes, folded already)
+template <class K> struct CsrMinK {
+    const K *hashes;
+    const uint64_t *off;
+    __device__ uint32_t count(uint32_t g) const { return (uint32_t)min((uint64_t)kMinK, off[g + 1] - off[g]); }
+    __device__ uint32_t at(uint32_t g, uint32_t i) const { return fold_hash(hashes[off[g] + i]); }
+};
+struct SigMinK {
+    const uint32_t *sig;   // RK_SIG_WORDS u32 per genome
+    __device__ uint32_t count(uint32_t g) const { return min(kMinK, sig[(size_t)g * RK_SIG_WORDS]); }
+    __device__ uint32_t at(uint32_t g, uint32_t i) const { return sig[(size_t)g * RK_SIG_WORDS + 1 + i]; }
+};
+
 // table slot = (hash << 32 | smallest genome that lists the hash among its kMinK smallest); open addressing.
 // (round 5) A workgroup holds 64 neighbouring genomes -- relatives, in a collection listed species by species -- and first settles
 // "the smallest genome per hash" among ITS 1,024 elements in an LDS table; only the winners go to the device-wide table.  Its loads
@@ -376,8 +390,8 @@ __device__ inline void minhash_insert_global(unsigned long long *table, uint32_t
         slot = (slot + 1) & mask;
     }
 }
-template <class K>
-__global__ __launch_bounds__(kInsertThreads) void k_minhash_insert(const K *hashes, const uint64_t *off, uint32_t n_genomes, unsigned long long *table, uint32_t mask)
+template <class Src>
+__global__ __launch_bounds__(kInsertThreads) void k_minhash_insert(Src src, uint32_t n_genomes, unsigned long long *table, uint32_t mask)
 {
     __shared__ unsigned long long loc[kInsertLocal];   // (at most half full: 1,024 elements)
     for (uint32_t s = threadIdx.x; s < kInsertLocal; s += kInsertThreads) loc[s] = kEmptySlot;
@@ -385,9 +399,8 @@ __global__ __launch_bounds__(kInsertThreads) void k_minhash_insert(const K *hash
     const uint64_t t = (uint64_t)blockIdx.x * kInsertThreads + threadIdx.x;
     const uint32_t g = (uint32_t)(t / kMinK), i = (uint32_t)(t % kMinK);
     if (g < n_genomes) {
-        const uint64_t e = off[g] + i;
-        if (e < off[g + 1]) {
-            const uint32_t h = fold_hash(hashes[e]);
+        if (i < src.count(g)) {
+            const uint32_t h = src.at(g, i);
             const unsigned long long mine = ((unsigned long long)h << 32) | g;
             uint32_t slot = (mix32(h) >> 11) & (kInsertLocal - 1);   // (other bits than the device-wide table's)
             for (uint32_t probe = 0; probe < kInsertLocal; probe++) {
@@ -412,20 +425,18 @@ __global__ __launch_bounds__(kInsertThreads) void k_minhash_insert(const K *hash
 }
 
 // parent[g] = the smallest genome below g that shares at least two of g's kMinK smallest hashes (g itself if none)
-template <class K>
-__global__ void k_minhash_vote(const K *hashes, const uint64_t *off, uint32_t n_genomes, const unsigned long long *table,
-                               uint32_t mask, uint32_t *parent)
+template <class Src>
+__global__ void k_minhash_vote(Src src, uint32_t n_genomes, const unsigned long long *table, uint32_t mask, uint32_t *parent)
 {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_genomes) return;
-    const uint64_t e0 = off[g];
-    const uint32_t n = (uint32_t)min((uint64_t)kMinK, off[g + 1] - e0);
+    const uint32_t n = src.count(g);
     uint32_t r[kMinK];
 #pragma unroll
     for (uint32_t i = 0; i < kMinK; i++) {
         r[i] = g;
         if (i < n) {
-            const uint32_t h = fold_hash(hashes[e0 + i]);
+            const uint32_t h = src.at(g, i);
             uint32_t slot = mix32(h) & mask;
             for (uint32_t probe = 0; probe <= mask; probe++) {
                 const unsigned long long cur = table[slot];
@@ -461,14 +472,15 @@ __global__ void k_cluster_keys(const uint32_t *parent, uint32_t n_genomes, int i
 }
 
 // sorted keys -> orig[internal id], sizes in internal order
+// (sizes_in: the sizes in the caller's order, when there is no CSR -- a build from keys)
 __global__ void k_order_from_keys(const unsigned long long *keys, uint32_t n_genomes, int id_bits, const uint64_t *off,
-                                  uint32_t *orig, uint32_t *sizes)
+                                  const uint32_t *sizes_in, uint32_t *orig, uint32_t *sizes)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_genomes) return;
     const uint32_t g = (uint32_t)(keys[i] & ((1ULL << id_bits) - 1ULL));
     orig[i] = g;
-    sizes[i] = (uint32_t)(off[g + 1] - off[g]);
+    sizes[i] = sizes_in ? sizes_in[g] : (uint32_t)(off[g + 1] - off[g]);
 }
 
 // single workgroup: off_new = exclusive scan of the sizes in internal order
@@ -528,13 +540,13 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_keys(const uint32_t *__re
         if (q < n && below[i]) atomicAdd(&rank[q], below[i]);
     }
 }
-__global__ void k_order_from_rank(const uint32_t *rank, uint32_t n_genomes, const uint64_t *off, uint32_t *orig, uint32_t *sizes)
+__global__ void k_order_from_rank(const uint32_t *rank, uint32_t n_genomes, const uint64_t *off, const uint32_t *sizes_in, uint32_t *orig, uint32_t *sizes)
 {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_genomes) return;
     const uint32_t i = rank[g];   // (the g-th key belongs to genome g: k_cluster_keys32)
     orig[i] = g;
-    sizes[i] = (uint32_t)(off[g + 1] - off[g]);
+    sizes[i] = sizes_in ? sizes_in[g] : (uint32_t)(off[g + 1] - off[g]);
 }
 
 // one wave per internal genome: its hashes move to their place in the internal-order CSR
@@ -615,6 +627,39 @@ int postings_in_caller_ids(rk_ctx *ctx, const rk_index *idx, hipStream_t st, uin
 
 #include "rk_index_fast.inc"
 #include "rk_index_tiles.inc"
+#include "rk_index_keys.inc"
+
+// What a build reads of its GENOMES (sizes and offsets, the hashes the renumbering looks at, whether they are sets) and of its
+// ELEMENTS (the partition source): the sketches themselves (rk_index_build, rk_index_build_shard), or the keys of one shard that
+// arrived from every rank with the all-gathered signatures of the genomes (rk_index_build_shard_keys).
+struct BuildSource {
+    uint32_t n = 0;                        // genomes
+    uint64_t total = 0;                    // postings of the whole collection
+    bool wide = false, is_set = false;
+    uint64_t max_size = 0, min_size = 0;   // largest, smallest non-empty sketch
+    const uint64_t *d_off = nullptr;       // u64[n + 1]: CSR offsets of the sketches (caller's order), or
+    const uint32_t *d_sizes = nullptr;     // u32[n]: the sizes (caller's order) and
+    const uint32_t *d_sig = nullptr;       // the signatures (RK_SIG_WORDS u32 per genome) the renumbering reads -- a build from keys
+    const rk_sketches *s = nullptr;        // elements: the sketches, or
+    const unsigned long long *keys = nullptr;   // the shard's keys (wire format of rk_sketches_shard_pack), n_keys of them
+    uint64_t n_keys = 0;
+};
+inline BuildSource source_of(const rk_sketches *s)
+{
+    BuildSource src;
+    src.n = s->n;
+    src.total = s->total;
+    src.wide = s->wide;
+    src.is_set = s->is_set;
+    src.max_size = s->max_size;
+    for (uint32_t g = 0; g < s->n; g++) {
+        const uint64_t sz = s->h_off[g + 1] - s->h_off[g];
+        if (sz && (!src.min_size || sz < src.min_size)) src.min_size = sz;
+    }
+    src.d_off = s->d_off;
+    src.s = s;
+    return src;
+}
 
 template <class T> int pool_array(rk_ctx *ctx, T **out, size_t n)
 {
@@ -869,7 +914,7 @@ int rk_index_self_stats(const rk_index *cidx, uint64_t out[4])
     return RK_OK;
 }
 
-static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out);
+static int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out);
 
 // (a failing build may leave kernels in flight on both of the context's streams that still write into temporaries its DevBufs
 // have just returned to the pool: nothing may be handed out again before they are done)
@@ -885,7 +930,8 @@ static int settle_streams(rk_ctx *ctx, int rc)
 
 int rk_index_build(rk_ctx *ctx, const rk_sketches *s, int hash_bits, rk_index **out)
 {
-    return settle_streams(ctx, index_build_impl(ctx, s, hash_bits, 0, 1, out));
+    if (!ctx || !s || !out) return RK_ERR_ARG;
+    return settle_streams(ctx, index_build_impl(ctx, source_of(s), hash_bits, 0, 1, out));
 }
 
 int rk_index_build_shard(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint32_t shard, uint32_t n_shards, rk_index **out)
@@ -893,20 +939,25 @@ int rk_index_build_shard(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint3
     if (!ctx) return RK_ERR_ARG;
     if (!n_shards || n_shards > kRecRegions || (n_shards & (n_shards - 1)) || shard >= n_shards)
         return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard: %u shards (a power of two up to %u), shard %u", n_shards, kRecRegions, shard);
-    return settle_streams(ctx, index_build_impl(ctx, s, hash_bits, shard, n_shards, out));
+    if (!s || !out) return RK_ERR_ARG;
+    return settle_streams(ctx, index_build_impl(ctx, source_of(s), hash_bits, shard, n_shards, out));
 }
 
-static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out)
+static int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out)
 {
-    if (!ctx || !s || !out) return RK_ERR_ARG;
+    if (!ctx || !out) return RK_ERR_ARG;
     *out = nullptr;
+    const rk_sketches *s = src.s;   // (null: a build from keys -- a shard of a sharded build, never the general path)
+    const bool from_keys = s == nullptr;
     if (hash_bits < 1) return rk_fail(ctx, RK_ERR_ARG, "hash_bits must be positive");
     if (hash_bits > 64) return rk_fail(ctx, RK_ERR_ARG, "hash_bits=%d", hash_bits);
-    if ((hash_bits > 32) != s->wide)
+    if ((hash_bits > 32) != src.wide)
         return rk_fail(ctx, RK_ERR_ARG, "hash_bits=%d does not match the sketches' %s-bit layout", hash_bits,
-                       s->wide ? "64" : "32");
-    const uint64_t H = s->total;
-    const uint32_t N = s->n;
+                       src.wide ? "64" : "32");
+    const uint64_t H = src.total;
+    const uint32_t N = src.n;
+    // the elements the partition reads: the whole collection, or the shard's keys (arrays that scale with postings are sized by these)
+    const uint64_t H_el = from_keys ? src.n_keys : H;
     // Bit 31 of a slice record tags its compact form, so posting offsets inside slice records stay below 2^31.  An index of
     // 2^31-1 .. 2^32-2 postings (all of GenBank's bacteria at ~1,200 hashes each) is built WITHOUT slice records: its
     // postings, list offsets and distinct hashes are complete (.dict / .index export, sparse self joins through the tile
@@ -914,7 +965,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
     // a hash -- is refused for it.  RK_INDEX_NO_SELF=1 builds any index that way (tests).
     if (H >= 0xFFFFFFFFULL || N >= 0x7FFFFFFFu) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "more than 2^32-2 postings or 2^31-1 genomes");
     const bool no_self = H >= 0x7FFFFFFFULL || ctx->sw_index_no_self;
-    if (no_self && !s->is_set)
+    if (no_self && !src.is_set)
         return rk_fail(ctx, RK_ERR_UNSUPPORTED, "an index of more than 2^31-1 postings needs set sketches (no hash twice in a genome)");
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -924,19 +975,16 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
     idx->n_ref = N;
     idx->H = H;
     idx->hash_bits = hash_bits;
-    idx->wide = s->wide;
-    idx->max_src_size = idx->max_ref_size = s->max_size;
-    for (uint32_t g = 0; g < s->n; g++) {
-        const uint64_t sz = s->h_off[g + 1] - s->h_off[g];
-        if (sz && (!idx->min_ref_size || sz < idx->min_ref_size)) idx->min_ref_size = sz;
-    }
+    idx->wide = src.wide;
+    idx->max_src_size = idx->max_ref_size = src.max_size;
+    idx->min_ref_size = src.min_size;
     struct Guard { rk_index *p; ~Guard() { if (p) rk_index_free(p); } } guard{idx};
 
     // distinct hashes: at most H, at most the hash space
-    const uint64_t Ucap = hash_bits < 40 ? std::min<uint64_t>(H, 1ULL << hash_bits) : H;
+    const uint64_t Ucap = hash_bits < 40 ? std::min<uint64_t>(H_el, 1ULL << hash_bits) : H_el;
     RK_TRY(pool_array(ctx, &idx->d_sizes, (size_t)N + 1));
     RK_TRY(pool_array(ctx, &idx->d_src_off, (size_t)N + 1));
-    RK_TRY(pool_array(ctx, &idx->d_postings, H + 8));   // (padded: the kernels read up to eight postings from any list start)
+    RK_TRY(pool_array(ctx, &idx->d_postings, H_el + 8));   // (padded: the kernels read up to eight postings from any list start)
     if (idx->wide) RK_TRY(pool_array(ctx, &idx->d_uhash64, Ucap + 1));
     else RK_TRY(pool_array(ctx, &idx->d_uhash, Ucap + 1));
     RK_TRY(pool_array(ctx, &idx->d_upos, Ucap + 2));
@@ -969,12 +1017,13 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
     // (at most kMaxBucketBits: a bigger collection gets fuller buckets, up to the LDS capacity -- beyond it the kernels raise the overflow flag)
     const uint64_t bucket_target = getenv("RK_INDEX_BUCKET_TARGET") ? std::max(64, atoi(getenv("RK_INDEX_BUCKET_TARGET"))) : kBucketTarget;
     while (B < eff_bits && B < kMaxBucketBits && ((H_pass + bucket_target - 1) / bucket_target) > (1ULL << B)) B++;
+    if (from_keys) B = std::max(B, std::min(7, eff_bits));   // (the keys are a filtered source: the two-pass partition, >= 128 buckets)
     while ((1ULL << gb) < N) gb++;
-    while ((1ULL << rb) < s->max_size) rb++;
+    while ((1ULL << rb) < src.max_size) rb++;
     const int low_bits = eff_bits - B;
     // (64-bit hashes -- use64, e.g. K12 L3: 36 bits -- take the same path as long as the key fields fit: the kernels that read
     // the sketches are templated on the hash type, the bucket sort itself only ever sees the low bits)
-    const bool fast_common = ctx->sw_index_fast && H && s->is_set && eff_bits >= 1 && B <= kMaxBucketBits && low_bits >= 0 && low_bits <= 31 && gb <= 31 && rb <= 31;
+    const bool fast_common = ctx->sw_index_fast && H && src.is_set && eff_bits >= 1 && B <= kMaxBucketBits && low_bits >= 0 && low_bits <= 31 && gb <= 31 && rb <= 31;
     const bool slices_ok = fast_common && !range_bits && !no_self && H < (1ULL << 30) && low_bits + gb + rb <= 63;   // (slice records: one pass, offsets below 2^30)
     const uint32_t n_blocks = (N + 31) / 32;
     const bool tiles_ok = fast_common && N >= 2 && n_blocks <= kTileMaxBlocks && low_bits + gb <= 63 && ctx->sw_index_tiles != 0;
@@ -1006,7 +1055,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         }
         return RK_OK;
     };
-    const bool relabel = ctx->sw_index_relabel && s->is_set && N > 1 && H;
+    const bool relabel = ctx->sw_index_relabel && src.is_set && N > 1 && H;
     const bool two_streams = relabel && !getenv("RK_INDEX_ONE_STREAM");
     if (two_streams) {
         if (!ctx->stream2) {
@@ -1050,12 +1099,18 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         RK_HIP(ctx, rl_parent.alloc(N));
         RK_HIP(ctx, hipMemsetAsync(rl_table.p, 0xFF, (size_t)slots * 8, s2));
         const unsigned nb_ins = (unsigned)(((uint64_t)N * kMinK + kInsertThreads - 1) / kInsertThreads), nb_n = blocks_for(N);
-        if (idx->wide) {
-            hipLaunchKernelGGL(k_minhash_insert<uint64_t>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, s->d_hashes64, s->d_off, N, rl_table.p, slots - 1);
-            hipLaunchKernelGGL(k_minhash_vote<uint64_t>, dim3(nb_n), dim3(kThreads), 0, s2, s->d_hashes64, s->d_off, N, rl_table.p, slots - 1, rl_parent.p);
+        if (src.d_sig) {
+            const SigMinK rs{src.d_sig};
+            hipLaunchKernelGGL(k_minhash_insert<SigMinK>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
+            hipLaunchKernelGGL(k_minhash_vote<SigMinK>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
+        } else if (idx->wide) {
+            const CsrMinK<uint64_t> rs{s->d_hashes64, s->d_off};
+            hipLaunchKernelGGL(k_minhash_insert<CsrMinK<uint64_t>>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
+            hipLaunchKernelGGL(k_minhash_vote<CsrMinK<uint64_t>>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
         } else {
-            hipLaunchKernelGGL(k_minhash_insert<uint32_t>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, s->d_hashes, s->d_off, N, rl_table.p, slots - 1);
-            hipLaunchKernelGGL(k_minhash_vote<uint32_t>, dim3(nb_n), dim3(kThreads), 0, s2, s->d_hashes, s->d_off, N, rl_table.p, slots - 1, rl_parent.p);
+            const CsrMinK<uint32_t> rs{s->d_hashes, s->d_off};
+            hipLaunchKernelGGL(k_minhash_insert<CsrMinK<uint32_t>>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
+            hipLaunchKernelGGL(k_minhash_vote<CsrMinK<uint32_t>>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
         }
         if (N <= kRankMaxN) {
             RK_HIP(ctx, rl_keys32.alloc(N));
@@ -1067,7 +1122,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
                 RK_HIP(ctx, hipEventRecord(ctx->ev_inv, s2));
                 inv_recorded = true;
             }
-            hipLaunchKernelGGL(k_order_from_rank, dim3(nb_n), dim3(kThreads), 0, s2, rl_rank.p, N, s->d_off, idx->d_orig, idx->d_sizes);
+            hipLaunchKernelGGL(k_order_from_rank, dim3(nb_n), dim3(kThreads), 0, s2, rl_rank.p, N, src.d_off, src.d_sizes, idx->d_orig, idx->d_sizes);
             hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
             inv = rl_rank.p;   // (a genome's rank among the keys IS its internal id)
         } else {
@@ -1078,9 +1133,13 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
             void *scratch = nullptr;
             RK_TRY(rk_prim_sort_keys_u64(ctx, rl_keys.p, rl_keys_sorted.p, N, 0, (unsigned)(2 * id_bits), s2, &scratch));
             rl_tmp.p = static_cast<char *>(scratch);
-            hipLaunchKernelGGL(k_order_from_keys, dim3(nb_n), dim3(kThreads), 0, s2, rl_keys_sorted.p, N, id_bits, s->d_off, idx->d_orig, idx->d_sizes);
-            hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
+            hipLaunchKernelGGL(k_order_from_keys, dim3(nb_n), dim3(kThreads), 0, s2, rl_keys_sorted.p, N, id_bits, src.d_off, src.d_sizes, idx->d_orig, idx->d_sizes);
             hipLaunchKernelGGL(k_invert_order, dim3(nb_n), dim3(kThreads), 0, s2, idx->d_orig, N, rl_inv.p);
+            if (forked) {   // (the translation table is all the bucket emission of tile records needs: it need not wait for the offsets' scan)
+                RK_HIP(ctx, hipEventRecord(ctx->ev_inv, s2));
+                inv_recorded = true;
+            }
+            hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
             inv = rl_inv.p;
         }
         if (want_tab) {
@@ -1096,7 +1155,12 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         }
       } else {
         hipLaunchKernelGGL(k_iota, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, st, N, idx->d_orig);
-        hipLaunchKernelGGL(k_sizes, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, st, s->d_off, N, idx->d_sizes, idx->d_src_off);
+        if (src.d_sizes) {
+            RK_HIP(ctx, hipMemcpyAsync(idx->d_sizes, src.d_sizes, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, st, idx->d_sizes, N, idx->d_src_off);
+        } else {
+            hipLaunchKernelGGL(k_sizes, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, st, src.d_off, N, idx->d_sizes, idx->d_src_off);
+        }
         if (idx->d_blk_min) hipLaunchKernelGGL(k_blk_min_sizes, dim3(blocks_for(n_blocks)), dim3(kThreads), 0, st, idx->d_sizes, N, n_blocks, idx->d_blk_min);
       }
       return RK_OK;
@@ -1110,10 +1174,11 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
     // ---- fast path: two-level bucket sort, second level and all emission in LDS (rk_index_fast.inc) -----------------
     if (ctx->sw_dist_debug && !fast_ok)
         fprintf(stderr, "[rk] index build: general path (H %llu, wide %d, sets %d, B %d, low bits %d, genome bits %d, position bits %d)\n",
-                (unsigned long long)H, (int)idx->wide, (int)s->is_set, B, low_bits, gb, rb);
+                (unsigned long long)H, (int)idx->wide, (int)src.is_set, B, low_bits, gb, rb);
     TileResult tr;
     memset(&tr, 0, sizeof tr);
     bool fast_refused = false;
+    unsigned long long refused_flags = 0;   // (what the kernels raised when they refused the bucket sort)
     DevBuf<uint2> t_contrib(ctx);
     DevBuf<uint32_t> t_rows(ctx), t_cols(ctx);
     DevBuf<uint4> t_dir_j(ctx), t_dir_c(ctx);
@@ -1121,6 +1186,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
     uint32_t t_region_cap = 0;
     uint64_t rec_cap_retry = 0;   // tile records the first attempt asked for, had they fit
     uint64_t keys_cap_retry = 0;  // keys of the fullest range pass, had they fit (the ranges of a real hash space are not equally full)
+    const uint64_t H_el_shard = from_keys ? H_el : H / n_shards;   // postings of this shard: known from keys, else estimated
     for (int attempt = 0; fast_ok && !built && attempt < 3; attempt++) {
         // (the tile records of an attempt did not fit their buffer -- wide species, lists scattered over many blocks --: the
         // attempt has counted what it needs, and the next one gets exactly that, within a budget of 6 records per posting; beyond
@@ -1130,7 +1196,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
             unsigned long long worst = 0;
             for (uint32_t q = 0; q < kRecRegions; q++) worst = std::max<unsigned long long>(worst, tr.rec_count[q]);
             rec_cap_retry = (worst + worst / 16 + 1024) * kRecRegions;
-            if (rec_cap_retry > 6 * (H / n_shards) + (1u << 22) || ctx->sw_tile_rec_cap) rec_cap_retry = 0;   // (RK_TILE_REC_CAP: a test forces the fallback)
+            if (rec_cap_retry > 6 * H_el_shard + (1u << 22) || ctx->sw_tile_rec_cap) rec_cap_retry = 0;   // (RK_TILE_REC_CAP: a test forces the fallback)
         }
         if (attempt == 2 || (attempt == 1 && !rec_cap_retry)) {
             if (!slices_ok) break;
@@ -1142,26 +1208,27 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         if (!tiles_mode) RK_TRY(alloc_slices());
         const uint32_t passes = tiles_mode ? n_pass : 1;
         FastArgs fa;
-        fa.hashes = idx->wide ? (const void *)s->d_hashes64 : (const void *)s->d_hashes;
-        fa.off = s->d_off;
+        fa.hashes = from_keys ? nullptr : idx->wide ? (const void *)s->d_hashes64 : (const void *)s->d_hashes;
+        fa.off = src.d_off;
         fa.orig = nullptr;           // the partition walks the sketches in the caller's order (see the renumbering above)
-        fa.off_new = s->d_off;
+        fa.off_new = src.d_off;
         fa.n_genomes = N;
-        fa.H = H;
+        fa.H = H_el;
         fa.hash_bits = hash_bits;
         fa.low_bits = low_bits;
         fa.gb = gb;
         fa.rb = tiles_mode ? 0 : rb;   // (tile records: nobody needs an element's position inside its sketch)
         fa.xcd_map = getenv("RK_INDEX_XCD") ? atoi(getenv("RK_INDEX_XCD")) : 1;
         fa.nb = 1u << B;
-        fa.n_chunks = (uint32_t)((H + kPartChunk - 1) / kPartChunk);
+        fa.n_chunks = (uint32_t)((H_el + kPartChunk - 1) / kPartChunk);
         fa.range_bits = tiles_mode ? range_bits : 0;
         fa.range_id = 0;
         // what a pass may hold: exactly H without ranges; with ranges an estimate + slack (a pass that exceeds it raises the overflow
         // flag in k_part_starts and the kernels behind it stand still)
         // (RK_INDEX_KEYS_CAP_PCT: tests make the estimate too small)
         const uint64_t keys_pct = getenv("RK_INDEX_KEYS_CAP_PCT") ? std::max(1, atoi(getenv("RK_INDEX_KEYS_CAP_PCT"))) : 125;
-        const uint64_t keys_cap = fa.range_bits ? std::min<uint64_t>(H, keys_cap_retry ? keys_cap_retry : H_pass * keys_pct / 100 + (keys_pct >= 100 ? (1u << 20) : 0)) : H;
+        // (from keys: the shard's exact key count -- a pass of it holds at most that many)
+        const uint64_t keys_cap = from_keys ? std::max<uint64_t>(1, H_el) : fa.range_bits ? std::min<uint64_t>(H, keys_cap_retry ? keys_cap_retry : H_pass * keys_pct / 100 + (keys_pct >= 100 ? (1u << 20) : 0)) : H;
         fa.keys_cap = keys_cap;
         fa.filtered = nullptr;
         fa.n_filtered = nullptr;
@@ -1178,7 +1245,11 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         // the two-pass partition needs six spare key bits and >= 128 buckets
         const bool part2 = (getenv("RK_INDEX_PART2") ? atoi(getenv("RK_INDEX_PART2")) != 0 : true) && B >= 7 && low_bits + gb + fa.rb <= 64 - (int)kFineBits;
         // a range pass partitions what k_range_filter kept of the hashes (RK_INDEX_FILTER=0: every kernel of the pass walks them all)
-        const bool use_filter = fa.range_bits && part2 && eff_bits + gb <= 64 && (getenv("RK_INDEX_FILTER") ? atoi(getenv("RK_INDEX_FILTER")) != 0 : true);
+        // (from keys: the keys ARE a filtered source -- of one pass as they arrived, of several through k_keys_pass_filter)
+        const bool use_filter = from_keys || (fa.range_bits && part2 && eff_bits + gb <= 64 && (getenv("RK_INDEX_FILTER") ? atoi(getenv("RK_INDEX_FILTER")) != 0 : true));
+        if (from_keys && !(part2 && tiles_mode && fa.range_bits))
+            return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard_keys: the key fields do not fit the two-pass partition (hash bits %d, %d buckets, genome bits %d)",
+                           hash_bits, B, gb);
         const uint32_t part_chunks = use_filter ? (uint32_t)((keys_cap + kPartChunk - 1) / kPartChunk) : fa.n_chunks;   // rows of the count matrix
         RK_HIP(ctx, chunk_first.alloc((size_t)fa.n_chunks + 1));
         RK_HIP(ctx, matrix.alloc((size_t)part_chunks * fa.nb));
@@ -1186,9 +1257,9 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         RK_HIP(ctx, bstart.alloc(nb1 * passes));   // (per pass: the list heads of a pass are placed while the next one partitions)
         RK_HIP(ctx, ucount.alloc(nb1 * passes));
         RK_HIP(ctx, ubase.alloc(nb1 * passes));
-        if (wide) RK_HIP(ctx, tmp_uhash64.alloc(H));
-        else RK_HIP(ctx, tmp_uhash.alloc(H));
-        RK_HIP(ctx, tmp_upos.alloc(H));
+        if (wide) RK_HIP(ctx, tmp_uhash64.alloc(H_el));
+        else RK_HIP(ctx, tmp_uhash.alloc(H_el));
+        RK_HIP(ctx, tmp_upos.alloc(H_el));
         RK_HIP(ctx, keys.alloc(keys_cap));
         uint64_t rec_cap = 0, tile_cap = 0, slot_cap = 0;
         uint32_t region_cap = 0;
@@ -1197,7 +1268,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
             // related lists write ~0.15-0.3 records per posting; chance collisions of a crowded hash space add H x lambda / 2
             // (lambda = postings per hash value: 500,000 genomes in 28 bits share every value twice over)
             const double lambda = hash_bits < 48 ? (double)H / (double)(1ULL << hash_bits) : 0.0;
-            rec_cap = ctx->sw_tile_rec_cap ? ctx->sw_tile_rec_cap : rec_cap_retry ? rec_cap_retry : (uint64_t)((double)(H / n_shards) * (0.5 + 0.6 * lambda)) + 65536;
+            rec_cap = ctx->sw_tile_rec_cap ? ctx->sw_tile_rec_cap : rec_cap_retry ? rec_cap_retry : (uint64_t)((double)H_el_shard * (0.5 + 0.6 * lambda)) + 65536;
             rec_cap = std::min<uint64_t>(rec_cap, 0x7FFF0000ULL);
             region_cap = (uint32_t)((rec_cap + kRecRegions - 1) / kRecRegions);
             rec_cap = (uint64_t)region_cap * kRecRegions;
@@ -1244,7 +1315,8 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
             RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_hist<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
             RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_scatter<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
         }
-        hipLaunchKernelGGL(k_chunk_first, dim3(blocks_for(std::max<uint64_t>((uint64_t)fa.n_chunks + 1, z_end))), dim3(kThreads), 0, st, s->d_off, N, fa.n_chunks,
+        // (from keys: no chunk walks the sketches -- the launch only zeroes, and chunk_first[0] is all it writes)
+        hipLaunchKernelGGL(k_chunk_first, dim3(blocks_for(std::max<uint64_t>((uint64_t)fa.n_chunks + 1, z_end))), dim3(kThreads), 0, st, src.d_off, N, from_keys ? 0u : fa.n_chunks,
                            chunk_first.p, zeroed.p, (uint32_t)z_end);
         DevBuf<unsigned long long> mid(ctx);
         if (part2) RK_HIP(ctx, mid.alloc(keys_cap));
@@ -1261,7 +1333,25 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
             uint32_t *const fine_cursor = reinterpret_cast<uint32_t *>(zeroed.p + z_cursor + w_cursor * pass);
             uint32_t *const seg_taken = reinterpret_cast<uint32_t *>(zeroed.p + z_taken + w_taken * pass);
             FastArgs pa = fa;   // what the partition kernels of this pass see
-            if (use_filter) {
+            if (from_keys) {
+                unsigned long long *const n_filt = zeroed.p + z_filt + pass;
+                // the caller's keys are never written: one pass partitions them as they are (k_part_fine writes `keys`, ours), several
+                // passes filter them into `keys` first -- a second attempt (tile records beyond their buffer) starts from intact keys
+                if (passes == 1) {
+                    hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(64), 0, st, n_filt, (unsigned long long)H_el);
+                    pa.filtered = src.keys;
+                } else {
+                    const uint64_t per_wg = (uint64_t)kKeysFilterThreads * kKeysFilterSteps;
+                    if (H_el)
+                        hipLaunchKernelGGL(k_keys_pass_filter, dim3((unsigned)((H_el + per_wg - 1) / per_wg)), dim3(kKeysFilterThreads), 0, st, src.keys, H_el, gb,
+                                           hash_bits - shard_bits, pass_bits, pass, keys.p, n_filt, (unsigned long long)keys_cap, fres);
+                    pa.filtered = keys.p;
+                }
+                pa.n_filtered = n_filt;
+                pa.hash_bits = eff_bits;
+                pa.range_bits = 0;
+                pa.range_id = 0;
+            } else if (use_filter) {
                 unsigned long long *const n_filt = zeroed.p + z_filt + pass;
                 // (the filtered elements lie in `keys`: the coarse pass reads them and writes `mid`, the fine pass writes `keys` again)
                 if (wide) hipLaunchKernelGGL(k_range_filter<uint64_t>, dim3(fa.n_chunks * kFilterSplit), dim3(kFilterThreads), 0, st, fa, chunk_first.p, keys.p, n_filt, fres);
@@ -1337,7 +1427,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
                 ea.debug = getenv("RK_INDEX_DEBUG") ? atoi(getenv("RK_INDEX_DEBUG")) : 0;
                 if (ea.debug) {  // developer ablations leave stages out: whatever they do not write must still be harmless downstream
                     RK_HIP(ctx, hipMemsetAsync(ucount_p, 0, (size_t)fa.nb * 4, st));
-                    RK_HIP(ctx, hipMemsetAsync(tmp_upos.p, 0, H * 4, st));
+                    RK_HIP(ctx, hipMemsetAsync(tmp_upos.p, 0, H_el * 4, st));
                 }
 #define RK_EMIT(TT) do { if (narrow) hipLaunchKernelGGL((k_bucket_emit_tiles<TT, uint32_t>), dim3(fa.nb), dim3(TT), 0, st, ea); \
                          else hipLaunchKernelGGL((k_bucket_emit_tiles<TT, unsigned long long>), dim3(fa.nb), dim3(TT), 0, st, ea); } while (0)
@@ -1467,7 +1557,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         if (ctx->sw_dist_debug)
             fprintf(stderr, "[rk] index build: fast path flags %llu (B %d, low bits %d, genome bits %d, position bits %d; shard %u of %u, %u pass(es), %llu postings)%s\n",
                     r.flags, B, low_bits, gb, rb, shard_id, n_shards, passes, n_postings, tiles_mode ? (tr.overflow ? ", tile records overflowed" : ", tile records") : "");
-        if ((r.flags & kFastOverflow) && use_filter && !keys_cap_retry) {
+        if ((r.flags & kFastOverflow) && use_filter && !from_keys && !keys_cap_retry) {
             // a range holds more keys than estimated: every pass's filter has counted what it needs -- once more with exactly that
             std::vector<unsigned long long> asked(passes);
             RK_TRY(rk_read_back(ctx, asked.data(), zeroed.p + z_filt, (size_t)passes * 8, st));
@@ -1483,6 +1573,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
         if (r.flags == 0 && !(tiles_mode && tr.overflow)) built = true;
         else if (r.flags) {   // a bucket beyond the LDS sort, a pass beyond its key buffer, or a hash outside the hash space: the general path decides
             fast_refused = true;
+            refused_flags = r.flags;
             r = BuildResult{0, 0, 0, 0, 0};
         }
         if (built && range_bits) idx->H = n_postings;   // (a shard: the postings of ITS hash range; all passes of one shard: == H)
@@ -1513,6 +1604,8 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
             for (uint32_t q = 0; q < kRecRegions; q++) idx->shard_rec_count[q] = tr.rec_count[q];
         }
     }
+    if (!built && from_keys && (refused_flags & kFastBadHash))
+        return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: a key outside the wire format (hash bits beyond the shard's range, or a genome id >= %u)", N);
     if (!built && n_shards > 1)
         return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard: the bucket sort refused this collection (flags %s: a bucket or a pass beyond its "
                                                 "buffer, a hash outside the hash space, or tile records beyond their capacity)", tr.overflow ? "tile overflow" : "bucket / key overflow");
@@ -1610,7 +1703,7 @@ static int index_build_impl(rk_ctx *ctx, const rk_sketches *s, int hash_bits, ui
     idx->U = r.U;
     idx->n_self = r.n_self;
     idx->slices_refused = no_self;
-    idx->ref_sets = s->is_set || r.dups == 0;
+    idx->ref_sets = src.is_set || r.dups == 0;
     idx->built_fast = built;
     if (built) {   // (the same rule as rk_dist.hip self_uses_tiles, which counts the records itself for an index built the general way)
         idx->spread = r.flagged * 8 > r.n_self;
@@ -1675,6 +1768,176 @@ int rk_index_shard_pack(const rk_index *idx, void *send_dev, void *stream_v)
     if (at) hipLaunchKernelGGL(k_shard_pack, dim3(64, kRecRegions), dim3(256), 0, (hipStream_t)stream_v, idx->d_shard_rec, idx->shard_region_cap, pa, (uint3 *)send_dev);
     RK_HIP(ctx, hipGetLastError());
     return RK_OK;
+}
+
+// ---- a sharded build from per-rank sketches (rk_index_keys.inc) ---------------------------------------------------------
+static int shard_bits_of(rk_ctx *ctx, const char *fn, uint32_t n_shards, int *bits)
+{
+    if (!n_shards || n_shards > kRecRegions || (n_shards & (n_shards - 1)))
+        return rk_fail(ctx, RK_ERR_ARG, "%s: %u shards (a power of two up to %u)", fn, n_shards, kRecRegions);
+    int b = 0;
+    while ((1u << b) < n_shards) b++;
+    *bits = b;
+    return RK_OK;
+}
+static int genome_bits_of(uint32_t n_genomes)   // (as index_build_impl: the smallest gb >= 1 with 2^gb >= n_genomes)
+{
+    int gb = 1;
+    while ((1ULL << gb) < n_genomes) gb++;
+    return gb;
+}
+
+// the checks both halves of the split share; fills the kernel arguments
+static int split_args(rk_ctx *ctx, const char *fn, const rk_sketches *local, uint32_t genome_base, uint32_t n_genomes, int hash_bits,
+                      uint32_t n_shards, SplitArgs *a)
+{
+    int shard_bits = 0;
+    RK_TRY(shard_bits_of(ctx, fn, n_shards, &shard_bits));
+    if (!local->n || (uint64_t)genome_base + local->n > n_genomes)
+        return rk_fail(ctx, RK_ERR_ARG, "%s: genomes %u .. %llu of a collection of %u", fn, genome_base, (unsigned long long)genome_base + local->n, n_genomes);
+    if (hash_bits < 1 || hash_bits > 64 || (hash_bits > 32) != local->wide || hash_bits <= shard_bits)
+        return rk_fail(ctx, RK_ERR_ARG, "%s: hash_bits=%d with %s-bit sketches and %u shards", fn, hash_bits, local->wide ? "64" : "32", n_shards);
+    if (!local->is_set)
+        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: a sharded build needs set sketches (a genome lists a hash twice)", fn);
+    const int gb = genome_bits_of(n_genomes);
+    if (hash_bits - shard_bits + gb > 64)
+        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: a key of %d hash bits and %d genome bits does not fit 64 bits", fn, hash_bits - shard_bits, gb);
+    a->hashes = local->wide ? (const void *)local->d_hashes64 : (const void *)local->d_hashes;
+    a->off = local->d_off;
+    a->H = local->total;
+    a->n_local = local->n;
+    a->genome_base = genome_base;
+    a->hash_bits = hash_bits;
+    a->shift = hash_bits - shard_bits;
+    a->gb = gb;
+    a->rem_mask = a->shift >= 64 ? ~0ULL : (1ULL << a->shift) - 1ULL;
+    a->n_dest = n_shards;
+    a->xcd_map = getenv("RK_INDEX_XCD") ? atoi(getenv("RK_INDEX_XCD")) : 1;
+    return RK_OK;
+}
+
+int rk_sketches_signature(rk_ctx *ctx, const rk_sketches *local, void *sig_dev, void *stream)
+{
+    if (!ctx || !local || !sig_dev) return RK_ERR_ARG;
+    if (local->max_size > 0xFFFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_sketches_signature: a sketch of 2^32 hashes or more");
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!local->n) return RK_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    if (local->wide)
+        hipLaunchKernelGGL(k_sketch_signature<uint64_t>, dim3(blocks_for(local->n)), dim3(kThreads), 0, st, local->d_hashes64, local->d_off, local->n, (uint32_t *)sig_dev);
+    else
+        hipLaunchKernelGGL(k_sketch_signature<uint32_t>, dim3(blocks_for(local->n)), dim3(kThreads), 0, st, local->d_hashes, local->d_off, local->n, (uint32_t *)sig_dev);
+    RK_HIP(ctx, hipGetLastError());
+    return RK_OK;
+}
+
+int rk_sketches_shard_keys(rk_ctx *ctx, const rk_sketches *local, uint32_t genome_base, uint32_t n_genomes, int hash_bits, uint32_t n_shards,
+                           uint64_t *counts_out)
+{
+    if (!ctx || !local || !counts_out) return RK_ERR_ARG;
+    SplitArgs a;
+    RK_TRY(split_args(ctx, "rk_sketches_shard_keys", local, genome_base, n_genomes, hash_bits, n_shards, &a));
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    DevBuf<unsigned long long> cnt(ctx);   // [0, 64) keys per destination, [64] the outside-the-hash-space flag
+    RK_HIP(ctx, cnt.alloc(kRecRegions + 1));
+    RK_HIP(ctx, hipMemsetAsync(cnt.p, 0, (kRecRegions + 1) * 8, st));
+    const uint32_t n_chunks = (uint32_t)((a.H + kPartChunk - 1) / kPartChunk);
+    unsigned int *bad = reinterpret_cast<unsigned int *>(cnt.p + kRecRegions);
+    if (n_chunks) {
+        if (local->wide) hipLaunchKernelGGL((k_sketch_split<uint64_t, false>), dim3(n_chunks * kSplitPerChunk), dim3(kSplitThreads), 0, st, a, nullptr, cnt.p, nullptr, bad);
+        else hipLaunchKernelGGL((k_sketch_split<uint32_t, false>), dim3(n_chunks * kSplitPerChunk), dim3(kSplitThreads), 0, st, a, nullptr, cnt.p, nullptr, bad);
+        RK_HIP(ctx, hipGetLastError());
+    }
+    unsigned long long v[kRecRegions + 1];
+    RK_TRY(rk_read_back(ctx, v, cnt.p, sizeof v, st));
+    if (v[kRecRegions])
+        return rk_fail(ctx, RK_ERR_ARG, "rk_sketches_shard_keys: a hash beyond %d bits", hash_bits);
+    for (uint32_t d = 0; d < n_shards; d++) counts_out[d] = v[d];
+    return RK_OK;
+}
+
+int rk_sketches_shard_pack(rk_ctx *ctx, const rk_sketches *local, uint32_t genome_base, uint32_t n_genomes, int hash_bits, uint32_t n_shards,
+                           void *send_dev, void *stream)
+{
+    if (!ctx || !local || !send_dev) return RK_ERR_ARG;
+    SplitArgs a;
+    RK_TRY(split_args(ctx, "rk_sketches_shard_pack", local, genome_base, n_genomes, hash_bits, n_shards, &a));
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t n_chunks = (uint32_t)((a.H + kPartChunk - 1) / kPartChunk);
+    if (!n_chunks) return RK_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    // (the temporaries go back to the pool once the stream has passed the kernels that use them: the call does not wait)
+    // [0, 64) keys per destination, [64, 128) cursors into the send buffer, [128] the count pass's flag for hashes beyond hash_bits
+    // (rk_sketches_shard_keys reports them; the pack leaves them out)
+    DevBuf<unsigned long long> cnt(ctx);
+    DevBuf<uint32_t> chunk_first(ctx);
+    RK_HIP(ctx, cnt.alloc(2 * kRecRegions + 1));
+    RK_HIP(ctx, chunk_first.alloc((size_t)n_chunks + 1));
+    hipLaunchKernelGGL(k_chunk_first, dim3(blocks_for(std::max<uint64_t>((uint64_t)n_chunks + 1, 2 * kRecRegions))), dim3(kThreads), 0, st, a.off, a.n_local,
+                       n_chunks, chunk_first.p, cnt.p, 2 * kRecRegions + 1);
+    unsigned int *const bad = reinterpret_cast<unsigned int *>(cnt.p + 2 * kRecRegions);
+    const dim3 grid(n_chunks * kSplitPerChunk);
+    if (local->wide) {
+        hipLaunchKernelGGL((k_sketch_split<uint64_t, false>), grid, dim3(kSplitThreads), 0, st, a, nullptr, cnt.p, nullptr, bad);
+        hipLaunchKernelGGL(k_split_bases, dim3(1), dim3(64), 0, st, cnt.p, n_shards, cnt.p + kRecRegions);
+        hipLaunchKernelGGL((k_sketch_split<uint64_t, true>), grid, dim3(kSplitThreads), 0, st, a, chunk_first.p, cnt.p + kRecRegions, (unsigned long long *)send_dev, nullptr);
+    } else {
+        hipLaunchKernelGGL((k_sketch_split<uint32_t, false>), grid, dim3(kSplitThreads), 0, st, a, nullptr, cnt.p, nullptr, bad);
+        hipLaunchKernelGGL(k_split_bases, dim3(1), dim3(64), 0, st, cnt.p, n_shards, cnt.p + kRecRegions);
+        hipLaunchKernelGGL((k_sketch_split<uint32_t, true>), grid, dim3(kSplitThreads), 0, st, a, chunk_first.p, cnt.p + kRecRegions, (unsigned long long *)send_dev, nullptr);
+    }
+    RK_HIP(ctx, hipGetLastError());
+    rk_pool_free_after(ctx, cnt.release(), st);
+    rk_pool_free_after(ctx, chunk_first.release(), st);
+    return RK_OK;
+}
+
+int rk_index_build_shard_keys(rk_ctx *ctx, const void *keys_dev, uint64_t n_keys, const void *sig_dev, uint32_t n_genomes, int hash_bits, uint32_t shard,
+                              uint32_t n_shards, rk_index **out)
+{
+    if (!ctx || !out || !sig_dev || (!keys_dev && n_keys)) return RK_ERR_ARG;
+    *out = nullptr;
+    int shard_bits = 0;
+    RK_TRY(shard_bits_of(ctx, "rk_index_build_shard_keys", n_shards, &shard_bits));
+    if (n_shards < 2 || shard >= n_shards)
+        return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: shard %u of %u (2 .. %u shards; one is rk_index_build)", shard, n_shards, kRecRegions);
+    if (!n_genomes || n_genomes >= 0x7FFFFFFFu) return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: %u genomes", n_genomes);
+    if (hash_bits < 1 || hash_bits > 64 || hash_bits <= shard_bits) return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: hash_bits=%d, %u shards", hash_bits, n_shards);
+    if (hash_bits - shard_bits + genome_bits_of(n_genomes) > 64)
+        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard_keys: a key of %d hash bits and %d genome bits does not fit 64 bits", hash_bits - shard_bits,
+                       genome_bits_of(n_genomes));
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t N = n_genomes;
+    const uint32_t *sig = static_cast<const uint32_t *>(sig_dev);
+    // the genomes as the build reads them: their sizes (caller's order) and the signatures themselves (the renumbering reads the first
+    // min(size, 16) hashes of every genome from them: the values rk_index_build_shard's renumbering reads of the sketches)
+    DevBuf<uint32_t> sizes(ctx);
+    DevBuf<unsigned long long> stats(ctx);
+    RK_HIP(ctx, sizes.alloc(N));
+    RK_HIP(ctx, stats.alloc(3));
+    RK_HIP(ctx, hipMemsetAsync(stats.p, 0, 16, st));
+    RK_HIP(ctx, hipMemsetAsync(stats.p + 2, 0xFF, 8, st));
+    hipLaunchKernelGGL(k_sig_sizes, dim3(std::min<uint32_t>(kSigSizesBlocks, (N + kSigSizesThreads - 1) / kSigSizesThreads)), dim3(kSigSizesThreads), 0, st,
+                       sig, N, sizes.p, stats.p);
+    RK_HIP(ctx, hipGetLastError());
+    unsigned long long st3[3];
+    RK_TRY(rk_read_back(ctx, st3, stats.p, sizeof st3, st));
+    if (n_keys > st3[0])
+        return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: %llu keys, but the signatures count %llu postings", (unsigned long long)n_keys, st3[0]);
+    BuildSource src;
+    src.n = N;
+    src.total = st3[0];
+    src.wide = hash_bits > 32;
+    src.is_set = true;   // (rk_sketches_shard_pack refuses sketches that are not sets)
+    src.max_size = st3[1];
+    src.min_size = st3[2] == 0xFFFFFFFFULL ? 0 : st3[2];
+    src.d_sizes = sizes.p;
+    src.d_sig = sig;
+    src.keys = static_cast<const unsigned long long *>(keys_dev);
+    src.n_keys = n_keys;
+    return settle_streams(ctx, index_build_impl(ctx, src, hash_bits, shard, n_shards, out));
 }
 
 // One process, one context per GPU (what `rabbit_kssd alldist --gpus N` does): the all-to-all of the shards' tile records by

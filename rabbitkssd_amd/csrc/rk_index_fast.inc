@@ -337,7 +337,14 @@ __global__ __launch_bounds__(kPartThreads) void k_part_hist(FastArgs a, const ui
                 for (int d = 0; d < D; d++) kv[d] = base + (uint64_t)d * kPartThreads < c1 ? a.filtered[base + (uint64_t)d * kPartThreads] : 0ULL;
 #pragma unroll
                 for (int d = 0; d < D; d++)
-                    if (base + (uint64_t)d * kPartThreads < c1) atomicAdd(&part_lds[(uint32_t)((kv[d] >> a.gb) >> a.low_bits)], 1u);
+                    if (base + (uint64_t)d * kPartThreads < c1) {
+                        // (keys that came from another rank, rk_index_build_shard_keys: one outside the wire format -- a hash beyond the
+                        // range's bits, a genome beyond the collection -- refuses the build instead of reaching past the counters)
+                        const unsigned long long hb = kv[d] >> a.gb;
+                        const uint32_t g = (uint32_t)(kv[d] & ((1ULL << a.gb) - 1ULL));
+                        if ((a.hash_bits < 64 && (hb >> a.hash_bits)) || g >= a.n_genomes) bad = true;
+                        else atomicAdd(&part_lds[(uint32_t)(hb >> a.low_bits)], 1u);
+                    }
             }
         }
     } else if (!a.orig) {

@@ -459,7 +459,13 @@ __global__ __launch_bounds__(T) void k_bucket_heavy(HeavyArgs h)
     uint16_t *nz = reinterpret_cast<uint16_t *>(heavy_lds + max(h.n_blocks, kBucketCap));
     uint16_t *rpos = reinterpret_cast<uint16_t *>(sb);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (a.stop && a.stop->flags) return;
+    if (a.stop && a.stop->flags) {
+        // (the build is refused, but k_heads_scan / k_heads_place still read every bucket's list count: the listed buckets get 0,
+        // as k_bucket_emit_tiles gives the others -- a count left from earlier contents of the buffer would place heads anywhere)
+        const uint32_t nb_listed = *h.n_big;
+        for (uint32_t k = blockIdx.x * T + tid; k < nb_listed; k += gridDim.x * T) a.ucount[h.big_list[k]] = 0;
+        return;
+    }
     const uint32_t n_big = *h.n_big;
     if (n_big == 0) return;   // (the usual case at 10,000 genomes: not even a ticket's round trip)
     const uint32_t gmask = (1u << a.gb) - 1u;
