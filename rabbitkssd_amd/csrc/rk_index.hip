@@ -691,9 +691,831 @@ int classify_lists(rk_ctx *ctx, rk_index *idx, hipStream_t st)
     return RK_OK;
 }
 
+// ==== the index build, host side: plan -> index arrays -> bucket-sort attempts -> general path -> finish ====
+#include "rk_index_plan.h"
+
+// The tile sort's buffers (launch_tile_sort): what the build and rk_index_join_shard both set up, sort into and hand to the index.
+struct TileSortBufs {
+    DevBuf<uint3> brec;                       // the records binned by row block
+    DevBuf<uint32_t> tb, bins, t_rows, t_cols;
+    DevBuf<uint4> proto, t_dir_j, t_dir_c;    // the directory's proto entries, the directories
+    DevBuf<unsigned long long> level_start;
+    DevBuf<uint2> t_contrib;
+    explicit TileSortBufs(rk_ctx *c) : brec(c), tb(c), bins(c), t_rows(c), t_cols(c), proto(c), t_dir_j(c), t_dir_c(c), level_start(c), t_contrib(c) {}
+    int alloc(rk_ctx *ctx, uint32_t n_blocks, uint64_t n_records, uint64_t tile_cap)
+    {
+        const uint64_t slot_cap = n_records + tile_cap;   // (every tile from an even slot on)
+        RK_HIP(ctx, brec.alloc(n_records));
+        RK_HIP(ctx, tb.alloc(3 * (size_t)n_blocks));
+        RK_HIP(ctx, bins.alloc((size_t)n_blocks + 1));   // bin starts (the counts and cursors are in `zeroed`)
+        RK_HIP(ctx, proto.alloc(2 * tile_cap));
+        RK_HIP(ctx, level_start.alloc(2 * (kTileTable + 1)));
+        RK_HIP(ctx, t_contrib.alloc(slot_cap + 256));
+        if (rowsort_stage(n_blocks)) {   // (the split copy serves the scalar-row variant of the tile kernel: short launches over small collections)
+            RK_HIP(ctx, t_rows.alloc(slot_cap + 256));
+            RK_HIP(ctx, t_cols.alloc(slot_cap + 256));
+        }
+        RK_HIP(ctx, t_dir_j.alloc(2 * tile_cap));
+        RK_HIP(ctx, t_dir_c.alloc(2 * tile_cap));
+        return RK_OK;
+    }
+    TileSortArgs args(const uint3 *rec, uint32_t region_cap, uint32_t n_blocks, const uint32_t *blk_min, const ZeroedLayout &z) const
+    {
+        TileSortArgs ta;
+        memset(&ta, 0, sizeof ta);
+        ta.rec = rec;
+        ta.cur = z.tile_cursors();
+        ta.region_cap = region_cap;
+        ta.n_blocks = n_blocks;
+        ta.bin_count = z.bin_count();
+        ta.bin_cursor = z.bin_cursor();
+        ta.bin_start = bins.p;
+        ta.brec = brec.p;
+        ta.blk_min = blk_min;
+        ta.contrib = t_contrib.p;
+        ta.rows = t_rows.p;
+        ta.cols = t_cols.p;
+        ta.tb_base = tb.p;
+        ta.tb_cnt = tb.p + n_blocks;
+        ta.order = tb.p + 2 * (size_t)n_blocks;
+        ta.proto = proto.p;
+        ta.level_start = level_start.p;
+        ta.dir[0] = t_dir_j.p;
+        ta.dir[1] = t_dir_c.p;
+        ta.tres = z.tile_res();
+        return ta;
+    }
+    void hand_over(rk_index *idx, const TileResult &tr)   // a finished sort: its results and counters into the index
+    {
+        idx->d_tile_contrib = t_contrib.release();
+        idx->d_tile_rows = t_rows.release();
+        idx->d_tile_cols = t_cols.release();
+        idx->d_tile_dir[0] = t_dir_j.release();
+        idx->d_tile_dir[1] = t_dir_c.release();
+        idx->n_tile_slots = tr.n_slots;
+        idx->n_tiles = tr.n_tiles;
+        idx->n_tile_records = tr.n_records;
+        idx->tile_max_records = tr.max_records;
+        for (int m = 0; m < 2; m++)
+            for (int k = 0; k < kTileTable; k++) idx->tile_prefix[m][k] = tr.level_count[m][k];
+        idx->tiles_ready = true;
+        idx->tiles_from_build = true;
+    }
+};
+
+// what every stage of one build works on
+struct BuildCtx {
+    rk_ctx *ctx;
+    const BuildSource &src;
+    const BuildPlan &p;
+    const BuildKnobs &k;
+    rk_index *idx;
+    hipStream_t st;   // the context's stream
+};
+
+int alloc_index_arrays(rk_ctx *ctx, rk_index *idx, const BuildPlan &p)
+{
+    RK_TRY(pool_array(ctx, &idx->d_sizes, (size_t)p.N + 1));
+    RK_TRY(pool_array(ctx, &idx->d_src_off, (size_t)p.N + 1));
+    RK_TRY(pool_array(ctx, &idx->d_postings, p.H_el + 8));   // (padded: the kernels read up to eight postings from any list start)
+    if (idx->wide) RK_TRY(pool_array(ctx, &idx->d_uhash64, p.Ucap + 1));
+    else RK_TRY(pool_array(ctx, &idx->d_uhash, p.Ucap + 1));
+    RK_TRY(pool_array(ctx, &idx->d_upos, p.Ucap + 2));
+    RK_TRY(pool_array(ctx, &idx->d_orig, (size_t)p.N + 1));
+    if (p.tiles_mode) RK_TRY(pool_array(ctx, &idx->d_blk_min, (size_t)p.n_blocks));
+    return RK_OK;
+}
+// (not for an index whose build emits tile records: rk_index_ensure_slices, on first use)
+int alloc_slices(rk_ctx *ctx, rk_index *idx, const BuildPlan &p)
+{
+    if (p.no_self || idx->d_selfrange) return RK_OK;
+    RK_TRY(pool_array(ctx, &idx->d_selfrange, p.H + 1));
+    RK_TRY(pool_array(ctx, &idx->d_self_off, (size_t)p.N + 1));
+    RK_TRY(pool_array(ctx, &idx->d_self_split, (size_t)p.N + 1));
+    return RK_OK;
+}
+void drop_blk_min(rk_ctx *ctx, rk_index *idx)   // (no tile records after all)
+{
+    rk_pool_free(ctx, idx->d_blk_min);
+    idx->d_blk_min = nullptr;
+}
+
+// the second stream of the build and the events of its fork/join protocol: created with the first build that uses them
+int ensure_stream2(rk_ctx *ctx, bool high_priority)
+{
+    if (ctx->stream2) return RK_OK;
+    // (its kernels are small and many: at the highest priority they are not queued behind the partition's workgroups)
+    int prio_lo = 0, prio_hi = 0;
+    if (high_priority && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess && prio_hi != prio_lo)
+        RK_HIP(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi));
+    else
+        RK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    RK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    RK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    RK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_inv, hipEventDisableTiming));
+    return RK_OK;
+}
+
+// ---- internal genome order: relatives next to each other (see k_minhash_insert) ---------------------------------
+// d_orig, d_sizes and d_src_off (the CSR offsets in internal order); the rest of the build, and every kernel that
+// uses the index, works in that order
+// (round 4) It runs on a stream of its own: the partition of the hashes does not need it -- it walks the sketches
+// in the CALLER's order and k_bucket_emit translates the genome ids through `inv` --, so the two overlap (≈ 70 us of
+// small dependent kernels next to ≈ 160 us of partition); join() makes ctx->stream wait for it where its results are
+// first used.  The temporaries live until the build returns (the pool's reuse is ordered on ctx->stream only): one
+// Renumbering per build, destroyed with it.
+struct Renumbering {
+    const BuildCtx &b;
+    DevBuf<unsigned long long> rl_table, rl_keys, rl_keys_sorted;
+    DevBuf<uint32_t> rl_parent, rl_keys32, rl_rank, rl_inv;
+    DevBuf<uint2> rl_tab;
+    DevBuf<char> rl_tmp;   // the sort's scratch (kept until the build returns: the sort runs on the second stream)
+    const uint32_t *inv = nullptr;   // caller's genome index -> internal id (null: identity)
+    bool forked = false, joined = true;
+    bool inv_recorded = false;   // ctx->ev_inv was recorded behind the kernel that completes `inv`
+    bool enqueued = false;
+    explicit Renumbering(const BuildCtx &bc)
+        : b(bc), rl_table(bc.ctx), rl_keys(bc.ctx), rl_keys_sorted(bc.ctx), rl_parent(bc.ctx), rl_keys32(bc.ctx), rl_rank(bc.ctx), rl_inv(bc.ctx),
+          rl_tab(bc.ctx), rl_tmp(bc.ctx) {}
+
+    int mark_fork()   // at the top of the build: everything enqueued on ctx->stream so far comes before the renumbering
+    {
+        if (!b.p.two_streams) return RK_OK;
+        RK_TRY(ensure_stream2(b.ctx, b.k.stream2_high));
+        RK_HIP(b.ctx, hipEventRecord(b.ctx->ev_fork, b.st));
+        return RK_OK;
+    }
+    int join()   // ctx->stream waits for whatever the second stream was last given
+    {
+        if (!joined) {
+            RK_HIP(b.ctx, hipStreamWaitEvent(b.st, b.ctx->ev_join, 0));
+            joined = true;
+        }
+        return RK_OK;
+    }
+    // tile records need the translation table alone (sizes and offsets in internal order are still on their way on the second
+    // stream: joined in front of the row sort)
+    int wait_inv()
+    {
+        if (inv_recorded && !joined) RK_HIP(b.ctx, hipStreamWaitEvent(b.st, b.ctx->ev_inv, 0));
+        else RK_TRY(join());
+        return RK_OK;
+    }
+    int ensure_table()   // (second attempt: the renumbering ran for tile records, without k_emit_table's table)
+    {
+        if (!inv || rl_tab.p) return RK_OK;
+        RK_HIP(b.ctx, rl_tab.alloc(b.p.N));
+        hipLaunchKernelGGL(k_emit_table, dim3(blocks_for(b.p.N)), dim3(kThreads), 0, b.st, inv, b.idx->d_src_off, b.p.N, rl_tab.p);
+        return RK_OK;
+    }
+    // the list heads of a one-pass build hang on the emission alone: they branch off to the second stream and are joined like the renumbering
+    int branch_heads(hipStream_t *sh)
+    {
+        RK_HIP(b.ctx, hipEventRecord(b.ctx->ev_fork, b.st));
+        RK_HIP(b.ctx, hipStreamWaitEvent(b.ctx->stream2, b.ctx->ev_fork, 0));
+        *sh = b.ctx->stream2;
+        return RK_OK;
+    }
+    int heads_branched()
+    {
+        RK_HIP(b.ctx, hipEventRecord(b.ctx->ev_join, b.ctx->stream2));
+        joined = false;
+        return RK_OK;
+    }
+    int enqueue(bool want_tab);
+    int enqueue_identity();
+};
+
+// The launches of the renumbering are ENQUEUED after the partition's (the fast path calls this once its own first
+// kernels are in the queue): the host needs ~5 us per launch, and with the renumbering's ten launches in front the
+// partition started 70 us late.  want_tab: the fast path is taken with slice records and wants k_emit_table's table.
+int Renumbering::enqueue(bool want_tab)
+{
+    if (enqueued) return RK_OK;
+    enqueued = true;
+    if (!b.p.relabel) return enqueue_identity();
+    rk_ctx *ctx = b.ctx;
+    rk_index *idx = b.idx;
+    const BuildSource &src = b.src;
+    const uint32_t N = b.p.N;
+    hipStream_t s2 = b.st;
+    if (b.p.two_streams) {
+        s2 = ctx->stream2;
+        RK_HIP(ctx, hipStreamWaitEvent(s2, ctx->ev_fork, 0));
+        forked = true;
+    }
+    const int id_bits = b.p.gb;
+    uint32_t slots = 1024;
+    // (at most half full, usually far less -- relatives share their smallest hashes.  Twice this size was 268 MB at 500,000 genomes:
+    // beyond the last-level cache, every probe a DRAM row of its own, and the kernels streaming beside it slowed to a third)
+    const unsigned long long want_slots = b.k.table_x * N * kMinK;
+    while (slots < want_slots && slots < (1u << 30)) slots <<= 1;
+    RK_HIP(ctx, rl_table.alloc(slots));
+    RK_HIP(ctx, rl_parent.alloc(N));
+    RK_HIP(ctx, hipMemsetAsync(rl_table.p, 0xFF, (size_t)slots * 8, s2));
+    const unsigned nb_ins = (unsigned)(((uint64_t)N * kMinK + kInsertThreads - 1) / kInsertThreads), nb_n = blocks_for(N);
+    auto insert_and_vote = [&](auto rs) {   // rs: where a genome's smallest hashes are read
+        using R = decltype(rs);
+        hipLaunchKernelGGL(k_minhash_insert<R>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
+        hipLaunchKernelGGL(k_minhash_vote<R>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
+    };
+    if (src.d_sig) insert_and_vote(SigMinK{src.d_sig});
+    else if (idx->wide) insert_and_vote(CsrMinK<uint64_t>{src.s->d_hashes64, src.s->d_off});
+    else insert_and_vote(CsrMinK<uint32_t>{src.s->d_hashes, src.s->d_off});
+    if (N <= kRankMaxN) {
+        RK_HIP(ctx, rl_keys32.alloc(N));
+        RK_HIP(ctx, rl_rank.alloc(N));
+        hipLaunchKernelGGL(k_cluster_keys32, dim3(nb_n), dim3(kThreads), 0, s2, rl_parent.p, N, id_bits, rl_keys32.p, rl_rank.p);
+        hipLaunchKernelGGL(k_rank_keys, dim3((N + kRankQ - 1) / kRankQ, (N + kRankStretch - 1) / kRankStretch), dim3(kRankThreads), 0, s2,
+                           rl_keys32.p, N, rl_rank.p);
+        if (forked) {   // (a genome's rank among the keys IS its internal id: all the bucket emission of tile records needs)
+            RK_HIP(ctx, hipEventRecord(ctx->ev_inv, s2));
+            inv_recorded = true;
+        }
+        hipLaunchKernelGGL(k_order_from_rank, dim3(nb_n), dim3(kThreads), 0, s2, rl_rank.p, N, src.d_off, src.d_sizes, idx->d_orig, idx->d_sizes);
+        hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
+        inv = rl_rank.p;   // (a genome's rank among the keys IS its internal id)
+    } else {
+        RK_HIP(ctx, rl_keys.alloc(N));
+        RK_HIP(ctx, rl_keys_sorted.alloc(N));
+        RK_HIP(ctx, rl_inv.alloc(N));
+        hipLaunchKernelGGL(k_cluster_keys, dim3(nb_n), dim3(kThreads), 0, s2, rl_parent.p, N, id_bits, rl_keys.p);
+        void *scratch = nullptr;
+        RK_TRY(rk_prim_sort_keys_u64(ctx, rl_keys.p, rl_keys_sorted.p, N, 0, (unsigned)(2 * id_bits), s2, &scratch));
+        rl_tmp.p = static_cast<char *>(scratch);
+        hipLaunchKernelGGL(k_order_from_keys, dim3(nb_n), dim3(kThreads), 0, s2, rl_keys_sorted.p, N, id_bits, src.d_off, src.d_sizes, idx->d_orig, idx->d_sizes);
+        hipLaunchKernelGGL(k_invert_order, dim3(nb_n), dim3(kThreads), 0, s2, idx->d_orig, N, rl_inv.p);
+        if (forked) {   // (the translation table is all the bucket emission of tile records needs: it need not wait for the offsets' scan)
+            RK_HIP(ctx, hipEventRecord(ctx->ev_inv, s2));
+            inv_recorded = true;
+        }
+        hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
+        inv = rl_inv.p;
+    }
+    if (want_tab) {
+        RK_HIP(ctx, rl_tab.alloc(N));
+        hipLaunchKernelGGL(k_emit_table, dim3(nb_n), dim3(kThreads), 0, s2, inv, idx->d_src_off, N, rl_tab.p);
+    }
+    if (idx->d_blk_min) hipLaunchKernelGGL(k_blk_min_sizes, dim3(blocks_for(b.p.n_blocks)), dim3(kThreads), 0, s2, idx->d_sizes, N, b.p.n_blocks, idx->d_blk_min);
+    idx->relabeled = true;
+    RK_HIP(ctx, hipGetLastError());
+    if (forked) {
+        RK_HIP(ctx, hipEventRecord(ctx->ev_join, s2));
+        joined = false;
+    }
+    return RK_OK;
+}
+int Renumbering::enqueue_identity()   // no renumbering: the caller's order, on the context's stream
+{
+    rk_index *idx = b.idx;
+    const uint32_t N = b.p.N;
+    hipLaunchKernelGGL(k_iota, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, b.st, N, idx->d_orig);
+    if (b.src.d_sizes) {
+        RK_HIP(b.ctx, hipMemcpyAsync(idx->d_sizes, b.src.d_sizes, (size_t)N * 4, hipMemcpyDeviceToDevice, b.st));
+        hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, b.st, idx->d_sizes, N, idx->d_src_off);
+    } else {
+        hipLaunchKernelGGL(k_sizes, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, b.st, b.src.d_off, N, idx->d_sizes, idx->d_src_off);
+    }
+    if (idx->d_blk_min) hipLaunchKernelGGL(k_blk_min_sizes, dim3(blocks_for(b.p.n_blocks)), dim3(kThreads), 0, b.st, idx->d_sizes, N, b.p.n_blocks, idx->d_blk_min);
+    return RK_OK;
+}
+
+// ---- fast path: two-level bucket sort, second level and all emission in LDS (rk_index_fast.inc) -----------------
+// the temporaries of one attempt
+struct AttemptBufs {
+    DevBuf<uint32_t> chunk_first, matrix, total, bstart, ucount, ubase, tmp_uhash, tmp_upos, n_open, n_cov, big_list;
+    DevBuf<unsigned long long> keys, mid, tmp_uhash64, zeroed;
+    DevBuf<uint2> self_raw;
+    DevBuf<uint3> t_rec;   // the unsorted tile records (64 regions); a shard's: grouped by destination shard (they leave for the exchange unsorted)
+    TileSortBufs sort;
+    ZeroedLayout z;
+    explicit AttemptBufs(rk_ctx *c)
+        : chunk_first(c), matrix(c), total(c), bstart(c), ucount(c), ubase(c), tmp_uhash(c), tmp_upos(c), n_open(c), n_cov(c), big_list(c), keys(c), mid(c),
+          tmp_uhash64(c), zeroed(c), self_raw(c), t_rec(c), sort(c) {}
+};
+inline size_t part_lds_bytes(uint32_t nb) { return (size_t)nb * 4 + 2 * kStageGenomes * 8; }   // bucket counters + the chunk's genome bounds
+
+// allocates an attempt's buffers, lays out `zeroed` and zeroes it (k_chunk_first, the first launch)
+int begin_attempt(const BuildCtx &b, const AttemptPlan &a, AttemptBufs &m)
+{
+    rk_ctx *ctx = b.ctx;
+    const BuildPlan &p = b.p;
+    const size_t nb1 = (size_t)a.nb + 1;
+    RK_HIP(ctx, m.chunk_first.alloc((size_t)a.n_chunks + 1));
+    RK_HIP(ctx, m.matrix.alloc((size_t)a.part_chunks * a.nb));
+    RK_HIP(ctx, m.total.alloc(a.nb));
+    RK_HIP(ctx, m.bstart.alloc(nb1 * a.passes));   // (per pass: the list heads of a pass are placed while the next one partitions)
+    RK_HIP(ctx, m.ucount.alloc(nb1 * a.passes));
+    RK_HIP(ctx, m.ubase.alloc(nb1 * a.passes));
+    if (p.wide) RK_HIP(ctx, m.tmp_uhash64.alloc(p.H_el));
+    else RK_HIP(ctx, m.tmp_uhash.alloc(p.H_el));
+    RK_HIP(ctx, m.tmp_upos.alloc(p.H_el));
+    RK_HIP(ctx, m.keys.alloc(a.keys_cap));
+    if (a.tiles_mode) RK_HIP(ctx, m.t_rec.alloc(a.rec_cap));
+    if (a.sort_here) RK_TRY(m.sort.alloc(ctx, p.n_blocks, a.rec_cap, std::min<uint64_t>(a.rec_cap, (uint64_t)p.n_blocks * (p.n_blocks + 1) / 2)));
+    if (!a.tiles_mode) {
+        RK_HIP(ctx, m.self_raw.alloc(p.H));
+        RK_HIP(ctx, m.n_open.alloc((size_t)p.N + 1));
+        RK_HIP(ctx, m.n_cov.alloc((size_t)p.N + 1));
+    }
+    m.z = ZeroedLayout::of_build(a.passes, a.part2, a.small_wgs, a.nb, a.n_chunks, a.sort_here, p.n_blocks);
+    RK_HIP(ctx, m.zeroed.alloc(m.z.z_end));
+    m.z.base = m.zeroed.p;
+    const size_t part_lds = part_lds_bytes(a.nb);
+    if (part_lds > 48 * 1024) {
+        RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_hist<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
+        RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_scatter<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
+        RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_hist<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
+        RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_scatter<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
+    }
+    // (from keys: no chunk walks the sketches -- the launch only zeroes, and chunk_first[0] is all it writes)
+    hipLaunchKernelGGL(k_chunk_first, dim3(blocks_for(std::max<uint64_t>((uint64_t)a.n_chunks + 1, m.z.z_end))), dim3(kThreads), 0, b.st, b.src.d_off, p.N,
+                       p.from_keys ? 0u : a.n_chunks, m.chunk_first.p, m.zeroed.p, (uint32_t)m.z.z_end);
+    if (a.part2) RK_HIP(ctx, m.mid.alloc(a.keys_cap));
+    if (a.big_ok) {
+        RK_HIP(ctx, m.big_list.alloc((size_t)a.nb * a.passes));
+        RK_HIP(ctx, hipFuncSetAttribute((const void *)k_bucket_heavy<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)heavy_lds_bytes(p.n_blocks)));
+    }
+    return RK_OK;
+}
+
+// what the kernels that walk the sketches see of an attempt (range_id: per pass)
+FastArgs fast_args(const BuildCtx &b, const AttemptPlan &a)
+{
+    const BuildPlan &p = b.p;
+    FastArgs fa;
+    fa.hashes = p.from_keys ? nullptr : p.wide ? (const void *)b.src.s->d_hashes64 : (const void *)b.src.s->d_hashes;
+    fa.off = b.src.d_off;
+    fa.orig = nullptr;           // the partition walks the sketches in the caller's order (see the renumbering above)
+    fa.off_new = b.src.d_off;
+    fa.n_genomes = p.N;
+    fa.H = p.H_el;
+    fa.hash_bits = p.hash_bits;
+    fa.low_bits = p.low_bits;
+    fa.gb = p.gb;
+    fa.rb = a.rb;
+    fa.xcd_map = b.k.xcd_map;
+    fa.nb = a.nb;
+    fa.n_chunks = a.n_chunks;
+    fa.range_bits = a.range_bits;
+    fa.range_id = 0;
+    fa.keys_cap = a.keys_cap;
+    fa.filtered = nullptr;
+    fa.n_filtered = nullptr;
+    return fa;
+}
+
+// one pass's partition: filter -> hist -> colscan -> starts -> coarse + fine, or scatter.  The pass's keys lie in m.keys, bucket by bucket.
+int launch_partition_pass(const BuildCtx &b, const AttemptPlan &a, AttemptBufs &m, FastArgs fa, uint32_t pass)
+{
+    rk_ctx *ctx = b.ctx;
+    const BuildPlan &p = b.p;
+    hipStream_t st = b.st;
+    BuildResult *const fres = m.z.res();
+    uint32_t *const bstart_p = m.bstart.p + ((size_t)a.nb + 1) * pass;
+    const size_t part_lds = part_lds_bytes(a.nb);
+    fa.range_id = (p.shard_id << p.pass_bits) | pass;
+    FastArgs pa = fa;   // what the partition kernels of this pass see
+    if (a.use_filter) {
+        unsigned long long *const n_filt = m.z.n_filtered(pass);
+        pa.filtered = m.keys.p;
+        if (p.from_keys && a.passes == 1) {
+            // the caller's keys are never written: one pass partitions them as they are (k_part_fine writes `keys`, ours), several
+            // passes filter them into `keys` first -- a second attempt (tile records beyond their buffer) starts from intact keys
+            hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(64), 0, st, n_filt, (unsigned long long)p.H_el);
+            pa.filtered = b.src.keys;
+        } else if (p.from_keys) {
+            const uint64_t per_wg = (uint64_t)kKeysFilterThreads * kKeysFilterSteps;
+            if (p.H_el)
+                hipLaunchKernelGGL(k_keys_pass_filter, dim3((unsigned)((p.H_el + per_wg - 1) / per_wg)), dim3(kKeysFilterThreads), 0, st, b.src.keys, p.H_el, p.gb,
+                                   p.hash_bits - p.shard_bits, p.pass_bits, pass, m.keys.p, n_filt, (unsigned long long)a.keys_cap, fres);
+        } else {
+            // (the filtered elements lie in `keys`: the coarse pass reads them and writes `mid`, the fine pass writes `keys` again)
+            RK_TRY(with_hash_type(p.wide, [&](auto ht) -> int {
+                hipLaunchKernelGGL(k_range_filter<decltype(ht)>, dim3(fa.n_chunks * kFilterSplit), dim3(kFilterThreads), 0, st, fa, m.chunk_first.p, m.keys.p, n_filt, fres);
+                return RK_OK;
+            }));
+            // (tried: starting the renumbering BEHIND the filter -- then k_part_hist takes 0.84 ms instead of 0.16 beside
+            // k_minhash_insert: whatever runs beside that kernel pays its 0.55 ms)
+        }
+        pa.n_filtered = n_filt;
+        pa.hash_bits = p.eff_bits;
+        pa.range_bits = 0;
+        pa.range_id = 0;
+    }
+    RK_TRY(with_hash_type(p.wide, [&](auto ht) -> int {
+        hipLaunchKernelGGL(k_part_hist<decltype(ht)>, dim3(a.part_chunks), dim3(kPartThreads), part_lds, st, pa, m.chunk_first.p, m.matrix.p, fres);
+        return RK_OK;
+    }));
+    hipLaunchKernelGGL(k_part_colscan, dim3((a.nb + 63) / 64), dim3(1024), 0, st, m.matrix.p, a.part_chunks, a.nb, m.total.p);
+    hipLaunchKernelGGL(k_part_starts, dim3(1), dim3(1024), 0, st, m.total.p, a.nb, bstart_p, fres, m.z.pass_base() + pass, (unsigned long long)a.keys_cap,
+                       a.big_ok ? m.big_list.p + (size_t)a.nb * pass : nullptr, m.z.n_big(pass));
+    // the partition itself: two coalescing passes (rk_index_fast.inc), or one scattering pass
+    return with_hash_type(p.wide, [&](auto ht) -> int {
+        using HT = decltype(ht);
+        if (!a.part2) {
+            hipLaunchKernelGGL(k_part_scatter<HT>, dim3(fa.n_chunks), dim3(kPartThreads), part_lds, st, fa, m.chunk_first.p, m.matrix.p, bstart_p, m.keys.p, fres);
+            return RK_OK;
+        }
+        auto coarse = [&](auto t, unsigned grid) -> int {
+            constexpr uint32_t TT = decltype(t)::value;
+            RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_coarse<TT, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part2_lds(TT)));
+            hipLaunchKernelGGL((k_part_coarse<TT, HT>), dim3(grid), dim3(TT), part2_lds(TT), st, pa, m.chunk_first.p, m.matrix.p, bstart_p, m.z.seg_taken(pass), m.mid.p, fres);
+            return RK_OK;
+        };
+        RK_TRY(a.small_wgs ? coarse(Threads<256>(), a.part_chunks * 4) : coarse(Threads<1024>(), a.part_chunks));
+        hipLaunchKernelGGL(k_part_fine, dim3(a.nb >> kFineBits, 16), dim3(kPartThreads), 0, st, pa, bstart_p, m.mid.p, m.keys.p, m.z.fine_cursor(pass), fres);
+        return RK_OK;
+    });
+}
+
+// one pass's emission out of the sorted buckets: tile or slice records (+ the heavy buckets), then the list heads
+int launch_emit_pass(const BuildCtx &b, Renumbering &rn, const AttemptPlan &a, AttemptBufs &m, uint32_t pass)
+{
+    rk_ctx *ctx = b.ctx;
+    const BuildPlan &p = b.p;
+    rk_index *idx = b.idx;
+    hipStream_t st = b.st;
+    const size_t nb1 = (size_t)a.nb + 1;
+    uint32_t *const bstart_p = m.bstart.p + nb1 * pass, *const ucount_p = m.ucount.p + nb1 * pass, *const ubase_p = m.ubase.p + nb1 * pass;
+    BuildResult *const fres = m.z.res();
+    unsigned long long *const pass_base = m.z.pass_base() + pass;
+    auto fill_common = [&](auto &ea) {   // what EmitArgs and TileEmitArgs share
+        ea.keys = m.keys.p;
+        ea.bstart = bstart_p;
+        ea.inv = rn.inv;
+        ea.low_bits = p.low_bits;
+        ea.gb = p.gb;
+        ea.rb = a.rb;
+        ea.nb = a.nb;
+        ea.postings = idx->d_postings;
+        ea.tmp_uhash = m.tmp_uhash.p;
+        ea.tmp_uhash64 = p.wide ? m.tmp_uhash64.p : nullptr;
+        ea.tmp_upos = m.tmp_upos.p;
+        ea.ucount = ucount_p;
+        ea.xcd_map = b.k.xcd_map;
+        ea.debug = b.k.debug;
+    };
+    if (b.k.debug) {  // developer ablations leave stages out: whatever they do not write must still be harmless downstream
+        RK_HIP(ctx, hipMemsetAsync(ucount_p, 0, (size_t)a.nb * 4, st));
+        if (!a.tiles_mode) RK_HIP(ctx, hipMemsetAsync(m.self_raw.p, 0, p.H * sizeof(uint2), st));
+        RK_HIP(ctx, hipMemsetAsync(m.tmp_upos.p, 0, p.H_el * 4, st));
+    }
+    if (a.tiles_mode) {
+        TileEmitArgs ea;
+        fill_common(ea);
+        ea.rec = m.t_rec.p;
+        ea.region_cap = a.region_cap;
+        ea.pass_base = pass_base;
+        ea.hash_base = a.range_bits ? ((unsigned long long)((p.shard_id << p.pass_bits) | pass) << p.eff_bits) : 0ULL;
+        ea.n_dest = p.n_shards;
+        ea.stop = a.range_bits ? fres : nullptr;
+        ea.big_ok = a.big_ok ? 1 : 0;
+        ea.big_list = a.big_ok ? m.big_list.p + (size_t)a.nb * pass : nullptr;
+        ea.n_big = m.z.n_big(pass);
+        ea.stop_rw = fres;
+        ea.tres = m.z.tile_res();
+        RK_TRY(with_emit_shape(b.k.emit_t, a.narrow, [&](auto t, auto key) -> int {
+            hipLaunchKernelGGL((k_bucket_emit_tiles<decltype(t)::value, decltype(key)>), dim3(a.nb), dim3(decltype(t)::value), 0, st, ea);
+            return RK_OK;
+        }));
+        if (a.big_ok) {
+            HeavyArgs ha;
+            ha.e = ea;
+            ha.big_list = ea.big_list;
+            ha.n_big = ea.n_big;
+            ha.next = m.z.heavy_next(pass);
+            ha.n_blocks = p.n_blocks;
+            hipLaunchKernelGGL(k_bucket_heavy<1024>, dim3((unsigned)std::max(1, ctx->num_cu)), dim3(1024), heavy_lds_bytes(p.n_blocks), st, ha);
+        }
+    } else {
+        EmitArgs ea;
+        fill_common(ea);
+        ea.off_new = idx->d_src_off;
+        ea.tab = rn.inv ? rn.rl_tab.p : nullptr;
+        ea.self_raw = m.self_raw.p;
+        ea.res = fres;
+        RK_TRY(with_emit_shape(b.k.emit_t, a.narrow, [&](auto t, auto key) -> int {
+            hipLaunchKernelGGL((k_bucket_emit<decltype(t)::value, decltype(key)>), dim3(a.nb), dim3(decltype(t)::value), 0, st, ea);
+            return RK_OK;
+        }));
+    }
+    // the list heads (scan + placement) hang on the emission alone: they go to the second stream (one pass) and run beside
+    // the rows / the tile sort; with several passes they stay in line (the next pass's partition is the bigger job)
+    hipStream_t sh = st;
+    const bool heads_aside = rn.forked && a.passes == 1;
+    if (heads_aside) RK_TRY(rn.branch_heads(&sh));
+    hipLaunchKernelGGL(k_heads_scan, dim3(1), dim3(1024), 0, sh, ucount_p, a.nb, ubase_p, fres);
+    RK_TRY(with_key_type(!p.wide, [&](auto h) -> int {   // (the list heads' hashes: 32 bits, or the 64-bit layout)
+        using HT = decltype(h);
+        hipLaunchKernelGGL(k_heads_place<HT>, dim3(a.nb), dim3(kThreads), 0, sh, p.wide ? (const HT *)m.tmp_uhash64.p : (const HT *)m.tmp_uhash.p, m.tmp_upos.p, bstart_p,
+                           ucount_p, ubase_p, a.nb, pass_base, p.wide ? (HT *)idx->d_uhash64 : (HT *)idx->d_uhash, idx->d_upos);
+        return RK_OK;
+    }));
+    if (heads_aside) RK_TRY(rn.heads_branched());
+    return RK_OK;
+}
+
+// (developer output: what k_bucket_heavy had to take)
+int report_heavy(const BuildCtx &b, const AttemptPlan &a, const AttemptBufs &m)
+{
+    rk_ctx *ctx = b.ctx;
+    const size_t nb1 = (size_t)a.nb + 1;
+    std::vector<uint32_t> nbig(a.passes), bs(nb1 * a.passes);
+    RK_TRY(rk_read_back(ctx, nbig.data(), m.z.n_big(0), (size_t)a.passes * 4, b.st));
+    RK_TRY(rk_read_back(ctx, bs.data(), m.bstart.p, bs.size() * 4, b.st));
+    for (uint32_t pass = 0; pass < a.passes; pass++) {
+        std::vector<uint32_t> bl(nbig[pass]);
+        if (nbig[pass]) RK_TRY(rk_read_back(ctx, bl.data(), m.big_list.p + (size_t)a.nb * pass, bl.size() * 4, b.st));
+        unsigned long long keys_in = 0, biggest = 0;
+        for (uint32_t bk : bl) {
+            const unsigned long long n = bs[nb1 * pass + bk + 1] - bs[nb1 * pass + bk];
+            keys_in += n;
+            biggest = std::max(biggest, n);
+        }
+        fprintf(stderr, "[rk] index build pass %u: %u of %u buckets for k_bucket_heavy, %llu keys, biggest %llu\n", pass, nbig[pass], a.nb, keys_in, biggest);
+    }
+    return RK_OK;
+}
+
+// How an attempt of the bucket sort ended.
+struct AttemptOutcome {
+    enum What {
+        Built,
+        RetryKeysCap,       // a range pass holds `need` keys, more than estimated: once more with buffers for them
+        RetryRecCap,        // the tile records did not fit: once more with room for the `need` the attempt counted
+        FallBackToSlices,   // ... beyond the budget of tile records: slice records after all
+        Refused             // the kernels raised `flags`, or (flags == 0) the tile records overflowed with no way on: the general path decides
+    } what;
+    unsigned long long need, flags;
+    BuildResult r;
+    TileResult tr;
+};
+
+// (the tile records of an attempt did not fit their buffer -- wide species, lists scattered over many blocks --: the
+// attempt has counted what it needs, and the next one gets exactly that, within a budget of 6 records per posting; beyond
+// it the index is built with slice records after all, where those can be had)
+void after_tile_overflow(const BuildCtx &b, const RetryState &rs, AttemptOutcome *o)
+{
+    unsigned long long worst = 0;
+    for (uint32_t q = 0; q < kRecRegions; q++) worst = std::max<unsigned long long>(worst, o->tr.rec_count[q]);
+    o->need = (worst + worst / 16 + 1024) * kRecRegions;
+    if (!rs.rec_cap_retry && o->need <= 6 * b.p.H_el_shard + (1u << 22) && !b.ctx->sw_tile_rec_cap) o->what = AttemptOutcome::RetryRecCap;   // (RK_TILE_REC_CAP: a test forces the fallback)
+    else o->what = b.p.slices_ok ? AttemptOutcome::FallBackToSlices : AttemptOutcome::Refused;
+}
+
+// One attempt of the bucket sort: allocate, partition and emit pass by pass, the tile sort or the rows, ONE synchronising read-back.
+int bucket_sort_attempt(const BuildCtx &b, Renumbering &rn, const RetryState &rs, AttemptOutcome *o)
+{
+    rk_ctx *ctx = b.ctx;
+    const BuildPlan &p = b.p;
+    rk_index *idx = b.idx;
+    hipStream_t st = b.st;
+    AttemptPlan a;
+    RK_TRY(plan_attempt(ctx, p, b.k, rs, &a));
+    if (!a.tiles_mode) RK_TRY(alloc_slices(ctx, idx, p));
+    AttemptBufs m(ctx);
+    RK_TRY(begin_attempt(b, a, m));
+    const FastArgs fa = fast_args(b, a);
+    for (uint32_t pass = 0; pass < a.passes; pass++) {
+        RK_TRY(launch_partition_pass(b, a, m, fa, pass));
+        if (pass == 0) {
+            RK_TRY(rn.enqueue(!a.tiles_mode));   // (behind the partition's launches in the host's queue, beside them on the device)
+            // the internal order is needed from here on: the translation table alone for tile records, everything for slice records
+            if (a.tiles_mode) RK_TRY(rn.wait_inv());
+            else {
+                RK_TRY(rn.join());
+                RK_TRY(rn.ensure_table());
+            }
+        }
+        RK_TRY(launch_emit_pass(b, rn, a, m, pass));
+    }
+    BuildResult *const fres = m.z.res();
+    if (a.sort_here) {
+        RK_TRY(launch_tile_sort(ctx, m.sort.args(m.t_rec.p, a.region_cap, p.n_blocks, idx->d_blk_min, m.z), st, [&]() { return rn.join(); }));
+    } else if (!a.tiles_mode) {
+        const unsigned wave_blocks = (p.N + 3) / 4;  // 4 waves (genomes) per 256-thread workgroup
+        hipLaunchKernelGGL(k_row_counts2, dim3(wave_blocks), dim3(kThreads), 0, st, idx->d_src_off, p.N, m.self_raw.p, m.n_open.p, m.n_cov.p);
+        hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(1024), 0, st, m.n_open.p, m.n_cov.p, p.N, idx->d_self_off, idx->d_self_split, fres);
+        hipLaunchKernelGGL(k_row_place2, dim3(wave_blocks), dim3(kThreads), 0, st, idx->d_src_off, p.N, m.self_raw.p, idx->d_self_off,
+                           idx->d_self_split, idx->d_selfrange);
+    }
+    RK_HIP(ctx, hipGetLastError());
+    RK_TRY(rn.join());
+    unsigned long long n_postings = 0;
+    {   // the one synchronisation of the build: both result records (and the postings of all passes) in one read-back
+        struct { BuildResult r; TileResult t; unsigned long long pass_base[257]; } both;
+        static_assert(sizeof(BuildResult) % 8 == 0 && offsetof(decltype(both), pass_base) == sizeof(BuildResult) + sizeof(TileResult), "the records lie back to back");
+        RK_TRY(rk_read_back(ctx, &both, fres, sizeof(BuildResult) + sizeof(TileResult) + ((size_t)a.passes + 1) * 8, st));
+        o->r = both.r;
+        o->tr = both.t;
+        n_postings = both.pass_base[a.passes];
+    }
+    const BuildResult &r = o->r;
+    const TileResult &tr = o->tr;
+    if (ctx->sw_dist_debug && a.big_ok) RK_TRY(report_heavy(b, a, m));
+    if (ctx->sw_dist_debug)
+        fprintf(stderr, "[rk] index build: fast path flags %llu (B %d, low bits %d, genome bits %d, position bits %d; shard %u of %u, %u pass(es), %llu postings)%s\n",
+                r.flags, p.B, p.low_bits, p.gb, p.rb, p.shard_id, p.n_shards, a.passes, n_postings, a.tiles_mode ? (tr.overflow ? ", tile records overflowed" : ", tile records") : "");
+    o->need = 0;
+    o->flags = r.flags;
+    if ((r.flags & kFastOverflow) && a.use_filter && !p.from_keys && !rs.keys_cap_retry) {
+        // a range holds more keys than estimated: every pass's filter has counted what it needs -- once more with exactly that
+        std::vector<unsigned long long> asked(a.passes);
+        RK_TRY(rk_read_back(ctx, asked.data(), m.z.n_filtered(0), (size_t)a.passes * 8, st));
+        o->need = *std::max_element(asked.begin(), asked.end());
+        if (o->need > a.keys_cap && o->need <= p.H) {
+            if (ctx->sw_dist_debug) fprintf(stderr, "[rk] index build: a range pass holds %llu keys (buffers for %llu): again\n", o->need, (unsigned long long)a.keys_cap);
+            o->what = AttemptOutcome::RetryKeysCap;
+            return RK_OK;
+        }
+    }
+    if (r.flags) {   // a bucket beyond the LDS sort, a pass beyond its key buffer, or a hash outside the hash space
+        o->what = AttemptOutcome::Refused;
+        return RK_OK;
+    }
+    if (a.tiles_mode && tr.overflow) {
+        after_tile_overflow(b, rs, o);
+        return RK_OK;
+    }
+    o->what = AttemptOutcome::Built;
+    if (p.range_bits) idx->H = n_postings;   // (a shard: the postings of ITS hash range; all passes of one shard: == H)
+    if (a.sort_here) {
+        m.sort.hand_over(idx, tr);
+        if (ctx->sw_dist_debug)
+            fprintf(stderr, "[rk] tiles from the build: %llu tiles, %llu records in %llu slots (capacity %llu), biggest tile %llu\n", tr.n_tiles, tr.n_records,
+                    tr.n_slots, (unsigned long long)a.rec_cap, tr.max_records);
+    }
+    if (a.tiles_mode && p.n_shards > 1) {   // the shard's records wait for the exchange (rk_index_shard_records / _pack)
+        idx->d_shard_rec = m.t_rec.release();
+        idx->shard_region_cap = a.region_cap;
+        idx->n_shards = p.n_shards;
+        idx->shard_id = p.shard_id;
+        for (uint32_t q = 0; q < kRecRegions; q++) idx->shard_rec_count[q] = tr.rec_count[q];
+    }
+    return RK_OK;
+}
+
+// ---- general path: device-wide stable radix sort of (hash, source element) -------------------------------------
+int build_general(const BuildCtx &b, BuildResult *res, BuildResult *r)
+{
+    rk_ctx *ctx = b.ctx;
+    rk_index *idx = b.idx;
+    const rk_sketches *s = b.src.s;
+    hipStream_t st = b.st;
+    const uint64_t H = b.p.H;
+    const uint32_t N = b.p.N;
+    const bool no_self = b.p.no_self;
+    const unsigned wave_blocks = (N + 3) / 4;  // 4 waves (genomes) per 256-thread workgroup
+    RK_HIP(ctx, hipMemsetAsync(res, 0, sizeof(BuildResult), st));
+    const void *src_hashes = idx->wide ? (const void *)s->d_hashes64 : (const void *)s->d_hashes;
+    const uint64_t *src_off = s->d_off;
+    DevBuf<char> perm_hashes(ctx);
+    if (idx->relabeled) {  // the sketches in internal order
+        RK_HIP(ctx, perm_hashes.alloc(H * (idx->wide ? 8 : 4)));
+        RK_TRY(with_hash_type(idx->wide, [&](auto ht) -> int {
+            using HT = decltype(ht);
+            hipLaunchKernelGGL(k_gather_sketches<HT>, dim3(wave_blocks), dim3(kThreads), 0, st, (const HT *)src_hashes, s->d_off, idx->d_orig,
+                               idx->d_src_off, N, (HT *)perm_hashes.p);
+            return RK_OK;
+        }));
+        src_hashes = perm_hashes.p;
+        src_off = idx->d_src_off;
+    }
+    DevBuf<uint32_t> iota(ctx), sorted_e(ctx), flags(ctx), gid(ctx), n_open(ctx), n_cov(ctx);
+    DevBuf<char> keys_sorted(ctx);
+    DevBuf<uint2> self_raw(ctx);
+    RK_HIP(ctx, iota.alloc(H));
+    RK_HIP(ctx, sorted_e.alloc(H));
+    RK_HIP(ctx, flags.alloc(H));
+    RK_HIP(ctx, gid.alloc(H));
+    RK_HIP(ctx, self_raw.alloc(no_self ? 1 : H));
+    RK_HIP(ctx, n_open.alloc((size_t)N + 1));
+    RK_HIP(ctx, n_cov.alloc((size_t)N + 1));
+    RK_HIP(ctx, keys_sorted.alloc(H * (idx->wide ? 8 : 4)));
+    hipLaunchKernelGGL(k_fill_gid, dim3(wave_blocks), dim3(kThreads), 0, st, src_off, N, gid.p, iota.p);
+    uint32_t *gidx = iota.p;  // (after the scan) 1-based group number of each sorted position
+    // stable LSD radix sort by hash; values = source element index (genome-major), so equal hashes stay in
+    // ascending genome order == hashMapId[hash].push_back(i) for i ascending (src/sketch.cpp:979-985)
+    if (idx->wide) RK_TRY(rk_prim_sort_pairs_u64_u32(ctx, (const uint64_t *)src_hashes, (uint64_t *)keys_sorted.p, iota.p, sorted_e.p, H, (unsigned)b.p.hash_bits, st));
+    else RK_TRY(rk_prim_sort_pairs_u32_u32(ctx, (const uint32_t *)src_hashes, (uint32_t *)keys_sorted.p, iota.p, sorted_e.p, H, (unsigned)b.p.hash_bits, st));
+    RK_TRY(with_hash_type(idx->wide, [&](auto ht) -> int {
+        using HT = decltype(ht);
+        hipLaunchKernelGGL(k_head_flags<HT>, dim3(blocks_for(H)), dim3(kThreads), 0, st, (const HT *)keys_sorted.p, H, flags.p);
+        RK_TRY(rk_prim_inclusive_scan_u32(ctx, flags.p, iota.p, H, st));
+        hipLaunchKernelGGL(k_scatter_heads<HT>, dim3(blocks_for(H)), dim3(kThreads), 0, st, (const HT *)keys_sorted.p, gidx, H,
+                           idx->wide ? (HT *)idx->d_uhash64 : (HT *)idx->d_uhash, idx->d_upos, res);
+        return RK_OK;
+    }));
+    if (no_self)
+        hipLaunchKernelGGL((k_postings_selfrange<false, true>), dim3(blocks_for(H)), dim3(kThreads), 0, st, sorted_e.p, gidx,
+                           idx->d_upos, gid.p, H, idx->d_postings, self_raw.p, res);
+    else if (s->is_set)
+        hipLaunchKernelGGL(k_postings_selfrange<false>, dim3(blocks_for(H)), dim3(kThreads), 0, st, sorted_e.p, gidx,
+                           idx->d_upos, gid.p, H, idx->d_postings, self_raw.p, res);
+    else
+        hipLaunchKernelGGL(k_postings_selfrange<true>, dim3(blocks_for(H)), dim3(kThreads), 0, st, sorted_e.p, gidx,
+                           idx->d_upos, gid.p, H, idx->d_postings, self_raw.p, res);
+    if (!no_self) {
+        // drop the empty slices (26 % of the elements at 10,000 genomes), covered slices last in their row
+        hipLaunchKernelGGL(k_row_counts, dim3(wave_blocks), dim3(kThreads), 0, st, src_off, N, self_raw.p, n_open.p, n_cov.p);
+        hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(1024), 0, st, n_open.p, n_cov.p, N, idx->d_self_off, idx->d_self_split, res);
+        hipLaunchKernelGGL(k_row_place, dim3(wave_blocks), dim3(kThreads), 0, st, src_off, N, self_raw.p,
+                           idx->d_self_off, idx->d_self_split, idx->d_postings, s->is_set, idx->d_selfrange);
+    }
+    RK_HIP(ctx, hipGetLastError());
+    return rk_read_back(ctx, r, res, sizeof(*r), st);  // the one synchronisation of the build
+}
+// no postings at all: empty lists, empty rows
+int build_empty(const BuildCtx &b)
+{
+    RK_HIP(b.ctx, hipMemsetAsync(b.idx->d_upos, 0, 8, b.st));
+    if (!b.p.no_self) {
+        RK_HIP(b.ctx, hipMemsetAsync(b.idx->d_self_off, 0, ((size_t)b.p.N + 1) * 8, b.st));
+        RK_HIP(b.ctx, hipMemsetAsync(b.idx->d_self_split, 0, ((size_t)b.p.N + 1) * 8, b.st));
+    }
+    RK_HIP(b.ctx, hipStreamSynchronize(b.st));
+    return RK_OK;
+}
+
+int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out)
+{
+    if (!ctx || !out) return RK_ERR_ARG;
+    *out = nullptr;
+    const BuildKnobs k = read_knobs();
+    BuildPlan p;
+    RK_TRY(plan_build(ctx, src, hash_bits, shard_id, n_shards, k, &p));
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    rk_index *idx = new (std::nothrow) rk_index;
+    if (!idx) return RK_ERR_NOMEM;
+    idx->ctx = ctx;
+    idx->n_ref = p.N;
+    idx->H = p.H;
+    idx->hash_bits = hash_bits;
+    idx->wide = src.wide;
+    idx->max_src_size = idx->max_ref_size = src.max_size;
+    idx->min_ref_size = src.min_size;
+    struct Guard { rk_index *p; ~Guard() { if (p) rk_index_free(p); } } guard{idx};
+    RK_TRY(alloc_index_arrays(ctx, idx, p));
+    const BuildCtx b{ctx, src, p, k, idx, ctx->stream};
+    Renumbering rn(b);
+    RK_TRY(rn.mark_fork());
+    DevBuf<BuildResult> res(ctx);   // the general path's result record
+    RK_HIP(ctx, res.alloc(1));
+    if (ctx->sw_dist_debug && !p.fast_ok())
+        fprintf(stderr, "[rk] index build: general path (H %llu, wide %d, sets %d, B %d, low bits %d, genome bits %d, position bits %d)\n",
+                (unsigned long long)p.H, (int)idx->wide, (int)src.is_set, p.B, p.low_bits, p.gb, p.rb);
+
+    // the bucket sort: at most one retry with bigger key buffers, one with room for more tile records, then slice records
+    RetryState rs{p.tiles_mode};
+    AttemptOutcome o;
+    memset(&o, 0, sizeof o);
+    o.what = AttemptOutcome::Refused;
+    for (bool again = p.fast_ok(); again;) {
+        RK_TRY(bucket_sort_attempt(b, rn, rs, &o));
+        switch (o.what) {
+        case AttemptOutcome::RetryKeysCap: rs.keys_cap_retry = o.need + o.need / 64 + 65536; break;
+        case AttemptOutcome::RetryRecCap: rs.rec_cap_retry = o.need; break;
+        case AttemptOutcome::FallBackToSlices:
+            rs.tiles_mode = false;
+            drop_blk_min(ctx, idx);
+            break;
+        default: again = false;
+        }
+    }
+    const bool built = o.what == AttemptOutcome::Built;
+    if (!built && p.from_keys && (o.flags & kFastBadHash))
+        return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: a key outside the wire format (hash bits beyond the shard's range, or a genome id >= %u)", p.N);
+    if (!built && n_shards > 1)
+        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard: the bucket sort refused this collection (flags %s: a bucket or a pass beyond its "
+                                                "buffer, a hash outside the hash space, or tile records beyond their capacity)", o.tr.overflow ? "tile overflow" : "bucket / key overflow");
+    if (!built) {
+        if (idx->d_blk_min) drop_blk_min(ctx, idx);
+        RK_TRY(alloc_slices(ctx, idx, p));
+    }
+
+    RK_TRY(rn.enqueue(false));
+    RK_TRY(rn.join());
+    BuildResult r = built ? o.r : BuildResult{0, 0, 0, 0, 0};
+    if (!built && p.H) RK_TRY(build_general(b, res.p, &r));
+    else if (!p.H) RK_TRY(build_empty(b));
+    idx->U = r.U;
+    idx->n_self = r.n_self;
+    idx->slices_refused = p.no_self;
+    idx->ref_sets = src.is_set || r.dups == 0;
+    idx->built_fast = built;
+    if (built) {   // (the same rule as rk_dist.hip self_uses_tiles, which counts the records itself for an index built the general way)
+        idx->spread = r.flagged * 8 > r.n_self;
+        idx->spread_known = 1;
+    }
+    set_dir_shape(idx);
+    guard.p = nullptr;
+    *out = idx;
+    return RK_OK;
+}
+
 }  // namespace
 
-// prefix directory into the sorted distinct hashes: built on first use (64-bit hashes, hash spaces above 2^30)
 // ---- slice records on first use (an index built with tile records has none) ------------------------------------------
 // one thread per posting list: the slice record of every member, by posting position, as the bucket emission writes them
 // (class carried by the record: slice_class2).  A list longer than a compact record walks once; the compact ones are short.
@@ -788,6 +1610,7 @@ int rk_index_ensure_slices(rk_ctx *ctx, rk_index *idx, hipStream_t st)
     return RK_OK;
 }
 
+// prefix directory into the sorted distinct hashes: built on first use (64-bit hashes, hash spaces above 2^30)
 int rk_index_ensure_dir(rk_ctx *ctx, rk_index *idx, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(idx->lazy_mu);
@@ -914,7 +1737,6 @@ int rk_index_self_stats(const rk_index *cidx, uint64_t out[4])
     return RK_OK;
 }
 
-static int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out);
 
 // (a failing build may leave kernels in flight on both of the context's streams that still write into temporaries its DevBufs
 // have just returned to the pool: nothing may be handed out again before they are done)
@@ -943,777 +1765,6 @@ int rk_index_build_shard(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint3
     return settle_streams(ctx, index_build_impl(ctx, source_of(s), hash_bits, shard, n_shards, out));
 }
 
-static int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_t shard_id, uint32_t n_shards, rk_index **out)
-{
-    if (!ctx || !out) return RK_ERR_ARG;
-    *out = nullptr;
-    const rk_sketches *s = src.s;   // (null: a build from keys -- a shard of a sharded build, never the general path)
-    const bool from_keys = s == nullptr;
-    if (hash_bits < 1) return rk_fail(ctx, RK_ERR_ARG, "hash_bits must be positive");
-    if (hash_bits > 64) return rk_fail(ctx, RK_ERR_ARG, "hash_bits=%d", hash_bits);
-    if ((hash_bits > 32) != src.wide)
-        return rk_fail(ctx, RK_ERR_ARG, "hash_bits=%d does not match the sketches' %s-bit layout", hash_bits,
-                       src.wide ? "64" : "32");
-    const uint64_t H = src.total;
-    const uint32_t N = src.n;
-    // the elements the partition reads: the whole collection, or the shard's keys (arrays that scale with postings are sized by these)
-    const uint64_t H_el = from_keys ? src.n_keys : H;
-    // Bit 31 of a slice record tags its compact form, so posting offsets inside slice records stay below 2^31.  An index of
-    // 2^31-1 .. 2^32-2 postings (all of GenBank's bacteria at ~1,200 hashes each) is built WITHOUT slice records: its
-    // postings, list offsets and distinct hashes are complete (.dict / .index export, sparse self joins through the tile
-    // kernel, which reads the posting lists themselves); what needs slice records -- a dense report, sketches that repeat
-    // a hash -- is refused for it.  RK_INDEX_NO_SELF=1 builds any index that way (tests).
-    if (H >= 0xFFFFFFFFULL || N >= 0x7FFFFFFFu) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "more than 2^32-2 postings or 2^31-1 genomes");
-    const bool no_self = H >= 0x7FFFFFFFULL || ctx->sw_index_no_self;
-    if (no_self && !src.is_set)
-        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "an index of more than 2^31-1 postings needs set sketches (no hash twice in a genome)");
-    RK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    rk_index *idx = new (std::nothrow) rk_index;
-    if (!idx) return RK_ERR_NOMEM;
-    idx->ctx = ctx;
-    idx->n_ref = N;
-    idx->H = H;
-    idx->hash_bits = hash_bits;
-    idx->wide = src.wide;
-    idx->max_src_size = idx->max_ref_size = src.max_size;
-    idx->min_ref_size = src.min_size;
-    struct Guard { rk_index *p; ~Guard() { if (p) rk_index_free(p); } } guard{idx};
-
-    // distinct hashes: at most H, at most the hash space
-    const uint64_t Ucap = hash_bits < 40 ? std::min<uint64_t>(H_el, 1ULL << hash_bits) : H_el;
-    RK_TRY(pool_array(ctx, &idx->d_sizes, (size_t)N + 1));
-    RK_TRY(pool_array(ctx, &idx->d_src_off, (size_t)N + 1));
-    RK_TRY(pool_array(ctx, &idx->d_postings, H_el + 8));   // (padded: the kernels read up to eight postings from any list start)
-    if (idx->wide) RK_TRY(pool_array(ctx, &idx->d_uhash64, Ucap + 1));
-    else RK_TRY(pool_array(ctx, &idx->d_uhash, Ucap + 1));
-    RK_TRY(pool_array(ctx, &idx->d_upos, Ucap + 2));
-    auto alloc_slices = [&]() -> int {   // (not for an index whose build emits tile records: rk_index_ensure_slices, on first use)
-        if (no_self || idx->d_selfrange) return RK_OK;
-        RK_TRY(pool_array(ctx, &idx->d_selfrange, H + 1));
-        RK_TRY(pool_array(ctx, &idx->d_self_off, (size_t)N + 1));
-        RK_TRY(pool_array(ctx, &idx->d_self_split, (size_t)N + 1));
-        return RK_OK;
-    };
-    RK_TRY(pool_array(ctx, &idx->d_orig, (size_t)N + 1));
-    // ---- which build: the bucket sort (rk_index_fast.inc) when the key fields fit, and then with TILE records as its product
-    // (rk_index_tiles.inc) from RK_DIST_TILES_MIN_GENOMES genomes on -- the self join runs on rk_tile_kernel from its first launch --,
-    // with slice records (rk_near_kernel, rk_dist_kernel) below
-    // (round 5) The hash space is covered in RANGES (its top bits): one range per shard of a multi-GPU build
-    // (rk_index_build_shard: this call builds the lists of ITS range only), and inside a shard as many passes as it takes to keep
-    // a pass's keys within 2^15 buckets of ~1,536 -- a collection of any size takes the bucket sort, pass after pass on one
-    // stream, the postings of a pass behind those of the pass before.
-    int shard_bits = 0, pass_bits = 0;
-    while ((1u << shard_bits) < n_shards) shard_bits++;
-    const uint64_t H_shard = H / n_shards + (n_shards > 1 ? H / (8ULL * n_shards) + 4096 : 0);   // (estimate: the hashes are spread evenly)
-    // (a pass may fill its 2^15 buckets to ~2,600 keys on average: the LDS sort holds 4,096, and every extra pass reads all hashes again)
-    while (pass_bits < 8 && (H_shard >> pass_bits) > (2600ULL << kMaxBucketBits)) pass_bits++;
-    if (getenv("RK_INDEX_PASS_BITS")) pass_bits = std::max(0, std::min(7, atoi(getenv("RK_INDEX_PASS_BITS"))));   // (tests: several passes over a small collection)
-    const int range_bits = shard_bits + pass_bits;
-    const uint32_t n_pass = 1u << pass_bits;
-    const int eff_bits = hash_bits - range_bits;   // hash bits inside a range
-    const uint64_t H_pass = range_bits ? (H_shard >> pass_bits) : H;
-    int B = 1, gb = 1, rb = 1;
-    // (at most kMaxBucketBits: a bigger collection gets fuller buckets, up to the LDS capacity -- beyond it the kernels raise the overflow flag)
-    const uint64_t bucket_target = getenv("RK_INDEX_BUCKET_TARGET") ? std::max(64, atoi(getenv("RK_INDEX_BUCKET_TARGET"))) : kBucketTarget;
-    while (B < eff_bits && B < kMaxBucketBits && ((H_pass + bucket_target - 1) / bucket_target) > (1ULL << B)) B++;
-    if (from_keys) B = std::max(B, std::min(7, eff_bits));   // (the keys are a filtered source: the two-pass partition, >= 128 buckets)
-    while ((1ULL << gb) < N) gb++;
-    while ((1ULL << rb) < src.max_size) rb++;
-    const int low_bits = eff_bits - B;
-    // (64-bit hashes -- use64, e.g. K12 L3: 36 bits -- take the same path as long as the key fields fit: the kernels that read
-    // the sketches are templated on the hash type, the bucket sort itself only ever sees the low bits)
-    const bool fast_common = ctx->sw_index_fast && H && src.is_set && eff_bits >= 1 && B <= kMaxBucketBits && low_bits >= 0 && low_bits <= 31 && gb <= 31 && rb <= 31;
-    const bool slices_ok = fast_common && !range_bits && !no_self && H < (1ULL << 30) && low_bits + gb + rb <= 63;   // (slice records: one pass, offsets below 2^30)
-    const uint32_t n_blocks = (N + 31) / 32;
-    const bool tiles_ok = fast_common && N >= 2 && n_blocks <= kTileMaxBlocks && low_bits + gb <= 63 && ctx->sw_index_tiles != 0;
-    bool tiles_mode = tiles_ok && (range_bits || no_self || ctx->sw_index_tiles == 1 || N >= (uint32_t)ctx->sw_dist_tiles_min_genomes);
-    const bool fast_ok = tiles_mode || slices_ok;
-    if (n_shards > 1 && !tiles_mode)
-        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard needs set sketches of 2 .. %u genomes whose key fields fit the bucket sort "
-                                                "(hash bits %d, %u shards)", kTileMaxBlocks * 32, hash_bits, n_shards);
-    if (tiles_mode) RK_TRY(pool_array(ctx, &idx->d_blk_min, (size_t)n_blocks));
-    const unsigned wave_blocks = (N + 3) / 4;  // 4 waves (genomes) per 256-thread workgroup
-
-    // ---- internal genome order: relatives next to each other (see k_minhash_insert) ---------------------------------
-    // d_orig, d_sizes and d_src_off (the CSR offsets in internal order); the rest of the build, and every kernel that
-    // uses the index, works in that order
-    // (round 4) It runs on a stream of its own: the partition of the hashes below does not need it -- it walks the sketches
-    // in the CALLER's order and k_bucket_emit translates the genome ids through `inv` --, so the two overlap (≈ 70 us of
-    // small dependent kernels next to ≈ 160 us of partition); `join()` makes ctx->stream wait for it where its results are
-    // first used.  The temporaries live until the function returns (the pool's reuse is ordered on ctx->stream only).
-    DevBuf<unsigned long long> rl_table(ctx), rl_keys(ctx), rl_keys_sorted(ctx);
-    DevBuf<uint32_t> rl_parent(ctx), rl_keys32(ctx), rl_rank(ctx), rl_inv(ctx);
-    DevBuf<uint2> rl_tab(ctx);
-    DevBuf<char> rl_tmp(ctx);   // the sort's scratch (kept until this function returns: the sort runs on the second stream)
-    const uint32_t *inv = nullptr;   // caller's genome index -> internal id (null: identity)
-    bool forked = false, joined = true;
-    auto join = [&]() -> int {
-        if (!joined) {
-            RK_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-            joined = true;
-        }
-        return RK_OK;
-    };
-    const bool relabel = ctx->sw_index_relabel && src.is_set && N > 1 && H;
-    const bool two_streams = relabel && !getenv("RK_INDEX_ONE_STREAM");
-    if (two_streams) {
-        if (!ctx->stream2) {
-            {   // (its kernels are small and many: at the highest priority they are not queued behind the partition's workgroups)
-                int prio_lo = 0, prio_hi = 0;
-                const bool hi = !getenv("RK_INDEX_STREAM2_PRIO") || atoi(getenv("RK_INDEX_STREAM2_PRIO")) != 0;
-                if (hi && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess && prio_hi != prio_lo)
-                    RK_HIP(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi));
-                else
-                    RK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-            }
-            RK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            RK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-            RK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_inv, hipEventDisableTiming));
-        }
-        RK_HIP(ctx, hipEventRecord(ctx->ev_fork, st));          // (everything enqueued on ctx->stream so far comes first)
-    }
-    // The launches of the renumbering are ENQUEUED after the partition's (the fast path calls this once its own first
-    // kernels are in the queue): the host needs ~5 us per launch, and with the renumbering's ten launches in front the
-    // partition started 70 us late.
-    bool inv_recorded = false;   // ctx->ev_inv was recorded behind the kernel that completes `inv`
-    bool renumbering_enqueued = false, want_tab = false;   // want_tab: the fast path is taken (H < 2^30) and wants k_emit_table's table
-    auto enqueue_renumbering = [&]() -> int {
-      if (renumbering_enqueued) return RK_OK;
-      renumbering_enqueued = true;
-      if (relabel) {
-        hipStream_t s2 = st;
-        if (two_streams) {
-            s2 = ctx->stream2;
-            RK_HIP(ctx, hipStreamWaitEvent(s2, ctx->ev_fork, 0));
-            forked = true;
-        }
-        int id_bits = 1;
-        while ((1ULL << id_bits) < N) id_bits++;
-        uint32_t slots = 1024;
-        // (at most half full, usually far less -- relatives share their smallest hashes.  Twice this size was 268 MB at 500,000 genomes:
-        // beyond the last-level cache, every probe a DRAM row of its own, and the kernels streaming beside it slowed to a third)
-        const unsigned long long want_slots = (getenv("RK_INDEX_TABLE_X") ? strtoull(getenv("RK_INDEX_TABLE_X"), nullptr, 10) : 2ULL) * N * kMinK;
-        while (slots < want_slots && slots < (1u << 30)) slots <<= 1;
-        RK_HIP(ctx, rl_table.alloc(slots));
-        RK_HIP(ctx, rl_parent.alloc(N));
-        RK_HIP(ctx, hipMemsetAsync(rl_table.p, 0xFF, (size_t)slots * 8, s2));
-        const unsigned nb_ins = (unsigned)(((uint64_t)N * kMinK + kInsertThreads - 1) / kInsertThreads), nb_n = blocks_for(N);
-        if (src.d_sig) {
-            const SigMinK rs{src.d_sig};
-            hipLaunchKernelGGL(k_minhash_insert<SigMinK>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
-            hipLaunchKernelGGL(k_minhash_vote<SigMinK>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
-        } else if (idx->wide) {
-            const CsrMinK<uint64_t> rs{s->d_hashes64, s->d_off};
-            hipLaunchKernelGGL(k_minhash_insert<CsrMinK<uint64_t>>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
-            hipLaunchKernelGGL(k_minhash_vote<CsrMinK<uint64_t>>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
-        } else {
-            const CsrMinK<uint32_t> rs{s->d_hashes, s->d_off};
-            hipLaunchKernelGGL(k_minhash_insert<CsrMinK<uint32_t>>, dim3(nb_ins), dim3(kInsertThreads), 0, s2, rs, N, rl_table.p, slots - 1);
-            hipLaunchKernelGGL(k_minhash_vote<CsrMinK<uint32_t>>, dim3(nb_n), dim3(kThreads), 0, s2, rs, N, rl_table.p, slots - 1, rl_parent.p);
-        }
-        if (N <= kRankMaxN) {
-            RK_HIP(ctx, rl_keys32.alloc(N));
-            RK_HIP(ctx, rl_rank.alloc(N));
-            hipLaunchKernelGGL(k_cluster_keys32, dim3(nb_n), dim3(kThreads), 0, s2, rl_parent.p, N, id_bits, rl_keys32.p, rl_rank.p);
-            hipLaunchKernelGGL(k_rank_keys, dim3((N + kRankQ - 1) / kRankQ, (N + kRankStretch - 1) / kRankStretch), dim3(kRankThreads), 0, s2,
-                               rl_keys32.p, N, rl_rank.p);
-            if (forked) {   // (a genome's rank among the keys IS its internal id: all the bucket emission of tile records needs)
-                RK_HIP(ctx, hipEventRecord(ctx->ev_inv, s2));
-                inv_recorded = true;
-            }
-            hipLaunchKernelGGL(k_order_from_rank, dim3(nb_n), dim3(kThreads), 0, s2, rl_rank.p, N, src.d_off, src.d_sizes, idx->d_orig, idx->d_sizes);
-            hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
-            inv = rl_rank.p;   // (a genome's rank among the keys IS its internal id)
-        } else {
-            RK_HIP(ctx, rl_keys.alloc(N));
-            RK_HIP(ctx, rl_keys_sorted.alloc(N));
-            RK_HIP(ctx, rl_inv.alloc(N));
-            hipLaunchKernelGGL(k_cluster_keys, dim3(nb_n), dim3(kThreads), 0, s2, rl_parent.p, N, id_bits, rl_keys.p);
-            void *scratch = nullptr;
-            RK_TRY(rk_prim_sort_keys_u64(ctx, rl_keys.p, rl_keys_sorted.p, N, 0, (unsigned)(2 * id_bits), s2, &scratch));
-            rl_tmp.p = static_cast<char *>(scratch);
-            hipLaunchKernelGGL(k_order_from_keys, dim3(nb_n), dim3(kThreads), 0, s2, rl_keys_sorted.p, N, id_bits, src.d_off, src.d_sizes, idx->d_orig, idx->d_sizes);
-            hipLaunchKernelGGL(k_invert_order, dim3(nb_n), dim3(kThreads), 0, s2, idx->d_orig, N, rl_inv.p);
-            if (forked) {   // (the translation table is all the bucket emission of tile records needs: it need not wait for the offsets' scan)
-                RK_HIP(ctx, hipEventRecord(ctx->ev_inv, s2));
-                inv_recorded = true;
-            }
-            hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, s2, idx->d_sizes, N, idx->d_src_off);
-            inv = rl_inv.p;
-        }
-        if (want_tab) {
-            RK_HIP(ctx, rl_tab.alloc(N));
-            hipLaunchKernelGGL(k_emit_table, dim3(nb_n), dim3(kThreads), 0, s2, inv, idx->d_src_off, N, rl_tab.p);
-        }
-        if (idx->d_blk_min) hipLaunchKernelGGL(k_blk_min_sizes, dim3(blocks_for(n_blocks)), dim3(kThreads), 0, s2, idx->d_sizes, N, n_blocks, idx->d_blk_min);
-        idx->relabeled = true;
-        RK_HIP(ctx, hipGetLastError());
-        if (forked) {
-            RK_HIP(ctx, hipEventRecord(ctx->ev_join, s2));
-            joined = false;
-        }
-      } else {
-        hipLaunchKernelGGL(k_iota, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, st, N, idx->d_orig);
-        if (src.d_sizes) {
-            RK_HIP(ctx, hipMemcpyAsync(idx->d_sizes, src.d_sizes, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_offsets_scan, dim3(1), dim3(1024), 0, st, idx->d_sizes, N, idx->d_src_off);
-        } else {
-            hipLaunchKernelGGL(k_sizes, dim3(blocks_for((uint64_t)N + 1)), dim3(kThreads), 0, st, src.d_off, N, idx->d_sizes, idx->d_src_off);
-        }
-        if (idx->d_blk_min) hipLaunchKernelGGL(k_blk_min_sizes, dim3(blocks_for(n_blocks)), dim3(kThreads), 0, st, idx->d_sizes, N, n_blocks, idx->d_blk_min);
-      }
-      return RK_OK;
-    };
-
-    DevBuf<BuildResult> res(ctx);
-    RK_HIP(ctx, res.alloc(1));
-    BuildResult r{0, 0, 0, 0, 0};
-    bool built = false;
-
-    // ---- fast path: two-level bucket sort, second level and all emission in LDS (rk_index_fast.inc) -----------------
-    if (ctx->sw_dist_debug && !fast_ok)
-        fprintf(stderr, "[rk] index build: general path (H %llu, wide %d, sets %d, B %d, low bits %d, genome bits %d, position bits %d)\n",
-                (unsigned long long)H, (int)idx->wide, (int)src.is_set, B, low_bits, gb, rb);
-    TileResult tr;
-    memset(&tr, 0, sizeof tr);
-    bool fast_refused = false;
-    unsigned long long refused_flags = 0;   // (what the kernels raised when they refused the bucket sort)
-    DevBuf<uint2> t_contrib(ctx);
-    DevBuf<uint32_t> t_rows(ctx), t_cols(ctx);
-    DevBuf<uint4> t_dir_j(ctx), t_dir_c(ctx);
-    DevBuf<uint3> t_rec(ctx);   // a shard's tile records, grouped by destination shard (they leave for the exchange unsorted)
-    uint32_t t_region_cap = 0;
-    uint64_t rec_cap_retry = 0;   // tile records the first attempt asked for, had they fit
-    uint64_t keys_cap_retry = 0;  // keys of the fullest range pass, had they fit (the ranges of a real hash space are not equally full)
-    const uint64_t H_el_shard = from_keys ? H_el : H / n_shards;   // postings of this shard: known from keys, else estimated
-    for (int attempt = 0; fast_ok && !built && attempt < 3; attempt++) {
-        // (the tile records of an attempt did not fit their buffer -- wide species, lists scattered over many blocks --: the
-        // attempt has counted what it needs, and the next one gets exactly that, within a budget of 6 records per posting; beyond
-        // it the index is built with slice records after all, where those can be had)
-        if (attempt >= 1 && (fast_refused || !tr.overflow)) break;
-        if (attempt == 1) {
-            unsigned long long worst = 0;
-            for (uint32_t q = 0; q < kRecRegions; q++) worst = std::max<unsigned long long>(worst, tr.rec_count[q]);
-            rec_cap_retry = (worst + worst / 16 + 1024) * kRecRegions;
-            if (rec_cap_retry > 6 * H_el_shard + (1u << 22) || ctx->sw_tile_rec_cap) rec_cap_retry = 0;   // (RK_TILE_REC_CAP: a test forces the fallback)
-        }
-        if (attempt == 2 || (attempt == 1 && !rec_cap_retry)) {
-            if (!slices_ok) break;
-            if (!tiles_mode) break;
-            tiles_mode = false;
-            rk_pool_free(ctx, idx->d_blk_min);
-            idx->d_blk_min = nullptr;
-        }
-        if (!tiles_mode) RK_TRY(alloc_slices());
-        const uint32_t passes = tiles_mode ? n_pass : 1;
-        FastArgs fa;
-        fa.hashes = from_keys ? nullptr : idx->wide ? (const void *)s->d_hashes64 : (const void *)s->d_hashes;
-        fa.off = src.d_off;
-        fa.orig = nullptr;           // the partition walks the sketches in the caller's order (see the renumbering above)
-        fa.off_new = src.d_off;
-        fa.n_genomes = N;
-        fa.H = H_el;
-        fa.hash_bits = hash_bits;
-        fa.low_bits = low_bits;
-        fa.gb = gb;
-        fa.rb = tiles_mode ? 0 : rb;   // (tile records: nobody needs an element's position inside its sketch)
-        fa.xcd_map = getenv("RK_INDEX_XCD") ? atoi(getenv("RK_INDEX_XCD")) : 1;
-        fa.nb = 1u << B;
-        fa.n_chunks = (uint32_t)((H_el + kPartChunk - 1) / kPartChunk);
-        fa.range_bits = tiles_mode ? range_bits : 0;
-        fa.range_id = 0;
-        // what a pass may hold: exactly H without ranges; with ranges an estimate + slack (a pass that exceeds it raises the overflow
-        // flag in k_part_starts and the kernels behind it stand still)
-        // (RK_INDEX_KEYS_CAP_PCT: tests make the estimate too small)
-        const uint64_t keys_pct = getenv("RK_INDEX_KEYS_CAP_PCT") ? std::max(1, atoi(getenv("RK_INDEX_KEYS_CAP_PCT"))) : 125;
-        // (from keys: the shard's exact key count -- a pass of it holds at most that many)
-        const uint64_t keys_cap = from_keys ? std::max<uint64_t>(1, H_el) : fa.range_bits ? std::min<uint64_t>(H, keys_cap_retry ? keys_cap_retry : H_pass * keys_pct / 100 + (keys_pct >= 100 ? (1u << 20) : 0)) : H;
-        fa.keys_cap = keys_cap;
-        fa.filtered = nullptr;
-        fa.n_filtered = nullptr;
-        DevBuf<uint32_t> chunk_first(ctx), matrix(ctx), total(ctx), bstart(ctx), ucount(ctx), ubase(ctx), tmp_uhash(ctx), tmp_upos(ctx), n_open(ctx), n_cov(ctx);
-        DevBuf<unsigned long long> keys(ctx), tmp_uhash64(ctx), zeroed(ctx);
-        DevBuf<uint2> self_raw(ctx);
-        // tile records: unsorted (64 regions), binned by row block, the directory's proto entries
-        DevBuf<uint32_t> bins(ctx), tb(ctx), big_list(ctx);
-        DevBuf<uint3> brec(ctx);
-        DevBuf<uint4> proto(ctx);
-        DevBuf<unsigned long long> level_start(ctx);
-        const bool wide = idx->wide;
-        const size_t nb1 = (size_t)fa.nb + 1;
-        // the two-pass partition needs six spare key bits and >= 128 buckets
-        const bool part2 = (getenv("RK_INDEX_PART2") ? atoi(getenv("RK_INDEX_PART2")) != 0 : true) && B >= 7 && low_bits + gb + fa.rb <= 64 - (int)kFineBits;
-        // a range pass partitions what k_range_filter kept of the hashes (RK_INDEX_FILTER=0: every kernel of the pass walks them all)
-        // (from keys: the keys ARE a filtered source -- of one pass as they arrived, of several through k_keys_pass_filter)
-        const bool use_filter = from_keys || (fa.range_bits && part2 && eff_bits + gb <= 64 && (getenv("RK_INDEX_FILTER") ? atoi(getenv("RK_INDEX_FILTER")) != 0 : true));
-        if (from_keys && !(part2 && tiles_mode && fa.range_bits))
-            return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard_keys: the key fields do not fit the two-pass partition (hash bits %d, %d buckets, genome bits %d)",
-                           hash_bits, B, gb);
-        const uint32_t part_chunks = use_filter ? (uint32_t)((keys_cap + kPartChunk - 1) / kPartChunk) : fa.n_chunks;   // rows of the count matrix
-        RK_HIP(ctx, chunk_first.alloc((size_t)fa.n_chunks + 1));
-        RK_HIP(ctx, matrix.alloc((size_t)part_chunks * fa.nb));
-        RK_HIP(ctx, total.alloc(fa.nb));
-        RK_HIP(ctx, bstart.alloc(nb1 * passes));   // (per pass: the list heads of a pass are placed while the next one partitions)
-        RK_HIP(ctx, ucount.alloc(nb1 * passes));
-        RK_HIP(ctx, ubase.alloc(nb1 * passes));
-        if (wide) RK_HIP(ctx, tmp_uhash64.alloc(H_el));
-        else RK_HIP(ctx, tmp_uhash.alloc(H_el));
-        RK_HIP(ctx, tmp_upos.alloc(H_el));
-        RK_HIP(ctx, keys.alloc(keys_cap));
-        uint64_t rec_cap = 0, tile_cap = 0, slot_cap = 0;
-        uint32_t region_cap = 0;
-        const bool sort_here = tiles_mode && n_shards == 1;   // (a shard's records leave for the exchange: rk_index_join_shard sorts what arrives)
-        if (tiles_mode) {
-            // related lists write ~0.15-0.3 records per posting; chance collisions of a crowded hash space add H x lambda / 2
-            // (lambda = postings per hash value: 500,000 genomes in 28 bits share every value twice over)
-            const double lambda = hash_bits < 48 ? (double)H / (double)(1ULL << hash_bits) : 0.0;
-            rec_cap = ctx->sw_tile_rec_cap ? ctx->sw_tile_rec_cap : rec_cap_retry ? rec_cap_retry : (uint64_t)((double)H_el_shard * (0.5 + 0.6 * lambda)) + 65536;
-            rec_cap = std::min<uint64_t>(rec_cap, 0x7FFF0000ULL);
-            region_cap = (uint32_t)((rec_cap + kRecRegions - 1) / kRecRegions);
-            rec_cap = (uint64_t)region_cap * kRecRegions;
-            RK_HIP(ctx, t_rec.alloc(rec_cap));
-            t_region_cap = region_cap;
-        }
-        if (sort_here) {
-            tile_cap = std::min<uint64_t>(rec_cap, (uint64_t)n_blocks * (n_blocks + 1) / 2);
-            slot_cap = rec_cap + tile_cap;   // (every tile from an even slot on)
-            RK_HIP(ctx, brec.alloc(rec_cap));
-            RK_HIP(ctx, tb.alloc(3 * (size_t)n_blocks));
-            RK_HIP(ctx, bins.alloc((size_t)n_blocks + 1));   // bin starts (the counts and cursors are in `zeroed`)
-            RK_HIP(ctx, proto.alloc(2 * tile_cap));
-            RK_HIP(ctx, level_start.alloc(2 * (kTileTable + 1)));
-            RK_HIP(ctx, t_contrib.alloc(slot_cap + 256));
-            if (rowsort_stage(n_blocks)) {   // (the split copy serves the scalar-row variant of the tile kernel: short launches over small collections)
-                RK_HIP(ctx, t_rows.alloc(slot_cap + 256));
-                RK_HIP(ctx, t_cols.alloc(slot_cap + 256));
-            }
-            RK_HIP(ctx, t_dir_j.alloc(2 * tile_cap));
-            RK_HIP(ctx, t_dir_c.alloc(2 * tile_cap));
-        }
-        if (!tiles_mode) {
-            RK_HIP(ctx, self_raw.alloc(H));
-            RK_HIP(ctx, n_open.alloc((size_t)N + 1));
-            RK_HIP(ctx, n_cov.alloc((size_t)N + 1));
-        }
-        // everything the kernels expect zeroed, in one buffer and one fill (each fill is ~5 us on the stream): the result
-        // records, where the postings of each pass start, the cursors of the two-pass partition (per pass) and of the tile sort
-        const bool small_wgs = (fa.nb >> kFineBits) <= 128;   // several workgroups per chunk: they share its stretch through counters
-        const size_t w_cursor = part2 ? (fa.nb + 1) / 2 : 0, w_taken = part2 && small_wgs ? ((size_t)fa.n_chunks * (fa.nb >> kFineBits) + 1) / 2 : 0;
-        const size_t z_res = 0, z_tres = z_res + (sizeof(BuildResult) + 7) / 8, z_pass = z_tres + (sizeof(TileResult) + 7) / 8,
-                     z_big = z_pass + passes + 1, z_filt = z_big + (passes + 1) / 2, z_hq = z_filt + passes, z_cursor = z_hq + (passes + 1) / 2, z_taken = z_cursor + w_cursor * passes, z_tcur = z_taken + w_taken * passes,
-                     z_bins = z_tcur + (sort_here ? (sizeof(TileCursors) + 7) / 8 : 0),
-                     z_end = z_bins + (sort_here ? (size_t)n_blocks + 1 : 0);   // bin counts (u32[n_blocks + 1]) + bin cursors (u32[n_blocks])
-        RK_HIP(ctx, zeroed.alloc(z_end));   // (zeroed by k_chunk_first, the first launch)
-        BuildResult *const fres = reinterpret_cast<BuildResult *>(zeroed.p + z_res);
-        TileResult *const tres = reinterpret_cast<TileResult *>(zeroed.p + z_tres);
-        unsigned long long *const pass_base = zeroed.p + z_pass;   // [passes + 1]: postings before pass p; the last one = all of them
-        const size_t part_lds = (size_t)fa.nb * 4 + 2 * kStageGenomes * 8;   // bucket counters + the chunk's genome bounds
-        if (part_lds > 48 * 1024) {
-            RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_hist<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
-            RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_scatter<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
-            RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_hist<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
-            RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_scatter<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_lds));
-        }
-        // (from keys: no chunk walks the sketches -- the launch only zeroes, and chunk_first[0] is all it writes)
-        hipLaunchKernelGGL(k_chunk_first, dim3(blocks_for(std::max<uint64_t>((uint64_t)fa.n_chunks + 1, z_end))), dim3(kThreads), 0, st, src.d_off, N, from_keys ? 0u : fa.n_chunks,
-                           chunk_first.p, zeroed.p, (uint32_t)z_end);
-        DevBuf<unsigned long long> mid(ctx);
-        if (part2) RK_HIP(ctx, mid.alloc(keys_cap));
-        const int emit_t = getenv("RK_INDEX_EMIT_T") ? atoi(getenv("RK_INDEX_EMIT_T")) : 512;
-        const bool narrow = low_bits + gb <= 32;  // (hash_low, genome) fits 32 bits
-        // buckets beyond the LDS sort (a hash shared by thousands of genomes) go to k_bucket_heavy: tile records, 32-bit sort keys
-        const bool big_ok = tiles_mode && narrow && ctx->sw_index_heavy;
-        if (big_ok) RK_HIP(ctx, big_list.alloc((size_t)fa.nb * passes));
-        const size_t heavy_lds = heavy_lds_bytes(n_blocks);
-        if (big_ok) RK_HIP(ctx, hipFuncSetAttribute((const void *)k_bucket_heavy<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)heavy_lds));
-        for (uint32_t pass = 0; pass < passes; pass++) {
-            fa.range_id = (shard_id << pass_bits) | pass;
-            uint32_t *const bstart_p = bstart.p + nb1 * pass, *const ucount_p = ucount.p + nb1 * pass, *const ubase_p = ubase.p + nb1 * pass;
-            uint32_t *const fine_cursor = reinterpret_cast<uint32_t *>(zeroed.p + z_cursor + w_cursor * pass);
-            uint32_t *const seg_taken = reinterpret_cast<uint32_t *>(zeroed.p + z_taken + w_taken * pass);
-            FastArgs pa = fa;   // what the partition kernels of this pass see
-            if (from_keys) {
-                unsigned long long *const n_filt = zeroed.p + z_filt + pass;
-                // the caller's keys are never written: one pass partitions them as they are (k_part_fine writes `keys`, ours), several
-                // passes filter them into `keys` first -- a second attempt (tile records beyond their buffer) starts from intact keys
-                if (passes == 1) {
-                    hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(64), 0, st, n_filt, (unsigned long long)H_el);
-                    pa.filtered = src.keys;
-                } else {
-                    const uint64_t per_wg = (uint64_t)kKeysFilterThreads * kKeysFilterSteps;
-                    if (H_el)
-                        hipLaunchKernelGGL(k_keys_pass_filter, dim3((unsigned)((H_el + per_wg - 1) / per_wg)), dim3(kKeysFilterThreads), 0, st, src.keys, H_el, gb,
-                                           hash_bits - shard_bits, pass_bits, pass, keys.p, n_filt, (unsigned long long)keys_cap, fres);
-                    pa.filtered = keys.p;
-                }
-                pa.n_filtered = n_filt;
-                pa.hash_bits = eff_bits;
-                pa.range_bits = 0;
-                pa.range_id = 0;
-            } else if (use_filter) {
-                unsigned long long *const n_filt = zeroed.p + z_filt + pass;
-                // (the filtered elements lie in `keys`: the coarse pass reads them and writes `mid`, the fine pass writes `keys` again)
-                if (wide) hipLaunchKernelGGL(k_range_filter<uint64_t>, dim3(fa.n_chunks * kFilterSplit), dim3(kFilterThreads), 0, st, fa, chunk_first.p, keys.p, n_filt, fres);
-                else hipLaunchKernelGGL(k_range_filter<uint32_t>, dim3(fa.n_chunks * kFilterSplit), dim3(kFilterThreads), 0, st, fa, chunk_first.p, keys.p, n_filt, fres);
-                // (tried: starting the renumbering BEHIND the filter -- then k_part_hist takes 0.84 ms instead of 0.16 beside
-                // k_minhash_insert: whatever runs beside that kernel pays its 0.55 ms)
-                pa.filtered = keys.p;
-                pa.n_filtered = n_filt;
-                pa.hash_bits = eff_bits;
-                pa.range_bits = 0;
-                pa.range_id = 0;
-            }
-            if (wide) hipLaunchKernelGGL(k_part_hist<uint64_t>, dim3(part_chunks), dim3(kPartThreads), part_lds, st, pa, chunk_first.p, matrix.p, fres);
-            else hipLaunchKernelGGL(k_part_hist<uint32_t>, dim3(part_chunks), dim3(kPartThreads), part_lds, st, pa, chunk_first.p, matrix.p, fres);
-            hipLaunchKernelGGL(k_part_colscan, dim3((fa.nb + 63) / 64), dim3(1024), 0, st, matrix.p, part_chunks, fa.nb, total.p);
-            uint32_t *const n_big_p = reinterpret_cast<uint32_t *>(zeroed.p + z_big) + pass;
-            hipLaunchKernelGGL(k_part_starts, dim3(1), dim3(1024), 0, st, total.p, fa.nb, bstart_p, fres, pass_base + pass, (unsigned long long)keys_cap,
-                               big_ok ? big_list.p + (size_t)fa.nb * pass : nullptr, n_big_p);
-            // the partition itself: two coalescing passes (rk_index_fast.inc), or one scattering pass
-            if (part2) {
-#define RK_COARSE(TT, HT, GRID)                                                                                                              \
-    do {                                                                                                                                     \
-        RK_HIP(ctx, hipFuncSetAttribute((const void *)k_part_coarse<TT, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part2_lds(TT))); \
-        hipLaunchKernelGGL((k_part_coarse<TT, HT>), dim3(GRID), dim3(TT), part2_lds(TT), st, pa, chunk_first.p, matrix.p, bstart_p, seg_taken, mid.p, fres); \
-    } while (0)
-                if (small_wgs) { if (wide) RK_COARSE(256, uint64_t, part_chunks * 4); else RK_COARSE(256, uint32_t, part_chunks * 4); }
-                else { if (wide) RK_COARSE(1024, uint64_t, part_chunks); else RK_COARSE(1024, uint32_t, part_chunks); }
-#undef RK_COARSE
-                hipLaunchKernelGGL(k_part_fine, dim3(fa.nb >> kFineBits, 16), dim3(kPartThreads), 0, st, pa, bstart_p, mid.p, keys.p, fine_cursor, fres);
-            } else if (wide) {
-                hipLaunchKernelGGL(k_part_scatter<uint64_t>, dim3(fa.n_chunks), dim3(kPartThreads), part_lds, st, fa, chunk_first.p, matrix.p, bstart_p, keys.p, fres);
-            } else {
-                hipLaunchKernelGGL(k_part_scatter<uint32_t>, dim3(fa.n_chunks), dim3(kPartThreads), part_lds, st, fa, chunk_first.p, matrix.p, bstart_p, keys.p, fres);
-            }
-            if (pass == 0) {
-                want_tab = !tiles_mode;
-                RK_TRY(enqueue_renumbering());   // (behind the partition's launches in the host's queue, beside them on the device)
-                // the internal order is needed from here on: the translation table alone for tile records (sizes and offsets in internal
-                // order are still on their way on the second stream: joined in front of the row sort), everything for slice records
-                if (tiles_mode && inv_recorded && !joined) RK_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_inv, 0));
-                else RK_TRY(join());
-                if (!tiles_mode && inv && !rl_tab.p) {   // (second attempt: the renumbering ran for tile records, without the table)
-                    RK_HIP(ctx, rl_tab.alloc(N));
-                    hipLaunchKernelGGL(k_emit_table, dim3(blocks_for(N)), dim3(kThreads), 0, st, inv, idx->d_src_off, N, rl_tab.p);
-                }
-            }
-            if (tiles_mode) {
-                TileEmitArgs ea;
-                ea.keys = keys.p;
-                ea.bstart = bstart_p;
-                ea.inv = inv;
-                ea.low_bits = low_bits;
-                ea.gb = gb;
-                ea.rb = 0;
-                ea.nb = fa.nb;
-                ea.postings = idx->d_postings;
-                ea.tmp_uhash = tmp_uhash.p;
-                ea.tmp_uhash64 = wide ? tmp_uhash64.p : nullptr;
-                ea.tmp_upos = tmp_upos.p;
-                ea.ucount = ucount_p;
-                ea.rec = t_rec.p;
-                ea.region_cap = region_cap;
-                ea.pass_base = pass_base + pass;
-                ea.hash_base = fa.range_bits ? ((unsigned long long)fa.range_id << eff_bits) : 0ULL;
-                ea.n_dest = n_shards;
-                ea.stop = fa.range_bits ? fres : nullptr;
-                ea.big_ok = big_ok ? 1 : 0;
-                ea.big_list = big_ok ? big_list.p + (size_t)fa.nb * pass : nullptr;
-                ea.n_big = n_big_p;
-                ea.stop_rw = fres;
-                ea.tres = tres;
-                ea.xcd_map = fa.xcd_map;
-                ea.debug = getenv("RK_INDEX_DEBUG") ? atoi(getenv("RK_INDEX_DEBUG")) : 0;
-                if (ea.debug) {  // developer ablations leave stages out: whatever they do not write must still be harmless downstream
-                    RK_HIP(ctx, hipMemsetAsync(ucount_p, 0, (size_t)fa.nb * 4, st));
-                    RK_HIP(ctx, hipMemsetAsync(tmp_upos.p, 0, H_el * 4, st));
-                }
-#define RK_EMIT(TT) do { if (narrow) hipLaunchKernelGGL((k_bucket_emit_tiles<TT, uint32_t>), dim3(fa.nb), dim3(TT), 0, st, ea); \
-                         else hipLaunchKernelGGL((k_bucket_emit_tiles<TT, unsigned long long>), dim3(fa.nb), dim3(TT), 0, st, ea); } while (0)
-                if (emit_t == 256) RK_EMIT(256);
-                else if (emit_t == 1024) RK_EMIT(1024);
-                else RK_EMIT(512);
-#undef RK_EMIT
-                if (big_ok) {
-                    HeavyArgs ha;
-                    ha.e = ea;
-                    ha.big_list = big_list.p + (size_t)fa.nb * pass;
-                    ha.n_big = n_big_p;
-                    ha.next = reinterpret_cast<uint32_t *>(zeroed.p + z_hq) + pass;
-                    ha.n_blocks = n_blocks;
-                    hipLaunchKernelGGL(k_bucket_heavy<1024>, dim3((unsigned)std::max(1, ctx->num_cu)), dim3(1024), heavy_lds, st, ha);
-                }
-            } else {
-                EmitArgs ea;
-                ea.keys = keys.p;
-                ea.bstart = bstart_p;
-                ea.off_new = idx->d_src_off;
-                ea.inv = inv;
-                ea.tab = inv ? rl_tab.p : nullptr;
-                ea.low_bits = low_bits;
-                ea.gb = gb;
-                ea.rb = rb;
-                ea.nb = fa.nb;
-                ea.postings = idx->d_postings;
-                ea.tmp_uhash = tmp_uhash.p;
-                ea.tmp_uhash64 = wide ? tmp_uhash64.p : nullptr;
-                ea.tmp_upos = tmp_upos.p;
-                ea.ucount = ucount_p;
-                ea.self_raw = self_raw.p;
-                ea.res = fres;
-                ea.xcd_map = fa.xcd_map;
-                ea.debug = getenv("RK_INDEX_DEBUG") ? atoi(getenv("RK_INDEX_DEBUG")) : 0;
-                if (ea.debug) {  // developer ablations leave stages out: whatever they do not write must still be harmless downstream
-                    RK_HIP(ctx, hipMemsetAsync(ucount_p, 0, (size_t)fa.nb * 4, st));
-                    RK_HIP(ctx, hipMemsetAsync(self_raw.p, 0, H * sizeof(uint2), st));
-                    RK_HIP(ctx, hipMemsetAsync(tmp_upos.p, 0, H * 4, st));
-                }
-#define RK_EMIT(TT) do { if (narrow) hipLaunchKernelGGL((k_bucket_emit<TT, uint32_t>), dim3(fa.nb), dim3(TT), 0, st, ea); \
-                         else hipLaunchKernelGGL((k_bucket_emit<TT, unsigned long long>), dim3(fa.nb), dim3(TT), 0, st, ea); } while (0)
-                if (emit_t == 256) RK_EMIT(256);
-                else if (emit_t == 1024) RK_EMIT(1024);
-                else RK_EMIT(512);
-#undef RK_EMIT
-            }
-            // the list heads (scan + placement) hang on the emission alone: they go to the second stream (one pass) and run beside
-            // the rows / the tile sort; with several passes they stay in line (the next pass's partition is the bigger job)
-            hipStream_t sh = st;
-            const bool heads_aside = forked && passes == 1;
-            if (heads_aside) {
-                RK_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
-                RK_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                sh = ctx->stream2;
-            }
-            hipLaunchKernelGGL(k_heads_scan, dim3(1), dim3(1024), 0, sh, ucount_p, fa.nb, ubase_p, fres);
-            if (wide)
-                hipLaunchKernelGGL(k_heads_place<unsigned long long>, dim3(fa.nb), dim3(kThreads), 0, sh, tmp_uhash64.p, tmp_upos.p, bstart_p, ucount_p, ubase_p,
-                                   fa.nb, pass_base + pass, (unsigned long long *)idx->d_uhash64, idx->d_upos);
-            else
-                hipLaunchKernelGGL(k_heads_place<uint32_t>, dim3(fa.nb), dim3(kThreads), 0, sh, tmp_uhash.p, tmp_upos.p, bstart_p, ucount_p, ubase_p, fa.nb,
-                                   pass_base + pass, idx->d_uhash, idx->d_upos);
-            if (heads_aside) {
-                RK_HIP(ctx, hipEventRecord(ctx->ev_join, sh));
-                joined = false;
-            }
-        }
-        TileSortArgs ta;
-        memset(&ta, 0, sizeof ta);
-        if (sort_here) {
-            ta.rec = t_rec.p;
-            ta.cur = reinterpret_cast<TileCursors *>(zeroed.p + z_tcur);
-            ta.region_cap = region_cap;
-            ta.n_blocks = n_blocks;
-            ta.bin_count = reinterpret_cast<uint32_t *>(zeroed.p + z_bins);
-            ta.bin_cursor = ta.bin_count + n_blocks + 1;
-            ta.bin_start = bins.p;
-            ta.brec = brec.p;
-            ta.blk_min = idx->d_blk_min;
-            ta.contrib = t_contrib.p;
-            ta.rows = t_rows.p;
-            ta.cols = t_cols.p;
-            ta.tb_base = tb.p;
-            ta.tb_cnt = tb.p + n_blocks;
-            ta.order = tb.p + 2 * (size_t)n_blocks;
-            ta.proto = proto.p;
-            ta.level_start = level_start.p;
-            ta.dir[0] = t_dir_j.p;
-            ta.dir[1] = t_dir_c.p;
-            ta.tres = tres;
-            RK_TRY(launch_tile_sort(ctx, ta, st, [&]() { return join(); }));
-        } else if (!tiles_mode) {
-            hipLaunchKernelGGL(k_row_counts2, dim3(wave_blocks), dim3(kThreads), 0, st, idx->d_src_off, N, self_raw.p, n_open.p, n_cov.p);
-            hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(1024), 0, st, n_open.p, n_cov.p, N, idx->d_self_off, idx->d_self_split, fres);
-            hipLaunchKernelGGL(k_row_place2, dim3(wave_blocks), dim3(kThreads), 0, st, idx->d_src_off, N, self_raw.p, idx->d_self_off,
-                               idx->d_self_split, idx->d_selfrange);
-        }
-        RK_HIP(ctx, hipGetLastError());
-        RK_TRY(join());
-        unsigned long long n_postings = 0;
-        {   // the one synchronisation of the build: both result records (and the postings of all passes) in one read-back
-            struct { BuildResult r; TileResult t; unsigned long long pass_base[257]; } both;
-            static_assert(sizeof(BuildResult) % 8 == 0 && offsetof(decltype(both), pass_base) == sizeof(BuildResult) + sizeof(TileResult), "the records lie back to back");
-            RK_TRY(rk_read_back(ctx, &both, fres, sizeof(BuildResult) + sizeof(TileResult) + ((size_t)passes + 1) * 8, st));
-            r = both.r;
-            tr = both.t;
-            n_postings = both.pass_base[passes];
-        }
-        if (ctx->sw_dist_debug && big_ok) {   // (developer output: what k_bucket_heavy had to take)
-            std::vector<uint32_t> nbig(passes), bs((size_t)nb1 * passes);
-            RK_TRY(rk_read_back(ctx, nbig.data(), zeroed.p + z_big, (size_t)passes * 4, st));
-            RK_TRY(rk_read_back(ctx, bs.data(), bstart.p, bs.size() * 4, st));
-            for (uint32_t pass = 0; pass < passes; pass++) {
-                std::vector<uint32_t> bl(nbig[pass]);
-                if (nbig[pass]) RK_TRY(rk_read_back(ctx, bl.data(), big_list.p + (size_t)fa.nb * pass, bl.size() * 4, st));
-                unsigned long long keys_in = 0, biggest = 0;
-                for (uint32_t b : bl) {
-                    const unsigned long long n = bs[nb1 * pass + b + 1] - bs[nb1 * pass + b];
-                    keys_in += n;
-                    biggest = std::max(biggest, n);
-                }
-                fprintf(stderr, "[rk] index build pass %u: %u of %u buckets for k_bucket_heavy, %llu keys, biggest %llu\n", pass, nbig[pass], fa.nb, keys_in, biggest);
-            }
-        }
-        if (ctx->sw_dist_debug)
-            fprintf(stderr, "[rk] index build: fast path flags %llu (B %d, low bits %d, genome bits %d, position bits %d; shard %u of %u, %u pass(es), %llu postings)%s\n",
-                    r.flags, B, low_bits, gb, rb, shard_id, n_shards, passes, n_postings, tiles_mode ? (tr.overflow ? ", tile records overflowed" : ", tile records") : "");
-        if ((r.flags & kFastOverflow) && use_filter && !from_keys && !keys_cap_retry) {
-            // a range holds more keys than estimated: every pass's filter has counted what it needs -- once more with exactly that
-            std::vector<unsigned long long> asked(passes);
-            RK_TRY(rk_read_back(ctx, asked.data(), zeroed.p + z_filt, (size_t)passes * 8, st));
-            const unsigned long long need = *std::max_element(asked.begin(), asked.end());
-            if (need > keys_cap && need <= H) {
-                keys_cap_retry = need + need / 64 + 65536;
-                if (ctx->sw_dist_debug) fprintf(stderr, "[rk] index build: a range pass holds %llu keys (buffers for %llu): again\n", need, (unsigned long long)keys_cap);
-                memset(&tr, 0, sizeof tr);
-                attempt--;
-                continue;
-            }
-        }
-        if (r.flags == 0 && !(tiles_mode && tr.overflow)) built = true;
-        else if (r.flags) {   // a bucket beyond the LDS sort, a pass beyond its key buffer, or a hash outside the hash space: the general path decides
-            fast_refused = true;
-            refused_flags = r.flags;
-            r = BuildResult{0, 0, 0, 0, 0};
-        }
-        if (built && range_bits) idx->H = n_postings;   // (a shard: the postings of ITS hash range; all passes of one shard: == H)
-        if (built && sort_here) {
-            idx->d_tile_contrib = t_contrib.release();
-            idx->d_tile_rows = t_rows.release();
-            idx->d_tile_cols = t_cols.release();
-            idx->d_tile_dir[0] = t_dir_j.release();
-            idx->d_tile_dir[1] = t_dir_c.release();
-            idx->n_tile_slots = tr.n_slots;
-            idx->n_tiles = tr.n_tiles;
-            idx->n_tile_records = tr.n_records;
-            idx->tile_max_records = tr.max_records;
-            for (int m = 0; m < 2; m++)
-                for (int k = 0; k < kTileTable; k++) idx->tile_prefix[m][k] = tr.level_count[m][k];
-            idx->tiles_ready = true;
-            idx->tiles_from_build = true;
-            t_rec.reset();
-            if (ctx->sw_dist_debug)
-                fprintf(stderr, "[rk] tiles from the build: %llu tiles, %llu records in %llu slots (capacity %llu), biggest tile %llu\n", tr.n_tiles, tr.n_records,
-                        tr.n_slots, (unsigned long long)rec_cap, tr.max_records);
-        }
-        if (built && tiles_mode && n_shards > 1) {   // the shard's records wait for the exchange (rk_index_shard_records / _pack)
-            idx->d_shard_rec = t_rec.release();
-            idx->shard_region_cap = t_region_cap;
-            idx->n_shards = n_shards;
-            idx->shard_id = shard_id;
-            for (uint32_t q = 0; q < kRecRegions; q++) idx->shard_rec_count[q] = tr.rec_count[q];
-        }
-    }
-    if (!built && from_keys && (refused_flags & kFastBadHash))
-        return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: a key outside the wire format (hash bits beyond the shard's range, or a genome id >= %u)", N);
-    if (!built && n_shards > 1)
-        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_index_build_shard: the bucket sort refused this collection (flags %s: a bucket or a pass beyond its "
-                                                "buffer, a hash outside the hash space, or tile records beyond their capacity)", tr.overflow ? "tile overflow" : "bucket / key overflow");
-    if (!built) {   // (no tile records after all)
-        t_contrib.reset();
-        t_rows.reset();
-        t_cols.reset();
-        t_dir_j.reset();
-        t_dir_c.reset();
-        if (idx->d_blk_min) { rk_pool_free(ctx, idx->d_blk_min); idx->d_blk_min = nullptr; }
-        RK_TRY(alloc_slices());
-    }
-
-    RK_TRY(enqueue_renumbering());
-    RK_TRY(join());
-    if (!built && H) {
-        RK_HIP(ctx, hipMemsetAsync(res.p, 0, sizeof(BuildResult), st));
-        // ---- general path: device-wide stable radix sort of (hash, source element) -------------------------------------
-        const uint32_t *src_hashes = s->d_hashes;
-        const uint64_t *src_hashes64 = s->d_hashes64;
-        const uint64_t *src_off = s->d_off;
-        DevBuf<uint32_t> perm_hashes(ctx);
-        DevBuf<uint64_t> perm_hashes64(ctx);
-        if (idx->relabeled) {  // the sketches in internal order
-            if (idx->wide) {
-                RK_HIP(ctx, perm_hashes64.alloc(H));
-                hipLaunchKernelGGL(k_gather_sketches<uint64_t>, dim3(wave_blocks), dim3(kThreads), 0, st, s->d_hashes64, s->d_off, idx->d_orig,
-                                   idx->d_src_off, N, perm_hashes64.p);
-                src_hashes64 = perm_hashes64.p;
-            } else {
-                RK_HIP(ctx, perm_hashes.alloc(H));
-                hipLaunchKernelGGL(k_gather_sketches<uint32_t>, dim3(wave_blocks), dim3(kThreads), 0, st, s->d_hashes, s->d_off, idx->d_orig,
-                                   idx->d_src_off, N, perm_hashes.p);
-                src_hashes = perm_hashes.p;
-            }
-            src_off = idx->d_src_off;
-        }
-        DevBuf<uint32_t> iota(ctx), keys_sorted(ctx), sorted_e(ctx), flags(ctx), gid(ctx), n_open(ctx), n_cov(ctx);
-        DevBuf<uint64_t> keys_sorted64(ctx);
-        DevBuf<uint2> self_raw(ctx);
-        DevBuf<char> tmp(ctx);
-        RK_HIP(ctx, iota.alloc(H));
-        RK_HIP(ctx, sorted_e.alloc(H));
-        RK_HIP(ctx, flags.alloc(H));
-        RK_HIP(ctx, gid.alloc(H));
-        RK_HIP(ctx, self_raw.alloc(no_self ? 1 : H));
-        RK_HIP(ctx, n_open.alloc((size_t)N + 1));
-        RK_HIP(ctx, n_cov.alloc((size_t)N + 1));
-        if (idx->wide) RK_HIP(ctx, keys_sorted64.alloc(H));
-        else RK_HIP(ctx, keys_sorted.alloc(H));
-        hipLaunchKernelGGL(k_fill_gid, dim3(wave_blocks), dim3(kThreads), 0, st, src_off, N, gid.p, iota.p);
-        // stable LSD radix sort by hash; values = source element index (genome-major), so equal hashes stay in
-        // ascending genome order == hashMapId[hash].push_back(i) for i ascending (src/sketch.cpp:979-985)
-        if (idx->wide) {
-            RK_TRY(rk_prim_sort_pairs_u64_u32(ctx, src_hashes64, keys_sorted64.p, iota.p, sorted_e.p, H, (unsigned)hash_bits, st));
-            hipLaunchKernelGGL(k_head_flags<uint64_t>, dim3(blocks_for(H)), dim3(kThreads), 0, st, keys_sorted64.p, H, flags.p);
-        } else {
-            RK_TRY(rk_prim_sort_pairs_u32_u32(ctx, src_hashes, keys_sorted.p, iota.p, sorted_e.p, H, (unsigned)hash_bits, st));
-            hipLaunchKernelGGL(k_head_flags<uint32_t>, dim3(blocks_for(H)), dim3(kThreads), 0, st, keys_sorted.p, H, flags.p);
-        }
-        RK_TRY(rk_prim_inclusive_scan_u32(ctx, flags.p, iota.p, H, st));
-        uint32_t *gidx = iota.p;  // 1-based group number of each sorted position
-        if (idx->wide)
-            hipLaunchKernelGGL(k_scatter_heads<uint64_t>, dim3(blocks_for(H)), dim3(kThreads), 0, st, keys_sorted64.p, gidx, H,
-                               idx->d_uhash64, idx->d_upos, res.p);
-        else
-            hipLaunchKernelGGL(k_scatter_heads<uint32_t>, dim3(blocks_for(H)), dim3(kThreads), 0, st, keys_sorted.p, gidx, H,
-                               idx->d_uhash, idx->d_upos, res.p);
-        if (no_self)
-            hipLaunchKernelGGL((k_postings_selfrange<false, true>), dim3(blocks_for(H)), dim3(kThreads), 0, st, sorted_e.p, gidx,
-                               idx->d_upos, gid.p, H, idx->d_postings, self_raw.p, res.p);
-        else if (s->is_set)
-            hipLaunchKernelGGL(k_postings_selfrange<false>, dim3(blocks_for(H)), dim3(kThreads), 0, st, sorted_e.p, gidx,
-                               idx->d_upos, gid.p, H, idx->d_postings, self_raw.p, res.p);
-        else
-            hipLaunchKernelGGL(k_postings_selfrange<true>, dim3(blocks_for(H)), dim3(kThreads), 0, st, sorted_e.p, gidx,
-                               idx->d_upos, gid.p, H, idx->d_postings, self_raw.p, res.p);
-        if (!no_self) {
-            // drop the empty slices (26 % of the elements at 10,000 genomes), covered slices last in their row
-            hipLaunchKernelGGL(k_row_counts, dim3(wave_blocks), dim3(kThreads), 0, st, src_off, N, self_raw.p, n_open.p, n_cov.p);
-            hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(1024), 0, st, n_open.p, n_cov.p, N, idx->d_self_off, idx->d_self_split, res.p);
-            hipLaunchKernelGGL(k_row_place, dim3(wave_blocks), dim3(kThreads), 0, st, src_off, N, self_raw.p,
-                               idx->d_self_off, idx->d_self_split, idx->d_postings, s->is_set, idx->d_selfrange);
-        }
-        RK_HIP(ctx, hipGetLastError());
-        RK_TRY(rk_read_back(ctx, &r, res.p, sizeof(r), st));  // the one synchronisation of the build
-    } else if (!H) {
-        RK_HIP(ctx, hipMemsetAsync(idx->d_upos, 0, 8, st));
-        if (!no_self) {
-            RK_HIP(ctx, hipMemsetAsync(idx->d_self_off, 0, ((size_t)N + 1) * 8, st));
-            RK_HIP(ctx, hipMemsetAsync(idx->d_self_split, 0, ((size_t)N + 1) * 8, st));
-        }
-        RK_HIP(ctx, hipStreamSynchronize(st));
-    }
-    idx->U = r.U;
-    idx->n_self = r.n_self;
-    idx->slices_refused = no_self;
-    idx->ref_sets = src.is_set || r.dups == 0;
-    idx->built_fast = built;
-    if (built) {   // (the same rule as rk_dist.hip self_uses_tiles, which counts the records itself for an index built the general way)
-        idx->spread = r.flagged * 8 > r.n_self;
-        idx->spread_known = 1;
-    }
-    set_dir_shape(idx);
-    guard.p = nullptr;
-    *out = idx;
-    return RK_OK;
-}
 
 // ---- the exchange of a sharded build -----------------------------------------------------------------------------
 namespace {
@@ -1771,20 +1822,12 @@ int rk_index_shard_pack(const rk_index *idx, void *send_dev, void *stream_v)
 }
 
 // ---- a sharded build from per-rank sketches (rk_index_keys.inc) ---------------------------------------------------------
-static int shard_bits_of(rk_ctx *ctx, const char *fn, uint32_t n_shards, int *bits)
+static int checked_shard_bits(rk_ctx *ctx, const char *fn, uint32_t n_shards, int *bits)
 {
     if (!n_shards || n_shards > kRecRegions || (n_shards & (n_shards - 1)))
         return rk_fail(ctx, RK_ERR_ARG, "%s: %u shards (a power of two up to %u)", fn, n_shards, kRecRegions);
-    int b = 0;
-    while ((1u << b) < n_shards) b++;
-    *bits = b;
+    *bits = shard_bits_of(n_shards);
     return RK_OK;
-}
-static int genome_bits_of(uint32_t n_genomes)   // (as index_build_impl: the smallest gb >= 1 with 2^gb >= n_genomes)
-{
-    int gb = 1;
-    while ((1ULL << gb) < n_genomes) gb++;
-    return gb;
 }
 
 // the checks both halves of the split share; fills the kernel arguments
@@ -1792,7 +1835,7 @@ static int split_args(rk_ctx *ctx, const char *fn, const rk_sketches *local, uin
                       uint32_t n_shards, SplitArgs *a)
 {
     int shard_bits = 0;
-    RK_TRY(shard_bits_of(ctx, fn, n_shards, &shard_bits));
+    RK_TRY(checked_shard_bits(ctx, fn, n_shards, &shard_bits));
     if (!local->n || (uint64_t)genome_base + local->n > n_genomes)
         return rk_fail(ctx, RK_ERR_ARG, "%s: genomes %u .. %llu of a collection of %u", fn, genome_base, (unsigned long long)genome_base + local->n, n_genomes);
     if (hash_bits < 1 || hash_bits > 64 || (hash_bits > 32) != local->wide || hash_bits <= shard_bits)
@@ -1812,7 +1855,7 @@ static int split_args(rk_ctx *ctx, const char *fn, const rk_sketches *local, uin
     a->gb = gb;
     a->rem_mask = a->shift >= 64 ? ~0ULL : (1ULL << a->shift) - 1ULL;
     a->n_dest = n_shards;
-    a->xcd_map = getenv("RK_INDEX_XCD") ? atoi(getenv("RK_INDEX_XCD")) : 1;
+    a->xcd_map = read_knobs().xcd_map;
     return RK_OK;
 }
 
@@ -1899,7 +1942,7 @@ int rk_index_build_shard_keys(rk_ctx *ctx, const void *keys_dev, uint64_t n_keys
     if (!ctx || !out || !sig_dev || (!keys_dev && n_keys)) return RK_ERR_ARG;
     *out = nullptr;
     int shard_bits = 0;
-    RK_TRY(shard_bits_of(ctx, "rk_index_build_shard_keys", n_shards, &shard_bits));
+    RK_TRY(checked_shard_bits(ctx, "rk_index_build_shard_keys", n_shards, &shard_bits));
     if (n_shards < 2 || shard >= n_shards)
         return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: shard %u of %u (2 .. %u shards; one is rk_index_build)", shard, n_shards, kRecRegions);
     if (!n_genomes || n_genomes >= 0x7FFFFFFFu) return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: %u genomes", n_genomes);
@@ -2067,51 +2110,16 @@ int rk_index_join_shard(rk_ctx *ctx, const rk_index *part, const void *recv_dev,
     }
     hipLaunchKernelGGL(k_blk_min_sizes, dim3(blocks_for(n_blocks)), dim3(kThreads), 0, st, idx->d_sizes, N, n_blocks, idx->d_blk_min);
     const uint32_t region_cap = (uint32_t)std::max<uint64_t>(1, (n_records + kRecRegions - 1) / kRecRegions);
-    const uint64_t tile_cap = std::max<uint64_t>(1, std::min<uint64_t>(n_records, (uint64_t)n_blocks * (n_blocks + 1) / 2)), slot_cap = n_records + tile_cap;
-    DevBuf<uint2> t_contrib(ctx);
-    DevBuf<uint32_t> t_rows(ctx), t_cols(ctx), bins(ctx), tb(ctx);
-    DevBuf<uint4> t_dir_j(ctx), t_dir_c(ctx), proto(ctx);
-    DevBuf<uint3> brec(ctx);
-    DevBuf<unsigned long long> level_start(ctx), zeroed(ctx);
-    RK_HIP(ctx, brec.alloc(std::max<uint64_t>(1, n_records)));
-    RK_HIP(ctx, tb.alloc(3 * (size_t)n_blocks));
-    RK_HIP(ctx, bins.alloc((size_t)n_blocks + 1));
-    RK_HIP(ctx, proto.alloc(2 * tile_cap));
-    RK_HIP(ctx, level_start.alloc(2 * (kTileTable + 1)));
-    RK_HIP(ctx, t_contrib.alloc(slot_cap + 256));
-    if (rowsort_stage(n_blocks)) {
-        RK_HIP(ctx, t_rows.alloc(slot_cap + 256));
-        RK_HIP(ctx, t_cols.alloc(slot_cap + 256));
-    }
-    RK_HIP(ctx, t_dir_j.alloc(2 * tile_cap));
-    RK_HIP(ctx, t_dir_c.alloc(2 * tile_cap));
-    const size_t z_tres = 0, z_tcur = z_tres + (sizeof(TileResult) + 7) / 8, z_bins = z_tcur + (sizeof(TileCursors) + 7) / 8, z_end = z_bins + (size_t)n_blocks + 1;
-    RK_HIP(ctx, zeroed.alloc(z_end));
-    RK_HIP(ctx, hipMemsetAsync(zeroed.p, 0, z_end * 8, st));
-    TileResult *const tres = reinterpret_cast<TileResult *>(zeroed.p + z_tres);
+    TileSortBufs sort(ctx);
+    RK_TRY(sort.alloc(ctx, n_blocks, n_records, std::max<uint64_t>(1, std::min<uint64_t>(n_records, (uint64_t)n_blocks * (n_blocks + 1) / 2))));
+    DevBuf<unsigned long long> zeroed(ctx);
+    ZeroedLayout z = ZeroedLayout::of_join(n_blocks);
+    RK_HIP(ctx, zeroed.alloc(z.z_end));
+    RK_HIP(ctx, hipMemsetAsync(zeroed.p, 0, z.z_end * 8, st));
+    z.base = zeroed.p;
+    TileResult *const tres = z.tile_res();
     hipLaunchKernelGGL(k_virtual_regions, dim3(1), dim3(64), 0, st, (unsigned long long)n_records, region_cap, &tres->rec_count[0]);
-    TileSortArgs ta;
-    memset(&ta, 0, sizeof ta);
-    ta.rec = (const uint3 *)recv_dev;
-    ta.cur = reinterpret_cast<TileCursors *>(zeroed.p + z_tcur);
-    ta.region_cap = region_cap;
-    ta.n_blocks = n_blocks;
-    ta.bin_count = reinterpret_cast<uint32_t *>(zeroed.p + z_bins);
-    ta.bin_cursor = ta.bin_count + n_blocks + 1;
-    ta.bin_start = bins.p;
-    ta.brec = brec.p;
-    ta.blk_min = idx->d_blk_min;
-    ta.contrib = t_contrib.p;
-    ta.rows = t_rows.p;
-    ta.cols = t_cols.p;
-    ta.tb_base = tb.p;
-    ta.tb_cnt = tb.p + n_blocks;
-    ta.order = tb.p + 2 * (size_t)n_blocks;
-    ta.proto = proto.p;
-    ta.level_start = level_start.p;
-    ta.dir[0] = t_dir_j.p;
-    ta.dir[1] = t_dir_c.p;
-    ta.tres = tres;
+    const TileSortArgs ta = sort.args((const uint3 *)recv_dev, region_cap, n_blocks, idx->d_blk_min, z);
     RK_TRY(launch_tile_sort(ctx, ta, st, []() { return RK_OK; }));
     TileResult tr;
     RK_TRY(rk_read_back(ctx, &tr, tres, sizeof(tr), st));
@@ -2129,19 +2137,7 @@ int rk_index_join_shard(rk_ctx *ctx, const rk_index *part, const void *recv_dev,
         fprintf(stderr, "[rk] join shard: %llu records in %u of %u row blocks; fullest %u, 64th %u, the 64 fullest hold %llu\n", all, non_empty, n_blocks, bc[0],
                 bc[std::min<uint32_t>(63, n_blocks - 1)], top);
     }
-    idx->d_tile_contrib = t_contrib.release();
-    idx->d_tile_rows = t_rows.release();
-    idx->d_tile_cols = t_cols.release();
-    idx->d_tile_dir[0] = t_dir_j.release();
-    idx->d_tile_dir[1] = t_dir_c.release();
-    idx->n_tile_slots = tr.n_slots;
-    idx->n_tiles = tr.n_tiles;
-    idx->n_tile_records = tr.n_records;
-    idx->tile_max_records = tr.max_records;
-    for (int m = 0; m < 2; m++)
-        for (int k = 0; k < kTileTable; k++) idx->tile_prefix[m][k] = tr.level_count[m][k];
-    idx->tiles_ready = true;
-    idx->tiles_from_build = true;
+    sort.hand_over(idx, tr);
     guard.p = nullptr;
     *out = idx;
     return RK_OK;
