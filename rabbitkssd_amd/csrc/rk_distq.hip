@@ -803,6 +803,9 @@ void plan_tiles(const rk_ctx *ctx, const rk_index *idx, int cbits, uint32_t *til
 bool distq_pipe(const rk_ctx *ctx, const rk_index *idx, int cbits, int look)
 {
     if (look != kLookRank || (getenv("RK_DISTQ_PIPE") && !atoi(getenv("RK_DISTQ_PIPE")))) return false;
+    // (its stage A loads a.urec without asking: references that repeat a hash have no list records -- ensure_urec -- and take
+    // the plain look-up, which reads the posting range from upos)
+    if (!idx->ref_sets) return false;
     uint32_t tile = 0, nt = 0, words = 0;
     plan_tiles(ctx, idx, cbits, &tile, &nt, &words);
     return (size_t)words * 4 >= 64 * 1024;
@@ -820,6 +823,7 @@ bool distq_sliced(const rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs,
     (void)ctx; (void)idx; (void)cbits;
     const char *e = getenv("RK_DISTQ_SLICED");
     if (look != kLookRank || !qs->is_set || qs->wide || !qs->n || qs->total >= 0xFFF00000ULL) return false;
+    if (!idx->ref_sets) return false;   // (the counting kernel's pre-resolved variant loads a.urec too)
     return e && *e && atoi(e) == 1;
 }
 

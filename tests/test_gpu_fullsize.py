@@ -203,7 +203,8 @@ def test_self_join_with_tiled_columns_90k(ctx):
 
 def test_config4_ref_vs_query_100k(ctx):
     """configs[4] shape at reduced query count: 100,000 reference sketches (76 hashes, 24-bit, L4K10S7)
-    against queries of 45,776 hashes (3 Gb genomes): tiled LDS row, resolved ranges, exact vs oracle."""
+    against queries of 45,776 hashes (3 Gb genomes): one 100 KB tile of 8-bit counters (the 76-hash references bound every
+    count), resolved ranges, exact vs oracle."""
     rn, rh, roff = synth.clade_sketches(100000, 76, 24, seed=31)
     qn, qh, qoff = synth.clade_sketches(24, 45776, 24, seed=32)
     # plant reference sketches inside the queries (a mammal-sized query "contains" some bacteria)

@@ -826,7 +826,8 @@ def test_row_sharding_union_equals_full(ctx):
 
 
 def test_ref_vs_query_random_and_tiled_reference(ctx):
-    # 45,000 references: the LDS counter row is tiled (2 tiles of <= 40,960 columns)
+    # 45,000 references of 24 hashes: 8-bit counters, ONE 45 KB tile (a tile holds 141,440 such columns; tiled rows are the
+    # subject of tests/test_gpu_query_edges.py)
     rn, rh, roff = synth.clade_sketches(45000, 24, 24, seed=4)
     qn, qh, qoff = synth.clade_sketches(40, 300, 24, seed=5)
     qh[: 24] = rh[: 24]  # make query 0 contain reference 0
