@@ -171,6 +171,22 @@ int rk_sketch_batch_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, cons
 int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
                             uint64_t packed_bytes, const uint64_t *gbeg, const uint64_t *gend,
                             uint32_t n_genomes, uint32_t min_count, void *stream, rk_sketches **out);
+/* What the last rk_sketch_packed_dev(_ex) call on this context did (rk_sketch_batch(_ex) end in one): the scan kernel as a
+ * profiler prints it (e.g. "rk_scan2_kernel<20, 8>", "rk_sketch_kernel<0, 0, false, 1>"), the LDS image (2 two-stage scan,
+ * 1 / 0 rk_sketch_kernel with the 64 / 144 KiB image) and whether the exact table confirms the survivors, the chunk length in
+ * 1 KiB blocks, the chunks, the workgroups launched and the ticket groups they draw from, the passes taken (2: a candidate
+ * region overflowed and the pass ran again with exact capacities), and of the last pass: the genomes sorted device-wide (region
+ * beyond the LDS sort), the largest candidate count and the largest region capacity of a genome.  Every field is host
+ * arithmetic of the call or comes home in its one read-back: the record costs no launch and no copy.  A call that scanned
+ * nothing (no chunks) leaves kernel empty and grid 0.  RK_ERR_ARG for null pointers, RK_ERR_UNSUPPORTED before the first call. */
+typedef struct rk_sketch_plan {
+    char kernel[64];
+    int32_t image, exact;
+    uint32_t chunk_blocks, n_chunks, grid, n_groups;
+    uint32_t attempts, n_big;
+    uint32_t max_candidates, max_reg_cap;
+} rk_sketch_plan;
+int rk_sketch_last_plan(const rk_ctx *ctx, rk_sketch_plan *out);
 /* host helpers for the packed layout: sizes first, then fill a caller buffer */
 int rk_pack_layout(const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_rec,
                    uint32_t n_genomes, uint64_t *gbeg, uint64_t *gend, uint64_t *packed_bytes);

@@ -22,7 +22,7 @@ EXPORTS = [
     "rk_device_count", "rk_ctx_create", "rk_ctx_destroy", "rk_ctx_trim", "rk_ctx_pool_stats", "rk_ctx_set_timing", "rk_ctx_set_single_shot", "rk_ctx_last_ms", "rk_dist_kernel_name", "rk_last_error", "rk_version",
     "rk_free_host", "rk_pinned_alloc", "rk_pinned_free", "rk_dev_alloc", "rk_dev_free", "rk_stream_create",
     "rk_stream_destroy", "rk_stream_sync", "rk_upload_async", "rk_dev_copy_async", "rk_params_init", "rk_hash_bits", "rk_filter_create", "rk_filter_free",
-    "rk_sketch_batch", "rk_sketch_batch_ex", "rk_sketch_packed_dev", "rk_sketch_packed_dev_ex", "rk_pack_layout", "rk_pack_genomes",
+    "rk_sketch_batch", "rk_sketch_batch_ex", "rk_sketch_packed_dev", "rk_sketch_packed_dev_ex", "rk_sketch_last_plan", "rk_pack_layout", "rk_pack_genomes",
     "rk_sketches_from_host", "rk_sketches_from_host64", "rk_sketches_download64", "rk_sketches_is64", "rk_sketches_from_dev", "rk_sketches_count", "rk_sketches_total", "rk_sketches_windows",
     "rk_sketches_download", "rk_sketches_hashes_dev", "rk_sketches_off_dev", "rk_sketches_free",
     "rk_index_build", "rk_index_import", "rk_index_export", "rk_index_export_lists", "rk_index_import64", "rk_index_export64", "rk_index_total",
@@ -44,6 +44,14 @@ class DistOpts(C.Structure):
     _fields_ = [("triangle", C.c_int32), ("metric", C.c_int32), ("kmer_size", C.c_int32),
                 ("row_block", C.c_int32), ("max_dist", C.c_double), ("row_first", C.c_uint32),
                 ("row_step", C.c_uint32)]
+
+
+class SketchPlan(C.Structure):
+    """rk_sketch_plan: what the last sketch call of a context did (rk_sketch_last_plan)"""
+    _fields_ = [("kernel", C.c_char * 64), ("image", C.c_int32), ("exact", C.c_int32),
+                ("chunk_blocks", C.c_uint32), ("n_chunks", C.c_uint32), ("grid", C.c_uint32),
+                ("n_groups", C.c_uint32), ("attempts", C.c_uint32), ("n_big", C.c_uint32),
+                ("max_candidates", C.c_uint32), ("max_reg_cap", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -147,6 +155,17 @@ class Context:
     def last_ms(self, which=0):
         """duration of the dominant kernel of the last pass (0: sketch kernel), HIP events on its stream"""
         return float(lib().rk_ctx_last_ms(self._h, int(which)))
+
+    def sketch_last_plan(self):
+        """the record of the last sketch call (rk_sketch_last_plan) as a dict; `kernel` is a str"""
+        L = lib()
+        L.rk_sketch_last_plan.argtypes = [C.c_void_p, C.POINTER(SketchPlan)]
+        p = SketchPlan()
+        self.check(L.rk_sketch_last_plan(self._h, C.byref(p)))
+        d = {name: int(getattr(p, name)) for name, _ in SketchPlan._fields_[1:]}
+        d["kernel"] = p.kernel.decode()
+        d["exact"] = bool(d["exact"])
+        return d
 
     def dist_kernel_name(self, index, queries, triangle, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
         opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),

@@ -49,6 +49,8 @@ struct rk_ctx {
     bool timing = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
     double last_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // RK_MS_* (include/rabbitkssd.h)
+    rk_sketch_plan sketch_plan = {};   // rk_sketch_last_plan: what the last sketch pass did
+    bool sketch_plan_set = false;
     // developer switches (environment), read once at context creation
     uint32_t sw_dist_threads = 0, sw_dist_rows = 0, sw_dist_pair = 1, sw_dist_pair_minwg = 3, sw_dist_persist = 1;
     uint32_t sw_dist_cand_cap = 0, sw_dist_stage_hits = 0, sw_dist_xcd_rows = 0;

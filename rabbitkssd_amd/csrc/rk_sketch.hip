@@ -672,8 +672,24 @@ sketch_kernel_t pick_kernel(int kmer, int out2, bool exact, int img)
 #undef RK_SK
 }
 
+// the name of what pick_kernel returns, as a profiler prints it (rk_sketch_last_plan)
+void kernel_name(char *buf, size_t cap, int kmer, int out2, bool exact, int img)
+{
+    const bool fixed = (kmer == 20 && (out2 == 8 || out2 == 6)) || (kmer == 16 && out2 == 6);
+    if (img == 2) snprintf(buf, cap, "rk_scan2_kernel<%d, %d>", kmer, out2);
+    else snprintf(buf, cap, "rk_sketch_kernel<%d, %d, %s, %d>", fixed ? kmer : 0, fixed ? out2 : 0, exact && !img ? "true" : "false", img ? 1 : 0);
+}
+
 }  // namespace
 extern "C" {
+
+int rk_sketch_last_plan(const rk_ctx *ctx, rk_sketch_plan *out)
+{
+    if (!ctx || !out) return RK_ERR_ARG;
+    if (!ctx->sketch_plan_set) return RK_ERR_UNSUPPORTED;
+    *out = ctx->sketch_plan;
+    return RK_OK;
+}
 
 int rk_filter_create(rk_ctx *ctx, const rk_params *p, const int32_t *shuffled_dim, rk_filter **out)
 {
@@ -1028,7 +1044,16 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
     DevBuf<char> sorted_out(ctx);
     std::vector<uint32_t> gcount(n_genomes, 0);
     SketchTail tail{0, 0};
+    rk_sketch_plan &plan = ctx->sketch_plan;  // rk_sketch_last_plan
+    plan = rk_sketch_plan{};
+    plan.image = f->img;
+    plan.exact = f->exact ? 1 : 0;
+    plan.chunk_blocks = (uint32_t)cb;
+    plan.n_chunks = n_chunks;
+    ctx->sketch_plan_set = true;
     for (int attempt = 0; attempt < 2; attempt++) {
+        plan.attempts = (uint32_t)attempt + 1;
+        plan.n_big = plan.max_candidates = plan.max_reg_cap = 0;
         uint64_t total_cap = 0;
         size_t small_lds = key_bytes;
         bool any_big = false;
@@ -1038,7 +1063,8 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
             size_t p2 = 1;
             while (p2 < rows[g].reg_cap) p2 <<= 1;
             rows[g].is_big = p2 * key_bytes > kDedupMaxBytes;
-            if (rows[g].is_big) any_big = true;
+            plan.max_reg_cap = std::max(plan.max_reg_cap, rows[g].reg_cap);
+            if (rows[g].is_big) { any_big = true; plan.n_big++; }
             else small_lds = std::max(small_lds, p2 * key_bytes);
         }
         if (cand.alloc(total_cap) != hipSuccess || sorted_out.alloc(total_cap * key_bytes) != hipSuccess)
@@ -1093,6 +1119,9 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
                 a.trace = d_trace.p;
             }
             if (!kern) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "no scan kernel for this parameter set");
+            kernel_name(plan.kernel, sizeof(plan.kernel), (int)P.kmer_size, 2 * P.half_outctx_len, f->exact, f->img);
+            plan.grid = grid;
+            plan.n_groups = a.n_groups;
             if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kSketchThreads), 0, stream, a);
             if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
@@ -1155,6 +1184,7 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
         memcpy(s->h_off.data(), pinned + sizeof(SketchTail), ((size_t)n_genomes + 1) * 8);
         if (n_genomes) memcpy(gcount.data(), pinned + sizeof(SketchTail) + ((size_t)n_genomes + 1) * 8, (size_t)n_genomes * 4);
         bool overflow = big_overflow || (tail.flags & kFlagOverflow) != 0;
+        for (uint32_t g = 0; g < n_genomes; g++) plan.max_candidates = std::max(plan.max_candidates, gcount[g]);
         for (uint32_t g = 0; g < n_genomes; g++)
             if (gcount[g] > rows[g].reg_cap) {
                 overflow = true;

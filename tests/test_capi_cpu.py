@@ -24,6 +24,13 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in L.rk_version()
 
 
+def test_sketch_last_plan_refuses_null_pointers():
+    L = capi.lib()
+    plan = capi.SketchPlan()
+    assert L.rk_sketch_last_plan(None, C.byref(plan)) == -1   # RK_ERR_ARG: no context (a context needs a GPU)
+    assert C.sizeof(capi.SketchPlan) == 64 + 10 * 4           # rk_sketch_plan: char[64] and ten 32-bit fields
+
+
 def test_no_gpu_means_loud_failure():
     import torch
     if torch.cuda.is_available():
