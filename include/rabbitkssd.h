@@ -17,6 +17,8 @@
  *   rk_topn_rows           <- -N max-heap of index_dist  src/dist.cpp:599,625-640,683-689
  *   rk_dist_topn           <- row loop of index_dist with -N (counting, epilogue and heap per
  *                             query row)             src/dist.cpp:560-692
+ *   rk_cluster_rows        <- row loop of index_tridist  src/dist.cpp:174-258, followed by the union-find its
+ *                             users run over the printed pairs (the reference has no clustering of its own)
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -99,6 +101,8 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 #define RK_MS_TOPN_DOWNLOAD 3
 #define RK_MS_TOPN_HOST 4
 #define RK_MS_TOPN_CANDIDATES 5
+/* rk_cluster_rows with timing on: its hook kernel alone (the last hook pass of the call). */
+#define RK_MS_CLUSTER_HOOK 6
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -428,6 +432,42 @@ int rk_topn_rows(rk_hit *hits, uint64_t *n_hits, uint64_t max_neighbor);
  * hits_out: library-allocated (rk_free_host). */
 int rk_dist_topn(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_dist_opts *opts,
                  uint64_t max_neighbor, rk_hit **hits_out, uint64_t *n_hits);
+
+/* ---- clusters --------------------------------------------------------------------- */
+/* Single-linkage clusters of the all-vs-all: the connected components of the graph whose edges are the pairs
+ * rk_dist_rows(ctx, idx, NULL, opts, ...) would report -- same metric, same strict threshold (dist < max_dist decided with the C
+ * library's log, src/dist.cpp:232), same row_first / row_step / row_block selection, any index that call accepts (the join-only
+ * index of rk_index_join_shard included).  labels_out[i] (host, rk_index_genomes(idx) entries, caller's genome order) = the
+ * SMALLEST caller index of i's component: labels_out[labels_out[i]] == labels_out[i] and labels_out[i] <= i.  The result does
+ * not depend on the order of hits, genomes or shards.
+ * The hit records never leave the device: the self join (rk_dist_rows_dev, threshold widened by 2^-46 as rk_dist_rows widens
+ * it) appends them to a device buffer of max(65,536, rows * 64) records (on overflow the join runs again with the exact count),
+ * a lock-free union-find links them in one pass, a second kernel writes the labels.  A record whose device distance lies within
+ * 2^-46 relative of the threshold is not linked on the device: it goes to a small buffer (4,096 records, RK_CLUSTER_EDGE_CAP; on
+ * overflow the linking pass alone runs again with the exact count), the host decides it with the C library's log and unites it
+ * into the labels.  PCIe traffic: 4 * N bytes of labels, the borderline records (20 bytes each, usually none) and two counters
+ * -- never O(hits); nothing is sorted.
+ * A dense report (a threshold above 1.0: every pair is a hit) is answered on the host from the row selection, without a join:
+ * all labels 0 for the whole collection; a row shard links its first row to every later genome of the internal order.
+ * -D within 2^-46 of 1.0 from below: the widening stops at 1.0 (beyond it the join would turn to the dense report).
+ * RK_ERR_ARG: triangle != 1, null pointers, an index rk_dist_rows refuses for a self join (imported, or one hash range of a
+ * sharded build).  RK_ERR_UNSUPPORTED comes from the join (rk_dist_rows_dev).  An index without genomes: RK_OK, nothing runs.
+ * stats is optional. */
+typedef struct rk_cluster_stats {
+    uint64_t edges;          /* hit records the hook pass consumed */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t hook_attempts;  /* 2: the borderline buffer overflowed once */
+    uint32_t n_clusters;     /* components, singletons included */
+    uint32_t pad_;
+} rk_cluster_stats;
+int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint32_t *labels_out /* host, N */,
+                    rk_cluster_stats *stats /* optional */);
+/* Host only: the components of the union of two partitions of n genomes, both given as label arrays of the form above, written
+ * in the same form -- what folds the labels of row shards and of GPUs into those of the collection.  out may alias a.
+ * RK_ERR_ARG for an entry >= n or null pointers. */
+int rk_cluster_merge(const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *out);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

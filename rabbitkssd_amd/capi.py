@@ -29,6 +29,7 @@ EXPORTS = [
     "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
+    "rk_cluster_rows", "rk_cluster_merge",
 ]
 
 
@@ -52,6 +53,13 @@ class SketchPlan(C.Structure):
                 ("chunk_blocks", C.c_uint32), ("n_chunks", C.c_uint32), ("grid", C.c_uint32),
                 ("n_groups", C.c_uint32), ("attempts", C.c_uint32), ("n_big", C.c_uint32),
                 ("max_candidates", C.c_uint32), ("max_reg_cap", C.c_uint32)]
+
+
+class ClusterStats(C.Structure):
+    """rk_cluster_stats: what one rk_cluster_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
+                ("join_attempts", C.c_uint32), ("hook_attempts", C.c_uint32), ("n_clusters", C.c_uint32),
+                ("pad_", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -376,6 +384,17 @@ class Context:
         lib().rk_free_host(hits)
         return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
 
+    def cluster_rows(self, index, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
+        """single-linkage clusters of the self join (rk_cluster_rows): (labels, stats) -- labels[i] = the smallest genome index
+        of i's component (uint32), stats a dict of the ClusterStats fields"""
+        opts = DistOpts(1, int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+        labels = np.zeros(index.genomes, dtype=np.uint32)
+        st = ClusterStats()
+        L = lib()
+        L.rk_cluster_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_void_p, C.POINTER(ClusterStats)]
+        self.check(L.rk_cluster_rows(self._h, index._h, C.byref(opts), _ptr(labels), C.byref(st)))
+        return labels, {name: int(getattr(st, name)) for name, _ in ClusterStats._fields_[:-1]}
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
@@ -551,6 +570,21 @@ def topn_rows(hits, max_neighbor):
     if rc:
         raise RkError(rc, "rk_topn_rows")
     return hits[: n.value]
+
+
+def cluster_merge(a, b):
+    """the components of the union of two partitions given as label arrays (rk_cluster_merge, host only)"""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("cluster_merge needs two label arrays of one length")
+    out = np.empty_like(a)
+    L = lib()
+    L.rk_cluster_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    rc = L.rk_cluster_merge(_ptr(a), _ptr(b), C.c_uint32(len(a)), _ptr(out))
+    if rc:
+        raise RkError(rc, "rk_cluster_merge: an entry beyond the number of genomes")
+    return out
 
 
 def format_hit(name_a, name_b, hit):

@@ -1205,17 +1205,34 @@ static void build_everywhere(GpuSet &set, const SketchSet &s, const string &path
     for (auto &th : pool) th.join();
 }
 
-static int cmd_alldist(const Args &a)
-{
-    if (!a.has("i")) die("alldist needs -i");
-    const double max_dist = a.real("D", 1.0);
-    if (max_dist < 0.0) die("command_alldist(), maxDist must be > 0\nUse -D to set the maxDist");
-    const string out = a.str("o", "result.out");
-    const int metric = a.num("M", 0);
-    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
-    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
-    const double t0 = get_sec();
+// What alldist and cluster share: the input (a .sketch file, or a genome list that is sketched first), the index on every GPU of
+// the set (the sharded build where it applies, the whole index everywhere otherwise) and the reference's phase lines around them.
+struct SelfJoin {
     SketchSet s;
+    vector<rk_index *> idx;   // one per GPU
+    bool sharded = false;     // idx[g] is the join-only index of GPU g's rows
+    double t1 = 0;            // start of the distance phase
+    // the options of GPU g's rows
+    rk_dist_opts opts(size_t g, size_t G, int metric, double max_dist) const
+    {
+        rk_dist_opts o{};
+        o.triangle = 1;
+        o.metric = metric;
+        o.kmer_size = 2 * s.info.half_k;
+        o.max_dist = max_dist;
+        if (G > 1 && !sharded) {   // (a join-only index of the sharded flow holds this GPU's rows and nothing else)
+            o.row_first = (uint32_t)g;
+            o.row_step = (uint32_t)G;
+            o.row_block = kRowBlock;
+        }
+        return o;
+    }
+    void prepare(const Args &a, GpuSet &set, double max_dist, int threads);
+};
+
+void SelfJoin::prepare(const Args &a, GpuSet &set, double max_dist, int threads)
+{
+    const double t0 = get_sec();
     string sketch_path;
     if (is_sketch_file(a.str("i", ""))) {  // read while the runtime starts
         string err;
@@ -1229,14 +1246,14 @@ static int cmd_alldist(const Args &a)
     // device index is always rebuilt from the sketches: faster than reading the 2^bits array
     const bool missing = !exist_file(sketch_path + ".index") || !exist_file(sketch_path + ".dict");
     const size_t G = set.size();
-    vector<rk_index *> idx(G, nullptr);
+    idx.assign(G, nullptr);
     // Several GPUs (round 5): the all-vs-all shards twice -- every GPU builds the posting lists of ITS range of the hash space, the
     // tile records change hands once (GPU d pulls what belongs to its rows over its own links), every GPU sorts what arrived and
     // joins its rows.  No index is replicated.  Taken for a power-of-two number of GPUs when the .dict / .index pair exists (writing
     // them needs the whole index on one GPU) and the collection takes the bucket sort with tile records (set sketches, 2 and more
     // genomes); anything else -- and RK_MULTI_REPLICATE=1 -- builds the whole index on every GPU as before.
     // (a dense report -- -D above 1.0: every pair -- needs counter rows over slice records, which a join-only index has not)
-    bool sharded = G > 1 && (G & (G - 1)) == 0 && !missing && !(1.0 < max_dist) && !(getenv("RK_MULTI_REPLICATE") && atoi(getenv("RK_MULTI_REPLICATE")));
+    sharded = G > 1 && (G & (G - 1)) == 0 && !missing && !(1.0 < max_dist) && !(getenv("RK_MULTI_REPLICATE") && atoi(getenv("RK_MULTI_REPLICATE")));
     if (sharded) {
         const int bits = 4 * (s.info.half_k - s.info.drlevel);
         vector<rk_index *> part(G, nullptr);
@@ -1278,21 +1295,28 @@ static int cmd_alldist(const Args &a)
     stamp("index built");
     // (the reference's phase line, src/dist.cpp:132-135: there the phase loads .dict/.index, here it builds the index on the device)
     cerr << "===================time of read index and offset sketch file is: " << get_sec() - t0 << endl;
-    const double t1 = get_sec();
+    t1 = get_sec();
     cerr << "=====total: " << s.size() << endl;
+}
+
+static int cmd_alldist(const Args &a)
+{
+    if (!a.has("i")) die("alldist needs -i");
+    const double max_dist = a.real("D", 1.0);
+    if (max_dist < 0.0) die("command_alldist(), maxDist must be > 0\nUse -D to set the maxDist");
+    const string out = a.str("o", "result.out");
+    const int metric = a.num("M", 0);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
+    SelfJoin j;
+    j.prepare(a, set, max_dist, threads);
+    const SketchSet &s = j.s;
+    const vector<rk_index *> &idx = j.idx;
+    const size_t G = set.size();
     vector<rk_hit *> hits(G, nullptr);
     vector<uint64_t> n_hits(G, 0);
     auto rows_of = [&](size_t g) {
-        rk_dist_opts o{};
-        o.triangle = 1;
-        o.metric = metric;
-        o.kmer_size = 2 * s.info.half_k;
-        o.max_dist = max_dist;
-        if (G > 1 && !sharded) {   // (a join-only index of the sharded flow holds this GPU's rows and nothing else)
-            o.row_first = (uint32_t)g;
-            o.row_step = (uint32_t)G;
-            o.row_block = kRowBlock;
-        }
+        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
         set[g].check(rk_dist_rows(set[g].ctx, idx[g], nullptr, &o, &hits[g], &n_hits[g], nullptr), "rk_dist_rows");
     };
     {
@@ -1302,7 +1326,7 @@ static int cmd_alldist(const Args &a)
         for (auto &th : pool) th.join();
     }
     stamp("distances on the host");
-    cerr << "===================time of multiple threads distance computing and save the subFile is: " << get_sec() - t1 << endl;
+    cerr << "===================time of multiple threads distance computing and save the subFile is: " << get_sec() - j.t1 << endl;
     vector<HitPart> parts(G);
     for (size_t g = 0; g < G; g++) {
         parts[g].hits = hits[g];
@@ -1314,6 +1338,69 @@ static int cmd_alldist(const Args &a)
     stamp("text written");
     // The output is on disk and the process is about to end: handing 50 MB of sketches, the hit records and the index back block
     // by block costs 4-5 ms that buy nothing (the tool's last stamp).  Straight out, like the GPU subcommands' `leave` in main.
+    stamp("done");
+    fflush(stdout);
+    fflush(stderr);
+    _exit(0);
+}
+
+// cluster: the single-linkage clusters of alldist's pairs (rk_cluster_rows on every GPU for its rows, folded with
+// rk_cluster_merge), one line per genome: cluster number (clusters ordered by their representative, the member with the smallest
+// index), cluster size, genome name; within a cluster the genomes by ascending index.
+static int cmd_cluster(const Args &a)
+{
+    if (!a.has("i")) die("cluster needs -i");
+    const double max_dist = a.real("D", 1.0);
+    if (max_dist < 0.0) die("command_cluster(), maxDist must be > 0\nUse -D to set the maxDist");
+    const string out = a.str("o", "result.out");
+    const int metric = a.num("M", 0);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
+    SelfJoin j;
+    j.prepare(a, set, max_dist, threads);
+    const size_t G = set.size(), N = j.s.size();
+    vector<vector<uint32_t>> labels(G, vector<uint32_t>(N ? N : 1));
+    vector<rk_cluster_stats> stats(G);
+    auto rows_of = [&](size_t g) {
+        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
+        set[g].check(rk_cluster_rows(set[g].ctx, j.idx[g], &o, labels[g].data(), &stats[g]), "rk_cluster_rows");
+    };
+    {
+        vector<std::thread> pool;
+        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
+        rows_of(0);
+        for (auto &th : pool) th.join();
+    }
+    for (size_t g = 1; g < G; g++)
+        if (rk_cluster_merge(labels[0].data(), labels[g].data(), (uint32_t)N, labels[0].data()) != 0) die("rk_cluster_merge failed");
+    stamp("clusters on the host");
+    cerr << "===================time of multiple threads distance computing and clustering is: " << get_sec() - j.t1 << endl;
+    const vector<uint32_t> &lab = labels[0];
+    // members by cluster, clusters by representative: a counting sort over the labels (label[i] <= i, a representative labels itself)
+    vector<uint32_t> number(N, 0), size(N, 0), start(N + 1, 0), order(N);
+    uint32_t n_clusters = 0;
+    for (size_t i = 0; i < N; i++) size[lab[i]]++;
+    for (size_t i = 0; i < N; i++) {
+        start[i + 1] = start[i] + size[i];
+        if (lab[i] == i) number[i] = n_clusters++;
+    }
+    {
+        vector<uint32_t> at(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < N; i++) order[at[lab[i]]++] = (uint32_t)i;
+    }
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    for (size_t k = 0; k < N; k++) {
+        const uint32_t i = order[k], rep = lab[i];
+        fprintf(fp, "%u\t%u\t%s\n", number[rep], size[rep], j.s.names[i].c_str());
+    }
+    fclose(fp);
+    if (getenv("RK_TIMING")) {
+        unsigned long long edges = 0, border = 0;
+        for (size_t g = 0; g < G; g++) { edges += stats[g].edges; border += stats[g].borderline; }
+        fprintf(stderr, "[timing] %u clusters of %zu genomes from %llu hit records (%llu borderline)\n", n_clusters, N, edges, border);
+    }
+    stamp("text written");
     stamp("done");
     fflush(stdout);
     fflush(stderr);
@@ -1705,10 +1792,11 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
+            "  cluster -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (single-linkage clusters of alldist's pairs)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -1747,7 +1835,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -1765,6 +1853,7 @@ int main(int argc, char **argv)
     };
     if (sub == "sketch") { cerr << "-----run the subcommand: sketch" << endl; return leave(cmd_sketch(parse_args(argc, argv, 2, alias, {"q"}))); }
     if (sub == "alldist") { cerr << "-----run the subcommand: alldist" << endl; return leave(cmd_alldist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "cluster") { cerr << "-----run the subcommand: cluster" << endl; return leave(cmd_cluster(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
