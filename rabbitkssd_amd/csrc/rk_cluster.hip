@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "rk_internal.h"
+#include "rk_dist_plan.h"
 
 namespace {
 
@@ -143,10 +144,8 @@ unsigned grid_for(const rk_ctx *ctx, uint64_t items)
 int cluster_dense(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, uint32_t *labels)
 {
     const uint32_t N = idx->n_ref;
-    const uint64_t row_step = o->row_step ? o->row_step : 1;
-    uint64_t row_block = o->row_block > 0 ? (uint64_t)o->row_block : 1;
-    if (row_step == 1 && o->row_first == 0) row_block = N;
-    const uint64_t first = (uint64_t)o->row_first * row_block;   // the first row of the first block of this shard
+    const RowShard rows(o, N, N);
+    const uint64_t first = (uint64_t)rows.row_first * rows.row_block;   // the first row of the first block of this shard
     std::iota(labels, labels + N, 0u);
     if (first + 1 >= N) return RK_OK;   // no selected row with a column behind it
     if (first == 0) {
@@ -176,9 +175,7 @@ int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, 
     const uint32_t N = idx->n_ref;
     if (!N) return RK_OK;
     if (!labels_out) return rk_fail(ctx, RK_ERR_ARG, "labels_out is null");
-    if (!idx->d_src_off) return rk_fail(ctx, RK_ERR_ARG, "queries == NULL needs triangle=1 and an index built by rk_index_build");
-    if (idx->n_shards > 1)
-        return rk_fail(ctx, RK_ERR_ARG, "a shard of a sharded build holds the lists of one hash range: join through rk_index_join_shard");
+    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
     RK_HIP(ctx, hipSetDevice(ctx->device));
     if (rk_dense_mode(opts)) {
         if (!idx->d_selfrange && (idx->slices_refused || idx->H >= (1ULL << 30)))   // (what the join itself answers for a dense report over such an index)
@@ -196,12 +193,7 @@ int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, 
     const double link_below = opts->max_dist > 0.0 ? opts->max_dist - opts->max_dist * kBorderRel : opts->max_dist;
     hipStream_t stream = ctx->stream;
 
-    const uint64_t row_step = opts->row_step ? opts->row_step : 1;
-    uint64_t row_block = opts->row_block > 0 ? (uint64_t)opts->row_block : 1;
-    if (row_step == 1 && opts->row_first == 0) row_block = N;
-    uint64_t n_sel = 0;   // rows of this shard, as rk_dist_rows counts them
-    for (uint64_t blk = opts->row_first; blk * row_block < N; blk += row_step) n_sel += std::min<uint64_t>(N, (blk + 1) * row_block) - blk * row_block;
-    uint64_t cap = std::max<uint64_t>(1 << 16, n_sel * 64);
+    uint64_t cap = rk_hit_capacity(RowShard(opts, N, N).n_rows());   // (the rows of this shard, as rk_dist_rows counts them)
     uint64_t edge_cap = kEdgeCapDefault;
     if (const char *e = getenv("RK_CLUSTER_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
 

@@ -31,6 +31,7 @@
 
 #include "rk_internal.h"
 #include "rk_dist_common.h"
+#include "rk_dist_plan.h"
 
 namespace {
 
@@ -825,7 +826,8 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 || THREADS == 768) ? 6 : 4
 struct Plan {
     uint32_t n_units, tile_cols, n_tiles, cnt_words, row_words;
     uint32_t cand_cap, stage_hits, units_per_wg, threads;
-    uint32_t row_first, row_step, row_block, units_per_block;
+    RowShard rows;  // row distribution: blocks of row_block rows dealt round-robin to row_step shards
+    uint32_t units_per_block;
     uint32_t slot_base, col_base;  // a band of the self join: its first unit slot and the first column of its LDS rows
     bool persist;
     size_t lds_bytes;
@@ -876,24 +878,19 @@ int make_plan(rk_ctx *ctx, const rk_index *idx, uint32_t n_query, uint64_t max_q
     p->row_words = ((p->u16 ? (tile + 1) / 2 : tile) + 3) & ~3u;  // whole 16-byte quads
 
     // row distribution: blocks of row_block rows dealt round-robin to row_step shards
-    p->row_step = o->row_step ? o->row_step : 1;
-    p->row_first = o->row_first;
-    p->row_block = o->row_block > 0 ? (uint32_t)o->row_block : 1;
-    if (p->row_step == 1 && p->row_first == 0) p->row_block = kRowsPerXcdChunk;  // all rows: every block is this shard's
+    p->rows = RowShard(o, n_query, kRowsPerXcdChunk);  // all rows: every block is this shard's
     p->mode = want_self && p->n_tiles == 1 ? kSelf : kFiltered;
     // pairs of neighbouring rows: blocks must hold whole pairs and two rows must fit in LDS next to
     // each other with room for at least three workgroups per CU (measured: with fewer, the lost
     // occupancy costs more than the saved walks: 14,142 columns 0.127 ms paired vs 0.113 single)
     // (pairs rest on set semantics: with a repeated hash inside a genome the "covered" test of the index build fails)
-    const bool pair_ok = allow_pair && p->mode == kSelf && p->row_block % 2 == 0 && idx->d_self_split && idx->ref_sets &&
+    const bool pair_ok = allow_pair && p->mode == kSelf && p->rows.row_block % 2 == 0 && idx->d_self_split && idx->ref_sets &&
                          (size_t)p->row_words * 8 + fixed + batch_extra <= lds_for_workgroups(std::max(1u, ctx->sw_dist_pair_minwg)) &&
                          ctx->sw_dist_pair != 2;
     if (pair_ok) p->mode = kSelfPair;
     const uint32_t unit_rows = p->mode == kSelfPair ? 2 : 1;
-    p->units_per_block = p->row_block / unit_rows;
-    const uint64_t n_blocks = ((uint64_t)n_query + p->row_block - 1) / p->row_block;
-    const uint64_t my_blocks = p->row_first < n_blocks ? (n_blocks - p->row_first + p->row_step - 1) / p->row_step : 0;
-    p->n_units = (uint32_t)std::min<uint64_t>(my_blocks * p->units_per_block, 0xFFFFFFF0u);
+    p->units_per_block = p->rows.row_block / unit_rows;
+    p->n_units = (uint32_t)std::min<uint64_t>(p->rows.my_blocks() * p->units_per_block, 0xFFFFFFF0u);
     p->cnt_words = p->row_words * unit_rows;
     if (p->mode != kSelfPair && small_rows) {  // 7 workgroups of 256 threads per CU, not persistent
         p->persist = false;
@@ -937,9 +934,9 @@ int launch_dist(rk_ctx *ctx, const rk_index *idx, const uint2 *ranges, const uin
     a.orig = idx->relabeled ? idx->d_orig : nullptr;
     a.n_query = n_query;
     a.n_ref = idx->n_ref;
-    a.row_first = p.row_first;
-    a.row_step = p.row_step;
-    a.row_block = p.row_block;
+    a.row_first = p.rows.row_first;
+    a.row_step = p.rows.row_step;
+    a.row_block = p.rows.row_block;
     a.units_per_block = p.units_per_block;
     a.n_units = p.n_units;
     a.slot_base = p.slot_base;
@@ -952,14 +949,8 @@ int launch_dist(rk_ctx *ctx, const rk_index *idx, const uint2 *ranges, const uin
     a.kmer_size = o->kmer_size;
     a.dense_mode = p.dense_mode;
     a.max_dist = o->max_dist;
-    // distance < D  <=>  jaccard > t/(2-t), t = exp(-k D)   (containment: c > t); 1e-6 relative slack
-    // keeps the reject conservative, the exact formula still decides.  Disabled in dense mode.
-    a.min_jorc = 0.0;
+    a.min_jorc = !p.dense_mode && o->max_dist > 0.0 ? rk_min_jorc(o) : 0.0;  // (the prefilter: disabled in dense mode)
     a.min_ref_size = (uint32_t)std::min<uint64_t>(idx->min_ref_size, 0xFFFFFFFFu);
-    if (!p.dense_mode && o->max_dist > 0.0) {
-        const double t = exp(-(double)o->kmer_size * o->max_dist);
-        a.min_jorc = (a.metric ? t : t / (2.0 - t)) * (1.0 - 1e-6);
-    }
     a.hits = hits_dev;
     a.cap = cap;
     a.n_hits = n_hits_dev;
@@ -1025,10 +1016,10 @@ int plan_bands(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, bool den
     int rc = make_plan(ctx, idx, n, idx->max_src_size, o, dense_mode, true, n, &cur);
     if (rc) return rc;
     bands->clear();
-    const uint64_t round_rows = (uint64_t)cur.row_step * cur.row_block;  // one block of every shard
+    const uint64_t round_rows = (uint64_t)cur.rows.row_step * cur.rows.row_block;  // one block of every shard
     const uint64_t n_rounds = ((uint64_t)n + round_rows - 1) / round_rows;
     // a band must be worth its launch (ramp-up, the tail of its last round): at least sw_dist_band_min_rows rows of THIS shard
-    const uint64_t min_rounds = std::max<uint64_t>(1, ((uint64_t)ctx->sw_dist_band_min_rows + cur.row_block - 1) / cur.row_block);
+    const uint64_t min_rounds = std::max<uint64_t>(1, ((uint64_t)ctx->sw_dist_band_min_rows + cur.rows.row_block - 1) / cur.rows.row_block);
     auto plan_at = [&](uint64_t round, Plan *q) -> int {
         const uint64_t row = round * round_rows;
         const uint32_t col_base = (uint32_t)row & ~63u;  // whole 128-byte stretches of a 16-bit row
@@ -1059,43 +1050,39 @@ int plan_bands(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, bool den
     }
     cur.n_units = cur.n_units > cur.slot_base ? cur.n_units - cur.slot_base : 0;  // to the end of the shard
     bands->push_back(cur);
-    if (ctx->sw_dist_debug)
-        for (const Plan &b : *bands)
-            fprintf(stderr, "[rk] band: columns from %u, units %u from slot %u, kernel <%s, %d, %u>, %zu B LDS, %u tile(s)\n", b.col_base,
-                    b.n_units, b.slot_base, b.u16 ? "u16" : "u32", b.mode, b.threads, b.lds_bytes, b.n_tiles);
     return RK_OK;
+}
+void print_bands(const std::vector<Plan> &bands)   // RK_DIST_DEBUG: once per plan that is launched or named
+{
+    for (const Plan &b : bands)
+        fprintf(stderr, "[rk] band: columns from %u, units %u from slot %u, kernel <%s, %d, %u>, %zu B LDS, %u tile(s)\n", b.col_base,
+                b.n_units, b.slot_base, b.u16 ? "u16" : "u32", b.mode, b.threads, b.lds_bytes, b.n_tiles);
 }
 
 // The near-window self join (rk_dist_near.inc) applies when the report is sparse, the sketches are sets (compact slices
-// exist) and a reportable pair needs a count the handful of chance hashes of a row cannot reach.
+// exist, or are made on first use: plan_self answers for them) and a reportable pair needs a count the handful of chance
+// hashes of a row cannot reach.
 struct NearPlan {
     bool use = false, pair = false;
     int uw = 1;             // waves that share a unit
     uint32_t grid = 0;
-    uint32_t row_first, row_step, row_block, units_per_block, n_units;
+    RowShard rows;
+    uint32_t units_per_block, n_units;
     double min_jorc = 0.0;
 };
-NearPlan plan_near(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, bool dense_mode)
+NearPlan plan_near(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, bool dense_mode, double min_jorc)
 {
     NearPlan np;
-    if (!ctx->sw_dist_near || dense_mode || !idx->ref_sets || !idx->d_selfrange || !idx->d_self_split || !idx->n_ref || o->kmer_size <= 0 ||
-        o->row_block < 0 || !(o->max_dist > 0.0))
+    if (!ctx->sw_dist_near || dense_mode || !idx->ref_sets || !idx->n_ref || o->kmer_size <= 0 || o->row_block < 0 || !(o->max_dist > 0.0))
         return np;
-    const int metric = o->metric != 0;
-    const double t = exp(-(double)o->kmer_size * o->max_dist);
-    np.min_jorc = (metric ? t : t / (2.0 - t)) * (1.0 - 1e-6);
+    np.min_jorc = min_jorc;
     // the smallest count a reportable pair of the SMALLEST sketch needs: below ~16 the chance hashes of a row reach it too
     // often and every unit would fall back (a loose -D: rk_dist_kernel alone is the better plan)
     if (floor(np.min_jorc * (double)idx->min_ref_size) < (double)ctx->sw_dist_near_min) return np;
-    np.row_step = o->row_step ? o->row_step : 1;
-    np.row_first = o->row_first;
-    np.row_block = o->row_block > 0 ? (uint32_t)o->row_block : 1;
-    if (np.row_step == 1 && np.row_first == 0) np.row_block = kRowsPerXcdChunk;  // all rows: every block is this shard's
-    np.pair = np.row_block % 2 == 0 && ctx->sw_dist_pair != 2;
-    np.units_per_block = np.row_block / (np.pair ? 2 : 1);
-    const uint64_t n_blocks = ((uint64_t)idx->n_ref + np.row_block - 1) / np.row_block;
-    const uint64_t my_blocks = np.row_first < n_blocks ? (n_blocks - np.row_first + np.row_step - 1) / np.row_step : 0;
-    np.n_units = (uint32_t)std::min<uint64_t>(my_blocks * np.units_per_block, 0xFFFFFFF0u);
+    np.rows = RowShard(o, idx->n_ref, kRowsPerXcdChunk);  // all rows: every block is this shard's
+    np.pair = np.rows.row_block % 2 == 0 && ctx->sw_dist_pair != 2;
+    np.units_per_block = np.rows.row_block / (np.pair ? 2 : 1);
+    np.n_units = (uint32_t)std::min<uint64_t>(np.rows.my_blocks() * np.units_per_block, 0xFFFFFFF0u);
     // waves per unit: one, unless the launch has fewer units than an eighth of the chip's wave slots -- then two share a
     // unit's steps (measured, 8,192 slots: 3,125 units 0.031 / 0.038 / 0.044 ms with 1 / 2 / 4 waves per unit, 625 units
     // 0.020 / 0.015 / 0.017 ms)
@@ -1123,39 +1110,10 @@ __global__ void k_count_flagged(const uint2 *selfrange, uint64_t n_self, unsigne
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(acc, mine);
 }
 
-// Which kernel takes a sparse self join over set sketches -- decided by the index's SIZE AND SHAPE and the options alone, never
-// by how often the index was joined before (until round 4 a resident index moved to the tile kernel at its second join: a
-// benchmark loop and a user got different kernels):
-//   * the index carries tile records (rk_index_build emits them from RK_DIST_TILES_MIN_GENOMES genomes on, rk_index_tiles.inc;
-//     or an earlier launch built them lazily): the tile kernel -- except for small row shards of an index that ALSO has slice
-//     records (a tile costs the same whatever the shard: the near-window kernel is the faster one below ~12,000 rows);
-//   * no slice records (2^31 postings and more): the tile kernel, records built lazily;
-//   * a sketch so small -- or a threshold so loose -- that rk_near_kernel's bound on the cells beyond its window cannot hold, or
-//     clusters wider than its window (known from the build's slice records): the tile kernel, records built lazily;
-//   * a completed launch of rk_near_kernel found rows in its fallback list (clusters a little wider than the window, which the
-//     build cannot see): the tile kernel from then on -- the one rule that looks at an earlier launch, and only at its RESULT;
-//   * RK_DIST_TILES=1 always, RK_DIST_TILES=0 never.
-int self_uses_tiles(rk_ctx *ctx, const rk_index *cidx, const rk_dist_opts *o, bool dense_mode, hipStream_t stream, bool *use)
+// clusters wider than the window of rk_near_kernel: many such records (counted once per index, unless the build did), or a
+// completed launch of rk_near_kernel that found rows in its fallback list
+int near_window_too_narrow(rk_ctx *ctx, const rk_index *cidx, hipStream_t stream, bool *too_narrow)
 {
-    *use = false;
-    if (dense_mode || !cidx->ref_sets || ((!cidx->d_postings || !cidx->d_upos) && !cidx->tiles_ready) || !cidx->d_src_off || !cidx->n_ref || o->kmer_size <= 0 ||
-        o->row_block < 0 || !(o->max_dist > 0.0) || cidx->tiles_unusable)
-        return RK_OK;   // (a join-only index -- rk_index_join_shard -- has tile records and no postings)
-    const bool can_rows = cidx->d_selfrange || (!cidx->slices_refused && cidx->H < (1ULL << 30));   // (slice records exist or can be made: rk_index_ensure_slices)
-    if (!ctx->sw_dist_tiles && can_rows) return RK_OK;
-    if (ctx->sw_dist_tiles == 1 || !can_rows) { *use = true; return RK_OK; }
-    if (!ctx->sw_dist_near) return RK_OK;   // (RK_DIST_NEAR=0 asks for the kernels with counter rows)
-    if (cidx->tiles_ready) {
-        const uint32_t step = o->row_step > 1 ? o->row_step : 1;
-        const bool small_shard = step > 2 && cidx->n_ref / step < (uint32_t)ctx->sw_dist_tiles_min_shard_rows;
-        *use = !(small_shard && cidx->d_selfrange);
-        return RK_OK;
-    }
-    {   // a sketch so small that the chance hashes of a row reach its threshold: rk_near_kernel would send every row to its fallback
-        const double t = exp(-(double)o->kmer_size * o->max_dist);
-        const double min_jorc = ((o->metric != 0) ? t : t / (2.0 - t)) * (1.0 - 1e-6);
-        if (floor(min_jorc * (double)cidx->min_ref_size) < (double)ctx->sw_dist_near_min) { *use = true; return RK_OK; }
-    }
     rk_index *idx = const_cast<rk_index *>(cidx);
     std::lock_guard<std::mutex> lk(idx->lazy_mu);
     if (!idx->spread_known) {
@@ -1173,8 +1131,73 @@ int self_uses_tiles(rk_ctx *ctx, const rk_index *cidx, const rk_dist_opts *o, bo
         idx->spread = flagged * 8 > idx->n_self;
         idx->spread_known = 1;
     }
-    *use = idx->spread || idx->fb_state == 3;
+    *too_narrow = idx->spread || idx->fb_state == 3;
     return RK_OK;
+}
+
+// The plan of a self join: the kernel, its launch shape, and what the launch must make first.  plan_self is the ONE place that
+// decides it -- launch_self launches what it says, rk_dist_kernel_name prints it -- from the index's current state; it builds
+// nothing (the cached count above is its only trace).
+struct SelfPlan {
+    enum Kind { kTiles, kNear, kBands } kind = kBands;
+    bool need_tiles = false, need_slices = false;   // a lazy product the launch must make first (and then plan again)
+    double min_jorc = 0.0;
+    TileShape tile;            // kTiles, once the records exist
+    NearPlan near;             // kNear
+    std::vector<Plan> bands;   // kBands
+};
+
+// Which kernel takes a sparse self join over set sketches -- decided by the index's SIZE AND SHAPE and the options alone, never
+// by how often the index was joined before (until round 4 a resident index moved to the tile kernel at its second join: a
+// benchmark loop and a user got different kernels):
+//   * the index carries tile records (rk_index_build emits them from RK_DIST_TILES_MIN_GENOMES genomes on, rk_index_tiles.inc;
+//     or an earlier launch built them lazily): the tile kernel -- except for small row shards of an index that ALSO has slice
+//     records (a tile costs the same whatever the shard: the near-window kernel is the faster one below ~12,000 rows);
+//   * no slice records (2^31 postings and more): the tile kernel, records built lazily;
+//   * a sketch so small -- or a threshold so loose -- that rk_near_kernel's bound on the cells beyond its window cannot hold, or
+//     clusters wider than its window (known from the build's slice records): the tile kernel, records built lazily;
+//   * a completed launch of rk_near_kernel found rows in its fallback list (clusters a little wider than the window, which the
+//     build cannot see): the tile kernel from then on -- the one rule that looks at an earlier launch, and only at its RESULT;
+//   * RK_DIST_TILES=1 always, RK_DIST_TILES=0 never.
+int plan_self(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, bool dense_mode, hipStream_t stream, SelfPlan *sp)
+{
+    sp->need_tiles = sp->need_slices = false;
+    sp->min_jorc = o->max_dist > 0.0 ? rk_min_jorc(o) : 0.0;
+    const bool can_rows = idx->d_selfrange || (!idx->slices_refused && idx->H < (1ULL << 30));   // (slice records exist or can be made: rk_index_ensure_slices)
+    // (a join-only index -- rk_index_join_shard -- has tile records and no postings)
+    const bool sparse_sets = !dense_mode && idx->ref_sets && ((idx->d_postings && idx->d_upos) || idx->tiles_ready) && idx->d_src_off && idx->n_ref &&
+                             o->kmer_size > 0 && o->row_block >= 0 && o->max_dist > 0.0 && !idx->tiles_unusable;
+    bool tiles = false;
+    if (!sparse_sets || (!ctx->sw_dist_tiles && can_rows)) tiles = false;
+    else if (ctx->sw_dist_tiles == 1 || !can_rows) tiles = true;
+    else if (!ctx->sw_dist_near) tiles = false;   // (RK_DIST_NEAR=0 asks for the kernels with counter rows)
+    else if (idx->tiles_ready) {
+        const uint32_t step = o->row_step > 1 ? o->row_step : 1;
+        const bool small_shard = step > 2 && idx->n_ref / step < (uint32_t)ctx->sw_dist_tiles_min_shard_rows;
+        tiles = !(small_shard && idx->d_selfrange);
+    } else if (floor(sp->min_jorc * (double)idx->min_ref_size) < (double)ctx->sw_dist_near_min) {
+        tiles = true;   // a sketch so small that the chance hashes of a row reach its threshold: rk_near_kernel would send every row to its fallback
+    } else {
+        int rc = near_window_too_narrow(ctx, idx, stream, &tiles);
+        if (rc) return rc;
+    }
+    if (tiles) {
+        sp->kind = SelfPlan::kTiles;
+        sp->need_tiles = !idx->tiles_ready;   // (the variant follows the launch size, which needs the tile directory)
+        if (!sp->need_tiles) sp->tile = tile_launch_shape(idx, o, sp->min_jorc);
+        return RK_OK;
+    }
+    if (!idx->d_selfrange) {   // the row kernels read slice records: an index built with tile records gets them on first use
+        if (!can_rows)
+            return rk_fail(ctx, RK_ERR_UNSUPPORTED, "this index has no slice records (2^31 postings or more): only sparse self joins (a threshold "
+                                                    "below distance 1.0) over set sketches run on it%s", idx->tiles_unusable ? ", and its tile records "
+                                                    "exceed the memory budget (lists scattered over thousands of genomes)" : "");
+        sp->need_slices = true;
+    }
+    const bool slices_coming = sp->need_slices && idx->d_src_off && idx->wide == (idx->d_uhash64 != nullptr);   // (what rk_index_ensure_slices asks, with ref_sets)
+    sp->near = slices_coming || idx->d_self_split ? plan_near(ctx, idx, o, dense_mode, sp->min_jorc) : NearPlan();
+    sp->kind = sp->near.use ? SelfPlan::kNear : SelfPlan::kBands;
+    return sp->near.use ? RK_OK : plan_bands(ctx, idx, o, dense_mode, &sp->bands);
 }
 
 // the fallback list of an index (allocated and zeroed once)
@@ -1193,119 +1216,124 @@ int ensure_fallback(rk_ctx *ctx, rk_index *idx, hipStream_t stream)
     return RK_OK;
 }
 
+int launch_near(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, const NearPlan &np, rk_hit *hits_dev, uint64_t cap,
+                unsigned long long *n_hits_dev, hipStream_t stream)
+{
+    NearArgs a;
+    a.ranges = idx->d_selfrange;
+    a.range_off = idx->d_self_off;
+    a.range_split = idx->d_self_split;
+    a.size_off = idx->d_src_off;
+    a.postings = idx->d_postings;
+    a.ref_sizes = idx->d_sizes;
+    a.orig = idx->relabeled ? idx->d_orig : nullptr;
+    a.n_ref = idx->n_ref;
+    a.row_first = np.rows.row_first;
+    a.row_step = np.rows.row_step;
+    a.row_block = np.rows.row_block;
+    a.units_per_block = np.units_per_block;
+    a.n_units = np.n_units;
+    a.metric = o->metric != 0;
+    a.kmer_size = o->kmer_size;
+    a.max_dist = o->max_dist;
+    a.min_jorc = np.min_jorc;
+    a.min_ref_size = (uint32_t)std::min<uint64_t>(idx->min_ref_size, 0xFFFFFFFFu);
+    a.hits = hits_dev;
+    a.cap = cap;
+    a.n_hits = n_hits_dev;
+    a.fb_count = idx->d_fb;
+    a.fb_rows = idx->d_fb + 4;
+    a.stage_hits = kNearStage;
+    a.debug = getenv("RK_NEAR_DEBUG") ? atoi(getenv("RK_NEAR_DEBUG")) : 0;
+#define RK_NEAR(P, U) hipLaunchKernelGGL((rk_near_kernel<P, U>), dim3(np.grid), dim3(kNearThreads), 0, stream, a)
+    if (np.pair) { if (np.uw == 1) RK_NEAR(true, 1); else if (np.uw == 2) RK_NEAR(true, 2); else RK_NEAR(true, 4); }
+    else { if (np.uw == 1) RK_NEAR(false, 1); else if (np.uw == 2) RK_NEAR(false, 2); else RK_NEAR(false, 4); }
+#undef RK_NEAR
+    RK_HIP(ctx, hipGetLastError());
+    return RK_OK;
+}
+
+// The gate of the fallback launch (rk_internal.h, fb_state): skip it once a completed launch with these very options has shown
+// the list to be empty; arm: this launch is the one whose completion will tell.
+struct FbGate { unsigned char key[sizeof(rk_index::fb_key)] = {0}; bool skip = false, arm = false; };
+FbGate fb_gate_begin(rk_ctx *ctx, rk_index *mut, const rk_dist_opts *o, bool dense_mode)
+{
+    FbGate g;
+    static_assert(sizeof(rk_dist_opts) + 1 <= sizeof g.key, "key holds the options and the report mode");
+    memcpy(g.key, o, sizeof(rk_dist_opts));
+    g.key[sizeof(rk_dist_opts)] = dense_mode ? 1 : 0;
+    if (ctx->sw_dist_fb_skip && mut->h_fb_seen) {
+        std::lock_guard<std::mutex> lk(mut->lazy_mu);
+        if (memcmp(g.key, mut->fb_key, sizeof g.key) != 0) {
+            memcpy(mut->fb_key, g.key, sizeof g.key);
+            mut->fb_state = 0;
+        }
+        if (mut->fb_state == 1) {
+            const hipError_t qe = hipEventQuery((hipEvent_t)mut->fb_event);
+            if (qe == hipSuccess) mut->fb_state = *(volatile uint32_t *)mut->h_fb_seen == 0 ? 2 : 3;
+            else (void)hipGetLastError();  // hipErrorNotReady is sticky for hipGetLastError
+        }
+        g.skip = mut->fb_state == 2;
+        if (mut->fb_state == 0) {
+            if (!mut->fb_event) {
+                hipEvent_t ev;
+                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem) == hipSuccess) mut->fb_event = ev;
+                else (void)hipGetLastError();
+            }
+            g.arm = mut->fb_event != nullptr;
+        }
+    }
+    return g;
+}
+void fb_gate_armed(rk_index *mut, const FbGate &g, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lk(mut->lazy_mu);
+    if (mut->fb_state == 0 && memcmp(g.key, mut->fb_key, sizeof g.key) == 0 &&
+        hipEventRecord((hipEvent_t)mut->fb_event, stream) == hipSuccess) mut->fb_state = 1;
+}
+
+// rk_near_kernel, then the rows whose far cells could be reportable (usually none): full counter rows, single rows, all columns
+int launch_near_and_fallback(rk_ctx *ctx, rk_index *mut, const rk_dist_opts *o, bool dense_mode, const NearPlan &np, rk_hit *hits_dev,
+                             uint64_t cap, unsigned long long *n_hits_dev, hipStream_t stream)
+{
+    int rc = ensure_fallback(ctx, mut, stream);
+    if (!rc && np.n_units) rc = launch_near(ctx, mut, o, np, hits_dev, cap, n_hits_dev, stream);
+    if (rc) return rc;
+    const FbGate gate = fb_gate_begin(ctx, mut, o, dense_mode);
+    if (gate.skip) return RK_OK;
+    Plan fp;
+    rk_dist_opts all = *o;
+    all.row_first = 0;
+    all.row_step = 1;
+    rc = make_plan(ctx, mut, mut->n_ref, mut->max_src_size, &all, false, true, mut->n_ref, &fp, false);
+    if (rc) return rc;
+    rc = launch_dist(ctx, mut, mut->d_selfrange, mut->d_self_off, mut->d_src_off, mut->n_ref, o, fp, hits_dev, cap, n_hits_dev,
+                     nullptr, stream, mut->d_fb);
+    if (!rc && gate.arm) fb_gate_armed(mut, gate, stream);
+    return rc;
+}
+
 int launch_self(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, bool dense_mode, rk_hit *hits_dev, uint64_t cap,
                 unsigned long long *n_hits_dev, hipStream_t stream)
 {
-    bool tiles = false;
-    {
-        int rc = self_uses_tiles(ctx, idx, o, dense_mode, stream, &tiles);
-        if (rc) return rc;
+    rk_index *mut = const_cast<rk_index *>(idx);   // the lazy products and the state of the fallback list live in the index
+    SelfPlan sp;
+    int rc = plan_self(ctx, idx, o, dense_mode, stream, &sp);
+    if (!rc && sp.need_tiles) {   // the plan stands once the records exist (a small row shard too: they are not built in vain) ...
+        rc = rk_tiles_build(ctx, mut, stream);
+        if (!rc && !idx->tiles_unusable) sp.tile = tile_launch_shape(idx, o, sp.min_jorc);
+        else if (!rc) rc = plan_self(ctx, idx, o, dense_mode, stream, &sp);   // ... unless they exceed the builder's budget: one of the row kernels
     }
-    if (tiles) {
-        int rc = rk_tiles_build(ctx, const_cast<rk_index *>(idx), stream);   // (a no-op for an index whose build emitted them)
-        if (rc) return rc;
-        if (!idx->tiles_unusable) {
-            const double t = exp(-(double)o->kmer_size * o->max_dist);
-            const double min_jorc = ((o->metric != 0) ? t : t / (2.0 - t)) * (1.0 - 1e-6);
-            return launch_tiles(ctx, idx, o, min_jorc, hits_dev, cap, n_hits_dev, stream);
-        }
+    if (!rc && sp.need_slices) {
+        rc = rk_index_ensure_slices(ctx, mut, stream);
+        if (!rc) rc = plan_self(ctx, idx, o, dense_mode, stream, &sp);
     }
-    if (!idx->d_selfrange) {   // the row kernels read slice records: an index built with tile records gets them on first use
-        if (idx->slices_refused || idx->H >= (1ULL << 30))
-            return rk_fail(ctx, RK_ERR_UNSUPPORTED, "this index has no slice records (2^31 postings or more): only sparse self joins (a threshold "
-                                                    "below distance 1.0) over set sketches run on it%s", idx->tiles_unusable ? ", and its tile records "
-                                                    "exceed the memory budget (lists scattered over thousands of genomes)" : "");
-        int rc = rk_index_ensure_slices(ctx, const_cast<rk_index *>(idx), stream);
-        if (rc) return rc;
-    }
-    const NearPlan np = plan_near(ctx, idx, o, dense_mode);
-    if (np.use) {
-        int rc = ensure_fallback(ctx, const_cast<rk_index *>(idx), stream);
-        if (rc) return rc;
-        if (np.n_units) {
-            NearArgs a;
-            a.ranges = idx->d_selfrange;
-            a.range_off = idx->d_self_off;
-            a.range_split = idx->d_self_split;
-            a.size_off = idx->d_src_off;
-            a.postings = idx->d_postings;
-            a.ref_sizes = idx->d_sizes;
-            a.orig = idx->relabeled ? idx->d_orig : nullptr;
-            a.n_ref = idx->n_ref;
-            a.row_first = np.row_first;
-            a.row_step = np.row_step;
-            a.row_block = np.row_block;
-            a.units_per_block = np.units_per_block;
-            a.n_units = np.n_units;
-            a.metric = o->metric != 0;
-            a.kmer_size = o->kmer_size;
-            a.max_dist = o->max_dist;
-            a.min_jorc = np.min_jorc;
-            a.min_ref_size = (uint32_t)std::min<uint64_t>(idx->min_ref_size, 0xFFFFFFFFu);
-            a.hits = hits_dev;
-            a.cap = cap;
-            a.n_hits = n_hits_dev;
-            a.fb_count = idx->d_fb;
-            a.fb_rows = idx->d_fb + 4;
-            a.stage_hits = kNearStage;
-            a.debug = getenv("RK_NEAR_DEBUG") ? atoi(getenv("RK_NEAR_DEBUG")) : 0;
-            const int uw = np.uw;
-            const uint32_t grid = np.grid;
-#define RK_NEAR(P, U) hipLaunchKernelGGL((rk_near_kernel<P, U>), dim3(grid), dim3(kNearThreads), 0, stream, a)
-            if (np.pair) { if (uw == 1) RK_NEAR(true, 1); else if (uw == 2) RK_NEAR(true, 2); else RK_NEAR(true, 4); }
-            else { if (uw == 1) RK_NEAR(false, 1); else if (uw == 2) RK_NEAR(false, 2); else RK_NEAR(false, 4); }
-#undef RK_NEAR
-            RK_HIP(ctx, hipGetLastError());
-        }
-        // the rows whose far cells could be reportable (usually none): full counter rows, single rows, all columns --
-        // unless a completed launch with these very options has shown the list to be empty (rk_internal.h, fb_state)
-        rk_index *mut = const_cast<rk_index *>(idx);
-        unsigned char key[sizeof mut->fb_key] = {0};
-        static_assert(sizeof(rk_dist_opts) + 1 <= sizeof key, "key holds the options and the report mode");
-        memcpy(key, o, sizeof(rk_dist_opts));
-        key[sizeof(rk_dist_opts)] = dense_mode ? 1 : 0;
-        bool skip = false, arm = false;
-        if (ctx->sw_dist_fb_skip && idx->h_fb_seen) {
-            std::lock_guard<std::mutex> lk(mut->lazy_mu);
-            if (memcmp(key, mut->fb_key, sizeof key) != 0) {
-                memcpy(mut->fb_key, key, sizeof key);
-                mut->fb_state = 0;
-            }
-            if (mut->fb_state == 1) {
-                const hipError_t qe = hipEventQuery((hipEvent_t)mut->fb_event);
-                if (qe == hipSuccess) mut->fb_state = *(volatile uint32_t *)idx->h_fb_seen == 0 ? 2 : 3;
-                else (void)hipGetLastError();  // hipErrorNotReady is sticky for hipGetLastError
-            }
-            skip = mut->fb_state == 2;
-            if (mut->fb_state == 0) {
-                if (!mut->fb_event) {
-                    hipEvent_t ev;
-                    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem) == hipSuccess) mut->fb_event = ev;
-                    else (void)hipGetLastError();
-                }
-                arm = mut->fb_event != nullptr;
-            }
-        }
-        if (skip) return RK_OK;
-        Plan fp;
-        rk_dist_opts all = *o;
-        all.row_first = 0;
-        all.row_step = 1;
-        rc = make_plan(ctx, idx, idx->n_ref, idx->max_src_size, &all, false, true, idx->n_ref, &fp, false);
-        if (rc) return rc;
-        rc = launch_dist(ctx, idx, idx->d_selfrange, idx->d_self_off, idx->d_src_off, idx->n_ref, o, fp, hits_dev, cap, n_hits_dev,
-                         nullptr, stream, idx->d_fb);
-        if (!rc && arm) {
-            std::lock_guard<std::mutex> lk(mut->lazy_mu);
-            if (mut->fb_state == 0 && memcmp(key, mut->fb_key, sizeof key) == 0 &&
-                hipEventRecord((hipEvent_t)mut->fb_event, stream) == hipSuccess) mut->fb_state = 1;
-        }
-        return rc;
-    }
-    std::vector<Plan> bands;
-    int rc = plan_bands(ctx, idx, o, dense_mode, &bands);
-    for (size_t b = 0; !rc && b < bands.size(); b++)
-        rc = launch_dist(ctx, idx, idx->d_selfrange, idx->d_self_off, idx->d_src_off, idx->n_ref, o, bands[b], hits_dev, cap,
+    if (rc) return rc;
+    if (sp.kind == SelfPlan::kTiles) return launch_tiles(ctx, idx, o, sp.min_jorc, sp.tile, hits_dev, cap, n_hits_dev, stream);
+    if (sp.kind == SelfPlan::kNear) return launch_near_and_fallback(ctx, mut, o, dense_mode, sp.near, hits_dev, cap, n_hits_dev, stream);
+    if (ctx->sw_dist_debug) print_bands(sp.bands);
+    for (size_t b = 0; !rc && b < sp.bands.size(); b++)
+        rc = launch_dist(ctx, idx, idx->d_selfrange, idx->d_self_off, idx->d_src_off, idx->n_ref, o, sp.bands[b], hits_dev, cap,
                          n_hits_dev, nullptr, stream);
     return rc;
 }
@@ -1344,6 +1372,42 @@ uint64_t host_exact_distances(rk_hit *h, uint64_t n, const rk_dist_opts *o)
     return w;
 }
 
+// The n hits of a join in (row, col) order on the host (malloc): big results are ordered on the device (45,000 hits: 0.1 ms
+// against 2 ms of std::sort); on any failure there the host sorts.
+int download_hits_in_order(rk_ctx *ctx, const rk_hit *hits_dev, unsigned long long n, uint32_t n_query, hipStream_t stream, rk_hit **out_p)
+{
+    rk_hit *out = (rk_hit *)malloc((n ? n : 1) * sizeof(rk_hit));
+    if (!out) return rk_fail(ctx, RK_ERR_NOMEM, "host allocation of %llu hits failed", n);
+    const rk_hit *src = hits_dev;
+    DevBuf<rk_hit> ordered(ctx);
+    bool on_device = false;
+    if (n > (ctx->single_shot ? (1ULL << 18) : 2048ULL)) {
+        DevBuf<unsigned long long> keys(ctx), keys_out(ctx);
+        int bits = 33;
+        while (bits < 64 && (1ULL << (bits - 32)) < n_query) bits++;
+        if (keys.alloc(n) == hipSuccess && keys_out.alloc(n) == hipSuccess && ordered.alloc(n) == hipSuccess) {
+            hipLaunchKernelGGL(k_hit_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hits_dev, n, keys.p);
+            on_device = rk_prim_sort_hits(ctx, keys.p, keys_out.p, hits_dev, ordered.p, n, (unsigned)bits, stream) == RK_OK;
+        }
+        if (on_device) src = ordered.p;
+        else (void)hipGetLastError();
+    }
+    if (n) {
+        hipError_t e = hipMemcpyAsync(out, src, n * sizeof(rk_hit), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) {
+            free(out);
+            return rk_fail(ctx, RK_ERR_HIP, "hit download failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (!on_device)
+        std::sort(out, out + n, [](const rk_hit &x, const rk_hit &y) {
+            return x.row != y.row ? x.row < y.row : x.col < y.col;
+        });
+    *out_p = out;
+    return RK_OK;
+}
+
 }  // namespace
 
 uint64_t rk_host_exact_distances(rk_hit *h, uint64_t n, const rk_dist_opts *o) { return host_exact_distances(h, n, o); }
@@ -1376,35 +1440,23 @@ int rk_dist_kernel_name(rk_ctx *ctx, const rk_index *idx, const rk_sketches *que
 {
     if (!ctx || !idx || !opts || !buf || !cap) return RK_ERR_ARG;
     if (queries) return rk_distq_kernel_name(ctx, idx, queries, buf, cap);
-    bool tiles = false;
-    int trc = self_uses_tiles(ctx, idx, opts, rk_dense_mode(opts), ctx->stream, &tiles);
-    if (trc) return trc;
-    if (tiles && !idx->tiles_ready) {   // (the variant follows the launch size, which needs the tile directory: not built here -- this call changes nothing)
-        snprintf(buf, cap, "rk_tile_kernel");
-        return RK_OK;
-    }
-    if (tiles) {
-        const double t = exp(-(double)opts->kmer_size * opts->max_dist);
-        unsigned long long grid = 0;
-        int threads = 256;
-        bool srow = false;
-        tile_launch_shape(idx, opts, ((opts->metric != 0) ? t : t / (2.0 - t)) * (1.0 - 1e-6), &grid, &threads, &srow);
-        snprintf(buf, cap, "rk_tile_kernel<%du, %s>", threads, srow ? "true" : "false");
-        return RK_OK;
-    }
-    const NearPlan np = plan_near(ctx, idx, opts, rk_dense_mode(opts));
-    if (np.use) {
-        snprintf(buf, cap, "rk_near_kernel<%s, %d>", np.pair ? "true" : "false", np.uw);
-        return RK_OK;
-    }
-    std::vector<Plan> bands;  // several bands: the variant of the first (widest rows)
-    int rc = plan_bands(ctx, idx, opts, rk_dense_mode(opts), &bands);
+    SelfPlan sp;
+    int rc = plan_self(ctx, idx, opts, rk_dense_mode(opts), ctx->stream, &sp);
     if (rc) return rc;
-    const Plan &p = bands[0];
-    if (bands.size() > 1)
-        snprintf(buf, cap, "rk_dist_kernel<%s, %d, %u> [%u bands]", p.u16 ? "true" : "false", p.mode, p.threads, (unsigned)bands.size());
-    else
-        snprintf(buf, cap, "rk_dist_kernel<%s, %d, %u>", p.u16 ? "true" : "false", p.mode, p.threads);
+    if (sp.kind == SelfPlan::kTiles && sp.need_tiles)   // (the variant follows the launch size, which needs the tile directory: not built here -- this call changes nothing)
+        snprintf(buf, cap, "rk_tile_kernel");
+    else if (sp.kind == SelfPlan::kTiles)
+        snprintf(buf, cap, "rk_tile_kernel<%du, %s>", sp.tile.threads, sp.tile.srow ? "true" : "false");
+    else if (sp.kind == SelfPlan::kNear)
+        snprintf(buf, cap, "rk_near_kernel<%s, %d>", sp.near.pair ? "true" : "false", sp.near.uw);
+    else {
+        if (ctx->sw_dist_debug) print_bands(sp.bands);
+        const Plan &p = sp.bands[0];   // several bands: the variant of the first (widest rows)
+        if (sp.bands.size() > 1)
+            snprintf(buf, cap, "rk_dist_kernel<%s, %d, %u> [%u bands]", p.u16 ? "true" : "false", p.mode, p.threads, (unsigned)sp.bands.size());
+        else
+            snprintf(buf, cap, "rk_dist_kernel<%s, %d, %u>", p.u16 ? "true" : "false", p.mode, p.threads);
+    }
     return RK_OK;
 }
 
@@ -1416,14 +1468,8 @@ int rk_index_tile_stats(const rk_index *idx, const rk_dist_opts *opts, uint64_t 
     out[0] = idx->n_tiles;
     out[2] = idx->n_tile_records;
     out[3] = idx->n_tile_slots;
-    if (opts && opts->kmer_size > 0 && opts->max_dist > 0.0) {
-        const double t = exp(-(double)opts->kmer_size * opts->max_dist);
-        unsigned long long grid = 0;
-        int threads = 256;
-        bool srow = false;
-        tile_launch_shape(idx, opts, ((opts->metric != 0) ? t : t / (2.0 - t)) * (1.0 - 1e-6), &grid, &threads, &srow);
-        out[1] = grid;
-    }
+    // (what a launch of the tile kernel would start, whichever kernel plan_self gives a join with these options)
+    if (opts && opts->kmer_size > 0 && opts->max_dist > 0.0) out[1] = tile_launch_shape(idx, opts, rk_min_jorc(opts)).grid;
     return RK_OK;
 }
 
@@ -1440,10 +1486,7 @@ int rk_dist_rows_dev(rk_ctx *ctx, const rk_index *idx, const rk_sketches *querie
         return rk_distq_launch(ctx, idx, queries, opts, rk_dense_mode(opts), hits_dev, hits_cap, (unsigned long long *)n_hits_dev,
                                nullptr, (hipStream_t)stream);
     }
-    if (!opts->triangle || !idx->d_src_off)
-        return rk_fail(ctx, RK_ERR_ARG, "queries == NULL needs triangle=1 and an index built by rk_index_build");
-    if (idx->n_shards > 1)
-        return rk_fail(ctx, RK_ERR_ARG, "a shard of a sharded build holds the lists of one hash range: join through rk_index_join_shard");
+    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
     return launch_self(ctx, idx, opts, rk_dense_mode(opts), hits_dev, hits_cap, (unsigned long long *)n_hits_dev, (hipStream_t)stream);
 }
 
@@ -1455,11 +1498,9 @@ int rk_dist_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
     *n_hits = 0;
     RK_HIP(ctx, hipSetDevice(ctx->device));
     const bool self = (queries == nullptr);
-    if (self && (!opts->triangle || !idx->d_src_off))
-        return rk_fail(ctx, RK_ERR_ARG, "queries == NULL needs triangle=1 and an index built by rk_index_build");
+    if (self)
+        if (int arc = rk_self_join_args(ctx, idx, opts)) return arc;
     if (self && common_dense) return rk_fail(ctx, RK_ERR_ARG, "common_dense needs explicit query sketches");
-    if (self && idx->n_shards > 1)
-        return rk_fail(ctx, RK_ERR_ARG, "a shard of a sharded build holds the lists of one hash range: join through rk_index_join_shard");
     const uint32_t n_query = self ? idx->n_ref : queries->n;
     if (opts->triangle && n_query != idx->n_ref)
         return rk_fail(ctx, RK_ERR_ARG, "triangle mode needs the indexed sketches as queries (%u vs %u)",
@@ -1485,16 +1526,12 @@ int rk_dist_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
 
     // sparse mode: optimistic capacity, exact retry on overflow.  dense mode: every
     // selected (row, col) cell is a hit, so the count is known up front.
-    const uint64_t row_step = opts->row_step ? opts->row_step : 1;
-    uint64_t row_block = opts->row_block > 0 ? (uint64_t)opts->row_block : 1;
-    if (row_step == 1 && opts->row_first == 0) row_block = std::max<uint64_t>(1, n_query);
-    uint64_t cap = 0, n_sel = 0;  // rows of this shard: blocks row_first, row_first + row_step, ... of row_block rows
-    for (uint64_t blk = opts->row_first; blk * row_block < n_query; blk += row_step)
-        for (uint64_t r = blk * row_block; r < std::min<uint64_t>(n_query, (blk + 1) * row_block); r++) {
-            n_sel++;
-            if (dense_mode) cap += opts->triangle ? idx->n_ref - 1 - r : idx->n_ref;
-        }
-    if (!dense_mode) cap = std::max<uint64_t>(1 << 16, n_sel * 64);
+    const RowShard rows(opts, n_query, n_query);   // (all rows: one block)
+    uint64_t cap = 0;
+    for (uint64_t blk = rows.row_first; dense_mode && blk * rows.row_block < n_query; blk += rows.row_step)
+        for (uint64_t r = blk * rows.row_block; r < std::min<uint64_t>(n_query, (blk + 1) * rows.row_block); r++)
+            cap += opts->triangle ? idx->n_ref - 1 - r : idx->n_ref;
+    if (!dense_mode) cap = rk_hit_capacity(rows.n_rows());
     for (int attempt = 0; attempt < 2; attempt++) {
         DevBuf<rk_hit> hits(ctx);
         if (hits.alloc(cap) != hipSuccess)
@@ -1513,34 +1550,9 @@ int rk_dist_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
             cap = n;
             continue;
         }
-        rk_hit *out = (rk_hit *)malloc((n ? n : 1) * sizeof(rk_hit));
-        if (!out) return rk_fail(ctx, RK_ERR_NOMEM, "host allocation of %llu hits failed", n);
-        const rk_hit *src = hits.p;
-        DevBuf<rk_hit> ordered(ctx);
-        bool on_device = false;
-        if (n > (ctx->single_shot ? (1ULL << 18) : 2048ULL)) {  // order the result on the device (45,000 hits: 0.1 ms against 2 ms of std::sort); on any failure the host sorts
-            DevBuf<unsigned long long> keys(ctx), keys_out(ctx);
-            int bits = 33;
-            while (bits < 64 && (1ULL << (bits - 32)) < n_query) bits++;
-            if (keys.alloc(n) == hipSuccess && keys_out.alloc(n) == hipSuccess && ordered.alloc(n) == hipSuccess) {
-                hipLaunchKernelGGL(k_hit_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hits.p, n, keys.p);
-                on_device = rk_prim_sort_hits(ctx, keys.p, keys_out.p, hits.p, ordered.p, n, (unsigned)bits, stream) == RK_OK;
-            }
-            if (on_device) src = ordered.p;
-            else (void)hipGetLastError();
-        }
-        if (n) {
-            hipError_t e = hipMemcpyAsync(out, src, n * sizeof(rk_hit), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) {
-                free(out);
-                return rk_fail(ctx, RK_ERR_HIP, "hit download failed: %s", hipGetErrorString(e));
-            }
-        }
-        if (!on_device)
-            std::sort(out, out + n, [](const rk_hit &x, const rk_hit &y) {
-                return x.row != y.row ? x.row < y.row : x.col < y.col;
-            });
+        rk_hit *out = nullptr;
+        rc = download_hits_in_order(ctx, hits.p, n, n_query, stream, &out);
+        if (rc) return rc;
         *hits_out = out;
         *n_hits = host_exact_distances(out, n, exact_opts);
         if (common_dense) {

@@ -534,7 +534,8 @@ __global__ __launch_bounds__(kTileThreads, kTileThreads == 256 ? 6 : 4) void rk_
 
 // launch shape of the tile kernel for these options: workgroups (= tiles of the density-ordered directory that may hold a
 // reportable cell, by the host's table; the kernel tests exactly) and threads per workgroup
-void tile_launch_shape(const rk_index *idx, const rk_dist_opts *o, double min_jorc, unsigned long long *grid_out, int *threads_out, bool *srow_out)
+struct TileShape { unsigned long long grid = 0; int threads = 256; bool srow = false; };
+TileShape tile_launch_shape(const rk_index *idx, const rk_dist_opts *o, double min_jorc)
 {
     const int metric = o->metric != 0;
     unsigned long long grid = idx->n_tiles;
@@ -559,12 +560,10 @@ void tile_launch_shape(const rk_index *idx, const rk_dist_opts *o, double min_jo
     // scalar caches does not scale
     bool srow = threads >= 512 && grid && idx->n_tile_records >= kTileSrowPerTile * grid && idx->d_tile_rows;   // (d_tile_rows: the split copy exists)
     if (getenv("RK_TILE_SROW")) srow = atoi(getenv("RK_TILE_SROW")) != 0 && idx->d_tile_rows;
-    *srow_out = srow;
-    *grid_out = grid;
-    *threads_out = threads;
+    return TileShape{grid, threads, srow};
 }
 
-int launch_tiles(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, double min_jorc, rk_hit *hits_dev, uint64_t cap,
+int launch_tiles(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, double min_jorc, const TileShape &shape, rk_hit *hits_dev, uint64_t cap,
                  unsigned long long *n_hits_dev, hipStream_t stream)
 {
     if (!idx->n_tiles) return RK_OK;
@@ -578,13 +577,10 @@ int launch_tiles(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, double
     a.n_ref = idx->n_ref;
     a.order = idx->d_tile_order[o->metric != 0];
     a.dir = idx->d_tile_dir[o->metric != 0];
-    unsigned long long grid = 0;
-    int threads = 256;
-    bool srow = false;
-    tile_launch_shape(idx, o, min_jorc, &grid, &threads, &srow);
-    a.row_step = o->row_step ? o->row_step : 1;
-    a.row_first = o->row_first;
-    a.row_block = o->row_block > 0 ? (uint32_t)o->row_block : 1;
+    const RowShard rows(o, idx->n_ref, 0);
+    a.row_step = rows.row_step;
+    a.row_first = rows.row_first;
+    a.row_block = rows.row_block;
     a.metric = o->metric != 0;
     a.kmer_size = o->kmer_size;
     a.max_dist = o->max_dist;
@@ -593,16 +589,16 @@ int launch_tiles(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *o, double
     a.cap = cap;
     a.n_hits = n_hits_dev;
     a.debug = getenv("RK_TILE_DEBUG") ? atoi(getenv("RK_TILE_DEBUG")) : 0;
-    if (!grid) return RK_OK;
-    if (grid > 0x7FFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "too many tiles for one launch (%llu)", (unsigned long long)idx->n_tiles);
+    if (!shape.grid) return RK_OK;
+    if (shape.grid > 0x7FFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "too many tiles for one launch (%llu)", (unsigned long long)idx->n_tiles);
 #define RK_TILE_LAUNCH(T)                                                                                                              \
     do {                                                                                                                               \
-        if (srow) hipLaunchKernelGGL((rk_tile_kernel<T, true>), dim3((unsigned)grid), dim3(T), 0, stream, a, (const uint2 *)idx->d_tile_contrib, (const uint32_t *)idx->d_tile_rows, (const uint32_t *)idx->d_tile_cols); \
-        else hipLaunchKernelGGL((rk_tile_kernel<T, false>), dim3((unsigned)grid), dim3(T), 0, stream, a, (const uint2 *)idx->d_tile_contrib, (const uint32_t *)idx->d_tile_rows, (const uint32_t *)idx->d_tile_cols); \
+        if (shape.srow) hipLaunchKernelGGL((rk_tile_kernel<T, true>), dim3((unsigned)shape.grid), dim3(T), 0, stream, a, (const uint2 *)idx->d_tile_contrib, (const uint32_t *)idx->d_tile_rows, (const uint32_t *)idx->d_tile_cols); \
+        else hipLaunchKernelGGL((rk_tile_kernel<T, false>), dim3((unsigned)shape.grid), dim3(T), 0, stream, a, (const uint2 *)idx->d_tile_contrib, (const uint32_t *)idx->d_tile_rows, (const uint32_t *)idx->d_tile_cols); \
     } while (0)
-    if (threads == 512)
+    if (shape.threads == 512)
         RK_TILE_LAUNCH(512);
-    else if (threads == 1024)
+    else if (shape.threads == 1024)
         RK_TILE_LAUNCH(1024);
     else
         RK_TILE_LAUNCH(256);

@@ -36,6 +36,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rk_dist_common.h"
+#include "rk_dist_plan.h"
 
 namespace {
 
@@ -775,7 +776,6 @@ int ensure_rankbm(rk_ctx *ctx, rk_index *idx, hipStream_t stream)
 struct PlanQ {
     int cbits, look;
     uint32_t tile_cols, n_tiles, cnt_words, threads, cand_cap, stage_hits, n_units, grid;
-    uint32_t row_first, row_step, row_block;
     size_t lds_bytes;
 };
 
@@ -910,12 +910,8 @@ static int distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs,
         if (waves >= best_waves && waves > 0) { best_waves = waves; p.threads = t; }
     }
     p.lds_bytes = row_bytes + fixed_bytes(p.threads);
-    p.row_step = o->row_step ? o->row_step : 1;
-    p.row_first = o->row_first;
-    p.row_block = o->row_block > 0 ? (uint32_t)o->row_block : 1;
-    const uint64_t n_blocks = ((uint64_t)qs->n + p.row_block - 1) / p.row_block;
-    const uint64_t my_blocks = p.row_first < n_blocks ? (n_blocks - p.row_first + p.row_step - 1) / p.row_step : 0;
-    p.n_units = (uint32_t)std::min<uint64_t>(my_blocks * p.row_block, 0xFFFFFFF0u / p.n_tiles);
+    const RowShard rows(o, qs->n, 0);
+    p.n_units = (uint32_t)std::min<uint64_t>(rows.my_blocks() * rows.row_block, 0xFFFFFFF0u / p.n_tiles);
     p.n_units = slot_base < p.n_units ? std::min(n_slots, p.n_units - slot_base) : 0u;
     if (!p.n_units) return RK_OK;
 
@@ -935,9 +931,9 @@ static int distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs,
     a.dir_shift = idx->dir_shift;
     a.n_query = qs->n;
     a.n_ref = idx->n_ref;
-    a.row_first = p.row_first;
-    a.row_step = p.row_step;
-    a.row_block = p.row_block;
+    a.row_first = rows.row_first;
+    a.row_step = rows.row_step;
+    a.row_block = rows.row_block;
     a.n_units = p.n_units;
     a.slot_base = slot_base;
     a.counts_only = counts_only ? 1 : 0;
@@ -951,14 +947,8 @@ static int distq_launch(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs,
     a.kmer_size = o->kmer_size;
     a.dense_mode = dense_mode ? 1 : 0;
     a.max_dist = o->max_dist;
-    a.min_jorc = 0.0;
+    a.min_jorc = !a.dense_mode && o->max_dist > 0.0 ? rk_min_jorc(o) : 0.0;
     a.min_ref_size = (uint32_t)std::min<uint64_t>(idx->min_ref_size, 0xFFFFFFFFu);
-    if (!a.dense_mode && o->max_dist > 0.0) {
-        // distance < D  <=>  jaccard > t/(2-t), t = exp(-k D)  (containment: c > t); 1e-6 relative slack keeps the
-        // reject conservative, the exact formula still decides
-        const double t = exp(-(double)o->kmer_size * o->max_dist);
-        a.min_jorc = (a.metric ? t : t / (2.0 - t)) * (1.0 - 1e-6);
-    }
     a.hits = hits_dev;
     a.cap = cap;
     a.n_hits = n_hits_dev;

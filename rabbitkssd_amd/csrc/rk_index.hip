@@ -1504,7 +1504,7 @@ int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_
     idx->slices_refused = p.no_self;
     idx->ref_sets = src.is_set || r.dups == 0;
     idx->built_fast = built;
-    if (built) {   // (the same rule as rk_dist.hip self_uses_tiles, which counts the records itself for an index built the general way)
+    if (built) {   // (the same rule as rk_dist.hip plan_self, which counts the records itself for an index built the general way)
         idx->spread = r.flagged * 8 > r.n_self;
         idx->spread_known = 1;
     }

@@ -59,7 +59,7 @@ struct rk_ctx {
     int sw_dist_near = 1;   // RK_DIST_NEAR=0: the self join always with full counter rows (rk_dist_kernel)
     int sw_dist_near_uw = 0;    // RK_DIST_NEAR_UW=1|2|4: waves that share a unit of the near-window kernel (default: by the launch's size)
     int sw_dist_fb_skip = 1;   // RK_DIST_FB_SKIP=0: always launch the fallback pass of the near-window self join
-    int sw_dist_tiles = 2;      // RK_DIST_TILES: 0 never the tile kernel (rk_dist_tile.inc), 1 for every sparse self join over sets, 2 by the index's size and shape (rk_dist.hip self_uses_tiles)
+    int sw_dist_tiles = 2;      // RK_DIST_TILES: 0 never the tile kernel (rk_dist_tile.inc), 1 for every sparse self join over sets, 2 by the index's size and shape (rk_dist.hip plan_self)
     // RK_DIST_TILES_MIN_GENOMES: from this many genomes on rk_index_build emits tile records (not slice records) and the self join
     // runs on the tile kernel from its first launch; _MIN_SHARD_ROWS: row shards smaller than this prefer the near-window kernel
     // when the index HAS slice records (a tile costs the same whatever the shard)
@@ -237,7 +237,7 @@ struct rk_index {
     unsigned long long shard_rec_count[64] = {};
     bool slices_refused = false;     // built without slice records on purpose (2^31 postings and more, RK_INDEX_NO_SELF): none on first use either
     bool tiles_unusable = false;     // rk_tiles_build found more records than its budget: the self join stays with the row kernels
-    int spread_known = 0;            // 1: `spread` below is valid (rk_dist.hip self_uses_tiles)
+    int spread_known = 0;            // 1: `spread` below is valid (rk_dist.hip plan_self)
     bool spread = false;             // many related lists span more than the 32-column window of rk_near_kernel
     std::mutex lazy_mu;              // serialises the lazy builders (prefix directory, rank bitmap, list records, sum of
                                      // squares): two host threads may query one index
@@ -290,5 +290,12 @@ uint64_t rk_host_exact_distances(rk_hit *h, uint64_t n, const rk_dist_opts *opts
 int rk_distq_kernel_name(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, char *buf, size_t cap);
 // true when every posting is reportable regardless of its count (the threshold admits distance 1.0)
 inline bool rk_dense_mode(const rk_dist_opts *o) { return o->triangle ? (1.0 < o->max_dist) : (1.0 <= o->max_dist); }
+// what a self join (queries == NULL) asks of its arguments (rk_dist_rows, rk_dist_rows_dev, rk_cluster_rows)
+inline int rk_self_join_args(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts)
+{
+    if (!opts->triangle || !idx->d_src_off) return rk_fail(ctx, RK_ERR_ARG, "queries == NULL needs triangle=1 and an index built by rk_index_build");
+    if (idx->n_shards > 1) return rk_fail(ctx, RK_ERR_ARG, "a shard of a sharded build holds the lists of one hash range: join through rk_index_join_shard");
+    return RK_OK;
+}
 // sets s->is_set / s->max_size from the device arrays (one small kernel + a 4-byte read-back)
 int rk_sketches_classify(rk_ctx *ctx, rk_sketches *s);
