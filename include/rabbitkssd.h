@@ -19,6 +19,7 @@
  *                             query row)             src/dist.cpp:560-692
  *   rk_cluster_rows        <- row loop of index_tridist  src/dist.cpp:174-258, followed by the union-find its
  *                             users run over the printed pairs (the reference has no clustering of its own)
+ *   rk_forest_rows         <- the same row loop, followed by the Kruskal its users run over the printed pairs
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -468,6 +469,50 @@ int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, 
  * in the same form -- what folds the labels of row shards and of GPUs into those of the collection.  out may alias a.
  * RK_ERR_ARG for an entry >= n or null pointers. */
 int rk_cluster_merge(const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *out);
+
+/* Minimum spanning forest of the all-vs-all: the single-linkage dendrogram up to -D.  The graph is that of rk_cluster_rows (the pairs
+ * rk_dist_rows(ctx, idx, NULL, opts, ...) would report: same metric, same strict threshold, same row selection, any index that call
+ * accepts, the join-only index of rk_index_join_shard included); an edge is one hit record.
+ * Order of edges: the ratio common / u descending (nearest pair first), then row ascending, then col ascending -- u = size0 + size1
+ * - common for metric 0, min(size0, size1) for metric 1: both distances fall strictly as the ratio rises, so no log orders edges.
+ * Ratios are compared exactly (25/75 and 20/60 tie: row and col decide).  The order is strict, so the forest is unique: the edges
+ * Kruskal accepts in this order.  edges_out (library-allocated, rk_free_host; at most rk_index_genomes(idx) - 1 records) lists them in
+ * this order; their jorc and dist are recomputed on the host with the C library's log, as rk_dist_rows does: the reference's values
+ * bit for bit.  Cut at any t <= max_dist (rk_forest_cut) the forest gives the labels rk_cluster_rows returns at t -- assuming only
+ * that the C library's log is monotone over the ratios that occur.  The result does not depend on the order of hits, genomes or
+ * shards.
+ * The hit records never leave the device (the frame of rk_cluster_rows: the join through rk_dist_rows_dev with the threshold widened
+ * by 2^-46 into max(65,536, rows * 64) records, once more with the exact count on overflow).  Boruvka rounds run over them: per round
+ * every component finds its best edge (a 64-bit atomic minimum on the weight key ~floor(common * 2^62 / u), then on row << 32 | col
+ * among the records that match it), the chosen records are appended to the forest buffer and their components united by the
+ * compare-and-swap hook of rk_cluster_rows; the host reads one counter per round and stops at the first round that appended nothing
+ * (at most 2 + ceil(log2 N) rounds).  The forest records are sorted on the device and downloaded: 40 bytes per edge, never O(hits).
+ * A record whose device distance lies within 2^-46 relative of the threshold (borderline), and a record outside 0 < common <= u (only
+ * sketches that repeat hashes have such), takes no part on the device: it goes to the small host buffer of rk_cluster_rows (4,096
+ * records, RK_CLUSTER_EDGE_CAP; on overflow that pass alone runs again), the host decides it with the C library's log and folds the
+ * kept ones in with a Kruskal over (forest + kept) -- MSF(E1 + E2) = MSF(MSF(E1) + E2).
+ * RK_ERR_ARG: triangle != 1, null pointers, a dense report (a threshold above 1.0: a forest over pairs that share nothing is not
+ * offered), an index rk_dist_rows refuses for a self join.  RK_ERR_UNSUPPORTED: a sketch of 2^30 hashes or more (the key), and what
+ * the join answers.  An index without genomes: RK_OK, no edge, *edges_out = NULL.  stats is optional. */
+typedef struct rk_forest_stats {
+    uint64_t edges;          /* hit records of the join */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts; /* 2: the host buffer overflowed once */
+    uint32_t rounds;         /* Boruvka rounds, the last (empty) one included; 0 when no record took part */
+    uint32_t n_trees;        /* genomes minus returned edges: components, singletons included */
+} rk_forest_stats;
+int rk_forest_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, rk_hit **edges_out, uint64_t *n_edges,
+                   rk_forest_stats *stats /* optional */);
+/* Host only: the forest of the union of two edge lists over n genomes (Kruskal in the order above; `metric` as rk_dist_opts.metric) --
+ * what folds the forests of row shards and of GPUs into that of the collection.  The lists need not be forests nor in order.  out is
+ * library-allocated (rk_free_host), in order.  RK_ERR_ARG for an edge that names a genome >= n or null pointers (a list of no edges
+ * may be NULL). */
+int rk_forest_merge(const rk_hit *a, uint64_t na, const rk_hit *b, uint64_t nb, uint32_t n, int metric, rk_hit **out, uint64_t *n_out);
+/* Host only: the labels of the forest cut at max_dist, in the form of rk_cluster_rows (labels_out[i] = the smallest index of i's
+ * component): an edge links iff its stored dist < max_dist.  RK_ERR_ARG for an edge that names a genome >= n or null pointers. */
+int rk_forest_cut(const rk_hit *edges, uint64_t n_edges, uint32_t n, double max_dist, uint32_t *labels_out /* n */);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

@@ -29,7 +29,7 @@ EXPORTS = [
     "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
-    "rk_cluster_rows", "rk_cluster_merge",
+    "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut",
 ]
 
 
@@ -60,6 +60,13 @@ class ClusterStats(C.Structure):
     _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
                 ("join_attempts", C.c_uint32), ("hook_attempts", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("pad_", C.c_uint32)]
+
+
+class ForestStats(C.Structure):
+    """rk_forest_stats: what one rk_forest_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
+                ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("rounds", C.c_uint32),
+                ("n_trees", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -395,6 +402,21 @@ class Context:
         self.check(L.rk_cluster_rows(self._h, index._h, C.byref(opts), _ptr(labels), C.byref(st)))
         return labels, {name: int(getattr(st, name)) for name, _ in ClusterStats._fields_[:-1]}
 
+    def forest_rows(self, index, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
+        """minimum spanning forest of the self join (rk_forest_rows): (edges, stats) -- edges as HIT_DTYPE in forest order (ratio
+        common / u descending, then row, then col), stats a dict of the ForestStats fields"""
+        opts = DistOpts(1, int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+        edges = C.c_void_p()
+        n = C.c_uint64()
+        st = ForestStats()
+        L = lib()
+        L.rk_forest_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                     C.POINTER(ForestStats)]
+        self.check(L.rk_forest_rows(self._h, index._h, C.byref(opts), C.byref(edges), C.byref(n), C.byref(st)))
+        buf = C.string_at(edges.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
+        L.rk_free_host(edges)
+        return np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in ForestStats._fields_}
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
@@ -585,6 +607,36 @@ def cluster_merge(a, b):
     if rc:
         raise RkError(rc, "rk_cluster_merge: an entry beyond the number of genomes")
     return out
+
+
+def forest_merge(a, b, n, metric):
+    """the minimum spanning forest of the union of two edge lists over n genomes (rk_forest_merge, host only), in forest order"""
+    a = np.ascontiguousarray(a, dtype=HIT_DTYPE)
+    b = np.ascontiguousarray(b, dtype=HIT_DTYPE)
+    out = C.c_void_p()
+    n_out = C.c_uint64()
+    L = lib()
+    L.rk_forest_merge.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_uint64)]
+    rc = L.rk_forest_merge(_ptr(a), C.c_uint64(len(a)), _ptr(b), C.c_uint64(len(b)), C.c_uint32(n), int(metric), C.byref(out), C.byref(n_out))
+    if rc:
+        raise RkError(rc, "rk_forest_merge: an edge names a genome beyond the number of genomes")
+    buf = C.string_at(out.value, n_out.value * HIT_DTYPE.itemsize) if n_out.value else b""
+    L.rk_free_host(out)
+    return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+
+
+def forest_cut(edges, n, max_dist):
+    """labels (the smallest index of each component, uint32) of a forest cut at max_dist: an edge links iff its dist < max_dist
+    (rk_forest_cut, host only)"""
+    edges = np.ascontiguousarray(edges, dtype=HIT_DTYPE)
+    labels = np.zeros(int(n), dtype=np.uint32)
+    L = lib()
+    L.rk_forest_cut.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p]
+    rc = L.rk_forest_cut(_ptr(edges), C.c_uint64(len(edges)), C.c_uint32(n), C.c_double(max_dist), _ptr(labels))
+    if rc:
+        raise RkError(rc, "rk_forest_cut: an edge names a genome beyond the number of genomes")
+    return labels
 
 
 def format_hit(name_a, name_b, hit):

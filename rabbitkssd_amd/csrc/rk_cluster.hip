@@ -27,6 +27,7 @@
 
 #include "rk_internal.h"
 #include "rk_dist_plan.h"
+#include "rk_union_find.h"
 
 namespace {
 
@@ -41,24 +42,6 @@ struct rk_edge {   // a borderline record: what rk_distance needs
 
 // counters of one call, 8 u32 words in front of the labels (one read-back brings both home)
 enum { kCntHits = 0, kCntBorder = 1, kCntBad = 2, kCntWords = 4 };   // (u64 each)
-
-__device__ __forceinline__ uint32_t p_load(const uint32_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of x.  Path halving: x's parent is replaced by its grandparent -- an ancestor of x, and ancestors stay ancestors
-// (links are only ever added at roots), so a late or lost store costs steps, never correctness.
-__device__ __forceinline__ uint32_t p_root(uint32_t *parent, uint32_t x)
-{
-    for (;;) {
-        const uint32_t p = p_load(parent + x);
-        if (p == x) return x;
-        const uint32_t g = p_load(parent + p);
-        if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = g;
-    }
-}
 
 __global__ void k_cluster_init(uint32_t *parent, uint32_t n)
 {
@@ -104,33 +87,6 @@ __global__ void k_cluster_flatten(const uint32_t *parent, uint32_t *label, uint3
         }
         label[i] = x;
     }
-}
-
-inline uint32_t host_root(uint32_t *parent, uint32_t x)
-{
-    while (parent[x] != x) {
-        parent[x] = parent[parent[x]];
-        x = parent[x];
-    }
-    return x;
-}
-
-inline void host_union(uint32_t *parent, uint32_t a, uint32_t b)
-{
-    a = host_root(parent, a);
-    b = host_root(parent, b);
-    if (a != b) parent[std::max(a, b)] = std::min(a, b);
-}
-
-// parent[x] <= x everywhere: ascending, every parent is final before its children
-inline uint32_t host_flatten(uint32_t *parent, uint32_t n)
-{
-    uint32_t roots = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        parent[i] = parent[parent[i]];
-        roots += parent[i] == i;
-    }
-    return roots;
 }
 
 unsigned grid_for(const rk_ctx *ctx, uint64_t items)

@@ -1,0 +1,422 @@
+// rk_forest.hip -- the minimum spanning forest of `alldist` on the device (rk_forest_rows) and its host side: the fold of two
+// forests (rk_forest_merge) and the cut at a threshold (rk_forest_cut).  The forest of the "reportable pair" graph is the
+// single-linkage dendrogram up to -D: cut at any t <= D it gives the clusters rk_cluster_rows returns at t, without a join.
+//
+// Order of edges (include/rabbitkssd.h, clusters section): the ratio common / u descending -- u = size0 + size1 - common (metric 0)
+// or min(size0, size1) (metric 1); both distances fall strictly as it rises --, then row ascending, then col ascending.  Strict,
+// so the forest is unique: the edges Kruskal accepts in this order.  On the device the ratio is the 64-bit key
+// floor(common * 2^62 / u), exact for 0 < common <= u < 2^31 (distinct fractions differ by more than 2^-62); `w` = ~key turns
+// "nearest first" into an unsigned minimum.
+//
+//   join      rk_dist_rows_dev (threshold widened by 2^-46) into max(65,536, rows * 64) records, one rerun with the exact count;
+//   k_keys    per record: w and row << 32 | col.  A record whose device distance is not below D (1 - 2^-46) is BORDERLINE, a
+//             record outside 0 < common <= u (multisets) has no key: both go to the small host buffer and are dead on the device;
+//   rounds    Boruvka: k_match_w (atomic minimum of w per component, both endpoints), k_match_rc (among the records that match
+//             that w, atomic minimum of row << 32 | col), k_link (a record that is the best edge of either of its components is
+//             appended once to the forest buffer, its roots linked with the compare-and-swap hook), k_flatten (label[i] =
+//             root(i), best arrays reset).  The host reads one counter per round and stops when a round appended nothing;
+//   sort      the <= N - 1 forest records by (w, row, col): two stable radix passes; download;
+//   host      borderline records decided by rk_host_exact_distances, Kruskal over (forest + kept), jorc / dist of the result
+//             recomputed with the C library's log.
+//
+// Termination and acyclicity: DESIGN.md 4.7.  In short: the order is strict, so the best edges of one round form a forest over the
+// round's components (a cycle would need an edge that is smaller than itself), apart from the edge both of its components chose,
+// which is ONE record and whose single thread appends it once.  Hence every k_link thread unites two different trees, whatever
+// the others do meanwhile, and its compare-and-swap loop ends as k_cluster_hook's does.  No loop waits for another workgroup.
+// Memory scope: label[] and the best arrays are written by one kernel and read by the next (plain loads behind the kernel
+// boundary; the minima themselves are agent-scope atomics); parent[] inside k_link only through agent-scope relaxed atomics.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "rk_internal.h"
+#include "rk_dist_plan.h"
+#include "rk_union_find.h"
+
+namespace {
+
+constexpr uint32_t kForestThreads = 256;
+constexpr uint64_t kEdgeCapDefault = 4096;   // records the first key pass has room for in the host buffer (RK_CLUSTER_EDGE_CAP)
+constexpr double kBorderRel = 0x1p-46;       // the widening of rk_dist_rows
+constexpr unsigned long long kDead = ~0ULL;  // w of a record that takes no part (any more)
+
+struct rk_edge {   // a record for the host: what rk_distance needs
+    uint32_t row, col;
+    int32_t common, size0, size1;
+};
+
+enum { kCntHits = 0, kCntBorder = 1, kCntBad = 2, kCntForest = 3, kCntWords = 4 };   // (u64 each)
+
+// common / u of a record as signed 64-bit terms (u may be <= 0 only for multisets whose counts are products of multiplicities)
+__host__ __device__ inline void ratio_terms(int32_t common, int32_t size0, int32_t size1, int metric, long long *c, long long *u)
+{
+    *c = common;
+    *u = metric ? (long long)(size0 < size1 ? size0 : size1) : (long long)size0 + size1 - common;
+}
+
+// floor(c * 2^62 / u) for 0 < c <= u < 2^31 in two division steps of 31 bits: every intermediate stays below 2^62
+__device__ __forceinline__ unsigned long long ratio_key(unsigned long long c, unsigned long long u)
+{
+    const unsigned long long q1 = (c << 31) / u, r1 = (c << 31) % u;
+    return (q1 << 31) | ((r1 << 31) / u);
+}
+
+__global__ void k_forest_init(uint32_t *parent, uint32_t *label, unsigned long long *best_w, unsigned long long *best_rc, uint32_t n)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        parent[i] = i;
+        label[i] = i;
+        best_w[i] = kDead;
+        best_rc[i] = kDead;
+    }
+}
+
+// n_hits_dev counts every hit of the join, those beyond `cap` included: the pass reads what was written.
+__global__ void __launch_bounds__(kForestThreads)
+k_forest_keys(const rk_hit *hits, const unsigned long long *n_hits_dev, unsigned long long cap, uint32_t n, double link_below, int metric,
+              unsigned long long *w_out, unsigned long long *rc_out, rk_edge *edges, unsigned long long edge_cap, unsigned long long *n_border,
+              unsigned long long *n_bad)
+{
+    const unsigned long long n_rec = min(*n_hits_dev, cap);
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        const rk_hit h = hits[e];
+        rc_out[e] = ((unsigned long long)h.row << 32) | h.col;
+        if (h.row >= n || h.col >= n) {   // (never from the join's kernels; nothing is indexed by such a record)
+            atomicAdd(n_bad, 1ULL);
+            w_out[e] = kDead;
+            continue;
+        }
+        long long c, u;
+        ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
+        if (!(h.dist < link_below) || c <= 0 || c > u) {
+            const unsigned long long at = atomicAdd(n_border, 1ULL);
+            if (at < edge_cap) edges[at] = rk_edge{h.row, h.col, h.common, h.size0, h.size1};
+            w_out[e] = kDead;
+            continue;
+        }
+        w_out[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (key >= 1: never kDead)
+    }
+}
+
+__device__ __forceinline__ void min_u64(unsigned long long *p, unsigned long long v)
+{
+    // the load saves the atomic of a record that cannot win (the values only fall: a stale one costs an atomic, nothing else)
+    if (v < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// label[] is the round's start: written by k_forest_flatten / k_forest_init, a kernel boundary away.  A record inside one component
+// stays inside it: dead from here on (its own thread is the only one that touches w[e]).
+__global__ void __launch_bounds__(kForestThreads)
+k_forest_match_w(unsigned long long *w, const unsigned long long *rc, const unsigned long long *n_hits_dev, unsigned long long cap,
+                 const uint32_t *label, unsigned long long *best_w)
+{
+    const unsigned long long n_rec = min(*n_hits_dev, cap);
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long we = w[e];
+        if (we == kDead) continue;
+        const unsigned long long p = rc[e];
+        const uint32_t la = label[(uint32_t)(p >> 32)], lb = label[(uint32_t)p];
+        if (la == lb) {
+            w[e] = kDead;
+            continue;
+        }
+        min_u64(best_w + la, we);
+        min_u64(best_w + lb, we);
+    }
+}
+
+__global__ void __launch_bounds__(kForestThreads)
+k_forest_match_rc(const unsigned long long *w, const unsigned long long *rc, const unsigned long long *n_hits_dev, unsigned long long cap,
+                  const uint32_t *label, const unsigned long long *best_w, unsigned long long *best_rc)
+{
+    const unsigned long long n_rec = min(*n_hits_dev, cap);
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long we = w[e];
+        if (we == kDead) continue;
+        const unsigned long long p = rc[e];
+        const uint32_t la = label[(uint32_t)(p >> 32)], lb = label[(uint32_t)p];
+        if (best_w[la] == we) min_u64(best_rc + la, p);
+        if (best_w[lb] == we) min_u64(best_rc + lb, p);
+    }
+}
+
+// la and lb are the roots of the record's trees at the round's start, so the walk to today's roots starts there
+__global__ void __launch_bounds__(kForestThreads)
+k_forest_link(const rk_hit *hits, unsigned long long *w, const unsigned long long *rc, const unsigned long long *n_hits_dev, unsigned long long cap,
+              const uint32_t *label, const unsigned long long *best_w, const unsigned long long *best_rc, uint32_t *parent, rk_hit *forest,
+              unsigned long long forest_cap, unsigned long long *n_forest)
+{
+    const unsigned long long n_rec = min(*n_hits_dev, cap);
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long we = w[e];
+        if (we == kDead) continue;
+        const unsigned long long p = rc[e];
+        const uint32_t la = label[(uint32_t)(p >> 32)], lb = label[(uint32_t)p];
+        const bool best = (best_w[la] == we && best_rc[la] == p) || (best_w[lb] == we && best_rc[lb] == p);
+        if (!best) continue;
+        const unsigned long long at = atomicAdd(n_forest, 1ULL);
+        if (at < forest_cap) forest[at] = hits[e];   // (a forest has at most N - 1 edges; the host checks the counter)
+        w[e] = kDead;
+        p_link(parent, la, lb);
+    }
+}
+
+// behind the kernel boundary: plain loads.  parent[] is not written here, so every thread walks a settled chain.
+__global__ void k_forest_flatten(const uint32_t *parent, uint32_t *label, unsigned long long *best_w, unsigned long long *best_rc, uint32_t n)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint32_t x = i, p = parent[x];
+        while (p != x) {
+            x = p;
+            p = parent[x];
+        }
+        label[i] = x;
+        best_w[i] = kDead;
+        best_rc[i] = kDead;
+    }
+}
+
+// sort keys of the forest records: pass 0 row << 32 | col, pass 1 w (the radix sort is stable)
+__global__ void k_forest_sort_keys(const rk_hit *forest, unsigned long long n, int metric, int pass, unsigned long long *keys)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const rk_hit h = forest[i];
+    if (!pass) {
+        keys[i] = ((unsigned long long)h.row << 32) | h.col;
+        return;
+    }
+    long long c, u;
+    ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
+    keys[i] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (only records k_forest_keys gave a key are here)
+}
+
+unsigned grid_for(const rk_ctx *ctx, uint64_t items)
+{
+    const uint64_t want = (items + kForestThreads - 1) / kForestThreads;
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)std::max(1, ctx->num_cu) * 8));
+}
+
+// ---- host: the order of edges, exactly ------------------------------------------------------------------------------------
+// ratio descending by cross-multiplication (128-bit: u reaches 2^32), then row, then col.  A record without a ratio (u <= 0 or
+// common < 0: no join reports one) comes behind every record that has one.
+struct EdgeLess {
+    int metric;
+    bool operator()(const rk_hit &a, const rk_hit &b) const
+    {
+        long long ca, ua, cb, ub;
+        ratio_terms(a.common, a.size0, a.size1, metric, &ca, &ua);
+        ratio_terms(b.common, b.size0, b.size1, metric, &cb, &ub);
+        const bool va = ua > 0 && ca >= 0, vb = ub > 0 && cb >= 0;
+        if (va != vb) return va;
+        if (va) {
+            const __int128 l = (__int128)ca * ub, r = (__int128)cb * ua;
+            if (l != r) return l > r;
+        }
+        return a.row != b.row ? a.row < b.row : a.col < b.col;
+    }
+};
+
+// Kruskal over edges that are in order already: the accepted ones, in order, compacted to the front.  Returns their number.
+uint64_t kruskal_sorted(rk_hit *e, uint64_t m, uint32_t n)
+{
+    std::vector<uint32_t> parent(n);
+    std::iota(parent.begin(), parent.end(), 0u);
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < m; i++)
+        if (host_union(parent.data(), e[i].row, e[i].col)) {
+            if (k != i) e[k] = e[i];
+            k++;
+        }
+    return k;
+}
+
+bool edges_within(const rk_hit *e, uint64_t m, uint32_t n)
+{
+    for (uint64_t i = 0; i < m; i++)
+        if (e[i].row >= n || e[i].col >= n) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rk_forest_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, rk_hit **edges_out, uint64_t *n_edges, rk_forest_stats *stats)
+{
+    if (!ctx || !idx || !opts) return RK_ERR_ARG;
+    rk_forest_stats st;
+    memset(&st, 0, sizeof st);
+    if (stats) *stats = st;
+    if (!edges_out || !n_edges) return rk_fail(ctx, RK_ERR_ARG, "edges_out or n_edges is null");
+    *edges_out = nullptr;
+    *n_edges = 0;
+    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_forest_rows spans a self join: triangle must be 1");
+    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_forest_rows: a dense report (a threshold above 1.0) has no forest: pairs that share nothing carry no order");
+    const uint32_t N = idx->n_ref;
+    if (!N) return RK_OK;
+    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
+    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_forest_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    rk_dist_opts widened = *opts;
+    if (widened.max_dist > 0.0) widened.max_dist = std::min(widened.max_dist + widened.max_dist * kBorderRel, 1.0);
+    const double link_below = opts->max_dist > 0.0 ? opts->max_dist - opts->max_dist * kBorderRel : opts->max_dist;
+    const int metric = opts->metric != 0;
+    hipStream_t stream = ctx->stream;
+
+    uint64_t cap = rk_hit_capacity(RowShard(opts, N, N).n_rows());
+    uint64_t edge_cap = kEdgeCapDefault;
+    if (const char *e = getenv("RK_CLUSTER_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    const uint64_t forest_cap = N - 1;
+    uint32_t max_rounds = 2;   // 2 + ceil(log2 N): the components with an edge left at least halve per round, the last round appends nothing
+    while ((1ULL << (max_rounds - 2)) < N) max_rounds++;
+
+    DevBuf<uint32_t> parent(ctx), label(ctx);
+    DevBuf<unsigned long long> best_w(ctx), best_rc(ctx), cnt(ctx);
+    DevBuf<rk_edge> edges(ctx);
+    DevBuf<rk_hit> forest(ctx);
+    RK_HIP(ctx, parent.alloc(N));
+    RK_HIP(ctx, label.alloc(N));
+    RK_HIP(ctx, best_w.alloc(N));
+    RK_HIP(ctx, best_rc.alloc(N));
+    RK_HIP(ctx, cnt.alloc(kCntWords));
+    RK_HIP(ctx, edges.alloc(edge_cap));
+    RK_HIP(ctx, forest.alloc(forest_cap));
+    hipLaunchKernelGGL(k_forest_init, dim3(grid_for(ctx, N)), dim3(kForestThreads), 0, stream, parent.p, label.p, best_w.p, best_rc.p, N);
+    RK_HIP(ctx, hipGetLastError());
+
+    unsigned long long c[kCntWords] = {0, 0, 0, 0};
+    std::vector<rk_hit> all;   // the forest of the device, then the kept borderline records
+    bool done = false;
+    for (int attempt = 0; attempt < 2 && !done; attempt++) {
+        DevBuf<rk_hit> hits(ctx);
+        DevBuf<unsigned long long> w(ctx), rc_(ctx);
+        if (hits.alloc(cap) != hipSuccess || w.alloc(cap) != hipSuccess || rc_.alloc(cap) != hipSuccess)
+            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)cap);
+        RK_HIP(ctx, hipMemsetAsync(cnt.p, 0, kCntWords * 8, stream));
+        int rc = rk_dist_rows_dev(ctx, idx, nullptr, &widened, hits.p, cap, (uint64_t *)(cnt.p + kCntHits), stream);
+        if (rc) return rc;
+        st.join_attempts++;
+        st.border_attempts = 0;
+        const unsigned grid = grid_for(ctx, cap);
+        bool keyed = false;
+        for (int pass = 0; pass < 2 && !keyed; pass++) {
+            hipLaunchKernelGGL(k_forest_keys, dim3(grid), dim3(kForestThreads), 0, stream, hits.p, cnt.p + kCntHits, (unsigned long long)cap, N,
+                               link_below, metric, w.p, rc_.p, edges.p, (unsigned long long)edge_cap, cnt.p + kCntBorder, cnt.p + kCntBad);
+            RK_HIP(ctx, hipGetLastError());
+            if (int r = rk_read_back(ctx, c, cnt.p, sizeof c, stream)) return r;
+            if (c[kCntBad]) return rk_fail(ctx, RK_ERR_HIP, "%llu hit records name a genome beyond the index", c[kCntBad]);
+            if (c[kCntHits] > cap) break;   // overflow: the join again with the exact count (nothing was linked yet)
+            st.border_attempts++;
+            if (c[kCntBorder] > edge_cap) {   // the key pass alone again, with room for every record of the host
+                edge_cap = c[kCntBorder];
+                RK_HIP(ctx, edges.alloc(edge_cap));
+                RK_HIP(ctx, hipMemsetAsync(cnt.p + kCntBorder, 0, 8, stream));
+                continue;
+            }
+            keyed = true;
+        }
+        if (c[kCntHits] > cap) {
+            cap = c[kCntHits];
+            continue;
+        }
+        if (!keyed) break;
+        // Boruvka rounds; the host reads one counter per round
+        unsigned long long n_forest = 0;
+        bool settled = c[kCntHits] == c[kCntBorder];   // no record takes part: no round
+        while (!settled) {
+            if (st.rounds == max_rounds) return rk_fail(ctx, RK_ERR_HIP, "rk_forest_rows: %u rounds did not settle the forest of %u genomes (internal error)", max_rounds, N);
+            hipLaunchKernelGGL(k_forest_match_w, dim3(grid), dim3(kForestThreads), 0, stream, w.p, rc_.p, cnt.p + kCntHits, (unsigned long long)cap, label.p, best_w.p);
+            hipLaunchKernelGGL(k_forest_match_rc, dim3(grid), dim3(kForestThreads), 0, stream, w.p, rc_.p, cnt.p + kCntHits, (unsigned long long)cap, label.p,
+                               best_w.p, best_rc.p);
+            hipLaunchKernelGGL(k_forest_link, dim3(grid), dim3(kForestThreads), 0, stream, hits.p, w.p, rc_.p, cnt.p + kCntHits, (unsigned long long)cap, label.p,
+                               best_w.p, best_rc.p, parent.p, forest.p, (unsigned long long)forest_cap, cnt.p + kCntForest);
+            hipLaunchKernelGGL(k_forest_flatten, dim3(grid_for(ctx, N)), dim3(kForestThreads), 0, stream, parent.p, label.p, best_w.p, best_rc.p, N);
+            RK_HIP(ctx, hipGetLastError());
+            unsigned long long now = 0;
+            if (int r = rk_read_back(ctx, &now, cnt.p + kCntForest, 8, stream)) return r;
+            st.rounds++;
+            if (now > forest_cap) return rk_fail(ctx, RK_ERR_HIP, "rk_forest_rows: %llu forest records for %u genomes (internal error)", now, N);
+            settled = now == n_forest;
+            n_forest = now;
+        }
+        // the forest in order: by (row, col), then stably by w
+        all.resize(n_forest);
+        if (n_forest) {
+            DevBuf<rk_hit> tmp(ctx);
+            DevBuf<unsigned long long> keys(ctx), keys_out(ctx);
+            if (tmp.alloc(n_forest) != hipSuccess || keys.alloc(n_forest) != hipSuccess || keys_out.alloc(n_forest) != hipSuccess)
+                return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate the sort buffers of %llu forest records", n_forest);
+            const unsigned sgrid = (unsigned)((n_forest + kForestThreads - 1) / kForestThreads);
+            hipLaunchKernelGGL(k_forest_sort_keys, dim3(sgrid), dim3(kForestThreads), 0, stream, forest.p, n_forest, metric, 0, keys.p);
+            RK_HIP(ctx, hipGetLastError());
+            if (int r = rk_prim_sort_hits(ctx, keys.p, keys_out.p, forest.p, tmp.p, n_forest, 64, stream)) return rk_fail(ctx, r, "sorting the forest records failed");
+            hipLaunchKernelGGL(k_forest_sort_keys, dim3(sgrid), dim3(kForestThreads), 0, stream, tmp.p, n_forest, metric, 1, keys.p);
+            RK_HIP(ctx, hipGetLastError());
+            if (int r = rk_prim_sort_hits(ctx, keys.p, keys_out.p, tmp.p, forest.p, n_forest, 64, stream)) return rk_fail(ctx, r, "sorting the forest records failed");
+            RK_HIP(ctx, hipMemcpyAsync(all.data(), forest.p, n_forest * sizeof(rk_hit), hipMemcpyDeviceToHost, stream));
+            RK_HIP(ctx, hipStreamSynchronize(stream));
+        }
+        if (c[kCntBorder]) {   // before `edges` goes back to the pool
+            std::vector<rk_edge> e(c[kCntBorder]);
+            RK_HIP(ctx, hipMemcpyAsync(e.data(), edges.p, e.size() * sizeof(rk_edge), hipMemcpyDeviceToHost, stream));
+            RK_HIP(ctx, hipStreamSynchronize(stream));
+            std::vector<rk_hit> h(e.size());
+            for (size_t i = 0; i < e.size(); i++) h[i] = rk_hit{e[i].row, e[i].col, e[i].common, e[i].size0, e[i].size1, 0, 0.0, 0.0};
+            st.borderline_kept = rk_host_exact_distances(h.data(), h.size(), opts);
+            h.resize(st.borderline_kept);
+            std::sort(h.begin(), h.end(), EdgeLess{metric});
+            const size_t mid = all.size();
+            all.insert(all.end(), h.begin(), h.end());
+            std::inplace_merge(all.begin(), all.begin() + mid, all.end(), EdgeLess{metric});
+        }
+        done = true;
+    }
+    if (!done) return rk_fail(ctx, RK_ERR_CAPACITY, "hit or borderline buffer overflow persisted after resize");
+    // MSF(E1 + E2) = MSF(MSF(E1) + E2): Kruskal over the device's forest and the kept records.  (Without kept records it accepts
+    // every edge -- the device's forest is one.)
+    const uint64_t device_edges = all.size() - st.borderline_kept;
+    const uint64_t kept = kruskal_sorted(all.data(), all.size(), N);
+    if (!st.borderline_kept && kept != device_edges) return rk_fail(ctx, RK_ERR_HIP, "rk_forest_rows: the device's forest holds a cycle (internal error)");
+    // the reference's values bit for bit (a record the device linked lies below the exact threshold: none is dropped)
+    if (rk_host_exact_distances(all.data(), kept, opts) != kept) return rk_fail(ctx, RK_ERR_HIP, "rk_forest_rows: a linked record lies beyond the exact threshold (internal error)");
+    rk_hit *out = (rk_hit *)malloc((kept ? kept : 1) * sizeof(rk_hit));
+    if (!out) return rk_fail(ctx, RK_ERR_NOMEM, "host allocation of %llu forest records failed", (unsigned long long)kept);
+    if (kept) memcpy(out, all.data(), kept * sizeof(rk_hit));
+    *edges_out = out;
+    *n_edges = kept;
+    st.edges = c[kCntHits];
+    st.borderline = c[kCntBorder];
+    st.n_trees = N - (uint32_t)kept;
+    if (stats) *stats = st;
+    return RK_OK;
+}
+
+int rk_forest_merge(const rk_hit *a, uint64_t na, const rk_hit *b, uint64_t nb, uint32_t n, int metric, rk_hit **out, uint64_t *n_out)
+{
+    if (!out || !n_out || (na && !a) || (nb && !b)) return RK_ERR_ARG;
+    if (!edges_within(a, na, n) || !edges_within(b, nb, n)) return RK_ERR_ARG;
+    rk_hit *all = (rk_hit *)malloc((na + nb ? na + nb : 1) * sizeof(rk_hit));
+    if (!all) return RK_ERR_NOMEM;
+    if (na) memcpy(all, a, na * sizeof(rk_hit));
+    if (nb) memcpy(all + na, b, nb * sizeof(rk_hit));
+    std::sort(all, all + na + nb, EdgeLess{metric != 0});
+    *n_out = kruskal_sorted(all, na + nb, n);
+    *out = all;
+    return RK_OK;
+}
+
+int rk_forest_cut(const rk_hit *edges, uint64_t n_edges, uint32_t n, double max_dist, uint32_t *labels_out)
+{
+    if ((n_edges && !edges) || (n && !labels_out)) return RK_ERR_ARG;
+    if (!edges_within(edges, n_edges, n)) return RK_ERR_ARG;
+    std::iota(labels_out, labels_out + n, 0u);
+    for (uint64_t i = 0; i < n_edges; i++)
+        if (edges[i].dist < max_dist) host_union(labels_out, edges[i].row, edges[i].col);
+    host_flatten(labels_out, n);
+    return RK_OK;
+}
+
+}  // extern "C"

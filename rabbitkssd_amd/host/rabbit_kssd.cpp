@@ -1407,6 +1407,71 @@ static int cmd_cluster(const Args &a)
     _exit(0);
 }
 
+// forest: the minimum spanning forest of alldist's pairs -- the single-linkage dendrogram up to -D (rk_forest_rows on every GPU for its
+// rows, folded with rk_forest_merge), one alldist line per edge in forest order: nearest pair first, ties by exact ratio, then by
+// the genomes' indices.
+static int cmd_forest(const Args &a)
+{
+    if (!a.has("i")) die("forest needs -i");
+    const double max_dist = a.real("D", 1.0);
+    if (max_dist < 0.0) die("command_forest(), maxDist must be > 0\nUse -D to set the maxDist");
+    if (1.0 < max_dist) die("command_forest(), maxDist must not exceed 1.0: pairs that share nothing carry no order");
+    const string out = a.str("o", "result.out");
+    const int metric = a.num("M", 0);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
+    SelfJoin j;
+    j.prepare(a, set, max_dist, threads);
+    const size_t G = set.size(), N = j.s.size();
+    vector<rk_hit *> edges(G, nullptr);
+    vector<uint64_t> n_edges(G, 0);
+    vector<rk_forest_stats> stats(G);
+    auto rows_of = [&](size_t g) {
+        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
+        set[g].check(rk_forest_rows(set[g].ctx, j.idx[g], &o, &edges[g], &n_edges[g], &stats[g]), "rk_forest_rows");
+    };
+    {
+        vector<std::thread> pool;
+        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
+        rows_of(0);
+        for (auto &th : pool) th.join();
+    }
+    for (size_t g = 1; g < G; g++) {
+        rk_hit *folded = nullptr;
+        uint64_t n_folded = 0;
+        if (rk_forest_merge(edges[0], n_edges[0], edges[g], n_edges[g], (uint32_t)N, metric, &folded, &n_folded) != 0) die("rk_forest_merge failed");
+        rk_free_host(edges[0]);
+        rk_free_host(edges[g]);
+        edges[0] = folded;
+        n_edges[0] = n_folded;
+    }
+    stamp("forest on the host");
+    cerr << "===================time of multiple threads distance computing and spanning forest is: " << get_sec() - j.t1 << endl;
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    vector<char> buf(1 << 16);
+    for (uint64_t k = 0; k < n_edges[0]; k++) {
+        const rk_hit &h = edges[0][k];
+        const string &x = j.s.names[h.col], &y = j.s.names[h.row];   // (the order of an alldist line, src/dist.cpp:233)
+        if (x.size() + y.size() + 128 > buf.size()) die("genome name too long");
+        const int len = rk_format_hit(buf.data(), buf.size(), x.c_str(), y.c_str(), &h);
+        if (len < 0) die("rk_format_hit failed");
+        fwrite(buf.data(), 1, (size_t)len, fp);
+    }
+    fclose(fp);
+    if (getenv("RK_TIMING")) {
+        unsigned long long hits = 0, border = 0, rounds = 0;
+        for (size_t g = 0; g < G; g++) { hits += stats[g].edges; border += stats[g].borderline; rounds = std::max<unsigned long long>(rounds, stats[g].rounds); }
+        fprintf(stderr, "[timing] %llu forest edges over %zu genomes from %llu hit records (%llu borderline), %llu rounds\n",
+                (unsigned long long)n_edges[0], N, hits, border, rounds);
+    }
+    stamp("text written");
+    stamp("done");
+    fflush(stdout);
+    fflush(stderr);
+    _exit(0);
+}
+
 static int cmd_dist(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("dist needs -r and -q");
@@ -1792,11 +1857,12 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
             "  cluster -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (single-linkage clusters of alldist's pairs)\n"
+            "  forest -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (minimum spanning forest of alldist's pairs: the single-linkage dendrogram up to -D, one alldist line per edge)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -1835,7 +1901,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -1854,6 +1920,7 @@ int main(int argc, char **argv)
     if (sub == "sketch") { cerr << "-----run the subcommand: sketch" << endl; return leave(cmd_sketch(parse_args(argc, argv, 2, alias, {"q"}))); }
     if (sub == "alldist") { cerr << "-----run the subcommand: alldist" << endl; return leave(cmd_alldist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "cluster") { cerr << "-----run the subcommand: cluster" << endl; return leave(cmd_cluster(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "forest") { cerr << "-----run the subcommand: forest" << endl; return leave(cmd_forest(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
