@@ -20,6 +20,9 @@
  *   rk_cluster_rows        <- row loop of index_tridist  src/dist.cpp:174-258, followed by the union-find its
  *                             users run over the printed pairs (the reference has no clustering of its own)
  *   rk_forest_rows         <- the same row loop, followed by the Kruskal its users run over the printed pairs
+ *   rk_greedy_rows         <- the same row loop, followed by the greedy incremental clustering its users run over the
+ *                             printed pairs (the rule of CD-HIT, Li & Godzik 2006, and of clust-greedy in RabbitTClust, the
+ *                             reference's sibling tool; the reference itself has no clustering)
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -104,6 +107,8 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 #define RK_MS_TOPN_CANDIDATES 5
 /* rk_cluster_rows with timing on: its hook kernel alone (the last hook pass of the call). */
 #define RK_MS_CLUSTER_HOOK 6
+/* rk_greedy_rows with timing on: all decision rounds of the last call (0 when no record took part). */
+#define RK_MS_GREEDY_ROUNDS 7
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -513,6 +518,58 @@ int rk_forest_merge(const rk_hit *a, uint64_t na, const rk_hit *b, uint64_t nb, 
 /* Host only: the labels of the forest cut at max_dist, in the form of rk_cluster_rows (labels_out[i] = the smallest index of i's
  * component): an edge links iff its stored dist < max_dist.  RK_ERR_ARG for an edge that names a genome >= n or null pointers. */
 int rk_forest_cut(const rk_hit *edges, uint64_t n_edges, uint32_t n, double max_dist, uint32_t *labels_out /* n */);
+
+/* ---- greedy representatives ------------------------------------------------------- */
+/* Greedy incremental clustering of the all-vs-all (the rule of CD-HIT and of clust-greedy in RabbitTClust): one representative per
+ * group of near genomes -- the list a dereplication feeds to its next `dist` run.  The graph is that of rk_cluster_rows for ALL rows:
+ * the pairs rk_dist_rows(ctx, idx, NULL, opts, ...) would report, same metric, same strict threshold decided with the C library's log.
+ * Genome a PRECEDES b iff (priority[a], a) < (priority[b], b); with priority == NULL the larger sketch comes first, then the smaller
+ * caller index: (-size[a], a) with the sizes the index holds.  Walking the genomes in this order, a genome is a representative iff no
+ * representative that precedes it is adjacent to it; every other genome is a member of the NEAREST adjacent representative that
+ * precedes it (a nearer one that comes later is not considered, as in the sequential loop).  Nearest: the largest ratio common / u in
+ * the exact order of rk_forest_rows (25/75 ties 20/60); ties go to the representative with the smallest caller index.  The result is
+ * unique: it does not depend on the order of hits, the internal genome order or the kernel the join took.  Representatives are
+ * pairwise not adjacent, and every member is adjacent to its own.
+ * rep_out[i] (host, rk_index_genomes(idx) entries) = the caller index of i's representative, i itself iff i is one.  links_out
+ * (library-allocated, rk_free_host; NULL when there is none) holds one record per member, by the member's caller index ascending: the
+ * hit record that joins it to its representative as the join reports it (row < col), jorc and dist recomputed on the host with the C
+ * library's log -- the reference's values bit for bit.  *n_links = genomes - representatives.
+ * The hit records never leave the device (the frame of rk_forest_rows: the join through rk_dist_rows_dev with the threshold widened by
+ * 2^-46 into max(65,536, rows * 64) records, once more with the exact count on overflow; the key pass with its small host buffer of
+ * RK_CLUSTER_EDGE_CAP borderline records, run again alone on overflow).  Unlike a forest, the representatives cannot be patched
+ * afterwards -- one kept borderline edge can flip representatives arbitrarily far away --, so the host decides the borderline records
+ * BEFORE the rounds and sends the slot numbers of the kept ones back (8 bytes each, usually none).  Then decision rounds: an edge pass
+ * marks the later endpoint of a record covered (the earlier one is a representative) or blocked for this round (both undecided), a
+ * vertex pass turns undecided genomes into members (covered) or representatives (neither covered nor blocked); the host reads a counter
+ * per round (per small batch of rounds later on) and stops when no genome is undecided.  Each round decides at least the first undecided
+ * genome of the order: at most N rounds -- species cliques take 2-3, a path laid in priority order takes N.  Three sweeps then give every
+ * member its nearest preceding representative (64-bit atomic minima on the weight key and on row << 32 | col).  PCIe traffic: 4 * N
+ * bytes of order up, 44 * N bytes of representatives and links down, the borderline records and a counter per batch: never O(hits).
+ * The rule does NOT compose from row shards the way components and forests do (whether a genome is a representative depends on every
+ * genome before it): row_step > 1 is refused, and so is the join-only index of rk_index_join_shard, which holds one shard's rows.
+ * RK_ERR_ARG: triangle != 1, null pointers, a row shard, a dense report (a threshold above 1.0), an index rk_dist_rows refuses for a
+ * self join, a join-only index.  RK_ERR_UNSUPPORTED: a sketch of 2^30 hashes or more (the key), what the join answers, and a record
+ * outside 0 < common <= u -- only sketches that repeat hashes produce such; the device key has no place for them (collections with
+ * repeats whose records stay in range run normally).  An index without genomes: RK_OK, nothing runs, *links_out = NULL.  stats is
+ * optional. */
+typedef struct rk_greedy_stats {
+    uint64_t edges;          /* hit records of the join */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts; /* 2: the host buffer overflowed once */
+    uint32_t rounds;         /* decision rounds up to the one that left no genome undecided; 0 when no record took part */
+    uint32_t n_reps;         /* representatives, isolated genomes included */
+} rk_greedy_stats;
+int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, const uint32_t *priority /* host, N, optional */,
+                   uint32_t *rep_out /* host, N */, rk_hit **links_out, uint64_t *n_links, rk_greedy_stats *stats /* optional */);
+/* Host only: the same rule over a hit list the caller already has (`metric` as rk_dist_opts.metric; one record per pair, as a join
+ * reports them).  The links are the caller's records, unchanged.  With priority == NULL the sizes come from the records (triangle 1:
+ * size0 = |S_row|, size1 = |S_col|); a genome without a record is isolated and needs none.  RK_ERR_ARG when records disagree about a
+ * genome's size (priority == NULL), when a record names a genome >= n or has row == col, and for null pointers (hits may be NULL when
+ * n_hits == 0). */
+int rk_greedy_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, const uint32_t *priority /* n, optional */, int metric,
+                   uint32_t *rep_out /* n */, rk_hit **links_out, uint64_t *n_links);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

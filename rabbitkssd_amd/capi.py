@@ -29,7 +29,7 @@ EXPORTS = [
     "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
-    "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut",
+    "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
 ]
 
 
@@ -67,6 +67,13 @@ class ForestStats(C.Structure):
     _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
                 ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("rounds", C.c_uint32),
                 ("n_trees", C.c_uint32)]
+
+
+class GreedyStats(C.Structure):
+    """rk_greedy_stats: what one rk_greedy_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
+                ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("rounds", C.c_uint32),
+                ("n_reps", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -417,6 +424,27 @@ class Context:
         L.rk_free_host(edges)
         return np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in ForestStats._fields_}
 
+    def greedy_rows(self, index, metric, kmer_size, max_dist, priority=None):
+        """greedy representatives of the self join (rk_greedy_rows): (rep, links, stats) -- rep[i] = the caller index of i's
+        representative (uint32; i itself iff i is one), links as HIT_DTYPE, one per member by ascending member index, stats a dict of
+        the GreedyStats fields.  priority: optional uint32 per genome, smaller first (default: larger sketch first)"""
+        opts = DistOpts(1, int(metric), int(kmer_size), 0, float(max_dist), 0, 1)
+        if priority is not None:
+            priority = np.ascontiguousarray(priority, dtype=np.uint32)
+            if priority.shape != (index.genomes,):
+                raise ValueError("greedy_rows needs one priority per genome")
+        rep = np.zeros(index.genomes, dtype=np.uint32)
+        links = C.c_void_p()
+        n = C.c_uint64()
+        st = GreedyStats()
+        L = lib()
+        L.rk_greedy_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_uint64), C.POINTER(GreedyStats)]
+        self.check(L.rk_greedy_rows(self._h, index._h, C.byref(opts), _ptr(priority), _ptr(rep), C.byref(links), C.byref(n), C.byref(st)))
+        buf = C.string_at(links.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
+        L.rk_free_host(links)
+        return rep, np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in GreedyStats._fields_}
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
@@ -637,6 +665,28 @@ def forest_cut(edges, n, max_dist):
     if rc:
         raise RkError(rc, "rk_forest_cut: an edge names a genome beyond the number of genomes")
     return labels
+
+
+def greedy_hits(hits, n, metric, priority=None):
+    """greedy representatives of a hit list over n genomes (rk_greedy_hits, host only): (rep, links) as Context.greedy_rows gives
+    them, the links being the caller's records unchanged"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if priority is not None:
+        priority = np.ascontiguousarray(priority, dtype=np.uint32)
+        if priority.shape != (int(n),):
+            raise ValueError("greedy_hits needs one priority per genome")
+    rep = np.zeros(int(n), dtype=np.uint32)
+    links = C.c_void_p()
+    n_links = C.c_uint64()
+    L = lib()
+    L.rk_greedy_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_uint64)]
+    rc = L.rk_greedy_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), _ptr(priority), int(metric), _ptr(rep), C.byref(links), C.byref(n_links))
+    if rc:
+        raise RkError(rc, "rk_greedy_hits: a record names a genome beyond the number of genomes or one genome twice, or records disagree about a size")
+    buf = C.string_at(links.value, n_links.value * HIT_DTYPE.itemsize) if n_links.value else b""
+    L.rk_free_host(links)
+    return rep, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
 
 
 def format_hit(name_a, name_b, hit):

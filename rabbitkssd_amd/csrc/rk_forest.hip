@@ -34,34 +34,15 @@
 #include "rk_internal.h"
 #include "rk_dist_plan.h"
 #include "rk_union_find.h"
+#include "rk_edge_order.h"
 
 namespace {
 
 constexpr uint32_t kForestThreads = 256;
 constexpr uint64_t kEdgeCapDefault = 4096;   // records the first key pass has room for in the host buffer (RK_CLUSTER_EDGE_CAP)
 constexpr double kBorderRel = 0x1p-46;       // the widening of rk_dist_rows
-constexpr unsigned long long kDead = ~0ULL;  // w of a record that takes no part (any more)
-
-struct rk_edge {   // a record for the host: what rk_distance needs
-    uint32_t row, col;
-    int32_t common, size0, size1;
-};
 
 enum { kCntHits = 0, kCntBorder = 1, kCntBad = 2, kCntForest = 3, kCntWords = 4 };   // (u64 each)
-
-// common / u of a record as signed 64-bit terms (u may be <= 0 only for multisets whose counts are products of multiplicities)
-__host__ __device__ inline void ratio_terms(int32_t common, int32_t size0, int32_t size1, int metric, long long *c, long long *u)
-{
-    *c = common;
-    *u = metric ? (long long)(size0 < size1 ? size0 : size1) : (long long)size0 + size1 - common;
-}
-
-// floor(c * 2^62 / u) for 0 < c <= u < 2^31 in two division steps of 31 bits: every intermediate stays below 2^62
-__device__ __forceinline__ unsigned long long ratio_key(unsigned long long c, unsigned long long u)
-{
-    const unsigned long long q1 = (c << 31) / u, r1 = (c << 31) % u;
-    return (q1 << 31) | ((r1 << 31) / u);
-}
 
 __global__ void k_forest_init(uint32_t *parent, uint32_t *label, unsigned long long *best_w, unsigned long long *best_rc, uint32_t n)
 {
@@ -98,12 +79,6 @@ k_forest_keys(const rk_hit *hits, const unsigned long long *n_hits_dev, unsigned
         }
         w_out[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (key >= 1: never kDead)
     }
-}
-
-__device__ __forceinline__ void min_u64(unsigned long long *p, unsigned long long v)
-{
-    // the load saves the atomic of a record that cannot win (the values only fall: a stale one costs an atomic, nothing else)
-    if (v < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // label[] is the round's start: written by k_forest_flatten / k_forest_init, a kernel boundary away.  A record inside one component
@@ -198,26 +173,6 @@ unsigned grid_for(const rk_ctx *ctx, uint64_t items)
     const uint64_t want = (items + kForestThreads - 1) / kForestThreads;
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)std::max(1, ctx->num_cu) * 8));
 }
-
-// ---- host: the order of edges, exactly ------------------------------------------------------------------------------------
-// ratio descending by cross-multiplication (128-bit: u reaches 2^32), then row, then col.  A record without a ratio (u <= 0 or
-// common < 0: no join reports one) comes behind every record that has one.
-struct EdgeLess {
-    int metric;
-    bool operator()(const rk_hit &a, const rk_hit &b) const
-    {
-        long long ca, ua, cb, ub;
-        ratio_terms(a.common, a.size0, a.size1, metric, &ca, &ua);
-        ratio_terms(b.common, b.size0, b.size1, metric, &cb, &ub);
-        const bool va = ua > 0 && ca >= 0, vb = ub > 0 && cb >= 0;
-        if (va != vb) return va;
-        if (va) {
-            const __int128 l = (__int128)ca * ub, r = (__int128)cb * ua;
-            if (l != r) return l > r;
-        }
-        return a.row != b.row ? a.row < b.row : a.col < b.col;
-    }
-};
 
 // Kruskal over edges that are in order already: the accepted ones, in order, compacted to the front.  Returns their number.
 uint64_t kruskal_sorted(rk_hit *e, uint64_t m, uint32_t n)

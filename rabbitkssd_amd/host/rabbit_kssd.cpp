@@ -1472,6 +1472,75 @@ static int cmd_forest(const Args &a)
     _exit(0);
 }
 
+// greedy: greedy incremental clustering of alldist's pairs (rk_greedy_rows; the rule of CD-HIT and clust-greedy: larger sketch first, a
+// genome is a representative unless an earlier representative lies within -D, else it joins the nearest such), one line per genome:
+// cluster number (clusters ordered by their representative's index), cluster size, genome name, representative's name, dist to it;
+// within a cluster the representative first, then the members by ascending index.  --reps: the representatives' names alone.
+static int cmd_greedy(const Args &a)
+{
+    if (!a.has("i")) die("greedy needs -i");
+    const double max_dist = a.real("D", 1.0);
+    if (max_dist < 0.0) die("command_greedy(), maxDist must be > 0\nUse -D to set the maxDist");
+    if (1.0 < max_dist) die("command_greedy(), maxDist must not exceed 1.0: pairs that share nothing carry no order");
+    if (a.num("gpus", 1) > 1) die("command_greedy(), greedy runs on one GPU: the rule does not compose from the shards of several (--gpus 1)");
+    const string out = a.str("o", "result.out");
+    const int metric = a.num("M", 0);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), 1, false);
+    SelfJoin j;
+    j.prepare(a, set, max_dist, threads);
+    const size_t N = j.s.size();
+    vector<uint32_t> rep(N ? N : 1);
+    rk_hit *links = nullptr;
+    uint64_t n_links = 0;
+    rk_greedy_stats stats{};
+    const rk_dist_opts o = j.opts(0, 1, metric, max_dist);
+    set[0].check(rk_greedy_rows(set[0].ctx, j.idx[0], &o, nullptr, rep.data(), &links, &n_links, &stats), "rk_greedy_rows");
+    stamp("representatives on the host");
+    cerr << "===================time of multiple threads distance computing and greedy clustering is: " << get_sec() - j.t1 << endl;
+    // members by cluster, clusters by representative: a counting sort over rep[] (a representative goes first in its cluster)
+    vector<uint32_t> number(N, 0), size(N, 0), start(N + 1, 0), order(N);
+    vector<double> dist(N, 0.0);
+    uint32_t n_reps = 0;
+    for (size_t i = 0, k = 0; i < N; i++) {
+        size[rep[i]]++;
+        if (rep[i] != i) dist[i] = links[k++].dist;   // (the links come by member index)
+    }
+    for (size_t i = 0; i < N; i++) {
+        start[i + 1] = start[i] + size[i];
+        if (rep[i] == i) number[i] = n_reps++;
+    }
+    {
+        vector<uint32_t> at(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < N; i++)
+            if (rep[i] == i) order[at[i]++] = (uint32_t)i;
+        for (size_t i = 0; i < N; i++)
+            if (rep[i] != i) order[at[rep[i]]++] = (uint32_t)i;
+    }
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    for (size_t k = 0; k < N; k++) {
+        const uint32_t i = order[k], r = rep[i];
+        fprintf(fp, "%u\t%u\t%s\t%s\t%f\n", number[r], size[r], j.s.names[i].c_str(), j.s.names[r].c_str(), dist[i]);
+    }
+    fclose(fp);
+    if (a.has("reps")) {
+        FILE *rp = fopen(a.str("reps", "").c_str(), "w");
+        if (!rp) die("cannot write %s", a.str("reps", "").c_str());
+        for (size_t i = 0; i < N; i++)
+            if (rep[i] == i) fprintf(rp, "%s\n", j.s.names[i].c_str());
+        fclose(rp);
+    }
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %u representatives of %zu genomes from %llu hit records (%llu borderline), %u rounds\n", n_reps, N,
+                (unsigned long long)stats.edges, (unsigned long long)stats.borderline, stats.rounds);
+    stamp("text written");
+    stamp("done");
+    fflush(stdout);
+    fflush(stderr);
+    _exit(0);
+}
+
 static int cmd_dist(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("dist needs -r and -q");
@@ -1857,12 +1926,13 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
             "  cluster -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (single-linkage clusters of alldist's pairs)\n"
             "  forest -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (minimum spanning forest of alldist's pairs: the single-linkage dendrogram up to -D, one alldist line per edge)\n"
+            "  greedy -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--reps FILE] [-L file.shuf] [--device N]   (greedy representatives of alldist's pairs: larger sketch first, a genome joins the nearest earlier representative within -D or becomes one; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -1883,7 +1953,7 @@ int main(int argc, char **argv)
         {"-n", "n"}, {"--leastNumKmer", "n"}, {"-Q", "Q"}, {"--leastQuality", "Q"}, {"-D", "D"}, {"--maxDist", "D"},
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
-        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}};
+        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -1901,7 +1971,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -1921,6 +1991,7 @@ int main(int argc, char **argv)
     if (sub == "alldist") { cerr << "-----run the subcommand: alldist" << endl; return leave(cmd_alldist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "cluster") { cerr << "-----run the subcommand: cluster" << endl; return leave(cmd_cluster(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "forest") { cerr << "-----run the subcommand: forest" << endl; return leave(cmd_forest(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "greedy") { cerr << "-----run the subcommand: greedy" << endl; return leave(cmd_greedy(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
