@@ -3,16 +3,15 @@
 // "reportable pair" graph are computed where the hit records already are: nothing of size O(hits) crosses PCIe, nothing is
 // sorted, no host libm pass over the hits.
 //
-//   join     rk_dist_rows_dev (self join, threshold widened by 2^-46 as rk_dist_rows widens it) appends unordered hit
-//            records to a device buffer of max(65,536, rows * 64) records; the counter tells an overflow (one rerun, exact);
+//   stage    rk_edge_stage.h: the self join into a device buffer, the first pass below, its two retries, the borderline records
+//            decided on the host.  The labels are the tail of its counter block: one read-back brings counters and labels home;
 //   k_init   parent[i] = i, indexed by the CALLER's genome index (rk_hit.row / .col carry caller indices);
-//   k_hook   one grid-stride pass over the records: a record whose device distance is below D (1 - 2^-46) links the roots of
-//            its two genomes, larger under smaller, with a compare-and-swap on the larger root; every other record is
-//            BORDERLINE (the device's log may differ from the C library's in the last bits): appended to a small buffer for
-//            the host, not linked;
+//   k_hook   the first pass, one grid-stride sweep over the records: a record whose device distance is below D (1 - 2^-46) links
+//            the roots of its two genomes, larger under smaller, with a compare-and-swap on the larger root (p_link); every other
+//            record is BORDERLINE: appended to the stage's buffer for the host, not linked.  parent[] is not reset between the
+//            stage's attempts: a link made once is a link of the result, and linking twice changes nothing;
 //   k_flatten  label[i] = root(i) = the smallest caller index of i's component;
-//   host     one read-back (two counters + N labels); borderline records decided by rk_host_exact_distances (the C
-//            library's log, the reference's strict `<` of src/dist.cpp:232) and united into the labels.
+//   host     the records the stage kept are united into the labels.
 //
 // Termination and memory scope of k_hook: DESIGN.md 4.6.  In short: parent[x] <= x at every moment and a root is only ever
 // linked under a smaller index, so every chain strictly decreases and every failed compare-and-swap has observed a strictly
@@ -20,7 +19,6 @@
 // atomic (the eight XCDs have L2s of their own: a plain load may return another XCD's stale line); k_flatten runs behind the
 // kernel boundary and reads plainly.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <vector>
@@ -28,71 +26,38 @@
 #include "rk_internal.h"
 #include "rk_dist_plan.h"
 #include "rk_union_find.h"
+#include "rk_edge_stage.h"
 
 namespace {
-
-constexpr uint32_t kClusterThreads = 256;
-constexpr uint64_t kEdgeCapDefault = 4096;   // borderline records the first hook pass has room for (RK_CLUSTER_EDGE_CAP)
-constexpr double kBorderRel = 0x1p-46;       // the widening of rk_dist_rows: orders beyond the 2 ulps between the two logs
-
-struct rk_edge {   // a borderline record: what rk_distance needs
-    uint32_t row, col;
-    int32_t common, size0, size1;
-};
-
-// counters of one call, 8 u32 words in front of the labels (one read-back brings both home)
-enum { kCntHits = 0, kCntBorder = 1, kCntBad = 2, kCntWords = 4 };   // (u64 each)
 
 __global__ void k_cluster_init(uint32_t *parent, uint32_t n)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) parent[i] = i;
 }
 
-// n_hits_dev counts every hit of the join, those beyond `cap` included: the pass reads what was written.
-__global__ void __launch_bounds__(kClusterThreads)
-k_cluster_hook(const rk_hit *hits, const unsigned long long *n_hits_dev, unsigned long long cap, uint32_t *parent, uint32_t n,
-               double link_below, rk_edge *edges, unsigned long long edge_cap, unsigned long long *n_border, unsigned long long *n_bad)
+// cnt[kCntHits] counts every hit of the join, those beyond `cap` included: the pass reads what was written.
+__global__ void __launch_bounds__(kStageThreads)
+k_cluster_hook(const rk_hit *hits, unsigned long long *cnt, unsigned long long cap, uint32_t *parent, uint32_t n, double link_below, rk_edge *edges,
+               unsigned long long edge_cap)
 {
-    const unsigned long long n_rec = min(*n_hits_dev, cap);
+    const unsigned long long n_rec = min(cnt[kCntHits], cap);
     for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
         const rk_hit h = hits[e];
         if (h.row >= n || h.col >= n) {   // (never from the join's kernels; nothing is written through such an index)
-            atomicAdd(n_bad, 1ULL);
+            atomicAdd(cnt + kCntBad, 1ULL);
             continue;
         }
         if (!(h.dist < link_below)) {
-            const unsigned long long at = atomicAdd(n_border, 1ULL);
-            if (at < edge_cap) edges[at] = rk_edge{h.row, h.col, h.common, h.size0, h.size1};
+            edge_append(h, e, edges, nullptr, edge_cap, cnt + kCntBorder);
             continue;
         }
-        uint32_t a = p_root(parent, h.row), b = p_root(parent, h.col);
-        while (a != b) {
-            const uint32_t hi = max(a, b), lo = min(a, b);
-            uint32_t seen = hi;
-            if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-            a = p_root(parent, seen);   // hi was linked meanwhile: seen < hi, on from there
-            b = p_root(parent, lo);
-        }
+        p_link(parent, h.row, h.col);
     }
 }
 
-// behind the kernel boundary: plain loads.  parent[] is not written here, so every thread walks a settled chain.
 __global__ void k_cluster_flatten(const uint32_t *parent, uint32_t *label, uint32_t n)
 {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        uint32_t x = i, p = parent[x];
-        while (p != x) {
-            x = p;
-            p = parent[x];
-        }
-        label[i] = x;
-    }
-}
-
-unsigned grid_for(const rk_ctx *ctx, uint64_t items)
-{
-    const uint64_t want = (items + kClusterThreads - 1) / kClusterThreads;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)std::max(1, ctx->num_cu) * 8));
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) label[i] = p_settled_root(parent, i);
 }
 
 // A dense report (-D above 1.0): every pair of a selected row and a later column is a hit, whatever it shares.  Rows are
@@ -142,91 +107,37 @@ int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, 
         if (stats) *stats = st;
         return RK_OK;
     }
-    // The join reports with the widened threshold, the device links what lies below the narrowed one, the host decides the rest.
-    // (-D within 2^-46 of 1.0 from below: the widening stops at 1.0 -- beyond it the public join would turn to the dense report.)
-    rk_dist_opts widened = *opts;
-    if (widened.max_dist > 0.0) widened.max_dist = std::min(widened.max_dist + widened.max_dist * kBorderRel, 1.0);
-    const double link_below = opts->max_dist > 0.0 ? opts->max_dist - opts->max_dist * kBorderRel : opts->max_dist;
     hipStream_t stream = ctx->stream;
-
-    uint64_t cap = rk_hit_capacity(RowShard(opts, N, N).n_rows());   // (the rows of this shard, as rk_dist_rows counts them)
-    uint64_t edge_cap = kEdgeCapDefault;
-    if (const char *e = getenv("RK_CLUSTER_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
-
-    DevBuf<uint32_t> parent(ctx), out(ctx);   // out: the counters (kCntWords u64), then the labels
-    DevBuf<rk_edge> edges(ctx);
+    EdgeStage stage(ctx, idx, opts, "rk_cluster_rows", (size_t)N * 4);   // the tail: the labels
+    DevBuf<uint32_t> parent(ctx);
     RK_HIP(ctx, parent.alloc(N));
-    RK_HIP(ctx, out.alloc((size_t)N + 2 * kCntWords));
-    RK_HIP(ctx, edges.alloc(edge_cap));
-    unsigned long long *cnt = (unsigned long long *)out.p;
-    uint32_t *label = out.p + 2 * kCntWords;
-    const size_t out_bytes = ((size_t)N + 2 * kCntWords) * 4;
-    const unsigned char *home = nullptr;   // the context's page-locked scratch (asked for behind the join, whose lazy builders use it too)
-    hipLaunchKernelGGL(k_cluster_init, dim3(grid_for(ctx, N)), dim3(kClusterThreads), 0, stream, parent.p, N);
+    hipLaunchKernelGGL(k_cluster_init, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, parent.p, N);
     RK_HIP(ctx, hipGetLastError());
     if (ctx->timing) ctx->last_ms[RK_MS_CLUSTER_HOOK] = 0.0;
-
-    unsigned long long n_hits = 0, n_border = 0;
-    bool done = false;
-    for (int attempt = 0; attempt < 2 && !done; attempt++) {
-        DevBuf<rk_hit> hits(ctx);
-        if (hits.alloc(cap) != hipSuccess) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records on the device", (unsigned long long)cap);
-        RK_HIP(ctx, hipMemsetAsync(cnt, 0, kCntWords * 8, stream));
-        int rc = rk_dist_rows_dev(ctx, idx, nullptr, &widened, hits.p, cap, (uint64_t *)(cnt + kCntHits), stream);
-        if (rc) return rc;
-        st.join_attempts++;
-        st.hook_attempts = 0;
-        for (int pass = 0; pass < 2 && !done; pass++) {
-            if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
-            hipLaunchKernelGGL(k_cluster_hook, dim3(grid_for(ctx, cap)), dim3(kClusterThreads), 0, stream, hits.p, cnt + kCntHits, (unsigned long long)cap,
-                               parent.p, N, link_below, edges.p, (unsigned long long)edge_cap, cnt + kCntBorder, cnt + kCntBad);
-            if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
-            RK_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_cluster_flatten, dim3(grid_for(ctx, N)), dim3(kClusterThreads), 0, stream, parent.p, label, N);
-            RK_HIP(ctx, hipGetLastError());
-            home = (const unsigned char *)rk_pinned_scratch(ctx, out_bytes);
-            if (!home) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %zu bytes of page-locked memory for the labels", out_bytes);
-            RK_HIP(ctx, hipMemcpyAsync((void *)home, out.p, out_bytes, hipMemcpyDeviceToHost, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));
-            unsigned long long c[kCntWords];
-            memcpy(c, home, sizeof c);
-            if (c[kCntBad]) return rk_fail(ctx, RK_ERR_HIP, "%llu hit records name a genome beyond the index", c[kCntBad]);
-            n_hits = c[kCntHits];
-            n_border = c[kCntBorder];
-            if (n_hits > cap) {   // overflow: the join again with the exact count (the links made so far are links of the result)
-                cap = n_hits;
-                break;
-            }
-            st.hook_attempts++;
-            if (ctx->timing) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_CLUSTER_HOOK] = ms;
-            }
-            if (n_border > edge_cap) {   // the hook pass alone again, with room for every borderline record (linking twice changes nothing)
-                edge_cap = n_border;
-                RK_HIP(ctx, edges.alloc(edge_cap));
-                RK_HIP(ctx, hipMemsetAsync(cnt + kCntBorder, 0, 8, stream));
-                continue;
-            }
-            done = true;
-        }
-        if (done && n_border) {   // before `hits` and `edges` go back to the pool
-            std::vector<rk_edge> e(n_border);
-            RK_HIP(ctx, hipMemcpyAsync(e.data(), edges.p, n_border * sizeof(rk_edge), hipMemcpyDeviceToHost, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));
-            std::vector<rk_hit> h(n_border);
-            for (size_t i = 0; i < e.size(); i++) h[i] = rk_hit{e[i].row, e[i].col, e[i].common, e[i].size0, e[i].size1, 0, 0.0, 0.0};
-            st.borderline_kept = rk_host_exact_distances(h.data(), n_border, opts);
-            h.resize(st.borderline_kept);
-            memcpy(labels_out, home + kCntWords * 8, (size_t)N * 4);
-            for (const rk_hit &k : h) host_union(labels_out, k.row, k.col);
-        } else if (done) {
-            memcpy(labels_out, home + kCntWords * 8, (size_t)N * 4);
-        }
+    int rc = stage.run([&](int) -> int {
+        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+        hipLaunchKernelGGL(k_cluster_hook, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
+                           (unsigned long long)stage.cap, parent.p, N, stage.link_below, stage.edges.p, (unsigned long long)stage.edge_cap);
+        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+        RK_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_cluster_flatten, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, parent.p, (uint32_t *)stage.tail(), N);
+        RK_HIP(ctx, hipGetLastError());
+        return RK_OK;
+    });
+    if (rc) return rc;
+    if (ctx->timing) {   // (the events of the last pass)
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_CLUSTER_HOOK] = ms;
     }
-    if (!done) return rk_fail(ctx, RK_ERR_CAPACITY, "hit or borderline buffer overflow persisted after resize");
-    st.edges = n_hits;
-    st.borderline = n_border;
+    std::vector<rk_hit> kept;
+    if ((rc = stage.decide(&kept))) return rc;
+    memcpy(labels_out, stage.home_tail(), (size_t)N * 4);
+    for (const rk_hit &k : kept) host_union(labels_out, k.row, k.col);
+    st.join_attempts = stage.join_attempts;
+    st.hook_attempts = stage.pass_attempts;
+    st.edges = stage.n_hits;
+    st.borderline = stage.n_border;
+    st.borderline_kept = kept.size();
     st.n_clusters = host_flatten(labels_out, N);
     if (stats) *stats = st;
     return RK_OK;

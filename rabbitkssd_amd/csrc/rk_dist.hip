@@ -1511,7 +1511,7 @@ int rk_dist_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
     // from the EXACT threshold: the default -D 1.0 of alldist (`1.0 < 1.0` is false, src/dist.cpp:232) stays sparse.
     const rk_dist_opts *exact_opts = opts;
     rk_dist_opts widened = *opts;
-    if (widened.max_dist > 0.0) widened.max_dist += widened.max_dist * 0x1p-46;
+    if (widened.max_dist > 0.0) widened.max_dist += widened.max_dist * kBorderRel;
     opts = &widened;
     const bool dense_mode = rk_dense_mode(exact_opts);
     hipStream_t stream = ctx->stream;

@@ -1,12 +1,16 @@
-// rk_dist_plan.h -- host arithmetic the distance joins share (rk_dist.hip, rk_distq.hip, rk_cluster.hip): the prefilter threshold,
-// the rows of a row shard, the first capacity of a hit buffer.  Nothing here launches or
-// allocates, and everything compiles without HIP (tools/dist_plan_check.cpp, tests/test_dist_plan_cpu.py).
+// rk_dist_plan.h -- host arithmetic the distance joins share (rk_dist.hip, rk_distq.hip, and rk_edge_stage.h for rk_cluster.hip,
+// rk_forest.hip and rk_greedy.hip): the prefilter threshold, the rows of a row shard, the first capacity of a hit buffer, the
+// widening of the device's threshold.  Nothing here launches or allocates, and everything compiles without HIP (tools/dist_plan_check.cpp, tests/test_dist_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "rabbitkssd.h"
+
+// The device reports with a threshold wider by this much, relative (~64 ulps: orders beyond the 2 ulps between the device's log and
+// the C library's), and the host decides exactly: rk_dist_rows every record, rk_edge_stage.h those within it of the threshold.
+constexpr double kBorderRel = 0x1p-46;
 
 // distance < D  <=>  jaccard > t/(2-t), t = exp(-k D)   (containment: c > t); 1e-6 relative slack
 // keeps the reject conservative, the exact formula still decides.  (Callers disable it -- 0.0 -- in dense mode and for D <= 0.)

@@ -1,4 +1,5 @@
-// rk_edge_order.h -- the order of hit records by nearness, shared by rk_forest.hip and rk_greedy.hip (not part of the public ABI).
+// rk_edge_order.h -- the order of hit records by nearness (not part of the public ABI): the keys of rk_edge_stage.h's key pass and of
+// the kernels of rk_forest.hip and rk_greedy.hip that follow it, and the exact order of their host sides.
 //
 // Order of edges (include/rabbitkssd.h, clusters section): the ratio common / u descending -- u = size0 + size1 - common (metric 0)
 // or min(size0, size1) (metric 1); both distances fall strictly as it rises --, then row ascending, then col ascending.  On the
@@ -14,11 +15,6 @@
 namespace {
 
 constexpr unsigned long long kDead = ~0ULL;  // w of a record that takes no part (any more)
-
-struct rk_edge {   // a record for the host: what rk_distance needs
-    uint32_t row, col;
-    int32_t common, size0, size1;
-};
 
 // common / u of a record as signed 64-bit terms (u may be <= 0 only for multisets whose counts are products of multiplicities)
 __host__ __device__ inline void ratio_terms(int32_t common, int32_t size0, int32_t size1, int metric, long long *c, long long *u)

@@ -4,12 +4,11 @@
 // genome is a REPRESENTATIVE unless a representative that precedes it is adjacent to it, otherwise a MEMBER of the nearest such
 // representative (order of rk_edge_order.h; ties to the smallest caller index).  The graph is that of rk_cluster_rows.
 //
-//   join      rk_dist_rows_dev (threshold widened by 2^-46) into max(65,536, rows * 64) records, one rerun with the exact count;
-//   k_keys    per record: w and row << 32 | col.  A record whose device distance is not below D (1 - 2^-46) is BORDERLINE: it goes,
-//             with its slot number, to the small host buffer and is dead for now.  A record outside 0 < common <= u (multisets) is
-//             counted: the call refuses such a collection;
-//   host      decides the borderline records with rk_host_exact_distances BEFORE any round (a kept edge can flip representatives
-//             arbitrarily far away); the slot numbers of the kept ones go back up and k_revive gives them their keys;
+//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (k_edge_keys<true>: per record w and
+//             row << 32 | col; a BORDERLINE record goes, with its slot number, to the small host buffer and is dead for now; a record
+//             outside 0 < common <= u -- multisets -- is counted: the call refuses such a collection), the two retries;
+//   host      the stage decides the borderline records BEFORE any round (a kept edge can flip representatives arbitrarily far
+//             away); the slot numbers of the kept ones go back up and k_revive gives them their keys;
 //   k_orient  per live record hi << 32 | lo: hi the endpoint of smaller rank (rank[] is the priority order, computed on the host);
 //   rounds    k_edges: hi a representative -> lo is covered, the record dead; hi a member -> dead; hi and lo undecided -> lo is
 //             blocked for this round.  k_vertices: an undecided genome that is covered becomes a member, one that is neither covered
@@ -28,7 +27,6 @@
 // round's number); a record's hl[e] is touched by its own thread only.  The only communication inside a kernel is the two
 // agent-scope relaxed minima of the assignment.  No loop waits for another workgroup: any grid works.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <vector>
@@ -36,16 +34,13 @@
 #include "rk_internal.h"
 #include "rk_dist_plan.h"
 #include "rk_edge_order.h"
+#include "rk_edge_stage.h"
 
 namespace {
 
-constexpr uint32_t kGreedyThreads = 256;
-constexpr uint64_t kEdgeCapDefault = 4096;   // records the first key pass has room for in the host buffer (RK_CLUSTER_EDGE_CAP)
-constexpr double kBorderRel = 0x1p-46;       // the widening of rk_dist_rows
 constexpr uint32_t kNone = 0xFFFFFFFFu;      // rep[] of a genome nobody wrote yet
 constexpr uint32_t kBatchMax = 8;            // rounds between two reads of the host
 
-enum { kCntHits = 0, kCntBorder = 1, kCntBad = 2, kCntRange = 3, kCntRound = 4, kCntWords = kCntRound + kBatchMax };   // (u64 each)
 enum : uint32_t { kUndecided = 0, kRep = 1, kMember = 2 };
 
 __global__ void k_greedy_init(uint32_t *state, uint32_t *covered, uint32_t *blocked, uint32_t *rep, unsigned long long *best_w,
@@ -61,39 +56,6 @@ __global__ void k_greedy_init(uint32_t *state, uint32_t *covered, uint32_t *bloc
     }
 }
 
-// n_hits_dev counts every hit of the join, those beyond `cap` included: the pass reads what was written.
-__global__ void __launch_bounds__(kGreedyThreads)
-k_greedy_keys(const rk_hit *hits, const unsigned long long *n_hits_dev, unsigned long long cap, uint32_t n, double link_below, int metric,
-              unsigned long long *w_out, unsigned long long *rc_out, rk_edge *edges, unsigned long long *slots, unsigned long long edge_cap,
-              unsigned long long *n_border, unsigned long long *n_bad, unsigned long long *n_range)
-{
-    const unsigned long long n_rec = min(*n_hits_dev, cap);
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
-        const rk_hit h = hits[e];
-        rc_out[e] = ((unsigned long long)h.row << 32) | h.col;
-        w_out[e] = kDead;
-        if (h.row >= n || h.col >= n || h.row == h.col) {   // (never from the join's kernels; nothing is indexed by such a record)
-            atomicAdd(n_bad, 1ULL);
-            continue;
-        }
-        long long c, u;
-        ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
-        if (c <= 0 || c > u) {   // no key, and no way to patch the representatives afterwards
-            atomicAdd(n_range, 1ULL);
-            continue;
-        }
-        if (!(h.dist < link_below)) {
-            const unsigned long long at = atomicAdd(n_border, 1ULL);
-            if (at < edge_cap) {
-                edges[at] = rk_edge{h.row, h.col, h.common, h.size0, h.size1};
-                slots[at] = e;
-            }
-            continue;
-        }
-        w_out[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (key >= 1: never kDead)
-    }
-}
-
 // the borderline records the host kept: alive from here on, their keys from the same integer function
 __global__ void k_greedy_revive(const rk_hit *hits, const unsigned long long *slots, unsigned long long n_kept, unsigned long long n_rec, int metric,
                                 unsigned long long *w)
@@ -101,11 +63,11 @@ __global__ void k_greedy_revive(const rk_hit *hits, const unsigned long long *sl
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_kept) return;
     const unsigned long long e = slots[i];
-    if (e >= n_rec) return;   // (the host sends back what k_greedy_keys wrote)
+    if (e >= n_rec) return;   // (the host sends back what k_edge_keys wrote)
     const rk_hit h = hits[e];
     long long c, u;
     ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
-    w[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (k_greedy_keys saw 0 < c <= u)
+    w[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (k_edge_keys saw 0 < c <= u)
 }
 
 // hi: the endpoint that precedes the other
@@ -115,7 +77,7 @@ __device__ __forceinline__ unsigned long long oriented(unsigned long long rc, co
     return rank[a] < rank[b] ? rc : ((unsigned long long)b << 32) | a;
 }
 
-__global__ void __launch_bounds__(kGreedyThreads)
+__global__ void __launch_bounds__(kStageThreads)
 k_greedy_orient(const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, const uint32_t *rank, unsigned long long *hl)
 {
     for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x)
@@ -123,7 +85,7 @@ k_greedy_orient(const unsigned long long *w, const unsigned long long *rc, unsig
 }
 
 // state[] is the round's start: written by k_greedy_vertices / k_greedy_init, a kernel boundary away
-__global__ void __launch_bounds__(kGreedyThreads)
+__global__ void __launch_bounds__(kStageThreads)
 k_greedy_edges(unsigned long long *hl, unsigned long long n_rec, const uint32_t *state, uint32_t *covered, uint32_t *blocked, uint32_t round)
 {
     for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
@@ -143,7 +105,7 @@ k_greedy_edges(unsigned long long *hl, unsigned long long n_rec, const uint32_t 
 }
 
 // the genomes still undecided behind this round go to *undecided, one atomic per wave
-__global__ void __launch_bounds__(kGreedyThreads)
+__global__ void __launch_bounds__(kStageThreads)
 k_greedy_vertices(uint32_t *state, const uint32_t *covered, const uint32_t *blocked, uint32_t *rep, uint32_t n, uint32_t round, unsigned long long *undecided)
 {
     uint32_t left = 0;
@@ -161,7 +123,7 @@ k_greedy_vertices(uint32_t *state, const uint32_t *covered, const uint32_t *bloc
 
 // STEP 0: the best w per member; 1: among the records that match it, the best row << 32 | col; 2: the winner writes
 template <int STEP>
-__global__ void __launch_bounds__(kGreedyThreads)
+__global__ void __launch_bounds__(kStageThreads)
 k_greedy_assign(const rk_hit *hits, const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, const uint32_t *rank,
                 const uint32_t *state, unsigned long long *best_w, unsigned long long *best_rc, uint32_t *rep, rk_hit *link)
 {
@@ -182,12 +144,6 @@ k_greedy_assign(const rk_hit *hits, const unsigned long long *w, const unsigned 
     }
 }
 
-unsigned grid_for(const rk_ctx *ctx, uint64_t items)
-{
-    const uint64_t want = (items + kGreedyThreads - 1) / kGreedyThreads;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)std::max(1, ctx->num_cu) * 8));
-}
-
 // rank[a] = the place of genome a in the priority order: (priority[a], a) ascending, or (-size[a], a) without a priority
 void rank_of(const uint32_t *priority, const uint32_t *size, uint32_t n, std::vector<uint32_t> *rank)
 {
@@ -197,11 +153,6 @@ void rank_of(const uint32_t *priority, const uint32_t *size, uint32_t n, std::ve
     else std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return size[a] > size[b]; });
     rank->resize(n);
     for (uint32_t k = 0; k < n; k++) (*rank)[order[k]] = k;
-}
-
-rk_hit *host_records(uint64_t n)
-{
-    return (rk_hit *)malloc((n ? n : 1) * sizeof(rk_hit));
 }
 
 }  // namespace
@@ -228,15 +179,11 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     if (!idx->d_postings) return rk_fail(ctx, RK_ERR_ARG, "rk_greedy_rows: a join-only index (rk_index_join_shard) holds the rows of one shard");
     if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_greedy_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
     RK_HIP(ctx, hipSetDevice(ctx->device));
-    rk_dist_opts widened = *opts;
-    if (widened.max_dist > 0.0) widened.max_dist = std::min(widened.max_dist + widened.max_dist * kBorderRel, 1.0);
-    const double link_below = opts->max_dist > 0.0 ? opts->max_dist - opts->max_dist * kBorderRel : opts->max_dist;
-    const int metric = opts->metric != 0;
     hipStream_t stream = ctx->stream;
-
-    uint64_t cap = rk_hit_capacity(RowShard(opts, N, N).n_rows());
-    uint64_t edge_cap = kEdgeCapDefault;
-    if (const char *e = getenv("RK_CLUSTER_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    EdgeStage stage(ctx, idx, opts, "rk_greedy_rows", 0, true);   // with slot numbers
+    stage.hits_what = "hit records and their keys";
+    stage.bad_what = "a genome beyond the index or one genome twice";
+    const int metric = stage.metric;
     const uint64_t max_rounds = (uint64_t)N + 1;   // every round with undecided genomes decides the first of them in rank order
 
     // the priority order, once: 4 * N bytes up (and, without a priority, the sizes and the genome order of the index down)
@@ -261,8 +208,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     }
 
     DevBuf<uint32_t> rank(ctx), state(ctx), covered(ctx), blocked(ctx), rep(ctx);
-    DevBuf<unsigned long long> best_w(ctx), best_rc(ctx), cnt(ctx), slots(ctx);
-    DevBuf<rk_edge> edges(ctx);
+    DevBuf<unsigned long long> best_w(ctx), best_rc(ctx), left_dev(ctx), w(ctx), rc_(ctx), hl(ctx);   // left_dev: the counters of a batch of rounds
     DevBuf<rk_hit> link(ctx);
     RK_HIP(ctx, rank.alloc(N));
     RK_HIP(ctx, state.alloc(N));
@@ -271,87 +217,50 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     RK_HIP(ctx, rep.alloc(N));
     RK_HIP(ctx, best_w.alloc(N));
     RK_HIP(ctx, best_rc.alloc(N));
-    RK_HIP(ctx, cnt.alloc(kCntWords));
-    RK_HIP(ctx, edges.alloc(edge_cap));
-    RK_HIP(ctx, slots.alloc(edge_cap));
+    RK_HIP(ctx, left_dev.alloc(kBatchMax));
     RK_HIP(ctx, link.alloc(N));
     RK_HIP(ctx, hipMemcpyAsync(rank.p, rank_h.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream));
     RK_HIP(ctx, hipStreamSynchronize(stream));   // (rank_h is pageable memory)
-    hipLaunchKernelGGL(k_greedy_init, dim3(grid_for(ctx, N)), dim3(kGreedyThreads), 0, stream, state.p, covered.p, blocked.p, rep.p, best_w.p, best_rc.p, N);
+    hipLaunchKernelGGL(k_greedy_init, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, state.p, covered.p, blocked.p, rep.p, best_w.p, best_rc.p, N);
     RK_HIP(ctx, hipGetLastError());
     if (ctx->timing) ctx->last_ms[RK_MS_GREEDY_ROUNDS] = 0.0;
 
-    unsigned long long c[kCntRound] = {0, 0, 0, 0};
+    // the key pass: nothing is decided before the stage is through
+    int rc = stage.run([&](int pass) -> int {
+        if (!pass && (w.alloc(stage.cap) != hipSuccess || rc_.alloc(stage.cap) != hipSuccess || hl.alloc(stage.cap) != hipSuccess))
+            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)stage.cap);
+        hipLaunchKernelGGL(k_edge_keys<true>, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
+                           (unsigned long long)stage.cap, N, stage.link_below, metric, w.p, rc_.p, stage.edges.p, stage.slots.p, (unsigned long long)stage.edge_cap);
+        RK_HIP(ctx, hipGetLastError());
+        return RK_OK;
+    });
+    if (rc) return rc;
+    st.join_attempts = stage.join_attempts;
+    st.border_attempts = stage.pass_attempts;
+    if (stage.n_border >= (1ULL << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_greedy_rows: %llu borderline records", stage.n_border);
+    const rk_hit *hits = stage.hits.p;
+    const unsigned long long n_rec = stage.n_hits;
+    const unsigned grid = grid_for(ctx, n_rec);
+    // the borderline records, decided before any round: the slot numbers of the kept ones go back up
+    {
+        std::vector<rk_hit> kept;
+        std::vector<unsigned long long> kept_slots;
+        if ((rc = stage.decide(&kept, &kept_slots))) return rc;
+        st.borderline_kept = kept.size();
+        if (!kept.empty()) {
+            RK_HIP(ctx, hipMemcpyAsync(stage.slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, stream));
+            RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept_slots is pageable memory)
+            hipLaunchKernelGGL(k_greedy_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream, hits,
+                               stage.slots.p, (unsigned long long)kept.size(), n_rec, metric, w.p);
+            RK_HIP(ctx, hipGetLastError());
+        }
+    }
     std::vector<uint32_t> rep_h(N);
     std::vector<rk_hit> link_h;
-    bool done = false;
-    for (int attempt = 0; attempt < 2 && !done; attempt++) {
-        DevBuf<rk_hit> hits(ctx);
-        DevBuf<unsigned long long> w(ctx), rc_(ctx), hl(ctx);
-        if (hits.alloc(cap) != hipSuccess || w.alloc(cap) != hipSuccess || rc_.alloc(cap) != hipSuccess || hl.alloc(cap) != hipSuccess)
-            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)cap);
-        RK_HIP(ctx, hipMemsetAsync(cnt.p, 0, kCntWords * 8, stream));
-        int rc = rk_dist_rows_dev(ctx, idx, nullptr, &widened, hits.p, cap, (uint64_t *)(cnt.p + kCntHits), stream);
-        if (rc) return rc;
-        st.join_attempts++;
-        st.border_attempts = 0;
-        bool keyed = false;
-        for (int pass = 0; pass < 2 && !keyed; pass++) {
-            hipLaunchKernelGGL(k_greedy_keys, dim3(grid_for(ctx, cap)), dim3(kGreedyThreads), 0, stream, hits.p, cnt.p + kCntHits, (unsigned long long)cap, N,
-                               link_below, metric, w.p, rc_.p, edges.p, slots.p, (unsigned long long)edge_cap, cnt.p + kCntBorder, cnt.p + kCntBad,
-                               cnt.p + kCntRange);
-            RK_HIP(ctx, hipGetLastError());
-            if (int r = rk_read_back(ctx, c, cnt.p, sizeof c, stream)) return r;
-            if (c[kCntBad]) return rk_fail(ctx, RK_ERR_HIP, "%llu hit records name a genome beyond the index or one genome twice", c[kCntBad]);
-            if (c[kCntHits] > cap) break;   // overflow: the join again with the exact count (nothing was decided yet)
-            if (c[kCntRange])
-                return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_greedy_rows: %llu hit records lie outside 0 < common <= u (sketches that repeat hashes): they have no place in the order",
-                               c[kCntRange]);
-            st.border_attempts++;
-            if (c[kCntBorder] >= (1ULL << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_greedy_rows: %llu borderline records", c[kCntBorder]);
-            if (c[kCntBorder] > edge_cap) {   // the key pass alone again, with room for every record of the host
-                edge_cap = c[kCntBorder];
-                RK_HIP(ctx, edges.alloc(edge_cap));
-                RK_HIP(ctx, slots.alloc(edge_cap));
-                RK_HIP(ctx, hipMemsetAsync(cnt.p + kCntBorder, 0, 8, stream));
-                continue;
-            }
-            keyed = true;
-        }
-        if (c[kCntHits] > cap) {
-            cap = c[kCntHits];
-            continue;
-        }
-        if (!keyed) break;
-        const unsigned long long n_rec = c[kCntHits];
-        const unsigned grid = grid_for(ctx, n_rec);
-        // the borderline records, decided before any round: the slot numbers of the kept ones go back up
-        if (c[kCntBorder]) {
-            const size_t nb = c[kCntBorder];
-            std::vector<rk_edge> e(nb);
-            std::vector<unsigned long long> slot(nb);
-            RK_HIP(ctx, hipMemcpyAsync(e.data(), edges.p, nb * sizeof(rk_edge), hipMemcpyDeviceToHost, stream));
-            RK_HIP(ctx, hipMemcpyAsync(slot.data(), slots.p, nb * 8, hipMemcpyDeviceToHost, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));
-            std::vector<rk_hit> h(nb);
-            for (size_t i = 0; i < nb; i++) h[i] = rk_hit{e[i].row, e[i].col, e[i].common, e[i].size0, e[i].size1, (int32_t)i, 0.0, 0.0};   // (pad_: the record's place in `slot`)
-            st.borderline_kept = rk_host_exact_distances(h.data(), nb, opts);
-            if (st.borderline_kept) {
-                std::vector<unsigned long long> kept(st.borderline_kept);
-                for (size_t i = 0; i < kept.size(); i++) kept[i] = slot[(size_t)h[i].pad_];
-                RK_HIP(ctx, hipMemcpyAsync(slots.p, kept.data(), kept.size() * 8, hipMemcpyHostToDevice, stream));
-                RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept is pageable memory)
-                hipLaunchKernelGGL(k_greedy_revive, dim3((unsigned)((kept.size() + kGreedyThreads - 1) / kGreedyThreads)), dim3(kGreedyThreads), 0, stream, hits.p,
-                                   slots.p, (unsigned long long)kept.size(), n_rec, metric, w.p);
-                RK_HIP(ctx, hipGetLastError());
-            }
-        }
-        if (c[kCntHits] - c[kCntBorder] + st.borderline_kept == 0) {   // no record takes part: no round, every genome its own representative
-            std::iota(rep_h.begin(), rep_h.end(), 0u);
-            done = true;
-            break;
-        }
-        hipLaunchKernelGGL(k_greedy_orient, dim3(grid), dim3(kGreedyThreads), 0, stream, w.p, rc_.p, n_rec, rank.p, hl.p);
+    if (stage.n_hits - stage.n_border + st.borderline_kept == 0) {   // no record takes part: no round, every genome its own representative
+        std::iota(rep_h.begin(), rep_h.end(), 0u);
+    } else {
+        hipLaunchKernelGGL(k_greedy_orient, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, rank.p, hl.p);
         RK_HIP(ctx, hipGetLastError());
         // decision rounds; the host reads the counters of a batch (one round at first: species cliques settle in two or three)
         if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
@@ -360,16 +269,16 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
         while (!settled) {
             const uint64_t batch = std::min<uint64_t>(rounds < 4 ? 1 : rounds < 16 ? 4 : kBatchMax, max_rounds - rounds);
             if (!batch) return rk_fail(ctx, RK_ERR_HIP, "rk_greedy_rows: %llu rounds did not decide %u genomes (internal error)", (unsigned long long)max_rounds, N);
-            RK_HIP(ctx, hipMemsetAsync(cnt.p + kCntRound, 0, batch * 8, stream));
+            RK_HIP(ctx, hipMemsetAsync(left_dev.p, 0, batch * 8, stream));
             for (uint64_t b = 0; b < batch; b++) {
                 const uint32_t round = (uint32_t)(rounds + b + 1);
-                hipLaunchKernelGGL(k_greedy_edges, dim3(grid), dim3(kGreedyThreads), 0, stream, hl.p, n_rec, state.p, covered.p, blocked.p, round);
-                hipLaunchKernelGGL(k_greedy_vertices, dim3(grid_for(ctx, N)), dim3(kGreedyThreads), 0, stream, state.p, covered.p, blocked.p, rep.p, N, round,
-                                   cnt.p + kCntRound + b);
+                hipLaunchKernelGGL(k_greedy_edges, dim3(grid), dim3(kStageThreads), 0, stream, hl.p, n_rec, state.p, covered.p, blocked.p, round);
+                hipLaunchKernelGGL(k_greedy_vertices, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, state.p, covered.p, blocked.p, rep.p, N, round,
+                                   left_dev.p + b);
             }
             RK_HIP(ctx, hipGetLastError());
             unsigned long long left[kBatchMax];
-            if (int r = rk_read_back(ctx, left, cnt.p + kCntRound, batch * 8, stream)) return r;
+            if (int r = rk_read_back(ctx, left, left_dev.p, batch * 8, stream)) return r;
             uint64_t ran = batch;
             for (uint64_t b = 0; b < batch && !settled; b++)
                 if (!left[b]) {
@@ -381,9 +290,9 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
         st.rounds = (uint32_t)rounds;
         if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
         // every member to its nearest preceding representative
-        hipLaunchKernelGGL(k_greedy_assign<0>, dim3(grid), dim3(kGreedyThreads), 0, stream, hits.p, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
-        hipLaunchKernelGGL(k_greedy_assign<1>, dim3(grid), dim3(kGreedyThreads), 0, stream, hits.p, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
-        hipLaunchKernelGGL(k_greedy_assign<2>, dim3(grid), dim3(kGreedyThreads), 0, stream, hits.p, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
+        hipLaunchKernelGGL(k_greedy_assign<0>, dim3(grid), dim3(kStageThreads), 0, stream, hits, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
+        hipLaunchKernelGGL(k_greedy_assign<1>, dim3(grid), dim3(kStageThreads), 0, stream, hits, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
+        hipLaunchKernelGGL(k_greedy_assign<2>, dim3(grid), dim3(kStageThreads), 0, stream, hits, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
         RK_HIP(ctx, hipGetLastError());
         link_h.resize(N);
         RK_HIP(ctx, hipMemcpyAsync(rep_h.data(), rep.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
@@ -393,9 +302,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_GREEDY_ROUNDS] = ms;
         }
-        done = true;
     }
-    if (!done) return rk_fail(ctx, RK_ERR_CAPACITY, "hit or borderline buffer overflow persisted after resize");
     // links in member order (link_h[m] was written iff rep_h[m] != m; without a round there is none)
     uint64_t n_members = 0;
     for (uint32_t i = 0; i < N; i++) {
@@ -417,8 +324,8 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     }
     *n_links = n_members;
     memcpy(rep_out, rep_h.data(), (size_t)N * 4);
-    st.edges = c[kCntHits];
-    st.borderline = c[kCntBorder];
+    st.edges = stage.n_hits;
+    st.borderline = stage.n_border;
     st.n_reps = N - (uint32_t)n_members;
     if (stats) *stats = st;
     return RK_OK;

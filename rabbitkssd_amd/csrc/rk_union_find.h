@@ -1,6 +1,7 @@
-// rk_union_find.h -- the lock-free union-find over caller genome indices shared by rk_cluster.hip and rk_forest.hip (device), and
-// the plain one of their host folds.  Invariant of both: parent[x] <= x, a root is only ever linked under a smaller index, so the
-// root of a tree is its smallest member.  Termination and memory scope of the device side: DESIGN.md 4.6.
+// rk_union_find.h -- the lock-free union-find over caller genome indices shared by rk_cluster.hip (k_cluster_hook) and rk_forest.hip
+// (k_forest_link) on the device, the root walk of their flatten kernels, and the plain union-find of their host folds.  Invariant
+// of all: parent[x] <= x, a root is only ever linked under a smaller index, so the root of a tree is its smallest member.
+// Termination and memory scope of the device side: DESIGN.md 4.6.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -36,6 +37,18 @@ __device__ __forceinline__ void p_link(uint32_t *parent, uint32_t x, uint32_t y)
         a = p_root(parent, seen);   // hi was linked meanwhile: seen < hi, on from there
         b = p_root(parent, lo);
     }
+}
+
+// root of x behind the kernel boundary of the last link: plain loads.  For kernels that do not write parent[], so that every
+// thread walks a settled chain.
+__device__ __forceinline__ uint32_t p_settled_root(const uint32_t *parent, uint32_t x)
+{
+    uint32_t p = parent[x];
+    while (p != x) {
+        x = p;
+        p = parent[x];
+    }
+    return x;
 }
 
 inline uint32_t host_root(uint32_t *parent, uint32_t x)

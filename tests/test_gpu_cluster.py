@@ -227,6 +227,24 @@ def test_borderline_overflow_runs_the_hook_pass_again(ctx, monkeypatch):
     assert st["hook_attempts"] == 1 and st["borderline"] == 300
 
 
+# ---- 5b. both overflows in one call -------------------------------------------------------------------------------------
+def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
+    """The hit overflow ends the first attempt before the borderline overflow is looked at; the hook pass behind the second join
+    overflows the borderline buffer and runs again (its links stand: parent[] is not reset in between)."""
+    import test_gpu_forest as tf
+    h, off = tf.both_overflows_collection()
+    orc = Oracle(h, off, 24)
+    idx = device_index(ctx, h, off, 24)
+    monkeypatch.setenv("RK_CLUSTER_EDGE_CAP", "4")
+    for D, want_hits, kept in tf.both_overflows_thresholds():
+        want, n_hits = orc.labels(0, D)
+        assert n_hits == want_hits > max(65536, 420 * 64)
+        labels, st = ctx.cluster_rows(idx, 0, KMER, D)
+        check(labels, st, want, n_hits)
+        assert st["join_attempts"] == 2 and st["hook_attempts"] == 2 and st["borderline"] == 10 and st["borderline_kept"] == kept
+        assert st["n_clusters"] == 21 - kept
+
+
 # ---- 6. every kernel of the join ----------------------------------------------------------------------------------------
 def with_empties(names, h, off, at):
     """the collection with an empty sketch in front of every genome index in `at`"""

@@ -261,6 +261,43 @@ def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
     assert st["border_attempts"] == 1 and st["borderline"] == 300
 
 
+# ---- 7b. both overflows in one call -------------------------------------------------------------------------------------
+def both_overflows_collection():
+    """400 copies of one sketch of 100 hashes (79,800 pairs at distance 0: more than the first hit capacity of 65,536) and 10 pairs
+    that share 80 of their 100 hashes, in a fixed random caller order; shared with the cluster and the greedy suites"""
+    rng = np.random.default_rng(21)
+    pool = np.unique(rng.integers(0, 1 << 24, size=2000))
+    rng.shuffle(pool)
+    assert len(pool) >= 100 + 10 * 120
+    parts = [np.sort(pool[:100])] * 400
+    for p in range(10):
+        mine = pool[100 + 120 * p: 220 + 120 * p]
+        parts += [np.sort(mine[:100]), np.sort(mine[20:120])]
+    return csr(permuted(parts, 17))
+
+
+def both_overflows_thresholds():
+    """(D, the oracle's hits, borderline records kept) one ulp above the distance of the ten pairs, and on it (strict <)"""
+    _, d0 = ok.distance(80, 100, 100, 0, KMER)
+    return ((float(np.nextafter(d0, 1.0)), 79810, 10), (d0, 79800, 0))
+
+
+def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
+    """The hit overflow ends the first attempt before the borderline overflow is looked at; the key pass behind the second join
+    overflows the borderline buffer and runs again."""
+    h, off = both_overflows_collection()
+    orc = Oracle(h, off, 24)
+    idx = device_index(ctx, h, off, 24)
+    monkeypatch.setenv("RK_CLUSTER_EDGE_CAP", "4")
+    for D, n_hits, kept in both_overflows_thresholds():
+        hits = orc.hits(0, D)
+        assert len(hits) == n_hits > max(65536, 420 * 64) and int(np.sum(hits["common"] == 80)) == kept
+        edges, st = ctx.forest_rows(idx, 0, KMER, D)
+        check(edges, st, hits, 420, 0)
+        assert st["join_attempts"] == 2 and st["border_attempts"] == 2 and st["borderline"] == 10 and st["borderline_kept"] == kept
+        assert len(edges) == 399 + kept and st["n_trees"] == 21 - kept
+
+
 # ---- 8. every kernel of the join, both metrics, 36-bit hashes -----------------------------------------------------------
 _collections = {}
 

@@ -255,6 +255,24 @@ def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
     assert got[2]["border_attempts"] == 1 and got[2]["borderline"] == 300
 
 
+# ---- 8b. both overflows in one call -------------------------------------------------------------------------------------
+def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
+    """The hit overflow ends the first attempt before the borderline overflow is looked at; the key pass behind the second join
+    overflows the borderline buffer and runs again."""
+    h, off = tf.both_overflows_collection()
+    orc = Oracle(h, off, 24)
+    idx = device_index(ctx, h, off, 24)
+    monkeypatch.setenv("RK_CLUSTER_EDGE_CAP", "4")
+    for D, n_hits, kept in tf.both_overflows_thresholds():
+        hits = orc.hits(0, D)
+        assert len(hits) == n_hits > max(65536, 420 * 64) and int(np.sum(hits["common"] == 80)) == kept
+        got = ctx.greedy_rows(idx, 0, KMER, D)
+        check(got, hits, 420, 0, sizes=orc.sizes)
+        st = got[2]
+        assert st["join_attempts"] == 2 and st["border_attempts"] == 2 and st["borderline"] == 10 and st["borderline_kept"] == kept
+        assert st["n_reps"] == 21 - kept and len(got[1]) == 399 + kept
+
+
 # ---- 9. every kernel of the join, both metrics, 36-bit hashes -----------------------------------------------------------
 @pytest.mark.parametrize("which,kernel,metric", [
     ("tiles", "rk_tile_kernel", 0), ("tiles", "rk_tile_kernel", 1), ("near", "rk_near_kernel", 0), ("near", "rk_near_kernel", 1),
