@@ -109,6 +109,9 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 #define RK_MS_CLUSTER_HOOK 6
 /* rk_greedy_rows with timing on: all decision rounds of the last call (0 when no record took part). */
 #define RK_MS_GREEDY_ROUNDS 7
+/* rk_knn_rows with timing on: degree pass through selection kernel of the last call (0 when no record took part or the call
+ * took the host path). */
+#define RK_MS_KNN_SELECT 8
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -570,6 +573,61 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
  * n_hits == 0). */
 int rk_greedy_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, const uint32_t *priority /* n, optional */, int metric,
                    uint32_t *rep_out /* n */, rk_hit **links_out, uint64_t *n_links);
+
+/* ---- k nearest neighbours --------------------------------------------------------- */
+/* For every genome its k nearest neighbours within -D: the kNN graph of the all-vs-all -- the input of community detection, of
+ * neighbour-graph layouts, of guide trees.  The graph is that of rk_cluster_rows: its edges are the pairs rk_dist_rows(ctx, idx, NULL,
+ * opts, ...) would report -- same metric, same strict threshold decided with the C library's log, same row_first / row_step / row_block
+ * selection, any index that call accepts, the join-only index of rk_index_join_shard included.
+ * A record is INCIDENT to its row and to its col; the NEIGHBOUR of genome i in such a record is the other endpoint.  The list of genome
+ * i holds the first min(k, degree(i)) incident records of the selected rows in this order: the ratio common / u descending, compared
+ * exactly (u as in rk_forest_rows: 25/75 ties 20/60), then the neighbour's caller index ascending -- the order of rk_forest_rows
+ * restricted to the records incident to one genome, whose (row, col) tie-break reads "neighbour ascending" there.  A record without a
+ * ratio (u <= 0 or common < 0: only sketches that repeat hashes produce such) comes behind every record that has one.  The order is
+ * strict, so the result is unique: it does not depend on the order of hits, the internal genome order, the join kernel or the sharding.
+ * off_out[i] .. off_out[i + 1] (host, rk_index_genomes(idx) + 1 entries, i the caller index) delimit genome i's records in *nbrs_out
+ * (library-allocated, rk_free_host; NULL when there is none), nearest first.  Each record is the hit record as the join reports it
+ * (row < col), so a pair can appear in two lists; jorc and dist are recomputed on the host with the C library's log -- the reference's
+ * values bit for bit.
+ * Device path (stats.path == 1) for 1 <= k <= 64, one list slot per lane of a wave64.  The hit records never leave the device (the frame
+ * of rk_forest_rows: the join through rk_dist_rows_dev with the threshold widened by 2^-46 into max(65,536, rows * 64) records, once more
+ * with the exact count on overflow; the key pass with its small host buffer of RK_CLUSTER_EDGE_CAP borderline records, run again alone
+ * on overflow).  A degree pass counts the live records per genome, two scans lay out a CSR adjacency of 16-byte entries {~ratio key,
+ * neighbour << 32 | record number} and the output, a fill pass writes the entries, and a selection kernel -- one wave64 per genome, the
+ * segment streamed in chunks of 64, a ballot filter against the current k-th, insertion by rank -- keeps the first k and writes their
+ * hit records.  PCIe traffic: 4 * (N + 1) bytes of offsets, 40 bytes per returned record, the borderline records: never O(hits).  The
+ * borderline records the host keeps are folded into their two endpoints' lists on the host (a kept edge changes only those two).
+ * Inside the call, as rk_dist_rows + rk_knn_hits with the same result (stats.path == 2): k above 64, N * k >= 2^32, 2^31 hit records or
+ * more, and RK_KNN_DEVICE=0.  k == 0: RK_OK, all offsets 0, nothing runs on the device (stats.path == 0); likewise an index without
+ * genomes.
+ * Row shards are accepted: a shard's call returns, for every genome, the first k of the records that shard owns; rk_knn_merge folds the
+ * shards' results exactly -- the first k of a union are the first k of the union of the first ks.
+ * RK_ERR_ARG: triangle != 1, null pointers, a dense report (a threshold above 1.0: pairs that share nothing carry no order), an index
+ * rk_dist_rows refuses for a self join.  RK_ERR_UNSUPPORTED: a sketch of 2^30 hashes or more (the key), and what the join answers.
+ * stats is optional. */
+typedef struct rk_knn_stats {
+    uint64_t edges;            /* hit records of the join */
+    uint64_t borderline;       /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint64_t neighbours;       /* records returned */
+    uint32_t join_attempts;    /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts;  /* 2: the host buffer overflowed once */
+    uint32_t max_degree;       /* most live records at one genome (device path) */
+    uint32_t path;             /* 0 nothing ran, 1 device selection, 2 rk_dist_rows + rk_knn_hits inside the call */
+} rk_knn_stats;                /* 48 bytes */
+int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint32_t k, uint64_t *off_out /* host, N + 1 */,
+                rk_hit **nbrs_out, uint64_t *n_nbrs, rk_knn_stats *stats /* optional */);
+/* Host only: the same lists from a hit list the caller already has (`metric` as rk_dist_opts.metric; one record per pair, as a join
+ * reports them); the records are returned unchanged.  RK_ERR_ARG when a record names a genome >= n or has row == col, and for null
+ * pointers (hits may be NULL when n_hits == 0). */
+int rk_knn_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t k, int metric, uint64_t *off_out /* n + 1 */,
+                rk_hit **nbrs_out, uint64_t *n_nbrs);
+/* Host only: per genome, the first k of the union of two lists (a pair present in both counts once) -- what folds the results of row
+ * shards and of GPUs into those of the collection.  Lists longer than k are cut to k; the lists need not be in order.  off_out may be
+ * a_off or b_off.  RK_ERR_ARG: null pointers (a record array may be NULL when its lists are empty), offsets that do not ascend, a record
+ * that names a genome >= n, has row == col or is not incident to the genome whose list holds it.  Nothing is written on a refusal. */
+int rk_knn_merge(const uint64_t *a_off, const rk_hit *a, const uint64_t *b_off, const rk_hit *b, uint32_t n, uint32_t k, int metric,
+                 uint64_t *off_out /* n + 1 */, rk_hit **out, uint64_t *n_out);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

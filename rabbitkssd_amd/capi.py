@@ -30,6 +30,7 @@ EXPORTS = [
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
+    "rk_knn_rows", "rk_knn_hits", "rk_knn_merge",
 ]
 
 
@@ -74,6 +75,12 @@ class GreedyStats(C.Structure):
     _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
                 ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("rounds", C.c_uint32),
                 ("n_reps", C.c_uint32)]
+
+
+class KnnStats(C.Structure):
+    """rk_knn_stats: what one rk_knn_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64), ("neighbours", C.c_uint64),
+                ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("max_degree", C.c_uint32), ("path", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -445,6 +452,23 @@ class Context:
         L.rk_free_host(links)
         return rep, np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in GreedyStats._fields_}
 
+    def knn_rows(self, index, metric, kmer_size, max_dist, k, row_first=0, row_step=1, row_block=0):
+        """the k nearest neighbours of every genome within max_dist (rk_knn_rows): (off, nbrs, stats) -- off (uint64, genomes + 1)
+        delimits genome i's records in nbrs (HIT_DTYPE, nearest first: ratio common / u descending, then the neighbour's index), stats
+        a dict of the KnnStats fields"""
+        opts = DistOpts(1, int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+        off = np.zeros(index.genomes + 1, dtype=np.uint64)
+        nbrs = C.c_void_p()
+        n = C.c_uint64()
+        st = KnnStats()
+        L = lib()
+        L.rk_knn_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_uint64), C.POINTER(KnnStats)]
+        self.check(L.rk_knn_rows(self._h, index._h, C.byref(opts), C.c_uint32(k), _ptr(off), C.byref(nbrs), C.byref(n), C.byref(st)))
+        buf = C.string_at(nbrs.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
+        L.rk_free_host(nbrs)
+        return off, np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in KnnStats._fields_}
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
@@ -687,6 +711,47 @@ def greedy_hits(hits, n, metric, priority=None):
     buf = C.string_at(links.value, n_links.value * HIT_DTYPE.itemsize) if n_links.value else b""
     L.rk_free_host(links)
     return rep, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+
+
+def knn_hits(hits, n, k, metric):
+    """the k nearest neighbours of every genome from a hit list over n genomes (rk_knn_hits, host only): (off, nbrs) as
+    Context.knn_rows gives them, the records being the caller's, unchanged"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.zeros(int(n) + 1, dtype=np.uint64)
+    nbrs = C.c_void_p()
+    n_nbrs = C.c_uint64()
+    L = lib()
+    L.rk_knn_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    rc = L.rk_knn_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), C.c_uint32(k), int(metric), _ptr(off), C.byref(nbrs), C.byref(n_nbrs))
+    if rc:
+        raise RkError(rc, "rk_knn_hits: a record names a genome beyond the number of genomes or one genome twice")
+    buf = C.string_at(nbrs.value, n_nbrs.value * HIT_DTYPE.itemsize) if n_nbrs.value else b""
+    L.rk_free_host(nbrs)
+    return off, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+
+
+def knn_merge(a_off, a, b_off, b, n, k, metric):
+    """per genome the first k of the union of two neighbour lists (rk_knn_merge, host only): (off, nbrs)"""
+    a_off = np.ascontiguousarray(a_off, dtype=np.uint64)
+    b_off = np.ascontiguousarray(b_off, dtype=np.uint64)
+    a = np.ascontiguousarray(a, dtype=HIT_DTYPE)
+    b = np.ascontiguousarray(b, dtype=HIT_DTYPE)
+    if a_off.shape != (int(n) + 1,) or b_off.shape != (int(n) + 1,):
+        raise ValueError("knn_merge needs n + 1 offsets per input")
+    if (len(a_off) and int(a_off.max()) > len(a)) or (len(b_off) and int(b_off.max()) > len(b)):
+        raise ValueError("knn_merge: offsets beyond the records")
+    off = np.zeros(int(n) + 1, dtype=np.uint64)
+    out = C.c_void_p()
+    n_out = C.c_uint64()
+    L = lib()
+    L.rk_knn_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                               C.POINTER(C.c_uint64)]
+    rc = L.rk_knn_merge(_ptr(a_off), _ptr(a), _ptr(b_off), _ptr(b), C.c_uint32(n), C.c_uint32(k), int(metric), _ptr(off), C.byref(out), C.byref(n_out))
+    if rc:
+        raise RkError(rc, "rk_knn_merge: offsets that do not ascend, or a record that is not incident to the genome whose list holds it")
+    buf = C.string_at(out.value, n_out.value * HIT_DTYPE.itemsize) if n_out.value else b""
+    L.rk_free_host(out)
+    return off, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
 
 
 def format_hit(name_a, name_b, hit):

@@ -1,0 +1,421 @@
+// rk_knn.hip -- the k nearest neighbours of every genome within -D, the kNN graph of `alldist`, on the device (rk_knn_rows), and
+// its host side: the same lists from a hit list the caller already has (rk_knn_hits) and the fold of two results (rk_knn_merge).
+// The graph is that of rk_cluster_rows.  A record is incident to its row and to its col; the list of genome v holds the first
+// min(k, degree(v)) records incident to v in the order of rk_edge_order.h restricted to v: the ratio common / u descending, compared
+// exactly, then the NEIGHBOUR's caller index ascending (the (row, col) tie-break of EdgeLess with one endpoint fixed).
+//
+//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (k_edge_keys<false>: per record w and
+//             row << 32 | col; a BORDERLINE record and a record outside 0 < common <= u -- multisets: no key -- go to the small host
+//             buffer and are dead on the device), the two retries;
+//   degree    k_knn_degree: per live record one atomicAdd on deg[row] and one on deg[col] -- behind the stage, whose pass may run twice;
+//   offsets   k_knn_offsets writes min(deg, k) and the largest degree; two exclusive scans give the adjacency offsets aoff[] and the
+//             output offsets koff[] (N + 1 words each);
+//   fill      k_knn_fill: per live record and endpoint v the 16-byte entry {w, other << 32 | e} at aoff[v] + atomicAdd(cur + v, 1).
+//             Entries compared as (first word, second word) ascending are exactly the order above (e < 2^31: more records fall
+//             back).  The place inside a segment depends on the run, the selection's result does not;
+//   select    k_knn_select: one wave64 per genome, the waves grid-striding over the genomes.  Lane l holds the l-th best entry so far
+//             or (kDead, kDead); lanes >= k stay dead.  The segment streams in chunks of 64, one 16-byte load per lane; a ballot keeps
+//             the candidates that beat the current k-th (lane k - 1); each survivor is broadcast, tested again against the tightened
+//             k-th, ranked by the number of lanes that precede it and inserted with one shuffle up.  Lane l < min(deg, k) writes
+//             hits[e] to out[koff[v] + l];
+//   host      koff[] and the records come home (4 (N + 1) + 40 * sum of min(deg, k) bytes, never O(hits)), jorc / dist recomputed
+//             with the C library's log; the stage's kept borderline records are folded into their two endpoints' lists with the
+//             routine rk_knn_merge uses (a kept edge changes those two lists only).
+//
+// Memory scope: w[], rc[], deg[], aoff[], koff[], cur[] and the entries are written by one kernel and read by a later one on the same
+// stream (plain accesses behind kernel boundaries).  The only communication inside a kernel is the relaxed agent-scope atomicAdds of
+// the degree and the fill pass (and the atomicMax of the largest degree).  No loop waits for another workgroup, and k_knn_select has no
+// barrier: the waves of a workgroup have different trip counts.  DESIGN.md 4.9.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "rk_internal.h"
+#include "rk_dist_plan.h"
+#include "rk_edge_order.h"
+#include "rk_edge_stage.h"
+
+namespace {
+
+constexpr uint32_t kKnnDeviceMax = 64;   // one list slot per lane of a wave64
+constexpr uint32_t kWave = 64;
+
+struct __align__(16) KnnEntry {
+    unsigned long long w, x;   // ~ratio key; neighbour << 32 | record number
+};
+
+__global__ void __launch_bounds__(kStageThreads)
+k_knn_degree(const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, uint32_t *deg)
+{
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        if (w[e] == kDead) continue;
+        const unsigned long long p = rc[e];
+        atomicAdd(deg + (uint32_t)(p >> 32), 1u);
+        atomicAdd(deg + (uint32_t)p, 1u);
+    }
+}
+
+// kmin[i] = min(deg[i], k); deg[N] is 0 (the scans then end in the totals); *max_deg: one atomic per wave
+__global__ void __launch_bounds__(kStageThreads)
+k_knn_offsets(const uint32_t *deg, uint32_t *kmin, uint32_t n, uint32_t k, uint32_t *max_deg)
+{
+    uint32_t most = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) {
+        const uint32_t d = deg[i];
+        kmin[i] = min(d, k);
+        most = max(most, d);
+    }
+    for (int d = warpSize / 2; d > 0; d >>= 1) most = max(most, (uint32_t)__shfl_down(most, d));
+    if ((threadIdx.x & (warpSize - 1)) == 0 && most) atomicMax(max_deg, most);
+}
+
+// aoff[v] + cur[v] stays below aoff[v + 1]: the degree pass counted the same live records
+__global__ void __launch_bounds__(kStageThreads)
+k_knn_fill(const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, const uint32_t *aoff, uint32_t *cur, KnnEntry *adj)
+{
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long we = w[e];
+        if (we == kDead) continue;
+        const unsigned long long p = rc[e];
+        const uint32_t a = (uint32_t)(p >> 32), b = (uint32_t)p;
+        adj[(unsigned long long)aoff[a] + atomicAdd(cur + a, 1u)] = KnnEntry{we, ((unsigned long long)b << 32) | e};
+        adj[(unsigned long long)aoff[b] + atomicAdd(cur + b, 1u)] = KnnEntry{we, ((unsigned long long)a << 32) | e};
+    }
+}
+
+__device__ __forceinline__ bool entry_less(unsigned long long aw, unsigned long long ax, unsigned long long bw, unsigned long long bx)
+{
+    return aw < bw || (aw == bw && ax < bx);
+}
+
+// the value lane `src` holds, src the same in every lane: two scalar reads, nothing through the LDS crossbar
+__device__ __forceinline__ unsigned long long lane_value(unsigned long long v, int src)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// 1 <= k <= 64.  Everything the loops branch on is the same in all lanes of a wave (aoff[v], ballots, broadcasts).
+__global__ void __launch_bounds__(kStageThreads)
+k_knn_select(const KnnEntry *adj, const uint32_t *aoff, const uint32_t *koff, const rk_hit *hits, uint32_t n, uint32_t k, rk_hit *out)
+{
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t n_waves = (gridDim.x * blockDim.x) / kWave;
+    const int kth = (int)k - 1;
+    for (uint32_t v = (blockIdx.x * blockDim.x + threadIdx.x) / kWave; v < n; v += n_waves) {
+        const unsigned long long beg = aoff[v], end = aoff[v + 1];
+        unsigned long long bw = kDead, bx = kDead;   // lane l: the l-th best entry so far
+        for (unsigned long long at = beg; at < end; at += kWave) {
+            unsigned long long cw = kDead, cx = kDead;
+            if (at + lane < end) {
+                const KnnEntry c = adj[at + lane];
+                cw = c.w;
+                cx = c.x;
+            }
+            unsigned long long mask = __ballot(entry_less(cw, cx, lane_value(bw, kth), lane_value(bx, kth)));
+            while (mask) {
+                const int src = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const unsigned long long sw = lane_value(cw, src), sx = lane_value(cx, src);
+                if (!entry_less(sw, sx, lane_value(bw, kth), lane_value(bx, kth))) continue;   // an earlier survivor tightened the k-th
+                const uint32_t rank = (uint32_t)__popcll(__ballot(entry_less(bw, bx, sw, sx)));   // < k: lane k - 1 does not precede it
+                const unsigned long long uw = __shfl_up(bw, 1), ux = __shfl_up(bx, 1);
+                if (lane < k && lane >= rank) {
+                    bw = lane == rank ? sw : uw;
+                    bx = lane == rank ? sx : ux;
+                }
+            }
+        }
+        if (lane < min((unsigned long long)k, end - beg)) out[koff[v] + lane] = hits[(uint32_t)bx];
+    }
+}
+
+inline uint32_t other_end(const rk_hit &h, uint32_t v) { return h.row == v ? h.col : h.row; }
+
+// the order of genome v's list: EdgeLess with the endpoint v fixed -- ratio first, then the neighbour's index
+struct NeighbourLess {
+    int metric;
+    uint32_t v;
+    bool operator()(const rk_hit &a, const rk_hit &b) const
+    {
+        rk_hit x = a, y = b;
+        x.row = y.row = 0;
+        x.col = other_end(a, v);
+        y.col = other_end(b, v);
+        return EdgeLess{metric}(x, y);
+    }
+};
+
+// `pool` (records incident to v, any order) -> its first k in the order, one record per neighbour
+void first_k(std::vector<rk_hit> *pool, uint32_t v, uint64_t k, int metric)
+{
+    std::sort(pool->begin(), pool->end(), NeighbourLess{metric, v});
+    size_t kept = 0;
+    for (size_t i = 0; i < pool->size() && kept < k; i++)
+        if (!kept || other_end((*pool)[kept - 1], v) != other_end((*pool)[i], v)) (*pool)[kept++] = (*pool)[i];
+    pool->resize(kept);
+}
+
+bool in_order(const rk_hit *rec, uint64_t m, uint32_t v, int metric)
+{
+    for (uint64_t j = 1; j < m; j++)
+        if (!NeighbourLess{metric, v}(rec[j - 1], rec[j])) return false;
+    return true;
+}
+
+// offsets ascend from wherever they start, every record of list i is incident to i and names genomes below n
+bool lists_valid(const uint64_t *off, const rk_hit *rec, uint32_t n)
+{
+    if (!off) return false;
+    for (uint32_t i = 0; i < n; i++)   // (all offsets before any record: a record is read only inside ascending offsets)
+        if (off[i] > off[i + 1]) return false;
+    if (off[0] < off[n] && !rec) return false;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint64_t at = off[i]; at < off[i + 1]; at++) {
+            const rk_hit &h = rec[at];
+            if (h.row >= n || h.col >= n || h.row == h.col || (h.row != i && h.col != i)) return false;
+        }
+    return true;
+}
+
+// per genome the first k of the union of two lists (validated by the caller)
+void fold_lists(const uint64_t *a_off, const rk_hit *a, const uint64_t *b_off, const rk_hit *b, uint32_t n, uint64_t k, int metric,
+                uint64_t *off_out, std::vector<rk_hit> *out)
+{
+    out->clear();
+    std::vector<rk_hit> pool;
+    off_out[0] = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        // one side empty, the other within k and in (strict) order already: nothing to fold
+        const uint64_t na = a_off[i + 1] - a_off[i], nb = b_off[i + 1] - b_off[i];
+        const rk_hit *one = na ? a + a_off[i] : b + b_off[i];
+        if ((!na || !nb) && na + nb <= k && in_order(one, na + nb, i, metric))
+            out->insert(out->end(), one, one + na + nb);
+        else {
+            pool.assign(a + a_off[i], a + a_off[i + 1]);
+            pool.insert(pool.end(), b + b_off[i], b + b_off[i + 1]);
+            first_k(&pool, i, k, metric);
+            out->insert(out->end(), pool.begin(), pool.end());
+        }
+        off_out[i + 1] = out->size();
+    }
+}
+
+// the lists of a hit list (validated by the caller): counting sort of record numbers by genome, then the first k of each
+void lists_of_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint64_t k, int metric, uint64_t *off_out, std::vector<rk_hit> *out)
+{
+    std::vector<uint64_t> start((size_t)n + 2, 0);
+    for (uint64_t e = 0; e < n_hits; e++) {
+        start[hits[e].row + 2]++;
+        start[hits[e].col + 2]++;
+    }
+    for (size_t i = 2; i < start.size(); i++) start[i] += start[i - 1];
+    std::vector<uint64_t> adj(2 * n_hits);
+    for (uint64_t e = 0; e < n_hits; e++) {   // (start[v + 1] runs from the begin of v's records to their end)
+        adj[start[hits[e].row + 1]++] = e;
+        adj[start[hits[e].col + 1]++] = e;
+    }
+    out->clear();
+    std::vector<rk_hit> pool;
+    off_out[0] = 0;
+    for (uint32_t v = 0; v < n; v++) {
+        pool.clear();
+        for (uint64_t at = start[v]; at < start[v + 1]; at++) pool.push_back(hits[adj[at]]);
+        first_k(&pool, v, k, metric);
+        out->insert(out->end(), pool.begin(), pool.end());
+        off_out[v + 1] = out->size();
+    }
+}
+
+// records for the caller of the library: NULL when there is none
+int hand_over(const std::vector<rk_hit> &rec, rk_hit **out, uint64_t *n_out)
+{
+    *out = nullptr;
+    *n_out = rec.size();
+    if (rec.empty()) return RK_OK;
+    rk_hit *p = host_records(rec.size());
+    if (!p) return RK_ERR_NOMEM;
+    memcpy(p, rec.data(), rec.size() * sizeof(rk_hit));
+    *out = p;
+    return RK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rk_knn_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t k, int metric, uint64_t *off_out, rk_hit **nbrs_out, uint64_t *n_nbrs)
+{
+    if ((n_hits && !hits) || !off_out || !nbrs_out || !n_nbrs) return RK_ERR_ARG;
+    for (uint64_t e = 0; e < n_hits; e++)
+        if (hits[e].row >= n || hits[e].col >= n || hits[e].row == hits[e].col) return RK_ERR_ARG;
+    std::vector<rk_hit> rec;
+    lists_of_hits(hits, n_hits, n, k, metric != 0, off_out, &rec);
+    return hand_over(rec, nbrs_out, n_nbrs);
+}
+
+int rk_knn_merge(const uint64_t *a_off, const rk_hit *a, const uint64_t *b_off, const rk_hit *b, uint32_t n, uint32_t k, int metric,
+                 uint64_t *off_out, rk_hit **out, uint64_t *n_out)
+{
+    if (!a_off || !b_off || !off_out || !out || !n_out) return RK_ERR_ARG;
+    if (!lists_valid(a_off, a, n) || !lists_valid(b_off, b, n)) return RK_ERR_ARG;
+    std::vector<uint64_t> off((size_t)n + 1);   // (off_out may be one of the inputs' offsets)
+    std::vector<rk_hit> rec;
+    fold_lists(a_off, a, b_off, b, n, k, metric != 0, off.data(), &rec);
+    if (int rc = hand_over(rec, out, n_out)) return rc;
+    memcpy(off_out, off.data(), off.size() * 8);
+    return RK_OK;
+}
+
+int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint32_t k, uint64_t *off_out, rk_hit **nbrs_out, uint64_t *n_nbrs,
+                rk_knn_stats *stats)
+{
+    if (!ctx || !idx || !opts) return RK_ERR_ARG;
+    rk_knn_stats st;
+    memset(&st, 0, sizeof st);
+    if (stats) *stats = st;
+    if (!off_out || !nbrs_out || !n_nbrs) return rk_fail(ctx, RK_ERR_ARG, "off_out, nbrs_out or n_nbrs is null");
+    *nbrs_out = nullptr;
+    *n_nbrs = 0;
+    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_knn_rows works on a self join: triangle must be 1");
+    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_knn_rows: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order");
+    const uint32_t N = idx->n_ref;
+    std::fill(off_out, off_out + (size_t)N + 1, (uint64_t)0);
+    if (!N) return RK_OK;
+    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
+    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_knn_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
+    if (!k) return RK_OK;
+    const int metric = opts->metric != 0;
+
+    // the same lists from the hit list on the host: what the device path has no room for
+    auto on_the_host = [&]() -> int {
+        rk_hit *hits = nullptr;
+        uint64_t n_hits = 0;
+        if (int rc = rk_dist_rows(ctx, idx, nullptr, opts, &hits, &n_hits, nullptr)) return rc;
+        std::vector<rk_hit> rec;
+        lists_of_hits(hits, n_hits, N, k, metric, off_out, &rec);
+        rk_free_host(hits);
+        if (hand_over(rec, nbrs_out, n_nbrs)) return rk_fail(ctx, RK_ERR_NOMEM, "host allocation of %llu neighbour records failed", (unsigned long long)rec.size());
+        memset(&st, 0, sizeof st);
+        st.edges = n_hits;
+        st.neighbours = rec.size();
+        st.path = 2;
+        if (stats) *stats = st;
+        return RK_OK;
+    };
+    const char *sw = getenv("RK_KNN_DEVICE");
+    if (k > kKnnDeviceMax || (uint64_t)N * k >= (1ULL << 32) || (sw && atoi(sw) == 0)) return on_the_host();
+
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    EdgeStage stage(ctx, idx, opts, "rk_knn_rows");
+    stage.hits_what = "hit records and their keys";
+    if (ctx->timing) ctx->last_ms[RK_MS_KNN_SELECT] = 0.0;
+    DevBuf<unsigned long long> w(ctx), rc_(ctx);
+    int rc = stage.run([&](int pass) -> int {
+        if (!pass && (w.alloc(stage.cap) != hipSuccess || rc_.alloc(stage.cap) != hipSuccess))
+            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)stage.cap);
+        hipLaunchKernelGGL(k_edge_keys<false>, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
+                           (unsigned long long)stage.cap, N, stage.link_below, metric, w.p, rc_.p, stage.edges.p, (unsigned long long *)nullptr,
+                           (unsigned long long)stage.edge_cap);
+        RK_HIP(ctx, hipGetLastError());
+        return RK_OK;
+    });
+    if (rc && !(rc == RK_ERR_NOMEM && stage.n_hits >= (1ULL << 31))) return rc;
+    if (stage.n_hits >= (1ULL << 31)) {   // the entries number the records in 31 bits
+        w.reset();
+        rc_.reset();
+        stage.hits.reset();
+        return on_the_host();
+    }
+    st.join_attempts = stage.join_attempts;
+    st.border_attempts = stage.pass_attempts;
+    st.path = 1;
+    const unsigned long long n_rec = stage.n_hits, n_live = n_rec - stage.n_border;
+
+    std::vector<uint64_t> off((size_t)N + 1, 0);
+    std::vector<rk_hit> rec;
+    if (n_live) {
+        DevBuf<uint32_t> deg(ctx), kmin(ctx), aoff(ctx), koff(ctx), most(ctx);
+        DevBuf<KnnEntry> adj(ctx);
+        DevBuf<rk_hit> out(ctx);
+        RK_HIP(ctx, deg.alloc((size_t)N + 1));
+        RK_HIP(ctx, kmin.alloc((size_t)N + 1));
+        RK_HIP(ctx, aoff.alloc((size_t)N + 1));
+        RK_HIP(ctx, koff.alloc((size_t)N + 1));
+        RK_HIP(ctx, most.alloc(1));
+        const uint64_t n_out_max = std::min<uint64_t>((uint64_t)N * k, 2 * n_live);
+        if (adj.alloc(2 * n_live) != hipSuccess || out.alloc(n_out_max) != hipSuccess)
+            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate the adjacency of %llu hit records on the device", n_live);
+        const unsigned grid = grid_for(ctx, n_rec), vgrid = grid_for(ctx, (uint64_t)N + 1);
+        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+        RK_HIP(ctx, hipMemsetAsync(deg.p, 0, ((size_t)N + 1) * 4, stream));
+        RK_HIP(ctx, hipMemsetAsync(most.p, 0, 4, stream));
+        hipLaunchKernelGGL(k_knn_degree, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, deg.p);
+        hipLaunchKernelGGL(k_knn_offsets, dim3(vgrid), dim3(kStageThreads), 0, stream, deg.p, kmin.p, N, k, most.p);
+        RK_HIP(ctx, hipGetLastError());
+        if (int r = rk_prim_exclusive_scan_u32(ctx, deg.p, aoff.p, (uint64_t)N + 1, stream)) return rk_fail(ctx, r, "rk_knn_rows: the scan of the degrees failed");
+        if (int r = rk_prim_exclusive_scan_u32(ctx, kmin.p, koff.p, (uint64_t)N + 1, stream)) return rk_fail(ctx, r, "rk_knn_rows: the scan of the list lengths failed");
+        RK_HIP(ctx, hipMemsetAsync(deg.p, 0, (size_t)N * 4, stream));   // from here on the cursors of the fill
+        hipLaunchKernelGGL(k_knn_fill, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, aoff.p, deg.p, adj.p);
+        const uint64_t waves_per_block = kStageThreads / kWave;
+        const unsigned sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((N + waves_per_block - 1) / waves_per_block, (uint64_t)std::max(1, ctx->num_cu) * 16));
+        hipLaunchKernelGGL(k_knn_select, dim3(sgrid), dim3(kStageThreads), 0, stream, adj.p, aoff.p, koff.p, stage.hits.p, N, k, out.p);
+        RK_HIP(ctx, hipGetLastError());
+        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+        // koff[], then the records it counts
+        std::vector<uint32_t> koff_h((size_t)N + 1);
+        uint32_t most_h = 0;
+        RK_HIP(ctx, hipMemcpyAsync(koff_h.data(), koff.p, koff_h.size() * 4, hipMemcpyDeviceToHost, stream));
+        RK_HIP(ctx, hipMemcpyAsync(&most_h, most.p, 4, hipMemcpyDeviceToHost, stream));
+        RK_HIP(ctx, hipStreamSynchronize(stream));
+        if (ctx->timing) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_KNN_SELECT] = ms;
+        }
+        st.max_degree = most_h;
+        const uint64_t total = koff_h[N];
+        if (total > n_out_max) return rk_fail(ctx, RK_ERR_HIP, "rk_knn_rows: %llu neighbour records where %llu are possible (internal error)", (unsigned long long)total, (unsigned long long)n_out_max);
+        rec.resize(total);
+        if (total) {
+            RK_HIP(ctx, hipMemcpyAsync(rec.data(), out.p, total * sizeof(rk_hit), hipMemcpyDeviceToHost, stream));
+            RK_HIP(ctx, hipStreamSynchronize(stream));
+        }
+        for (uint32_t i = 0; i <= N; i++) off[i] = koff_h[i];
+        for (uint32_t i = 0; i < N; i++) {
+            if (off[i] > off[i + 1] || off[i + 1] - off[i] > k) return rk_fail(ctx, RK_ERR_HIP, "rk_knn_rows: the list of genome %u is out of shape (internal error)", i);
+            for (uint64_t at = off[i]; at < off[i + 1]; at++)
+                if ((rec[at].row != i && rec[at].col != i) || rec[at].row >= N || rec[at].col >= N || rec[at].row == rec[at].col)
+                    return rk_fail(ctx, RK_ERR_HIP, "rk_knn_rows: a record in the list of genome %u is not incident to it (internal error)", i);
+        }
+        // the reference's values bit for bit (a record that took part lies below the exact threshold: none is dropped)
+        if (rk_host_exact_distances(rec.data(), total, opts) != total)
+            return rk_fail(ctx, RK_ERR_HIP, "rk_knn_rows: a neighbour record lies beyond the exact threshold (internal error)");
+    }
+    // the borderline records the host keeps: their own lists, folded in
+    {
+        std::vector<rk_hit> kept;
+        if ((rc = stage.decide(&kept))) return rc;
+        st.borderline_kept = kept.size();
+        if (!kept.empty()) {
+            for (const rk_hit &h : kept)
+                if (h.row >= N || h.col >= N || h.row == h.col) return rk_fail(ctx, RK_ERR_HIP, "rk_knn_rows: a borderline record names a genome beyond the index (internal error)");
+            std::vector<uint64_t> b_off((size_t)N + 1), f_off((size_t)N + 1);
+            std::vector<rk_hit> b, folded;
+            lists_of_hits(kept.data(), kept.size(), N, k, metric, b_off.data(), &b);
+            fold_lists(off.data(), rec.data(), b_off.data(), b.data(), N, k, metric, f_off.data(), &folded);
+            off.swap(f_off);
+            rec.swap(folded);
+        }
+    }
+    if (hand_over(rec, nbrs_out, n_nbrs)) return rk_fail(ctx, RK_ERR_NOMEM, "host allocation of %llu neighbour records failed", (unsigned long long)rec.size());
+    memcpy(off_out, off.data(), off.size() * 8);
+    st.edges = stage.n_hits;
+    st.borderline = stage.n_border;
+    st.neighbours = rec.size();
+    if (stats) *stats = st;
+    return RK_OK;
+}
+
+}  // extern "C"

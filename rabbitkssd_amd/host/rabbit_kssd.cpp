@@ -1541,6 +1541,83 @@ static int cmd_greedy(const Args &a)
     _exit(0);
 }
 
+// knn: the k nearest neighbours of every genome among alldist's pairs -- the kNN graph within -D (rk_knn_rows on every GPU for its rows,
+// folded with rk_knn_merge), one alldist-format line per (genome, neighbour): genomes by ascending index, nearest neighbour first, ties
+// by exact ratio, then by the neighbour's index.  The genome's name comes first, the neighbour's second, and common|size|size follows
+// that orientation.
+static int cmd_knn(const Args &a)
+{
+    if (!a.has("i")) die("knn needs -i");
+    const double max_dist = a.real("D", 1.0);
+    if (max_dist < 0.0) die("command_knn(), maxDist must be > 0\nUse -D to set the maxDist");
+    if (1.0 < max_dist) die("command_knn(), maxDist must not exceed 1.0: pairs that share nothing carry no order");
+    if (!a.has("N") || a.num("N", 0) < 1) die("command_knn(), maxNeighbor must be >= 1\nUse -N to set the maxNeighbor");
+    const uint32_t k = (uint32_t)a.num("N", 1);
+    const string out = a.str("o", "result.out");
+    const int metric = a.num("M", 0);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
+    SelfJoin j;
+    j.prepare(a, set, max_dist, threads);
+    const size_t G = set.size(), N = j.s.size();
+    vector<vector<uint64_t>> off(G, vector<uint64_t>(N + 1, 0));
+    vector<rk_hit *> nbrs(G, nullptr);
+    vector<uint64_t> n_nbrs(G, 0);
+    vector<rk_knn_stats> stats(G);
+    auto rows_of = [&](size_t g) {
+        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
+        set[g].check(rk_knn_rows(set[g].ctx, j.idx[g], &o, k, off[g].data(), &nbrs[g], &n_nbrs[g], &stats[g]), "rk_knn_rows");
+    };
+    {
+        vector<std::thread> pool;
+        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
+        rows_of(0);
+        for (auto &th : pool) th.join();
+    }
+    for (size_t g = 1; g < G; g++) {
+        rk_hit *folded = nullptr;
+        uint64_t n_folded = 0;
+        if (rk_knn_merge(off[0].data(), nbrs[0], off[g].data(), nbrs[g], (uint32_t)N, k, metric, off[0].data(), &folded, &n_folded) != 0) die("rk_knn_merge failed");
+        rk_free_host(nbrs[0]);
+        rk_free_host(nbrs[g]);
+        nbrs[0] = folded;
+        n_nbrs[0] = n_folded;
+    }
+    stamp("neighbours on the host");
+    cerr << "===================time of multiple threads distance computing and neighbour selection is: " << get_sec() - j.t1 << endl;
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    vector<char> buf(1 << 16);
+    for (size_t i = 0; i < N; i++)
+        for (uint64_t at = off[0][i]; at < off[0][i + 1]; at++) {
+            rk_hit h = nbrs[0][at];
+            const uint32_t other = h.row == i ? h.col : h.row;
+            if (h.col == i) std::swap(h.size0, h.size1);   // the genome's size first
+            const string &x = j.s.names[i], &y = j.s.names[other];
+            if (x.size() + y.size() + 128 > buf.size()) die("genome name too long");
+            const int len = rk_format_hit(buf.data(), buf.size(), x.c_str(), y.c_str(), &h);
+            if (len < 0) die("rk_format_hit failed");
+            fwrite(buf.data(), 1, (size_t)len, fp);
+        }
+    fclose(fp);
+    if (getenv("RK_TIMING")) {
+        unsigned long long hits = 0, border = 0, most = 0, path = 0;
+        for (size_t g = 0; g < G; g++) {
+            hits += stats[g].edges;
+            border += stats[g].borderline;
+            most = std::max<unsigned long long>(most, stats[g].max_degree);
+            path = std::max<unsigned long long>(path, stats[g].path);
+        }
+        fprintf(stderr, "[timing] %llu neighbour records (k = %u) over %zu genomes from %llu hit records (%llu borderline), largest degree %llu, path %llu\n",
+                (unsigned long long)n_nbrs[0], k, N, hits, border, most, path);
+    }
+    stamp("text written");
+    stamp("done");
+    fflush(stdout);
+    fflush(stderr);
+    _exit(0);
+}
+
 static int cmd_dist(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("dist needs -r and -q");
@@ -1926,13 +2003,14 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
             "  cluster -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (single-linkage clusters of alldist's pairs)\n"
             "  forest -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (minimum spanning forest of alldist's pairs: the single-linkage dendrogram up to -D, one alldist line per edge)\n"
             "  greedy -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--reps FILE] [-L file.shuf] [--device N]   (greedy representatives of alldist's pairs: larger sketch first, a genome joins the nearest earlier representative within -D or becomes one; one GPU)\n"
+            "  knn -i in.sketch|genomes.list -o out -N k [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (the k nearest neighbours of every genome among alldist's pairs: one alldist-format line per genome and neighbour, nearest first)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -1971,7 +2049,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -1992,6 +2070,7 @@ int main(int argc, char **argv)
     if (sub == "cluster") { cerr << "-----run the subcommand: cluster" << endl; return leave(cmd_cluster(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "forest") { cerr << "-----run the subcommand: forest" << endl; return leave(cmd_forest(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "greedy") { cerr << "-----run the subcommand: greedy" << endl; return leave(cmd_greedy(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "knn") { cerr << "-----run the subcommand: knn" << endl; return leave(cmd_knn(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
