@@ -137,6 +137,23 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _opts(triangle, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
+    """rk_dist_opts; a self join is triangle = 1"""
+    return DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+
+
+def _take_hits(ptr, n):
+    """takes over an rk_hit buffer the library returned: copied out as a HIT_DTYPE array, then freed"""
+    buf = C.string_at(ptr.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
+    lib().rk_free_host(ptr)
+    return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+
+
+def _stats_dict(st, fields=None):
+    """a stats structure as a dict of ints"""
+    return {name: int(getattr(st, name)) for name, _ in (st._fields_ if fields is None else fields)}
+
+
 def params_init(half_k, half_subk, drlevel):
     p = Params()
     rc = lib().rk_params_init(half_k, half_subk, drlevel, C.byref(p))
@@ -197,8 +214,7 @@ class Context:
         return d
 
     def dist_kernel_name(self, index, queries, triangle, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
-        opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
-                        int(row_first), int(row_step))
+        opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
         buf = C.create_string_buffer(128)
         self.check(lib().rk_dist_kernel_name(self._h, index._h, queries._h if queries is not None else None, C.byref(opts),
                                              buf, C.c_size_t(128)))
@@ -377,8 +393,7 @@ class Context:
     # ---- distances
     def dist_rows(self, index, queries, triangle, metric, kmer_size, max_dist, row_first=0,
                   row_step=1, want_dense=False, row_block=0):
-        opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
-                        int(row_first), int(row_step))
+        opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
         hits = C.c_void_p()
         n = C.c_uint64()
         dense = None
@@ -387,39 +402,34 @@ class Context:
             dense = np.zeros((nq, index.genomes), dtype=np.int32)
         self.check(lib().rk_dist_rows(self._h, index._h, queries._h if queries is not None else None,
                                       C.byref(opts), C.byref(hits), C.byref(n), _ptr(dense)))
-        buf = C.string_at(hits.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
-        lib().rk_free_host(hits)
-        return np.frombuffer(buf, dtype=HIT_DTYPE).copy(), dense
+        return _take_hits(hits, n), dense
 
     def dist_topn(self, index, queries, metric, kmer_size, max_dist, max_neighbor, row_first=0, row_step=1,
                   row_block=0, triangle=0):
         """-N on the device: per query row the max_neighbor nearest references, in the reference heap's pop order
         (the records of dist_rows + topn_rows), as HIT_DTYPE."""
-        opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
-                        int(row_first), int(row_step))
+        opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
         hits = C.c_void_p()
         n = C.c_uint64()
         self.check(lib().rk_dist_topn(self._h, index._h, queries._h if queries is not None else None,
                                       C.byref(opts), C.c_uint64(max_neighbor), C.byref(hits), C.byref(n)))
-        buf = C.string_at(hits.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
-        lib().rk_free_host(hits)
-        return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+        return _take_hits(hits, n)
 
     def cluster_rows(self, index, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
         """single-linkage clusters of the self join (rk_cluster_rows): (labels, stats) -- labels[i] = the smallest genome index
         of i's component (uint32), stats a dict of the ClusterStats fields"""
-        opts = DistOpts(1, int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+        opts = _opts(1, metric, kmer_size, max_dist, row_first, row_step, row_block)
         labels = np.zeros(index.genomes, dtype=np.uint32)
         st = ClusterStats()
         L = lib()
         L.rk_cluster_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_void_p, C.POINTER(ClusterStats)]
         self.check(L.rk_cluster_rows(self._h, index._h, C.byref(opts), _ptr(labels), C.byref(st)))
-        return labels, {name: int(getattr(st, name)) for name, _ in ClusterStats._fields_[:-1]}
+        return labels, _stats_dict(st, ClusterStats._fields_[:-1])
 
     def forest_rows(self, index, metric, kmer_size, max_dist, row_first=0, row_step=1, row_block=0):
         """minimum spanning forest of the self join (rk_forest_rows): (edges, stats) -- edges as HIT_DTYPE in forest order (ratio
         common / u descending, then row, then col), stats a dict of the ForestStats fields"""
-        opts = DistOpts(1, int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+        opts = _opts(1, metric, kmer_size, max_dist, row_first, row_step, row_block)
         edges = C.c_void_p()
         n = C.c_uint64()
         st = ForestStats()
@@ -427,15 +437,13 @@ class Context:
         L.rk_forest_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                      C.POINTER(ForestStats)]
         self.check(L.rk_forest_rows(self._h, index._h, C.byref(opts), C.byref(edges), C.byref(n), C.byref(st)))
-        buf = C.string_at(edges.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
-        L.rk_free_host(edges)
-        return np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in ForestStats._fields_}
+        return _take_hits(edges, n), _stats_dict(st)
 
     def greedy_rows(self, index, metric, kmer_size, max_dist, priority=None):
         """greedy representatives of the self join (rk_greedy_rows): (rep, links, stats) -- rep[i] = the caller index of i's
         representative (uint32; i itself iff i is one), links as HIT_DTYPE, one per member by ascending member index, stats a dict of
         the GreedyStats fields.  priority: optional uint32 per genome, smaller first (default: larger sketch first)"""
-        opts = DistOpts(1, int(metric), int(kmer_size), 0, float(max_dist), 0, 1)
+        opts = _opts(1, metric, kmer_size, max_dist)
         if priority is not None:
             priority = np.ascontiguousarray(priority, dtype=np.uint32)
             if priority.shape != (index.genomes,):
@@ -448,15 +456,13 @@ class Context:
         L.rk_greedy_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_uint64), C.POINTER(GreedyStats)]
         self.check(L.rk_greedy_rows(self._h, index._h, C.byref(opts), _ptr(priority), _ptr(rep), C.byref(links), C.byref(n), C.byref(st)))
-        buf = C.string_at(links.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
-        L.rk_free_host(links)
-        return rep, np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in GreedyStats._fields_}
+        return rep, _take_hits(links, n), _stats_dict(st)
 
     def knn_rows(self, index, metric, kmer_size, max_dist, k, row_first=0, row_step=1, row_block=0):
         """the k nearest neighbours of every genome within max_dist (rk_knn_rows): (off, nbrs, stats) -- off (uint64, genomes + 1)
         delimits genome i's records in nbrs (HIT_DTYPE, nearest first: ratio common / u descending, then the neighbour's index), stats
         a dict of the KnnStats fields"""
-        opts = DistOpts(1, int(metric), int(kmer_size), int(row_block), float(max_dist), int(row_first), int(row_step))
+        opts = _opts(1, metric, kmer_size, max_dist, row_first, row_step, row_block)
         off = np.zeros(index.genomes + 1, dtype=np.uint64)
         nbrs = C.c_void_p()
         n = C.c_uint64()
@@ -465,14 +471,11 @@ class Context:
         L.rk_knn_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_uint64), C.POINTER(KnnStats)]
         self.check(L.rk_knn_rows(self._h, index._h, C.byref(opts), C.c_uint32(k), _ptr(off), C.byref(nbrs), C.byref(n), C.byref(st)))
-        buf = C.string_at(nbrs.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
-        L.rk_free_host(nbrs)
-        return off, np.frombuffer(buf, dtype=HIT_DTYPE).copy(), {name: int(getattr(st, name)) for name, _ in KnnStats._fields_}
+        return off, _take_hits(nbrs, n), _stats_dict(st)
 
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
-        opts = DistOpts(int(triangle), int(metric), int(kmer_size), int(row_block), float(max_dist),
-                        int(row_first), int(row_step))
+        opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
         self.check(lib().rk_dist_rows_dev(self._h, index._h, queries._h if queries is not None else None, C.byref(opts),
                                           C.c_void_p(hits_dev_ptr), C.c_uint64(hits_cap),
                                           C.c_void_p(n_hits_dev_ptr), C.c_void_p(stream)))
@@ -596,7 +599,7 @@ class Index(_Obj):
 
     def tile_stats(self, triangle=1, metric=0, kmer_size=20, max_dist=0.05):
         """(tiles with records, tiles a launch with these options starts, tile records, record slots) -- rk_index_tile_stats"""
-        opts = DistOpts(int(triangle), int(metric), int(kmer_size), 0, float(max_dist), 0, 1)
+        opts = _opts(triangle, metric, kmer_size, max_dist)
         out = (C.c_uint64 * 4)()
         L = lib()
         L.rk_index_tile_stats.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
@@ -673,9 +676,7 @@ def forest_merge(a, b, n, metric):
     rc = L.rk_forest_merge(_ptr(a), C.c_uint64(len(a)), _ptr(b), C.c_uint64(len(b)), C.c_uint32(n), int(metric), C.byref(out), C.byref(n_out))
     if rc:
         raise RkError(rc, "rk_forest_merge: an edge names a genome beyond the number of genomes")
-    buf = C.string_at(out.value, n_out.value * HIT_DTYPE.itemsize) if n_out.value else b""
-    L.rk_free_host(out)
-    return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+    return _take_hits(out, n_out)
 
 
 def forest_cut(edges, n, max_dist):
@@ -708,9 +709,7 @@ def greedy_hits(hits, n, metric, priority=None):
     rc = L.rk_greedy_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), _ptr(priority), int(metric), _ptr(rep), C.byref(links), C.byref(n_links))
     if rc:
         raise RkError(rc, "rk_greedy_hits: a record names a genome beyond the number of genomes or one genome twice, or records disagree about a size")
-    buf = C.string_at(links.value, n_links.value * HIT_DTYPE.itemsize) if n_links.value else b""
-    L.rk_free_host(links)
-    return rep, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+    return rep, _take_hits(links, n_links)
 
 
 def knn_hits(hits, n, k, metric):
@@ -725,9 +724,7 @@ def knn_hits(hits, n, k, metric):
     rc = L.rk_knn_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), C.c_uint32(k), int(metric), _ptr(off), C.byref(nbrs), C.byref(n_nbrs))
     if rc:
         raise RkError(rc, "rk_knn_hits: a record names a genome beyond the number of genomes or one genome twice")
-    buf = C.string_at(nbrs.value, n_nbrs.value * HIT_DTYPE.itemsize) if n_nbrs.value else b""
-    L.rk_free_host(nbrs)
-    return off, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+    return off, _take_hits(nbrs, n_nbrs)
 
 
 def knn_merge(a_off, a, b_off, b, n, k, metric):
@@ -749,9 +746,7 @@ def knn_merge(a_off, a, b_off, b, n, k, metric):
     rc = L.rk_knn_merge(_ptr(a_off), _ptr(a), _ptr(b_off), _ptr(b), C.c_uint32(n), C.c_uint32(k), int(metric), _ptr(off), C.byref(out), C.byref(n_out))
     if rc:
         raise RkError(rc, "rk_knn_merge: offsets that do not ascend, or a record that is not incident to the genome whose list holds it")
-    buf = C.string_at(out.value, n_out.value * HIT_DTYPE.itemsize) if n_out.value else b""
-    L.rk_free_host(out)
-    return off, np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+    return off, _take_hits(out, n_out)
 
 
 def format_hit(name_a, name_b, hit):

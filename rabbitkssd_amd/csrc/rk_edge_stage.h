@@ -1,5 +1,6 @@
-// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip and rk_greedy.hip (not part of the public ABI): the self join
-// into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device may decide.  DESIGN.md 4.6.
+// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip and rk_knn.hip (not part of the public ABI): the
+// self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device may decide.
+// DESIGN.md 4.6.  The key pass of the last three lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings its own.
 //
 //   join     rk_dist_rows_dev with the threshold widened by 2^-46 (capped at 1.0: beyond it the public join would turn to the dense
 //            report) appends unordered hit records to a buffer of max(65,536, rows * 64) records; its counter counts every hit,
@@ -44,6 +45,25 @@ inline unsigned grid_for(const rk_ctx *ctx, uint64_t items)
 inline rk_hit *host_records(uint64_t n)
 {
     return (rk_hit *)malloc((n ? n : 1) * sizeof(rk_hit));
+}
+
+// The adjacency of a hit list over n genomes (the caller has checked row, col < n): the numbers of the records incident to genome v,
+// ascending, are adj[start[v] .. start[v + 1]) -- a counting sort of record numbers by endpoint.
+inline void hit_adjacency(const rk_hit *hits, uint64_t n_hits, uint32_t n, std::vector<uint64_t> *start, std::vector<uint64_t> *adj)
+{
+    std::vector<uint64_t> &at = *start;
+    at.assign((size_t)n + 2, 0);
+    for (uint64_t e = 0; e < n_hits; e++) {
+        at[hits[e].row + 2]++;
+        at[hits[e].col + 2]++;
+    }
+    for (size_t i = 2; i < at.size(); i++) at[i] += at[i - 1];
+    adj->resize(2 * n_hits);
+    for (uint64_t e = 0; e < n_hits; e++) {   // (at[v + 1] runs from the begin of v's records to their end)
+        (*adj)[at[hits[e].row + 1]++] = e;
+        (*adj)[at[hits[e].col + 1]++] = e;
+    }
+    at.pop_back();
 }
 
 // record e is borderline: counted always, stored while there is room (the host sees the overflow from the counter)
@@ -165,6 +185,21 @@ struct EdgeStage {
             cap = n_hits;
         }
         return rk_fail(ctx, RK_ERR_CAPACITY, "hit or borderline buffer overflow persisted after resize");
+    }
+
+    // The key pass of the forest, the greedy rule and the neighbour lists as pass k of run(): k_edge_keys<GREEDY> over w and rc of
+    // `cap` records each.  The buffers are the caller's (its later passes read them), allocated here at k = 0, and `extra` (greedy's
+    // hl) with them where one is given.
+    template <bool GREEDY>
+    int key_pass(int k, DevBuf<unsigned long long> &w, DevBuf<unsigned long long> &rc, DevBuf<unsigned long long> *extra = nullptr)
+    {
+        if (!k && (w.alloc(cap) != hipSuccess || rc.alloc(cap) != hipSuccess || (extra && extra->alloc(cap) != hipSuccess)))
+            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)cap);
+        hipLaunchKernelGGL(k_edge_keys<GREEDY>, dim3(grid_for(ctx, cap)), dim3(kStageThreads), 0, ctx->stream, hits.p, cnt(), (unsigned long long)cap,
+                           idx->n_ref, link_below, metric, w.p, rc.p, edges.p, GREEDY ? slots.p : (unsigned long long *)nullptr,
+                           (unsigned long long)edge_cap);
+        RK_HIP(ctx, hipGetLastError());
+        return RK_OK;
     }
 
     // The borderline records, decided: the ones the exact threshold keeps, in the order the pass stored them, with the C library's

@@ -8,7 +8,7 @@
 // floor(common * 2^62 / u), exact for 0 < common <= u < 2^31 (distinct fractions differ by more than 2^-62); `w` = ~key turns
 // "nearest first" into an unsigned minimum.
 //
-//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (k_edge_keys<false>: per record w and
+//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (EdgeStage::key_pass<false>: per record w and
 //             row << 32 | col; a BORDERLINE record and a record outside 0 < common <= u -- multisets: no key -- go to the small host
 //             buffer and are dead on the device), the two retries, the host's decision about the records of that buffer;
 //   rounds    Boruvka: k_match_w (atomic minimum of w per component, both endpoints), k_match_rc (among the records that match
@@ -192,15 +192,7 @@ int rk_forest_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, r
     RK_HIP(ctx, hipGetLastError());
 
     // the key pass: nothing is linked before the stage is through
-    int rc = stage.run([&](int pass) -> int {
-        if (!pass && (w.alloc(stage.cap) != hipSuccess || rc_.alloc(stage.cap) != hipSuccess))
-            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)stage.cap);
-        hipLaunchKernelGGL(k_edge_keys<false>, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
-                           (unsigned long long)stage.cap, N, stage.link_below, metric, w.p, rc_.p, stage.edges.p, (unsigned long long *)nullptr,
-                           (unsigned long long)stage.edge_cap);
-        RK_HIP(ctx, hipGetLastError());
-        return RK_OK;
-    });
+    int rc = stage.run([&](int pass) { return stage.key_pass<false>(pass, w, rc_); });
     if (rc) return rc;
     st.join_attempts = stage.join_attempts;
     st.border_attempts = stage.pass_attempts;

@@ -4,7 +4,7 @@
 // genome is a REPRESENTATIVE unless a representative that precedes it is adjacent to it, otherwise a MEMBER of the nearest such
 // representative (order of rk_edge_order.h; ties to the smallest caller index).  The graph is that of rk_cluster_rows.
 //
-//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (k_edge_keys<true>: per record w and
+//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (EdgeStage::key_pass<true>: per record w and
 //             row << 32 | col; a BORDERLINE record goes, with its slot number, to the small host buffer and is dead for now; a record
 //             outside 0 < common <= u -- multisets -- is counted: the call refuses such a collection), the two retries;
 //   host      the stage decides the borderline records BEFORE any round (a kept edge can flip representatives arbitrarily far
@@ -226,14 +226,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     if (ctx->timing) ctx->last_ms[RK_MS_GREEDY_ROUNDS] = 0.0;
 
     // the key pass: nothing is decided before the stage is through
-    int rc = stage.run([&](int pass) -> int {
-        if (!pass && (w.alloc(stage.cap) != hipSuccess || rc_.alloc(stage.cap) != hipSuccess || hl.alloc(stage.cap) != hipSuccess))
-            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)stage.cap);
-        hipLaunchKernelGGL(k_edge_keys<true>, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
-                           (unsigned long long)stage.cap, N, stage.link_below, metric, w.p, rc_.p, stage.edges.p, stage.slots.p, (unsigned long long)stage.edge_cap);
-        RK_HIP(ctx, hipGetLastError());
-        return RK_OK;
-    });
+    int rc = stage.run([&](int pass) { return stage.key_pass<true>(pass, w, rc_, &hl); });
     if (rc) return rc;
     st.join_attempts = stage.join_attempts;
     st.border_attempts = stage.pass_attempts;
@@ -340,7 +333,6 @@ int rk_greedy_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, const uint32
     metric = metric != 0;
     // the records: genomes below n, no loop, one size per genome; the adjacency as record numbers per genome
     std::vector<int64_t> seen(priority ? 0 : n, -1);
-    std::vector<uint64_t> start((size_t)n + 2, 0);
     for (uint64_t e = 0; e < n_hits; e++) {
         const rk_hit &h = hits[e];
         if (h.row >= n || h.col >= n || h.row == h.col) return RK_ERR_ARG;
@@ -350,8 +342,6 @@ int rk_greedy_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, const uint32
             seen[h.row] = h.size0;
             seen[h.col] = h.size1;
         }
-        start[h.row + 2]++;
-        start[h.col + 2]++;
     }
     std::vector<uint32_t> rank;
     if (priority) rank_of(priority, nullptr, n, &rank);
@@ -360,12 +350,8 @@ int rk_greedy_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, const uint32
         for (uint32_t i = 0; i < n; i++) size[i] = seen[i] < 0 ? 0u : (uint32_t)seen[i];   // (a genome without a record is isolated: its place does not matter)
         rank_of(nullptr, size.data(), n, &rank);
     }
-    for (size_t i = 2; i < start.size(); i++) start[i] += start[i - 1];
-    std::vector<uint64_t> adj(2 * n_hits);
-    for (uint64_t e = 0; e < n_hits; e++) {   // (start[v + 1] runs from the begin of v's records to their end)
-        adj[start[hits[e].row + 1]++] = e;
-        adj[start[hits[e].col + 1]++] = e;
-    }
+    std::vector<uint64_t> start, adj;
+    hit_adjacency(hits, n_hits, n, &start, &adj);
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; i++) order[rank[i]] = i;
     // the sequential rule

@@ -4,7 +4,7 @@
 // min(k, degree(v)) records incident to v in the order of rk_edge_order.h restricted to v: the ratio common / u descending, compared
 // exactly, then the NEIGHBOUR's caller index ascending (the (row, col) tie-break of EdgeLess with one endpoint fixed).
 //
-//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (k_edge_keys<false>: per record w and
+//   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (EdgeStage::key_pass<false>: per record w and
 //             row << 32 | col; a BORDERLINE record and a record outside 0 < common <= u -- multisets: no key -- go to the small host
 //             buffer and are dead on the device), the two retries;
 //   degree    k_knn_degree: per live record one atomicAdd on deg[row] and one on deg[col] -- behind the stage, whose pass may run twice;
@@ -202,20 +202,11 @@ void fold_lists(const uint64_t *a_off, const rk_hit *a, const uint64_t *b_off, c
     }
 }
 
-// the lists of a hit list (validated by the caller): counting sort of record numbers by genome, then the first k of each
+// the lists of a hit list (validated by the caller): its adjacency, then the first k of each genome's records
 void lists_of_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint64_t k, int metric, uint64_t *off_out, std::vector<rk_hit> *out)
 {
-    std::vector<uint64_t> start((size_t)n + 2, 0);
-    for (uint64_t e = 0; e < n_hits; e++) {
-        start[hits[e].row + 2]++;
-        start[hits[e].col + 2]++;
-    }
-    for (size_t i = 2; i < start.size(); i++) start[i] += start[i - 1];
-    std::vector<uint64_t> adj(2 * n_hits);
-    for (uint64_t e = 0; e < n_hits; e++) {   // (start[v + 1] runs from the begin of v's records to their end)
-        adj[start[hits[e].row + 1]++] = e;
-        adj[start[hits[e].col + 1]++] = e;
-    }
+    std::vector<uint64_t> start, adj;
+    hit_adjacency(hits, n_hits, n, &start, &adj);
     out->clear();
     std::vector<rk_hit> pool;
     off_out[0] = 0;
@@ -313,15 +304,7 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
     stage.hits_what = "hit records and their keys";
     if (ctx->timing) ctx->last_ms[RK_MS_KNN_SELECT] = 0.0;
     DevBuf<unsigned long long> w(ctx), rc_(ctx);
-    int rc = stage.run([&](int pass) -> int {
-        if (!pass && (w.alloc(stage.cap) != hipSuccess || rc_.alloc(stage.cap) != hipSuccess))
-            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)stage.cap);
-        hipLaunchKernelGGL(k_edge_keys<false>, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
-                           (unsigned long long)stage.cap, N, stage.link_below, metric, w.p, rc_.p, stage.edges.p, (unsigned long long *)nullptr,
-                           (unsigned long long)stage.edge_cap);
-        RK_HIP(ctx, hipGetLastError());
-        return RK_OK;
-    });
+    int rc = stage.run([&](int pass) { return stage.key_pass<false>(pass, w, rc_); });
     if (rc && !(rc == RK_ERR_NOMEM && stage.n_hits >= (1ULL << 31))) return rc;
     if (stage.n_hits >= (1ULL << 31)) {   // the entries number the records in 31 bits
         w.reset();

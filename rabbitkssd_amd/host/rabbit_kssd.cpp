@@ -1183,6 +1183,15 @@ struct GpuSet {
     Gpu &operator[](size_t g) { return gpus[g]->get(); }
 };
 
+// f(g) for every GPU of a set: GPUs 1 .. G-1 on threads of their own, GPU 0 on the caller; back when all are through
+template <class F> static void on_every_gpu(size_t G, F &&f)
+{
+    vector<std::thread> pool;
+    for (size_t g = 1; g < G; g++) pool.emplace_back([&f, g] { f(g); });
+    f(0);
+    for (auto &th : pool) th.join();
+}
+
 static const int kRowBlock = 32;   // rows are dealt to the GPUs in blocks of 32: a multiple of the tile kernel's block, an even number for the row pairs
 
 // The index on every GPU of the set.  Default: every GPU uploads the sketches over its own PCIe link and builds its own
@@ -1199,21 +1208,46 @@ static void build_everywhere(GpuSet &set, const SketchSet &s, const string &path
         set[0].check(rk_index_broadcast(idx[0], peers.data(), (uint32_t)peers.size(), idx.data() + 1), "rk_index_broadcast");
         return;
     }
-    vector<std::thread> pool;
-    for (size_t g = 1; g < G; g++) pool.emplace_back([&, g] { idx[g] = build_index(set[g], s, path, false); });
-    idx[0] = build_index(set[0], s, path, write_files);
-    for (auto &th : pool) th.join();
+    on_every_gpu(G, [&](size_t g) { idx[g] = build_index(set[g], s, path, g == 0 && write_files); });
 }
 
-// What alldist and cluster share: the input (a .sketch file, or a genome list that is sketched first), the index on every GPU of
-// the set (the sharded build where it applies, the whole index everywhere otherwise) and the reference's phase lines around them.
+// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn): the common arguments, the input (a .sketch file, or a
+// genome list that is sketched first), the index on every GPU of the set (the sharded build where it applies, the whole index
+// everywhere otherwise), the reference's phase lines around them and the way out.
 struct SelfJoin {
+    const Args &a;
+    const double max_dist;
+    const string out;
+    const int metric, threads;
+    std::unique_ptr<GpuSet> gpus;
     SketchSet s;
     vector<rk_index *> idx;   // one per GPU
     bool sharded = false;     // idx[g] is the join-only index of GPU g's rows
     double t1 = 0;            // start of the distance phase
+    size_t G = 0, N = 0;      // GPUs, genomes
+
+    // The common arguments and what every command refuses in them.  ordered: the command ranks pairs, so it refuses the dense report
+    // (-D above 1.0) that alldist and cluster accept.  Nothing is opened or started here: the command's own refusals come next.
+    SelfJoin(const Args &args, const char *cmd, bool ordered)
+        : a(args), max_dist(a.real("D", 1.0)), out(a.str("o", "result.out")), metric(a.num("M", 0)),
+          threads(a.num("t", (int)std::thread::hardware_concurrency()))
+    {
+        if (!a.has("i")) die("%s needs -i", cmd);
+        if (max_dist < 0.0) die("command_%s(), maxDist must be > 0\nUse -D to set the maxDist", cmd);
+        if (ordered && 1.0 < max_dist) die("command_%s(), maxDist must not exceed 1.0: pairs that share nothing carry no order", cmd);
+    }
+    // the GPUs first: their runtimes start on threads of their own while the .sketch file is read
+    void prepare(int n_gpus, bool same_device)
+    {
+        gpus.reset(new GpuSet(a.num("device", 0), n_gpus, same_device));
+        G = gpus->size();
+        build();
+        N = s.size();
+    }
+    void prepare() { prepare(a.num("gpus", 1), a.has("same-device")); }
+    Gpu &gpu(size_t g) { return (*gpus)[g]; }
     // the options of GPU g's rows
-    rk_dist_opts opts(size_t g, size_t G, int metric, double max_dist) const
+    rk_dist_opts opts(size_t g) const
     {
         rk_dist_opts o{};
         o.triangle = 1;
@@ -1227,11 +1261,30 @@ struct SelfJoin {
         }
         return o;
     }
-    void prepare(const Args &a, GpuSet &set, double max_dist, int threads);
+    // the results are on the host: the stamp and the reference's phase line
+    void phase_done(const char *what, const char *phase) const
+    {
+        stamp(what);
+        cerr << "===================time of multiple threads distance computing and " << phase << " is: " << get_sec() - t1 << endl;
+    }
+    // The output is on disk and the process is about to end: handing 50 MB of sketches, the hit records and the index back block
+    // by block costs 4-5 ms that buy nothing (the tool's last stamp).  Straight out, like the GPU subcommands' `leave` in main.
+    [[noreturn]] static void leave()
+    {
+        stamp("text written");
+        stamp("done");
+        fflush(stdout);
+        fflush(stderr);
+        _exit(0);
+    }
+
+private:
+    void build();
 };
 
-void SelfJoin::prepare(const Args &a, GpuSet &set, double max_dist, int threads)
+void SelfJoin::build()
 {
+    GpuSet &set = *gpus;
     const double t0 = get_sec();
     string sketch_path;
     if (is_sketch_file(a.str("i", ""))) {  // read while the runtime starts
@@ -1245,7 +1298,6 @@ void SelfJoin::prepare(const Args &a, GpuSet &set, double max_dist, int threads)
     // the .dict/.index pair is (re)written only if missing (src/subCommand.cpp:165-169); the
     // device index is always rebuilt from the sketches: faster than reading the 2^bits array
     const bool missing = !exist_file(sketch_path + ".index") || !exist_file(sketch_path + ".dict");
-    const size_t G = set.size();
     idx.assign(G, nullptr);
     // Several GPUs (round 5): the all-vs-all shards twice -- every GPU builds the posting lists of ITS range of the hash space, the
     // tile records change hands once (GPU d pulls what belongs to its rows over its own links), every GPU sorts what arrived and
@@ -1263,12 +1315,7 @@ void SelfJoin::prepare(const Args &a, GpuSet &set, double max_dist, int threads)
             rcs[g] = rk_index_build_shard(set[g].ctx, sk, bits, (uint32_t)g, (uint32_t)G, &part[g]);
             rk_sketches_free(sk);
         };
-        {
-            vector<std::thread> pool;
-            for (size_t g = 1; g < G; g++) pool.emplace_back(build_part, g);
-            build_part(0);
-            for (auto &th : pool) th.join();
-        }
+        on_every_gpu(G, build_part);
         bool ok = true;
         for (size_t g = 0; g < G; g++) ok = ok && rcs[g] == 0;
         vector<void *> recv(G, nullptr);
@@ -1276,11 +1323,7 @@ void SelfJoin::prepare(const Args &a, GpuSet &set, double max_dist, int threads)
         if (ok) ok = rk_index_shard_exchange(part.data(), (uint32_t)G, recv.data(), n_recv.data()) == 0;
         if (ok) stamp("shards built, tile records exchanged");
         if (ok) {
-            auto join_part = [&](size_t g) { rcs[g] = rk_index_join_shard(set[g].ctx, part[g], recv[g], n_recv[g], &idx[g]); };
-            vector<std::thread> pool;
-            for (size_t g = 1; g < G; g++) pool.emplace_back(join_part, g);
-            join_part(0);
-            for (auto &th : pool) th.join();
+            on_every_gpu(G, [&](size_t g) { rcs[g] = rk_index_join_shard(set[g].ctx, part[g], recv[g], n_recv[g], &idx[g]); });
             for (size_t g = 0; g < G; g++) ok = ok && rcs[g] == 0;
         }
         for (size_t g = 0; g < G; g++) {
@@ -1299,49 +1342,72 @@ void SelfJoin::prepare(const Args &a, GpuSet &set, double max_dist, int threads)
     cerr << "=====total: " << s.size() << endl;
 }
 
+// ---- what the self-join subcommands share beyond the frame -----------------------------------------------------------------------
+// GPU g's records folded into GPU 0's, g = 1 .. G-1: merge(g, &folded, &n_folded) is the library's fold of rec[0] and rec[g]
+template <class Merge> static void fold_records(vector<rk_hit *> &rec, vector<uint64_t> &n_rec, const char *merge_name, Merge &&merge)
+{
+    for (size_t g = 1; g < rec.size(); g++) {
+        rk_hit *folded = nullptr;
+        uint64_t n_folded = 0;
+        if (merge(g, &folded, &n_folded) != 0) die("%s failed", merge_name);
+        rk_free_host(rec[0]);
+        rk_free_host(rec[g]);
+        rec[0] = folded;
+        n_rec[0] = n_folded;
+    }
+}
+
+// one line of alldist's format: the names as given, then the record
+static void put_hit_line(FILE *fp, vector<char> &buf, const string &x, const string &y, const rk_hit &h)
+{
+    if (x.size() + y.size() + 128 > buf.size()) die("genome name too long");
+    const int len = rk_format_hit(buf.data(), buf.size(), x.c_str(), y.c_str(), &h);
+    if (len < 0) die("rk_format_hit failed");
+    fwrite(buf.data(), 1, (size_t)len, fp);
+}
+
+// Members by cluster, clusters by representative: a counting sort over rep[] (rep[i] = the representative of i's cluster, i itself for
+// a representative).  order: the genomes cluster by cluster, a representative first, then its members by ascending index (where the
+// representative is the smallest member, as in cluster's labels, that is ascending throughout); number[r] and size[r]: of r's cluster.
+struct ClusterOrder {
+    vector<uint32_t> order, number, size;
+    uint32_t n_clusters = 0;
+    ClusterOrder(const vector<uint32_t> &rep, size_t N) : order(N), number(N, 0), size(N, 0)
+    {
+        vector<uint32_t> at(N + 1, 0);
+        for (size_t i = 0; i < N; i++) size[rep[i]]++;
+        for (size_t i = 0; i < N; i++) {
+            at[i + 1] = at[i] + size[i];
+            if (rep[i] == i) number[i] = n_clusters++;
+        }
+        for (size_t i = 0; i < N; i++)
+            if (rep[i] == i) order[at[i]++] = (uint32_t)i;
+        for (size_t i = 0; i < N; i++)
+            if (rep[i] != i) order[at[rep[i]]++] = (uint32_t)i;
+    }
+};
+
 static int cmd_alldist(const Args &a)
 {
-    if (!a.has("i")) die("alldist needs -i");
-    const double max_dist = a.real("D", 1.0);
-    if (max_dist < 0.0) die("command_alldist(), maxDist must be > 0\nUse -D to set the maxDist");
-    const string out = a.str("o", "result.out");
-    const int metric = a.num("M", 0);
-    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
-    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
-    SelfJoin j;
-    j.prepare(a, set, max_dist, threads);
-    const SketchSet &s = j.s;
-    const vector<rk_index *> &idx = j.idx;
-    const size_t G = set.size();
+    SelfJoin j(a, "alldist", false);
+    j.prepare();
+    const size_t G = j.G;
     vector<rk_hit *> hits(G, nullptr);
     vector<uint64_t> n_hits(G, 0);
-    auto rows_of = [&](size_t g) {
-        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
-        set[g].check(rk_dist_rows(set[g].ctx, idx[g], nullptr, &o, &hits[g], &n_hits[g], nullptr), "rk_dist_rows");
-    };
-    {
-        vector<std::thread> pool;
-        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
-        rows_of(0);
-        for (auto &th : pool) th.join();
-    }
-    stamp("distances on the host");
-    cerr << "===================time of multiple threads distance computing and save the subFile is: " << get_sec() - j.t1 << endl;
+    on_every_gpu(G, [&](size_t g) {
+        const rk_dist_opts o = j.opts(g);
+        j.gpu(g).check(rk_dist_rows(j.gpu(g).ctx, j.idx[g], nullptr, &o, &hits[g], &n_hits[g], nullptr), "rk_dist_rows");
+    });
+    j.phase_done("distances on the host", "save the subFile");
     vector<HitPart> parts(G);
     for (size_t g = 0; g < G; g++) {
         parts[g].hits = hits[g];
         parts[g].n = n_hits[g];
-        for (uint32_t r = 0; r < (uint32_t)s.size(); r++)
+        for (uint32_t r = 0; r < (uint32_t)j.N; r++)
             if (G == 1 || (r / kRowBlock) % G == g) parts[g].rows.push_back(r);
     }
-    write_hits(out, parts, true, s.names, s.names, threads);
-    stamp("text written");
-    // The output is on disk and the process is about to end: handing 50 MB of sketches, the hit records and the index back block
-    // by block costs 4-5 ms that buy nothing (the tool's last stamp).  Straight out, like the GPU subcommands' `leave` in main.
-    stamp("done");
-    fflush(stdout);
-    fflush(stderr);
-    _exit(0);
+    write_hits(j.out, parts, true, j.s.names, j.s.names, j.threads);
+    j.leave();
 }
 
 // cluster: the single-linkage clusters of alldist's pairs (rk_cluster_rows on every GPU for its rows, folded with
@@ -1349,62 +1415,33 @@ static int cmd_alldist(const Args &a)
 // index), cluster size, genome name; within a cluster the genomes by ascending index.
 static int cmd_cluster(const Args &a)
 {
-    if (!a.has("i")) die("cluster needs -i");
-    const double max_dist = a.real("D", 1.0);
-    if (max_dist < 0.0) die("command_cluster(), maxDist must be > 0\nUse -D to set the maxDist");
-    const string out = a.str("o", "result.out");
-    const int metric = a.num("M", 0);
-    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
-    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
-    SelfJoin j;
-    j.prepare(a, set, max_dist, threads);
-    const size_t G = set.size(), N = j.s.size();
+    SelfJoin j(a, "cluster", false);
+    j.prepare();
+    const size_t G = j.G, N = j.N;
     vector<vector<uint32_t>> labels(G, vector<uint32_t>(N ? N : 1));
     vector<rk_cluster_stats> stats(G);
-    auto rows_of = [&](size_t g) {
-        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
-        set[g].check(rk_cluster_rows(set[g].ctx, j.idx[g], &o, labels[g].data(), &stats[g]), "rk_cluster_rows");
-    };
-    {
-        vector<std::thread> pool;
-        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
-        rows_of(0);
-        for (auto &th : pool) th.join();
-    }
+    on_every_gpu(G, [&](size_t g) {
+        const rk_dist_opts o = j.opts(g);
+        j.gpu(g).check(rk_cluster_rows(j.gpu(g).ctx, j.idx[g], &o, labels[g].data(), &stats[g]), "rk_cluster_rows");
+    });
     for (size_t g = 1; g < G; g++)
         if (rk_cluster_merge(labels[0].data(), labels[g].data(), (uint32_t)N, labels[0].data()) != 0) die("rk_cluster_merge failed");
-    stamp("clusters on the host");
-    cerr << "===================time of multiple threads distance computing and clustering is: " << get_sec() - j.t1 << endl;
-    const vector<uint32_t> &lab = labels[0];
-    // members by cluster, clusters by representative: a counting sort over the labels (label[i] <= i, a representative labels itself)
-    vector<uint32_t> number(N, 0), size(N, 0), start(N + 1, 0), order(N);
-    uint32_t n_clusters = 0;
-    for (size_t i = 0; i < N; i++) size[lab[i]]++;
-    for (size_t i = 0; i < N; i++) {
-        start[i + 1] = start[i] + size[i];
-        if (lab[i] == i) number[i] = n_clusters++;
-    }
-    {
-        vector<uint32_t> at(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < N; i++) order[at[lab[i]]++] = (uint32_t)i;
-    }
-    FILE *fp = fopen(out.c_str(), "w");
-    if (!fp) die("cannot write %s", out.c_str());
+    j.phase_done("clusters on the host", "clustering");
+    const vector<uint32_t> &lab = labels[0];   // (label[i] <= i, a representative labels itself)
+    const ClusterOrder c(lab, N);
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
     for (size_t k = 0; k < N; k++) {
-        const uint32_t i = order[k], rep = lab[i];
-        fprintf(fp, "%u\t%u\t%s\n", number[rep], size[rep], j.s.names[i].c_str());
+        const uint32_t i = c.order[k], rep = lab[i];
+        fprintf(fp, "%u\t%u\t%s\n", c.number[rep], c.size[rep], j.s.names[i].c_str());
     }
     fclose(fp);
     if (getenv("RK_TIMING")) {
         unsigned long long edges = 0, border = 0;
         for (size_t g = 0; g < G; g++) { edges += stats[g].edges; border += stats[g].borderline; }
-        fprintf(stderr, "[timing] %u clusters of %zu genomes from %llu hit records (%llu borderline)\n", n_clusters, N, edges, border);
+        fprintf(stderr, "[timing] %u clusters of %zu genomes from %llu hit records (%llu borderline)\n", c.n_clusters, N, edges, border);
     }
-    stamp("text written");
-    stamp("done");
-    fflush(stdout);
-    fflush(stderr);
-    _exit(0);
+    j.leave();
 }
 
 // forest: the minimum spanning forest of alldist's pairs -- the single-linkage dendrogram up to -D (rk_forest_rows on every GPU for its
@@ -1412,51 +1449,26 @@ static int cmd_cluster(const Args &a)
 // the genomes' indices.
 static int cmd_forest(const Args &a)
 {
-    if (!a.has("i")) die("forest needs -i");
-    const double max_dist = a.real("D", 1.0);
-    if (max_dist < 0.0) die("command_forest(), maxDist must be > 0\nUse -D to set the maxDist");
-    if (1.0 < max_dist) die("command_forest(), maxDist must not exceed 1.0: pairs that share nothing carry no order");
-    const string out = a.str("o", "result.out");
-    const int metric = a.num("M", 0);
-    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
-    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
-    SelfJoin j;
-    j.prepare(a, set, max_dist, threads);
-    const size_t G = set.size(), N = j.s.size();
+    SelfJoin j(a, "forest", true);
+    j.prepare();
+    const size_t G = j.G, N = j.N;
     vector<rk_hit *> edges(G, nullptr);
     vector<uint64_t> n_edges(G, 0);
     vector<rk_forest_stats> stats(G);
-    auto rows_of = [&](size_t g) {
-        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
-        set[g].check(rk_forest_rows(set[g].ctx, j.idx[g], &o, &edges[g], &n_edges[g], &stats[g]), "rk_forest_rows");
-    };
-    {
-        vector<std::thread> pool;
-        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
-        rows_of(0);
-        for (auto &th : pool) th.join();
-    }
-    for (size_t g = 1; g < G; g++) {
-        rk_hit *folded = nullptr;
-        uint64_t n_folded = 0;
-        if (rk_forest_merge(edges[0], n_edges[0], edges[g], n_edges[g], (uint32_t)N, metric, &folded, &n_folded) != 0) die("rk_forest_merge failed");
-        rk_free_host(edges[0]);
-        rk_free_host(edges[g]);
-        edges[0] = folded;
-        n_edges[0] = n_folded;
-    }
-    stamp("forest on the host");
-    cerr << "===================time of multiple threads distance computing and spanning forest is: " << get_sec() - j.t1 << endl;
-    FILE *fp = fopen(out.c_str(), "w");
-    if (!fp) die("cannot write %s", out.c_str());
+    on_every_gpu(G, [&](size_t g) {
+        const rk_dist_opts o = j.opts(g);
+        j.gpu(g).check(rk_forest_rows(j.gpu(g).ctx, j.idx[g], &o, &edges[g], &n_edges[g], &stats[g]), "rk_forest_rows");
+    });
+    fold_records(edges, n_edges, "rk_forest_merge", [&](size_t g, rk_hit **folded, uint64_t *n_folded) {
+        return rk_forest_merge(edges[0], n_edges[0], edges[g], n_edges[g], (uint32_t)N, j.metric, folded, n_folded);
+    });
+    j.phase_done("forest on the host", "spanning forest");
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
     vector<char> buf(1 << 16);
     for (uint64_t k = 0; k < n_edges[0]; k++) {
         const rk_hit &h = edges[0][k];
-        const string &x = j.s.names[h.col], &y = j.s.names[h.row];   // (the order of an alldist line, src/dist.cpp:233)
-        if (x.size() + y.size() + 128 > buf.size()) die("genome name too long");
-        const int len = rk_format_hit(buf.data(), buf.size(), x.c_str(), y.c_str(), &h);
-        if (len < 0) die("rk_format_hit failed");
-        fwrite(buf.data(), 1, (size_t)len, fp);
+        put_hit_line(fp, buf, j.s.names[h.col], j.s.names[h.row], h);   // (the order of an alldist line, src/dist.cpp:233)
     }
     fclose(fp);
     if (getenv("RK_TIMING")) {
@@ -1465,11 +1477,7 @@ static int cmd_forest(const Args &a)
         fprintf(stderr, "[timing] %llu forest edges over %zu genomes from %llu hit records (%llu borderline), %llu rounds\n",
                 (unsigned long long)n_edges[0], N, hits, border, rounds);
     }
-    stamp("text written");
-    stamp("done");
-    fflush(stdout);
-    fflush(stderr);
-    _exit(0);
+    j.leave();
 }
 
 // greedy: greedy incremental clustering of alldist's pairs (rk_greedy_rows; the rule of CD-HIT and clust-greedy: larger sketch first, a
@@ -1478,50 +1486,26 @@ static int cmd_forest(const Args &a)
 // within a cluster the representative first, then the members by ascending index.  --reps: the representatives' names alone.
 static int cmd_greedy(const Args &a)
 {
-    if (!a.has("i")) die("greedy needs -i");
-    const double max_dist = a.real("D", 1.0);
-    if (max_dist < 0.0) die("command_greedy(), maxDist must be > 0\nUse -D to set the maxDist");
-    if (1.0 < max_dist) die("command_greedy(), maxDist must not exceed 1.0: pairs that share nothing carry no order");
+    SelfJoin j(a, "greedy", true);
     if (a.num("gpus", 1) > 1) die("command_greedy(), greedy runs on one GPU: the rule does not compose from the shards of several (--gpus 1)");
-    const string out = a.str("o", "result.out");
-    const int metric = a.num("M", 0);
-    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
-    GpuSet set(a.num("device", 0), 1, false);
-    SelfJoin j;
-    j.prepare(a, set, max_dist, threads);
-    const size_t N = j.s.size();
+    j.prepare(1, false);
+    const size_t N = j.N;
     vector<uint32_t> rep(N ? N : 1);
     rk_hit *links = nullptr;
     uint64_t n_links = 0;
     rk_greedy_stats stats{};
-    const rk_dist_opts o = j.opts(0, 1, metric, max_dist);
-    set[0].check(rk_greedy_rows(set[0].ctx, j.idx[0], &o, nullptr, rep.data(), &links, &n_links, &stats), "rk_greedy_rows");
-    stamp("representatives on the host");
-    cerr << "===================time of multiple threads distance computing and greedy clustering is: " << get_sec() - j.t1 << endl;
-    // members by cluster, clusters by representative: a counting sort over rep[] (a representative goes first in its cluster)
-    vector<uint32_t> number(N, 0), size(N, 0), start(N + 1, 0), order(N);
+    const rk_dist_opts o = j.opts(0);
+    j.gpu(0).check(rk_greedy_rows(j.gpu(0).ctx, j.idx[0], &o, nullptr, rep.data(), &links, &n_links, &stats), "rk_greedy_rows");
+    j.phase_done("representatives on the host", "greedy clustering");
+    const ClusterOrder c(rep, N);
     vector<double> dist(N, 0.0);
-    uint32_t n_reps = 0;
-    for (size_t i = 0, k = 0; i < N; i++) {
-        size[rep[i]]++;
+    for (size_t i = 0, k = 0; i < N; i++)
         if (rep[i] != i) dist[i] = links[k++].dist;   // (the links come by member index)
-    }
-    for (size_t i = 0; i < N; i++) {
-        start[i + 1] = start[i] + size[i];
-        if (rep[i] == i) number[i] = n_reps++;
-    }
-    {
-        vector<uint32_t> at(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < N; i++)
-            if (rep[i] == i) order[at[i]++] = (uint32_t)i;
-        for (size_t i = 0; i < N; i++)
-            if (rep[i] != i) order[at[rep[i]]++] = (uint32_t)i;
-    }
-    FILE *fp = fopen(out.c_str(), "w");
-    if (!fp) die("cannot write %s", out.c_str());
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
     for (size_t k = 0; k < N; k++) {
-        const uint32_t i = order[k], r = rep[i];
-        fprintf(fp, "%u\t%u\t%s\t%s\t%f\n", number[r], size[r], j.s.names[i].c_str(), j.s.names[r].c_str(), dist[i]);
+        const uint32_t i = c.order[k], r = rep[i];
+        fprintf(fp, "%u\t%u\t%s\t%s\t%f\n", c.number[r], c.size[r], j.s.names[i].c_str(), j.s.names[r].c_str(), dist[i]);
     }
     fclose(fp);
     if (a.has("reps")) {
@@ -1532,13 +1516,9 @@ static int cmd_greedy(const Args &a)
         fclose(rp);
     }
     if (getenv("RK_TIMING"))
-        fprintf(stderr, "[timing] %u representatives of %zu genomes from %llu hit records (%llu borderline), %u rounds\n", n_reps, N,
+        fprintf(stderr, "[timing] %u representatives of %zu genomes from %llu hit records (%llu borderline), %u rounds\n", c.n_clusters, N,
                 (unsigned long long)stats.edges, (unsigned long long)stats.borderline, stats.rounds);
-    stamp("text written");
-    stamp("done");
-    fflush(stdout);
-    fflush(stderr);
-    _exit(0);
+    j.leave();
 }
 
 // knn: the k nearest neighbours of every genome among alldist's pairs -- the kNN graph within -D (rk_knn_rows on every GPU for its rows,
@@ -1547,57 +1527,32 @@ static int cmd_greedy(const Args &a)
 // that orientation.
 static int cmd_knn(const Args &a)
 {
-    if (!a.has("i")) die("knn needs -i");
-    const double max_dist = a.real("D", 1.0);
-    if (max_dist < 0.0) die("command_knn(), maxDist must be > 0\nUse -D to set the maxDist");
-    if (1.0 < max_dist) die("command_knn(), maxDist must not exceed 1.0: pairs that share nothing carry no order");
+    SelfJoin j(a, "knn", true);
     if (!a.has("N") || a.num("N", 0) < 1) die("command_knn(), maxNeighbor must be >= 1\nUse -N to set the maxNeighbor");
     const uint32_t k = (uint32_t)a.num("N", 1);
-    const string out = a.str("o", "result.out");
-    const int metric = a.num("M", 0);
-    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
-    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
-    SelfJoin j;
-    j.prepare(a, set, max_dist, threads);
-    const size_t G = set.size(), N = j.s.size();
+    j.prepare();
+    const size_t G = j.G, N = j.N;
     vector<vector<uint64_t>> off(G, vector<uint64_t>(N + 1, 0));
     vector<rk_hit *> nbrs(G, nullptr);
     vector<uint64_t> n_nbrs(G, 0);
     vector<rk_knn_stats> stats(G);
-    auto rows_of = [&](size_t g) {
-        const rk_dist_opts o = j.opts(g, G, metric, max_dist);
-        set[g].check(rk_knn_rows(set[g].ctx, j.idx[g], &o, k, off[g].data(), &nbrs[g], &n_nbrs[g], &stats[g]), "rk_knn_rows");
-    };
-    {
-        vector<std::thread> pool;
-        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
-        rows_of(0);
-        for (auto &th : pool) th.join();
-    }
-    for (size_t g = 1; g < G; g++) {
-        rk_hit *folded = nullptr;
-        uint64_t n_folded = 0;
-        if (rk_knn_merge(off[0].data(), nbrs[0], off[g].data(), nbrs[g], (uint32_t)N, k, metric, off[0].data(), &folded, &n_folded) != 0) die("rk_knn_merge failed");
-        rk_free_host(nbrs[0]);
-        rk_free_host(nbrs[g]);
-        nbrs[0] = folded;
-        n_nbrs[0] = n_folded;
-    }
-    stamp("neighbours on the host");
-    cerr << "===================time of multiple threads distance computing and neighbour selection is: " << get_sec() - j.t1 << endl;
-    FILE *fp = fopen(out.c_str(), "w");
-    if (!fp) die("cannot write %s", out.c_str());
+    on_every_gpu(G, [&](size_t g) {
+        const rk_dist_opts o = j.opts(g);
+        j.gpu(g).check(rk_knn_rows(j.gpu(g).ctx, j.idx[g], &o, k, off[g].data(), &nbrs[g], &n_nbrs[g], &stats[g]), "rk_knn_rows");
+    });
+    fold_records(nbrs, n_nbrs, "rk_knn_merge", [&](size_t g, rk_hit **folded, uint64_t *n_folded) {
+        return rk_knn_merge(off[0].data(), nbrs[0], off[g].data(), nbrs[g], (uint32_t)N, k, j.metric, off[0].data(), folded, n_folded);
+    });
+    j.phase_done("neighbours on the host", "neighbour selection");
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
     vector<char> buf(1 << 16);
     for (size_t i = 0; i < N; i++)
         for (uint64_t at = off[0][i]; at < off[0][i + 1]; at++) {
             rk_hit h = nbrs[0][at];
             const uint32_t other = h.row == i ? h.col : h.row;
             if (h.col == i) std::swap(h.size0, h.size1);   // the genome's size first
-            const string &x = j.s.names[i], &y = j.s.names[other];
-            if (x.size() + y.size() + 128 > buf.size()) die("genome name too long");
-            const int len = rk_format_hit(buf.data(), buf.size(), x.c_str(), y.c_str(), &h);
-            if (len < 0) die("rk_format_hit failed");
-            fwrite(buf.data(), 1, (size_t)len, fp);
+            put_hit_line(fp, buf, j.s.names[i], j.s.names[other], h);
         }
     fclose(fp);
     if (getenv("RK_TIMING")) {
@@ -1611,11 +1566,7 @@ static int cmd_knn(const Args &a)
         fprintf(stderr, "[timing] %llu neighbour records (k = %u) over %zu genomes from %llu hit records (%llu borderline), largest degree %llu, path %llu\n",
                 (unsigned long long)n_nbrs[0], k, N, hits, border, most, path);
     }
-    stamp("text written");
-    stamp("done");
-    fflush(stdout);
-    fflush(stderr);
-    _exit(0);
+    j.leave();
 }
 
 static int cmd_dist(const Args &a)
@@ -1687,12 +1638,7 @@ static int cmd_dist(const Args &a)
         for (uint64_t i = 0; i < n_hits[g]; i++) hits[g][i].row += q0[g];
         rk_sketches_free(qs);
     };
-    {
-        vector<std::thread> pool;
-        for (size_t g = 1; g < G; g++) pool.emplace_back(rows_of, g);
-        rows_of(0);
-        for (auto &th : pool) th.join();
-    }
+    on_every_gpu(G, rows_of);
     cerr << "===================time of multiple threads distance computing and save the subFile is: " << get_sec() - t1 << endl;
     vector<HitPart> parts(G);
     for (size_t g = 0; g < G; g++) {

@@ -1,78 +1,22 @@
 """rk_cluster_rows: the single-linkage clusters of the self join against a Python union-find over the ORACLE's hit list
 (ok.index_build32 + ok.index_dist32, triangle 1) -- label for label.  Every case says from the call's stats that it reached the
 edge it is about (a retry, a borderline record, a kernel)."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from _selfjoin_cases import (KMER, TOOL, Oracle, borderline_overflow_collection, both_overflows_collection, both_overflows_thresholds,
+                             bridge_collection, csr, device_index, hit_overflow_collection, labels_of, permuted)
 from oracle import oracle as ok
 from rabbitkssd_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
-TOOL = os.path.join(ROOT, "rabbitkssd_amd", "rabbit_kssd")
-KMER = 20
 
 
 @pytest.fixture(scope="module")
 def ctx():
     return capi.Context(0)
-
-
-def labels_of(pairs, n):
-    """labels[i] = the smallest member of i's component of the graph with these edges"""
-    parent = list(range(n))
-
-    def find(x):
-        while parent[x] != x:
-            parent[x] = parent[parent[x]]
-            x = parent[x]
-        return x
-    for a, b in pairs:
-        a, b = find(a), find(b)
-        if a != b:
-            parent[max(a, b)] = min(a, b)
-    return np.array([find(i) for i in range(n)], dtype=np.uint32)
-
-
-def csr(parts, dtype=np.uint32):
-    off = np.zeros(len(parts) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(p) for p in parts])
-    return (np.concatenate(parts).astype(dtype) if len(parts) else np.zeros(0, dtype=dtype)), off
-
-
-def permuted(parts, seed, keep_last=0):
-    """the sketches in a fixed random caller order (the last keep_last stay where they are)"""
-    n = len(parts)
-    order = np.concatenate([np.random.default_rng(seed).permutation(n - keep_last), np.arange(n - keep_last, n)]).astype(np.int64)
-    return [parts[i] for i in order]
-
-
-class Oracle:
-    """the oracle's index of one collection, built once; the expected labels of a threshold from its hit list"""
-    def __init__(self, h, off, bits, wide=False):
-        self.h, self.off, self.bits, self.wide = h, off, bits, wide
-        self.n = len(off) - 1
-        self.sizes = np.diff(off).astype(np.uint32)
-        self.built = ok.index_build64(h, off) if wide else ok.index_build32(h, off, bits)
-
-    def hits(self, metric, D, kmer=KMER):
-        if self.wide:
-            uhash, ucount, postings = self.built
-            return ok.index_dist64(uhash, ucount, postings, self.sizes, self.h, self.off, 1, metric, kmer, D, threads=4)[0]
-        postings, counts = self.built
-        return ok.index_dist32(counts, self.bits, postings, self.sizes, self.h, self.off, 1, metric, kmer, D, threads=4)[0]
-
-    def labels(self, metric, D, kmer=KMER):
-        hits = self.hits(metric, D, kmer)
-        return labels_of(zip(hits["row"].tolist(), hits["col"].tolist()), self.n), len(hits)
-
-
-def device_index(ctx, h, off, bits, wide=False):
-    sk = ctx.sketches_from_host64(h, off) if wide else ctx.sketches_from_host(h, off)
-    return ctx.index_build(sk, bits)
 
 
 def check(labels, stats, want, n_hits=None):
@@ -128,20 +72,6 @@ def test_star_of_3000_leaves(ctx):
     assert st["n_clusters"] == 1 and st["edges"] >= 3000
 
 
-def bridge_collection(clique, seed):
-    """two cliques of identical sketches (A: 100 hashes, B: 100 others); a in A's clique keeps 70 of A's hashes, b 70 of B's, and
-    the two share 30 others: a-A and b-B at d = -ln(0.7)/20 = 0.0178, a-b at -ln(0.3)/20 = 0.0602 under both metrics, every other
-    pair across the cliques at 1.0.  a and b are the LAST two genomes; the rest in a fixed random order."""
-    rng = np.random.default_rng(seed)
-    pool = np.unique(rng.integers(0, 1 << 24, size=400))
-    rng.shuffle(pool)
-    A, B, X = np.sort(pool[:100]), np.sort(pool[100:200]), pool[200:230]
-    a = np.sort(np.concatenate([A[:70], X]))
-    b = np.sort(np.concatenate([B[:70], X]))
-    parts = permuted([A] * (clique - 1) + [B] * (clique - 1), seed + 1) + [a, b]
-    return csr(parts)
-
-
 def test_two_cliques_bridged_by_the_two_largest_indices(ctx):
     h, off = bridge_collection(150, 3)
     n = len(off) - 1
@@ -160,11 +90,7 @@ def test_two_cliques_bridged_by_the_two_largest_indices(ctx):
 
 # ---- 3. more pairs than the hit buffer holds ----------------------------------------------------------------------------
 def test_hit_buffer_overflow_runs_the_join_again(ctx):
-    rng = np.random.default_rng(4)
-    one = np.unique(rng.integers(0, 1 << 24, size=130))[:100]
-    others = [np.unique(rng.integers(0, 1 << 24, size=130))[:100] for _ in range(3)]
-    parts = permuted([one] * 400 + others, 14)
-    h, off = csr(parts)
+    h, off = hit_overflow_collection()
     orc = Oracle(h, off, 24)
     want, n_hits = orc.labels(0, 0.05)
     assert n_hits == 400 * 399 // 2 > max(65536, 403 * 64)
@@ -196,15 +122,7 @@ def test_bridge_exactly_on_the_threshold(ctx, metric):
 
 # ---- 5. more borderline records than their buffer holds -----------------------------------------------------------------
 def test_borderline_overflow_runs_the_hook_pass_again(ctx, monkeypatch):
-    rng = np.random.default_rng(6)
-    pool = np.unique(rng.integers(0, 1 << 24, size=300 * 130))
-    rng.shuffle(pool)
-    parts = []
-    for p in range(300):   # a pair shares 80 of 100
-        mine = pool[120 * p: 120 * p + 120]
-        parts += [np.sort(mine[:100]), np.sort(mine[20:120])]
-    parts = permuted(parts, 16)
-    h, off = csr(parts)
+    h, off = borderline_overflow_collection()
     _, d0 = ok.distance(80, 100, 100, 0, KMER)
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
@@ -231,12 +149,11 @@ def test_borderline_overflow_runs_the_hook_pass_again(ctx, monkeypatch):
 def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
     """The hit overflow ends the first attempt before the borderline overflow is looked at; the hook pass behind the second join
     overflows the borderline buffer and runs again (its links stand: parent[] is not reset in between)."""
-    import test_gpu_forest as tf
-    h, off = tf.both_overflows_collection()
+    h, off = both_overflows_collection()
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
     monkeypatch.setenv("RK_CLUSTER_EDGE_CAP", "4")
-    for D, want_hits, kept in tf.both_overflows_thresholds():
+    for D, want_hits, kept in both_overflows_thresholds():
         want, n_hits = orc.labels(0, D)
         assert n_hits == want_hits > max(65536, 420 * 64)
         labels, st = ctx.cluster_rows(idx, 0, KMER, D)
@@ -262,7 +179,8 @@ _collections = {}
 
 
 def collection(which):
-    """(names, h, off, bits, wide, Oracle) of the named collection, built once per session and never changed"""
+    """(names, h, off, bits, wide, Oracle) of the named collection, built once per session and never changed.  This suite's own:
+    "tiles" and "near" with empty sketches among their genomes, and "tree" on top"""
     if which not in _collections:
         wide, bits = False, 24
         if which == "tiles":     # 4,200 genomes and more than 4,000: tile records come with the build

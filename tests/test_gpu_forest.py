@@ -9,59 +9,19 @@ import numpy as np
 import pytest
 
 import _forest_ref as fr
-from conftest import GOLDEN, ROOT
+from _selfjoin_cases import (KMER, TOOL, Oracle, borderline_overflow_collection, both_overflows_collection, both_overflows_thresholds,
+                             bridge_collection, collection, csr, device_index, hit_overflow_collection, identical, permuted,
+                             tie_collection)
+from conftest import GOLDEN
 from oracle import oracle as ok
 from rabbitkssd_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
-TOOL = os.path.join(ROOT, "rabbitkssd_amd", "rabbit_kssd")
-KMER = 20
 
 
 @pytest.fixture(scope="module")
 def ctx():
     return capi.Context(0)
-
-
-def csr(parts, dtype=np.uint32):
-    off = np.zeros(len(parts) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(p) for p in parts])
-    return (np.concatenate(parts).astype(dtype) if len(parts) else np.zeros(0, dtype=dtype)), off
-
-
-def permuted(parts, seed, keep_last=0):
-    """the sketches in a fixed random caller order (the last keep_last stay where they are)"""
-    n = len(parts)
-    order = np.concatenate([np.random.default_rng(seed).permutation(n - keep_last), np.arange(n - keep_last, n)]).astype(np.int64)
-    return [parts[i] for i in order]
-
-
-class Oracle:
-    """the oracle's index of one collection, built once; its hit list and the reference forest of a threshold (cached, read-only)"""
-    def __init__(self, h, off, bits, wide=False):
-        self.h, self.off, self.bits, self.wide = h, off, bits, wide
-        self.n = len(off) - 1
-        self.sizes = np.diff(off).astype(np.uint32)
-        self.built = ok.index_build64(h, off) if wide else ok.index_build32(h, off, bits)
-        self._hits = {}
-
-    def hits(self, metric, D, kmer=KMER):
-        key = (metric, D, kmer)
-        if key not in self._hits:
-            if self.wide:
-                uhash, ucount, postings = self.built
-                got = ok.index_dist64(uhash, ucount, postings, self.sizes, self.h, self.off, 1, metric, kmer, D, threads=4)[0]
-            else:
-                postings, counts = self.built
-                got = ok.index_dist32(counts, self.bits, postings, self.sizes, self.h, self.off, 1, metric, kmer, D, threads=4)[0]
-            got.setflags(write=False)
-            self._hits[key] = got
-        return self._hits[key]
-
-
-def device_index(ctx, h, off, bits, wide=False):
-    sk = ctx.sketches_from_host64(h, off) if wide else ctx.sketches_from_host(h, off)
-    return ctx.index_build(sk, bits)
 
 
 def expect(hits, n, metric):
@@ -107,10 +67,7 @@ def test_path_of_2048_genomes(ctx):
 
 # ---- 2. every pair at distance 0 ----------------------------------------------------------------------------------------
 def test_all_ties_give_the_star_of_genome_0(ctx):
-    rng = np.random.default_rng(2)
-    one = np.unique(rng.integers(0, 1 << 24, size=130))[:100]
-    parts = permuted([one] * 300, 12)
-    h, off = csr(parts)
+    h, off = csr(permuted(identical(300, 2), 12))
     orc = Oracle(h, off, 24)
     hits = orc.hits(0, 0.05)
     assert len(hits) == 300 * 299 // 2 == 44850 and np.all(hits["dist"] == 0.0)
@@ -121,27 +78,6 @@ def test_all_ties_give_the_star_of_genome_0(ctx):
 
 
 # ---- 3. one ratio from different counts ---------------------------------------------------------------------------------
-def tie_collection(seed):
-    """Six triangles, one per assignment of the roles to ascending caller indices: A and B of 50 hashes share 25, C of 30 hashes
-    shares 20 with each (10 of them with both) -- jaccard 25/75 = 20/60 = 20/60 -- and six pairs at 26/75 (50 and 51 hashes)."""
-    import itertools
-    rng = np.random.default_rng(seed)
-    pool = np.unique(rng.integers(0, 1 << 24, size=4000))
-    rng.shuffle(pool)
-    take = iter(range(0, len(pool), 1)).__next__
-
-    def fresh(k):
-        return np.array([pool[take()] for _ in range(k)], dtype=np.uint32)
-    parts = []
-    for roles in itertools.permutations(range(3)):
-        abc, ab, ac, bc, a_own, b_own = fresh(10), fresh(15), fresh(10), fresh(10), fresh(15), fresh(15)
-        tri = [np.concatenate([abc, ab, ac, a_own]), np.concatenate([abc, ab, bc, b_own]), np.concatenate([abc, ac, bc])]
-        parts += [np.sort(tri[r]) for r in roles]
-        both, p_own, q_own = fresh(26), fresh(24), fresh(25)
-        parts += [np.sort(np.concatenate([both, p_own])), np.sort(np.concatenate([both, q_own]))]
-    return csr(parts)
-
-
 @pytest.mark.parametrize("metric", [0, 1])
 def test_equal_ratio_from_different_counts(ctx, metric):
     h, off = tie_collection(3)
@@ -160,18 +96,6 @@ def test_equal_ratio_from_different_counts(ctx, metric):
 
 
 # ---- 4. bridges and a star ----------------------------------------------------------------------------------------------
-def bridge_collection(clique, seed):
-    """two cliques of identical sketches (A: 100 hashes, B: 100 others); a keeps 70 of A's hashes, b 70 of B's, and the two share 30
-    others: a-A and b-B at d = -ln(0.7)/20 = 0.0178, a-b at -ln(0.3)/20 = 0.0602 under both metrics.  a and b are the LAST two."""
-    rng = np.random.default_rng(seed)
-    pool = np.unique(rng.integers(0, 1 << 24, size=400))
-    rng.shuffle(pool)
-    A, B, X = np.sort(pool[:100]), np.sort(pool[100:200]), pool[200:230]
-    a = np.sort(np.concatenate([A[:70], X]))
-    b = np.sort(np.concatenate([B[:70], X]))
-    return csr(permuted([A] * (clique - 1) + [B] * (clique - 1), seed + 1) + [a, b])
-
-
 def test_two_cliques_and_their_bridge(ctx):
     h, off = bridge_collection(150, 3)
     n = len(off) - 1
@@ -204,11 +128,7 @@ def test_star_of_3000_leaves(ctx):
 
 # ---- 5. more pairs than the hit buffer holds ----------------------------------------------------------------------------
 def test_hit_buffer_overflow_runs_the_join_again(ctx):
-    rng = np.random.default_rng(4)
-    one = np.unique(rng.integers(0, 1 << 24, size=130))[:100]
-    others = [np.unique(rng.integers(0, 1 << 24, size=130))[:100] for _ in range(3)]
-    parts = permuted([one] * 400 + others, 14)
-    h, off = csr(parts)
+    h, off = hit_overflow_collection()
     orc = Oracle(h, off, 24)
     hits = orc.hits(0, 0.05)
     assert len(hits) == 400 * 399 // 2 > max(65536, 403 * 64)
@@ -235,15 +155,7 @@ def test_bridge_on_the_threshold_and_one_ulp_either_side(ctx, metric):
 
 # ---- 7. more borderline records than their buffer holds -----------------------------------------------------------------
 def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
-    rng = np.random.default_rng(6)
-    pool = np.unique(rng.integers(0, 1 << 24, size=300 * 130))
-    rng.shuffle(pool)
-    parts = []
-    for p in range(300):   # a pair shares 80 of 100
-        mine = pool[120 * p: 120 * p + 120]
-        parts += [np.sort(mine[:100]), np.sort(mine[20:120])]
-    parts = permuted(parts, 16)
-    h, off = csr(parts)
+    h, off = borderline_overflow_collection()
     _, d0 = ok.distance(80, 100, 100, 0, KMER)
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
@@ -262,26 +174,6 @@ def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
 
 
 # ---- 7b. both overflows in one call -------------------------------------------------------------------------------------
-def both_overflows_collection():
-    """400 copies of one sketch of 100 hashes (79,800 pairs at distance 0: more than the first hit capacity of 65,536) and 10 pairs
-    that share 80 of their 100 hashes, in a fixed random caller order; shared with the cluster and the greedy suites"""
-    rng = np.random.default_rng(21)
-    pool = np.unique(rng.integers(0, 1 << 24, size=2000))
-    rng.shuffle(pool)
-    assert len(pool) >= 100 + 10 * 120
-    parts = [np.sort(pool[:100])] * 400
-    for p in range(10):
-        mine = pool[100 + 120 * p: 220 + 120 * p]
-        parts += [np.sort(mine[:100]), np.sort(mine[20:120])]
-    return csr(permuted(parts, 17))
-
-
-def both_overflows_thresholds():
-    """(D, the oracle's hits, borderline records kept) one ulp above the distance of the ten pairs, and on it (strict <)"""
-    _, d0 = ok.distance(80, 100, 100, 0, KMER)
-    return ((float(np.nextafter(d0, 1.0)), 79810, 10), (d0, 79800, 0))
-
-
 def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
     """The hit overflow ends the first attempt before the borderline overflow is looked at; the key pass behind the second join
     overflows the borderline buffer and runs again."""
@@ -299,33 +191,6 @@ def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
 
 
 # ---- 8. every kernel of the join, both metrics, 36-bit hashes -----------------------------------------------------------
-_collections = {}
-
-
-def collection(which):
-    """(names, h, off, bits, wide, Oracle) of the named collection, built once per session and never changed"""
-    if which not in _collections:
-        wide, bits = False, 24
-        if which == "tiles":     # more than 4,000 genomes: tile records come with the build
-            names, h, off = synth.clade_sketches(4200, 120, 24, strains_per_clade=10, seed=31, tiny=20)
-        elif which == "near":    # below 4,000 genomes, clades inside the window: the near-window kernel
-            names, h, off = synth.clade_sketches(1200, 120, 24, strains_per_clade=10, seed=32)
-        elif which == "repeat":  # one sketch lists a hash twice: no sets, rk_dist_kernel
-            names, h, off = synth.clade_sketches(64, 200, 24, strains_per_clade=10, seed=33)
-            h = np.concatenate([h[:1], h])
-            off = off.copy()
-            off[1:] += np.uint64(1)
-        elif which == "wide":    # 36-bit hashes, the 64-bit layout
-            names, h, off = synth.clade_sketches(1500, 150, 36, kmer_size=24, seed=15, wide=True)
-            wide, bits = True, 36
-        else:
-            raise KeyError(which)
-        if which != "repeat":
-            names, h, off = synth.permute_genomes(names, h, off, synth.genome_order(len(names), "shuffled", seed=len(names)))
-        _collections[which] = (names, h, off, bits, wide, Oracle(h, off, bits, wide))
-    return _collections[which]
-
-
 @pytest.mark.parametrize("which,kernel,metric", [
     ("tiles", "rk_tile_kernel", 0), ("tiles", "rk_tile_kernel", 1), ("near", "rk_near_kernel", 0), ("near", "rk_near_kernel", 1),
     ("repeat", "rk_dist_kernel", 0), ("repeat", "rk_dist_kernel", 1), ("wide", None, 0), ("wide", None, 1)])

@@ -1,6 +1,6 @@
 """rk_greedy_rows: the greedy representatives of the self join against tests/_greedy_ref.py's sequential rule (exact rational
-ratios) over the ORACLE's hit list, set up as tests/test_gpu_forest.py sets its cases up (its Oracle, device_index and collections,
-built once per session): rep, the exact link tuples, and jorc / dist of the links bit for bit.  Every case says from the call's
+ratios) over the ORACLE's hit list, set up from tests/_selfjoin_cases.py (its Oracle, device_index and collections, built
+once per session): rep, the exact link tuples, and jorc / dist of the links bit for bit.  Every case says from the call's
 stats that it reached the edge it is about; the number of rounds is that of the reference's model of the rounds."""
 import ctypes as C
 import os
@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 import _greedy_ref as gr
-import test_gpu_forest as tf
+from _selfjoin_cases import (KMER, TOOL, Oracle, borderline_overflow_collection, both_overflows_collection, both_overflows_thresholds,
+                             collection, csr, device_index, hit_overflow_collection, identical, permuted, trio)
 from conftest import GOLDEN
 from oracle import oracle as ok
 from rabbitkssd_amd import capi, synth
-from test_gpu_forest import KMER, TOOL, Oracle, csr, device_index, permuted
 
 pytestmark = pytest.mark.gpu
 RK_ERR_ARG, RK_ERR_UNSUPPORTED = -1, -6
@@ -82,12 +82,6 @@ def test_path_laid_in_priority_order(ctx):
 
 
 # ---- 2. every pair at distance 0 ----------------------------------------------------------------------------------------
-def identical(count, seed, others=0):
-    rng = np.random.default_rng(seed)
-    one = np.unique(rng.integers(0, 1 << 24, size=130))[:100]
-    return [one] * count + [np.unique(rng.integers(0, 1 << 24, size=130))[:100] for _ in range(others)]
-
-
 _identical_300 = {}
 
 
@@ -110,24 +104,6 @@ def test_identical_sketches_have_one_representative(ctx):
 
 
 # ---- 3. one ratio from different counts ---------------------------------------------------------------------------------
-def trio(seed, sizes, shares, roles):
-    """Three sketches by role: two representatives of sizes[0] and sizes[1] hashes that share shares[0] and shares[1] hashes with
-    the member of sizes[2] -- and with each other only what the member forces (shares[0] + shares[1] - sizes[2]).  roles[k] = the
-    role at caller index k."""
-    rng = np.random.default_rng(seed)
-    pool = np.unique(rng.integers(0, 1 << 24, size=600))
-    rng.shuffle(pool)
-    member = pool[:sizes[2]]
-    both = shares[0] + shares[1] - sizes[2]
-    assert 0 <= both <= min(shares)
-    rest = pool[sizes[2]:]
-    a = np.concatenate([member[:shares[0]], rest[:sizes[0] - shares[0]]])
-    b = np.concatenate([member[shares[0] - both: shares[0] - both + shares[1]], rest[200: 200 + sizes[1] - shares[1]]])
-    made = [np.sort(a), np.sort(b), np.sort(member)]
-    assert [len(np.unique(p)) for p in made] == list(sizes)
-    return csr([made[r] for r in roles])
-
-
 @pytest.mark.parametrize("metric", [0, 1])
 def test_equal_ratio_from_different_counts(ctx, metric):
     # metric 0: the member's 30 hashes, 20 of them in a representative of 50 (20/60) and 25 in one of 70 (25/75); the two share the
@@ -171,7 +147,7 @@ def test_custom_priority(ctx):
     got = ctx.greedy_rows(device_index(ctx, h, off, 24), 0, KMER, 0.05, priority)
     check(got, orc.hits(0, 0.05), 300, 0, priority)
     assert np.all(got[0] == 299) and got[2]["n_reps"] == 1
-    names, h, off, bits, wide, orc = tf.collection("near")
+    names, h, off, bits, wide, orc = collection("near")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     plain = ctx.greedy_rows(idx, 0, KMER, 0.05)
@@ -186,7 +162,7 @@ def test_custom_priority(ctx):
 
 # ---- 6. more pairs than the hit buffer holds ----------------------------------------------------------------------------
 def test_hit_buffer_overflow_runs_the_join_again(ctx):
-    h, off = csr(permuted(identical(400, 4, others=3), 14))
+    h, off = hit_overflow_collection()
     orc = Oracle(h, off, 24)
     hits = orc.hits(0, 0.05)
     assert len(hits) == 400 * 399 // 2 > max(65536, 403 * 64)
@@ -227,14 +203,7 @@ def test_borderline_record_flips_the_outcome_down_a_chain(ctx, metric):
 
 # ---- 8. more borderline records than their buffer holds -----------------------------------------------------------------
 def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
-    rng = np.random.default_rng(6)
-    pool = np.unique(rng.integers(0, 1 << 24, size=300 * 130))
-    rng.shuffle(pool)
-    parts = []
-    for p in range(300):   # a pair shares 80 of 100
-        mine = pool[120 * p: 120 * p + 120]
-        parts += [np.sort(mine[:100]), np.sort(mine[20:120])]
-    h, off = csr(permuted(parts, 16))
+    h, off = borderline_overflow_collection()
     _, d0 = ok.distance(80, 100, 100, 0, KMER)
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
@@ -259,11 +228,11 @@ def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
 def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
     """The hit overflow ends the first attempt before the borderline overflow is looked at; the key pass behind the second join
     overflows the borderline buffer and runs again."""
-    h, off = tf.both_overflows_collection()
+    h, off = both_overflows_collection()
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
     monkeypatch.setenv("RK_CLUSTER_EDGE_CAP", "4")
-    for D, n_hits, kept in tf.both_overflows_thresholds():
+    for D, n_hits, kept in both_overflows_thresholds():
         hits = orc.hits(0, D)
         assert len(hits) == n_hits > max(65536, 420 * 64) and int(np.sum(hits["common"] == 80)) == kept
         got = ctx.greedy_rows(idx, 0, KMER, D)
@@ -278,7 +247,7 @@ def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
     ("tiles", "rk_tile_kernel", 0), ("tiles", "rk_tile_kernel", 1), ("near", "rk_near_kernel", 0), ("near", "rk_near_kernel", 1),
     ("repeat", "rk_dist_kernel", 0), ("repeat", "rk_dist_kernel", 1), ("wide", None, 0), ("wide", None, 1)])
 def test_every_join_kernel_both_metrics_and_wide_hashes(ctx, which, kernel, metric):
-    names, h, off, bits, wide, orc = tf.collection(which)
+    names, h, off, bits, wide, orc = collection(which)
     kmer = 24 if wide else KMER
     n = len(names)
     idx = device_index(ctx, h, off, bits, wide)
@@ -326,7 +295,7 @@ def raw_call(ctx, idx, opts, n, rep=True, links=True, n_links=True, stats=True):
 
 
 def test_arguments_that_are_refused(ctx):
-    names, h, off, bits, wide, orc = tf.collection("repeat")
+    names, h, off, bits, wide, orc = collection("repeat")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     for D in (1.5, float(np.nextafter(1.0, 2.0))):
@@ -390,7 +359,7 @@ def test_shards_of_a_sharded_build_are_refused(ctx):
 
 # ---- 11. the host rule over the join's own hit list ---------------------------------------------------------------------
 def test_greedy_hits_over_dist_rows_equals_greedy_rows(ctx):
-    names, h, off, bits, wide, orc = tf.collection("near")
+    names, h, off, bits, wide, orc = collection("near")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     for metric in (0, 1):

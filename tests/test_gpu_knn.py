@@ -1,5 +1,5 @@
 """rk_knn_rows: the k nearest neighbours of every genome against tests/_knn_ref.py (exact rational ratios) over the ORACLE's hit list,
-set up as tests/test_gpu_forest.py sets its cases up (its Oracle, device_index and collections, built once per session): the
+set up from tests/_selfjoin_cases.py (its Oracle, device_index and collections, built once per session): the
 offsets, the exact record tuples, and jorc / dist bit for bit.  Every case says from the call's stats that it reached the edge it is
 about."""
 import ctypes as C
@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 
 import _knn_ref as kr
-import test_gpu_forest as tf
+from _selfjoin_cases import (KMER, TOOL, Oracle, borderline_overflow_collection, both_overflows_collection, both_overflows_thresholds,
+                             bridge_collection, collection, csr, device_index, hit_overflow_collection, identical, permuted,
+                             tie_collection, trio)
 from conftest import GOLDEN
 from oracle import oracle as ok
 from rabbitkssd_amd import capi, synth
-from test_gpu_forest import KMER, TOOL, Oracle, csr, device_index, permuted
-from test_gpu_greedy import trio
 
 pytestmark = pytest.mark.gpu
 RK_ERR_ARG = -1
@@ -57,9 +57,7 @@ def degrees(hits, n):
 
 # ---- 1. every pair at distance 0 ----------------------------------------------------------------------------------------
 def test_all_ties_give_the_smallest_indices(ctx):
-    rng = np.random.default_rng(2)
-    one = np.unique(rng.integers(0, 1 << 24, size=130))[:100]
-    h, off = csr(permuted([one] * 300, 12))
+    h, off = csr(permuted(identical(300, 2), 12))
     hits = Oracle(h, off, 24).hits(0, 0.05)
     assert len(hits) == 300 * 299 // 2 and np.all(hits["dist"] == 0.0)
     got = ctx.knn_rows(device_index(ctx, h, off, 24), 0, KMER, 0.05, 5)
@@ -183,7 +181,7 @@ def test_equal_ratio_from_different_counts(ctx, metric):
         got = ctx.knn_rows(device_index(ctx, h, off, 24), metric, KMER, 0.05, 1)
         want = check(got, hits, 3, 1, metric)
         assert want == [[tuples[0]], [tuples[1]], [tuples[0]]] and got[2]["path"] == 1
-    h, off = tf.tie_collection(3)   # six triangles, one per assignment of the roles to ascending indices, and six plain pairs
+    h, off = tie_collection(3)   # six triangles, one per assignment of the roles to ascending indices, and six plain pairs
     n = len(off) - 1
     hits = Oracle(h, off, 24).hits(metric, 0.06)
     two = kr.knn(kr.hit_tuples(hits), n, 2, metric)
@@ -199,7 +197,7 @@ def test_equal_ratio_from_different_counts(ctx, metric):
 # ---- 6. a pair exactly on the threshold, and one ulp either side --------------------------------------------------------
 @pytest.mark.parametrize("metric", [0, 1])
 def test_bridge_on_the_threshold_and_one_ulp_either_side(ctx, metric):
-    h, off = tf.bridge_collection(2, 5)   # A, B, then a (70 of A's hashes) and b (70 of B's), who share 30 others: the bridge
+    h, off = bridge_collection(2, 5)   # A, B, then a (70 of A's hashes) and b (70 of B's), who share 30 others: the bridge
     n = len(off) - 1
     a, b = n - 2, n - 1
     _, d0 = ok.distance(30, 100, 100, metric, KMER)
@@ -221,10 +219,7 @@ def test_bridge_on_the_threshold_and_one_ulp_either_side(ctx, metric):
 
 # ---- 7. overflows -------------------------------------------------------------------------------------------------------
 def test_hit_buffer_overflow_runs_the_join_again(ctx):
-    rng = np.random.default_rng(4)
-    one = np.unique(rng.integers(0, 1 << 24, size=130))[:100]
-    others = [np.unique(rng.integers(0, 1 << 24, size=130))[:100] for _ in range(3)]
-    h, off = csr(permuted([one] * 400 + others, 14))
+    h, off = hit_overflow_collection()
     hits = Oracle(h, off, 24).hits(0, 0.05)
     assert len(hits) == 400 * 399 // 2 > max(65536, 403 * 64)
     got = ctx.knn_rows(device_index(ctx, h, off, 24), 0, KMER, 0.05, 3)
@@ -234,14 +229,7 @@ def test_hit_buffer_overflow_runs_the_join_again(ctx):
 
 
 def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
-    rng = np.random.default_rng(6)
-    pool = np.unique(rng.integers(0, 1 << 24, size=300 * 130))
-    rng.shuffle(pool)
-    parts = []
-    for p in range(300):   # a pair shares 80 of 100
-        mine = pool[120 * p: 120 * p + 120]
-        parts += [np.sort(mine[:100]), np.sort(mine[20:120])]
-    h, off = csr(permuted(parts, 16))
+    h, off = borderline_overflow_collection()
     _, d0 = ok.distance(80, 100, 100, 0, KMER)
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
@@ -258,11 +246,11 @@ def test_borderline_overflow_runs_the_key_pass_again(ctx, monkeypatch):
 
 
 def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
-    h, off = tf.both_overflows_collection()
+    h, off = both_overflows_collection()
     orc = Oracle(h, off, 24)
     idx = device_index(ctx, h, off, 24)
     monkeypatch.setenv("RK_CLUSTER_EDGE_CAP", "4")
-    for D, n_hits, kept in tf.both_overflows_thresholds():
+    for D, n_hits, kept in both_overflows_thresholds():
         hits = orc.hits(0, D)
         assert len(hits) == n_hits
         got = ctx.knn_rows(idx, 0, KMER, D, 2)
@@ -277,7 +265,7 @@ def test_hit_and_borderline_overflow_in_one_call(ctx, monkeypatch):
     ("tiles", "rk_tile_kernel", 0), ("tiles", "rk_tile_kernel", 1), ("near", "rk_near_kernel", 0), ("near", "rk_near_kernel", 1),
     ("repeat", "rk_dist_kernel", 0), ("repeat", "rk_dist_kernel", 1), ("wide", None, 0), ("wide", None, 1)])
 def test_every_join_kernel_both_metrics_and_wide_hashes(ctx, which, kernel, metric):
-    names, h, off, bits, wide, orc = tf.collection(which)
+    names, h, off, bits, wide, orc = collection(which)
     kmer = 24 if wide else KMER
     n = len(names)
     idx = device_index(ctx, h, off, bits, wide)
@@ -293,7 +281,7 @@ def test_every_join_kernel_both_metrics_and_wide_hashes(ctx, which, kernel, metr
 
 # ---- 9. shards ----------------------------------------------------------------------------------------------------------
 def test_three_row_shards_fold_to_the_whole(ctx):
-    names, h, off, bits, wide, orc = tf.collection("near")
+    names, h, off, bits, wide, orc = collection("near")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     hits = orc.hits(0, 0.05)
@@ -351,7 +339,7 @@ def test_join_only_indexes_of_a_two_shard_build_fold_to_the_whole(ctx):
 
 # ---- 10. the paths around the device selection --------------------------------------------------------------------------
 def test_fallback_paths(ctx, monkeypatch):
-    names, h, off, bits, wide, orc = tf.collection("near")
+    names, h, off, bits, wide, orc = collection("near")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     hits = orc.hits(0, 0.05)
@@ -371,14 +359,14 @@ def test_fallback_paths(ctx, monkeypatch):
         if f != "pad":
             assert np.array_equal(host[1][f], device[1][f]), f
     monkeypatch.delenv("RK_KNN_DEVICE")
-    names, h, off, bits, wide, orc = tf.collection("repeat")   # 64 genomes: k larger than N on the device
+    names, h, off, bits, wide, orc = collection("repeat")   # 64 genomes: k larger than N on the device
     got = ctx.knn_rows(device_index(ctx, h, off, bits), 0, KMER, 1.0, 64)
     want = check(got, orc.hits(0, 1.0), len(names), 64, 0)
     assert got[2]["path"] == 1 and len(names) <= 64 and max(len(one) for one in want) < 64
 
 
 def test_knn_hits_over_dist_rows_equals_knn_rows(ctx):
-    names, h, off, bits, wide, orc = tf.collection("near")
+    names, h, off, bits, wide, orc = collection("near")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     for metric in (0, 1):
@@ -425,7 +413,7 @@ def raw_call(ctx, idx, opts, n, k=3, off=True, nbrs=True, n_nbrs=True, stats=Tru
 
 
 def test_arguments_that_are_refused(ctx):
-    names, h, off, bits, wide, orc = tf.collection("repeat")
+    names, h, off, bits, wide, orc = collection("repeat")
     n = len(names)
     idx = device_index(ctx, h, off, bits)
     for D in (1.5, float(np.nextafter(1.0, 2.0))):
