@@ -23,6 +23,8 @@
  *   rk_greedy_rows         <- the same row loop, followed by the greedy incremental clustering its users run over the
  *                             printed pairs (the rule of CD-HIT, Li & Godzik 2006, and of clust-greedy in RabbitTClust, the
  *                             reference's sibling tool; the reference itself has no clustering)
+ *   rk_dbscan_rows         <- the same row loop, followed by the DBSCAN its users run over the printed pairs (Ester et al.
+ *                             1996; min_pts as scikit-learn's min_samples; the reference itself has no clustering)
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -112,6 +114,8 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 /* rk_knn_rows with timing on: degree pass through selection kernel of the last call (0 when no record took part or the call
  * took the host path). */
 #define RK_MS_KNN_SELECT 8
+/* rk_dbscan_rows with timing on: hook kernel through label kernel of the last call (0 when the call took the host path). */
+#define RK_MS_DBSCAN 9
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -628,6 +632,62 @@ int rk_knn_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t k, int
  * that names a genome >= n, has row == col or is not incident to the genome whose list holds it.  Nothing is written on a refusal. */
 int rk_knn_merge(const uint64_t *a_off, const rk_hit *a, const uint64_t *b_off, const rk_hit *b, uint32_t n, uint32_t k, int metric,
                  uint64_t *off_out /* n + 1 */, rk_hit **out, uint64_t *n_out);
+
+/* ---- density-based clusters ------------------------------------------------------- */
+/* DBSCAN over the all-vs-all: clusters that do NOT chain.  Single linkage merges two species through one contaminated or chimeric
+ * assembly that lies within -D of both; here such a genome joins them only if it is itself in a dense neighbourhood.
+ * Graph.  The graph of rk_cluster_rows for ALL rows: its edges are the pairs rk_dist_rows(ctx, idx, NULL, opts, ...) would report --
+ * same metric, same strict threshold (dist < max_dist decided with the C library's log).
+ * Parameters and kinds.  deg(v) is the number of records incident to v.  min_pts >= 1 counts the genome itself, as scikit-learn's
+ * min_samples does.  v is CORE iff deg(v) + 1 >= min_pts.
+ * Clusters and labels.  Clusters are the connected components of the subgraph induced by the core genomes.  The label of a cluster is
+ * the smallest caller index among its CORE genomes.  With min_pts = 1 the labels are those of rk_cluster_rows; with min_pts = 2 they
+ * are those labels, with isolated genomes as noise.
+ * Border genomes.  A non-core v with at least one core neighbour is BORDER.  It takes the label of its NEAREST core neighbour, in the
+ * order of rk_forest_rows restricted to v: the ratio common / u descending, compared exactly (25/75 ties 20/60), then the core
+ * neighbour's caller index ascending.  This is where textbook DBSCAN is order-dependent; here it is a function of the graph.  via[v]
+ * names that neighbour.
+ * Noise.  Every other non-core genome is noise: label = via = RK_DBSCAN_NOISE.
+ * labels_out[v], kind_out[v] (0 noise, 1 border, 2 core), via_out[v] (RK_DBSCAN_NOISE unless v is border) and degree_out[v] = deg(v)
+ * are host arrays of rk_index_genomes(idx) entries in the caller's genome order; via_out and degree_out are optional.  The result is
+ * unique: it does not depend on the order of hits, the internal genome order or the kernel the join took.
+ * The hit records never leave the device (the frame of rk_greedy_rows: the join through rk_dist_rows_dev with the threshold widened by
+ * 2^-46 into max(65,536, rows * 64) records, once more with the exact count on overflow; the key pass with its small host buffer of
+ * RK_CLUSTER_EDGE_CAP borderline records and their slot numbers, run again alone on overflow).  One kept borderline edge can make a
+ * genome core and merge two clusters arbitrarily far away, so the host decides the borderline records BEFORE any degree is counted and
+ * sends the slot numbers of the kept ones back (8 bytes each, usually none).  Then three sweeps over the keyed records -- the degrees; the
+ * hook (both endpoints core: the compare-and-swap link of rk_cluster_rows; exactly one core: a 64-bit atomic minimum of the weight key
+ * at the other); the border settle (a 32-bit atomic minimum of the core neighbour's index among the records that match that key) --
+ * and one pass per genome that writes kind, label, via and degree.  PCIe traffic: 13 * N bytes of results, four counters and the
+ * borderline records: never O(hits).
+ * The core test does NOT compose from row shards (the degrees of a shard are partial): row_step > 1 is refused, and so is the join-only
+ * index of rk_index_join_shard, which holds one shard's rows.  RK_DBSCAN_DEVICE=0 answers inside the call as rk_dist_rows +
+ * rk_dbscan_hits, with the same result.
+ * RK_ERR_ARG: triangle != 1, null pointers (labels_out, kind_out), min_pts == 0, a row shard, a dense report (a threshold above 1.0),
+ * an index rk_dist_rows refuses for a self join, a join-only index.  RK_ERR_UNSUPPORTED: a sketch of 2^30 hashes or more (the key),
+ * what the join answers, and a record outside 0 < common <= u -- only sketches that repeat hashes produce such; it has no place in the
+ * nearness order (collections with repeats whose records stay in range run normally).  An index without genomes: RK_OK, nothing
+ * runs.  stats is optional. */
+#define RK_DBSCAN_NOISE 0xFFFFFFFFu
+typedef struct rk_dbscan_stats {
+    uint64_t edges;          /* hit records of the join */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts; /* 2: the host buffer overflowed once */
+    uint32_t n_clusters;     /* components of the core genomes */
+    uint32_t n_core;
+    uint32_t n_border;
+    uint32_t n_noise;
+} rk_dbscan_stats;           /* 48 bytes */
+int rk_dbscan_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint32_t min_pts, uint32_t *labels_out /* host, N */,
+                   uint8_t *kind_out /* host, N: 0 noise, 1 border, 2 core */, uint32_t *via_out /* host, N, optional */,
+                   uint32_t *degree_out /* host, N, optional */, rk_dbscan_stats *stats /* optional */);
+/* Host only: the same rule over a hit list the caller already has (`metric` as rk_dist_opts.metric; one record per pair, as a join
+ * reports them).  RK_ERR_ARG when a record names a genome >= n or has row == col, for min_pts == 0 and for null pointers (hits may be
+ * NULL when n_hits == 0; via_out and degree_out are optional).  Nothing is written on a refusal. */
+int rk_dbscan_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t min_pts, int metric, uint32_t *labels_out /* n */,
+                   uint8_t *kind_out /* n */, uint32_t *via_out /* n, optional */, uint32_t *degree_out /* n, optional */);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

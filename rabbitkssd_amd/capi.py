@@ -30,8 +30,11 @@ EXPORTS = [
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
-    "rk_knn_rows", "rk_knn_hits", "rk_knn_merge",
+    "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits",
 ]
+
+DBSCAN_NOISE = 0xFFFFFFFF   # RK_DBSCAN_NOISE: label and via of a noise genome
+DBSCAN_KINDS = ("noise", "border", "core")   # kind 0, 1, 2
 
 
 class Params(C.Structure):
@@ -81,6 +84,13 @@ class KnnStats(C.Structure):
     """rk_knn_stats: what one rk_knn_rows call did"""
     _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64), ("neighbours", C.c_uint64),
                 ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("max_degree", C.c_uint32), ("path", C.c_uint32)]
+
+
+class DbscanStats(C.Structure):
+    """rk_dbscan_stats: what one rk_dbscan_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
+                ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("n_clusters", C.c_uint32),
+                ("n_core", C.c_uint32), ("n_border", C.c_uint32), ("n_noise", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -147,6 +157,11 @@ def _take_hits(ptr, n):
     buf = C.string_at(ptr.value, n.value * HIT_DTYPE.itemsize) if n.value else b""
     lib().rk_free_host(ptr)
     return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+
+
+def _dbscan_outputs(n):
+    """labels, kind, via and degree of n genomes, for the library to fill"""
+    return np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
 
 
 def _stats_dict(st, fields=None):
@@ -473,6 +488,21 @@ class Context:
         self.check(L.rk_knn_rows(self._h, index._h, C.byref(opts), C.c_uint32(k), _ptr(off), C.byref(nbrs), C.byref(n), C.byref(st)))
         return off, _take_hits(nbrs, n), _stats_dict(st)
 
+    def dbscan_rows(self, index, metric, kmer_size, max_dist, min_pts, row_first=0, row_step=1, row_block=0):
+        """density-based clusters of the self join (rk_dbscan_rows): (labels, kind, via, degree, stats) -- labels[i] = the smallest
+        core index of i's cluster or DBSCAN_NOISE (uint32), kind[i] = 0 noise, 1 border, 2 core (uint8), via[i] = the nearest core
+        neighbour of a border genome, DBSCAN_NOISE otherwise, degree[i] = the pairs of i within max_dist, stats a dict of the
+        DbscanStats fields.  min_pts counts the genome itself"""
+        opts = _opts(1, metric, kmer_size, max_dist, row_first, row_step, row_block)
+        labels, kind, via, degree = _dbscan_outputs(index.genomes)
+        st = DbscanStats()
+        L = lib()
+        L.rk_dbscan_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(DbscanStats)]
+        self.check(L.rk_dbscan_rows(self._h, index._h, C.byref(opts), C.c_uint32(min_pts), _ptr(labels), _ptr(kind), _ptr(via), _ptr(degree),
+                                    C.byref(st)))
+        return labels, kind, via, degree, _stats_dict(st)
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -747,6 +777,20 @@ def knn_merge(a_off, a, b_off, b, n, k, metric):
     if rc:
         raise RkError(rc, "rk_knn_merge: offsets that do not ascend, or a record that is not incident to the genome whose list holds it")
     return off, _take_hits(out, n_out)
+
+
+def dbscan_hits(hits, n, min_pts, metric):
+    """density-based clusters of a hit list over n genomes (rk_dbscan_hits, host only): (labels, kind, via, degree) as
+    Context.dbscan_rows gives them"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    labels, kind, via, degree = _dbscan_outputs(int(n))
+    L = lib()
+    L.rk_dbscan_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.rk_dbscan_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), C.c_uint32(min_pts), int(metric), _ptr(labels), _ptr(kind), _ptr(via),
+                          _ptr(degree))
+    if rc:
+        raise RkError(rc, "rk_dbscan_hits: min_pts is 0, or a record names a genome beyond the number of genomes or one genome twice")
+    return labels, kind, via, degree
 
 
 def format_hit(name_a, name_b, hit):

@@ -1,6 +1,8 @@
-// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip and rk_knn.hip (not part of the public ABI): the
-// self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device may decide.
-// DESIGN.md 4.6.  The key pass of the last three lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings its own.
+// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip, rk_knn.hip and rk_dbscan.hip (not part of the
+// public ABI): the self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device
+// may decide.  DESIGN.md 4.6.  The key pass of the last four lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings
+// its own.  Two passes over the keyed records that more than one caller runs behind the stage follow it: k_edge_revive (greedy,
+// dbscan) and k_edge_degree (knn, dbscan).
 //
 //   join     rk_dist_rows_dev with the threshold widened by 2^-46 (capped at 1.0: beyond it the public join would turn to the dense
 //            report) appends unordered hit records to a buffer of max(65,536, rows * 64) records; its counter counts every hit,
@@ -103,6 +105,33 @@ k_edge_keys(const rk_hit *hits, unsigned long long *cnt, unsigned long long cap,
     }
 }
 
+// the borderline records the host kept (their slot numbers, sent back up): alive from here on, their keys from the same integer
+// function.  (maybe_unused, here and below: not every file that includes the stage runs these two)
+[[maybe_unused]] __global__ void k_edge_revive(const rk_hit *hits, const unsigned long long *slots, unsigned long long n_kept, unsigned long long n_rec, int metric,
+                              unsigned long long *w)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_kept) return;
+    const unsigned long long e = slots[i];
+    if (e >= n_rec) return;   // (the host sends back what k_edge_keys wrote)
+    const rk_hit h = hits[e];
+    long long c, u;
+    ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
+    w[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (k_edge_keys saw 0 < c <= u)
+}
+
+// deg[v] += the live records incident to v.  Behind the stage, never inside its pass: the pass may run twice
+[[maybe_unused]] __global__ void __launch_bounds__(kStageThreads)
+k_edge_degree(const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, uint32_t *deg)
+{
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
+        if (w[e] == kDead) continue;
+        const unsigned long long p = rc[e];
+        atomicAdd(deg + (uint32_t)(p >> 32), 1u);
+        atomicAdd(deg + (uint32_t)p, 1u);
+    }
+}
+
 struct EdgeStage {
     rk_ctx *ctx;
     const rk_index *idx;
@@ -119,6 +148,7 @@ struct EdgeStage {
     DevBuf<unsigned long long> slots, block;   // slots: with_slots only.  block: the counters, then the caller's tail
     size_t tail_bytes;
     bool with_slots;
+    bool tail_in_pass = true;                  // false: the pass does not write the tail; run() brings the counters home alone and the caller's fetch_home() the tail
     const unsigned char *home = nullptr;       // counters and tail of the last pass in the context's page-locked scratch
     unsigned long long n_hits = 0, n_border = 0;
     uint32_t join_attempts = 0, pass_attempts = 0;   // (pass_attempts: those behind the last join)
@@ -162,10 +192,7 @@ struct EdgeStage {
             pass_attempts = 0;
             for (int k = 0; k < 2; k++) {
                 if (int rc = pass(k)) return rc;
-                home = (const unsigned char *)rk_pinned_scratch(ctx, block_bytes);   // (asked for behind the join, whose lazy builders use it too)
-                if (!home) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %zu bytes of page-locked memory for the labels", block_bytes);
-                RK_HIP(ctx, hipMemcpyAsync((void *)home, block.p, block_bytes, hipMemcpyDeviceToHost, stream));
-                RK_HIP(ctx, hipStreamSynchronize(stream));
+                if (int rc = fetch_home(tail_in_pass)) return rc;   // (the scratch is asked for behind the join, whose lazy builders use it too)
                 unsigned long long c[kCntWords];
                 memcpy(c, home, sizeof c);
                 if (c[kCntBad]) return rk_fail(ctx, RK_ERR_HIP, "%llu hit records name %s", c[kCntBad], bad_what);
@@ -187,7 +214,18 @@ struct EdgeStage {
         return rk_fail(ctx, RK_ERR_CAPACITY, "hit or borderline buffer overflow persisted after resize");
     }
 
-    // The key pass of the forest, the greedy rule and the neighbour lists as pass k of run(): k_edge_keys<GREEDY> over w and rc of
+    // counters and (with_tail) tail of the block into the context's page-locked scratch: one copy, one synchronisation
+    int fetch_home(bool with_tail = true)
+    {
+        const size_t bytes = kCntWords * 8 + (with_tail ? tail_bytes : 0);
+        home = (const unsigned char *)rk_pinned_scratch(ctx, bytes);
+        if (!home) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %zu bytes of page-locked memory for the labels", bytes);
+        RK_HIP(ctx, hipMemcpyAsync((void *)home, block.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return RK_OK;
+    }
+
+    // The key pass of the forest, the greedy rule, the neighbour lists and the density clusters as pass k of run(): k_edge_keys<GREEDY> over w and rc of
     // `cap` records each.  The buffers are the caller's (its later passes read them), allocated here at k = 0, and `extra` (greedy's
     // hl) with them where one is given.
     template <bool GREEDY>

@@ -8,7 +8,7 @@
 //             row << 32 | col; a BORDERLINE record goes, with its slot number, to the small host buffer and is dead for now; a record
 //             outside 0 < common <= u -- multisets -- is counted: the call refuses such a collection), the two retries;
 //   host      the stage decides the borderline records BEFORE any round (a kept edge can flip representatives arbitrarily far
-//             away); the slot numbers of the kept ones go back up and k_revive gives them their keys;
+//             away); the slot numbers of the kept ones go back up and k_edge_revive gives them their keys;
 //   k_orient  per live record hi << 32 | lo: hi the endpoint of smaller rank (rank[] is the priority order, computed on the host);
 //   rounds    k_edges: hi a representative -> lo is covered, the record dead; hi a member -> dead; hi and lo undecided -> lo is
 //             blocked for this round.  k_vertices: an undecided genome that is covered becomes a member, one that is neither covered
@@ -54,20 +54,6 @@ __global__ void k_greedy_init(uint32_t *state, uint32_t *covered, uint32_t *bloc
         best_w[i] = kDead;
         best_rc[i] = kDead;
     }
-}
-
-// the borderline records the host kept: alive from here on, their keys from the same integer function
-__global__ void k_greedy_revive(const rk_hit *hits, const unsigned long long *slots, unsigned long long n_kept, unsigned long long n_rec, int metric,
-                                unsigned long long *w)
-{
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_kept) return;
-    const unsigned long long e = slots[i];
-    if (e >= n_rec) return;   // (the host sends back what k_edge_keys wrote)
-    const rk_hit h = hits[e];
-    long long c, u;
-    ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
-    w[e] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (k_edge_keys saw 0 < c <= u)
 }
 
 // hi: the endpoint that precedes the other
@@ -243,7 +229,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
         if (!kept.empty()) {
             RK_HIP(ctx, hipMemcpyAsync(stage.slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, stream));
             RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept_slots is pageable memory)
-            hipLaunchKernelGGL(k_greedy_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream, hits,
+            hipLaunchKernelGGL(k_edge_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream, hits,
                                stage.slots.p, (unsigned long long)kept.size(), n_rec, metric, w.p);
             RK_HIP(ctx, hipGetLastError());
         }

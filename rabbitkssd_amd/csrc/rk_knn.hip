@@ -7,7 +7,7 @@
 //   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (EdgeStage::key_pass<false>: per record w and
 //             row << 32 | col; a BORDERLINE record and a record outside 0 < common <= u -- multisets: no key -- go to the small host
 //             buffer and are dead on the device), the two retries;
-//   degree    k_knn_degree: per live record one atomicAdd on deg[row] and one on deg[col] -- behind the stage, whose pass may run twice;
+//   degree    k_edge_degree: per live record one atomicAdd on deg[row] and one on deg[col] -- behind the stage, whose pass may run twice;
 //   offsets   k_knn_offsets writes min(deg, k) and the largest degree; two exclusive scans give the adjacency offsets aoff[] and the
 //             output offsets koff[] (N + 1 words each);
 //   fill      k_knn_fill: per live record and endpoint v the 16-byte entry {w, other << 32 | e} at aoff[v] + atomicAdd(cur + v, 1).
@@ -44,17 +44,6 @@ constexpr uint32_t kWave = 64;
 struct __align__(16) KnnEntry {
     unsigned long long w, x;   // ~ratio key; neighbour << 32 | record number
 };
-
-__global__ void __launch_bounds__(kStageThreads)
-k_knn_degree(const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, uint32_t *deg)
-{
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
-        if (w[e] == kDead) continue;
-        const unsigned long long p = rc[e];
-        atomicAdd(deg + (uint32_t)(p >> 32), 1u);
-        atomicAdd(deg + (uint32_t)p, 1u);
-    }
-}
 
 // kmin[i] = min(deg[i], k); deg[N] is 0 (the scans then end in the totals); *max_deg: one atomic per wave
 __global__ void __launch_bounds__(kStageThreads)
@@ -335,7 +324,7 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
         if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
         RK_HIP(ctx, hipMemsetAsync(deg.p, 0, ((size_t)N + 1) * 4, stream));
         RK_HIP(ctx, hipMemsetAsync(most.p, 0, 4, stream));
-        hipLaunchKernelGGL(k_knn_degree, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, deg.p);
+        hipLaunchKernelGGL(k_edge_degree, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, deg.p);
         hipLaunchKernelGGL(k_knn_offsets, dim3(vgrid), dim3(kStageThreads), 0, stream, deg.p, kmin.p, N, k, most.p);
         RK_HIP(ctx, hipGetLastError());
         if (int r = rk_prim_exclusive_scan_u32(ctx, deg.p, aoff.p, (uint64_t)N + 1, stream)) return rk_fail(ctx, r, "rk_knn_rows: the scan of the degrees failed");

@@ -1211,7 +1211,7 @@ static void build_everywhere(GpuSet &set, const SketchSet &s, const string &path
     on_every_gpu(G, [&](size_t g) { idx[g] = build_index(set[g], s, path, g == 0 && write_files); });
 }
 
-// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn): the common arguments, the input (a .sketch file, or a
+// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn, dbscan): the common arguments, the input (a .sketch file, or a
 // genome list that is sketched first), the index on every GPU of the set (the sharded build where it applies, the whole index
 // everywhere otherwise), the reference's phase lines around them and the way out.
 struct SelfJoin {
@@ -1566,6 +1566,57 @@ static int cmd_knn(const Args &a)
         fprintf(stderr, "[timing] %llu neighbour records (k = %u) over %zu genomes from %llu hit records (%llu borderline), largest degree %llu, path %llu\n",
                 (unsigned long long)n_nbrs[0], k, N, hits, border, most, path);
     }
+    j.leave();
+}
+
+// dbscan: density-based clusters of alldist's pairs (rk_dbscan_rows; a genome with -m genomes, itself included, within -D is core, the
+// clusters are the components of the core genomes, a non-core genome next to a core one is a border genome of its nearest core
+// neighbour's cluster, the rest is noise), one line per genome: cluster number (from 1, clusters ordered by their label, the smallest
+// core index), cluster size, kind, genome name, degree, the name of the core neighbour a border genome came in through (else -);
+// within a cluster the core genomes by ascending index, then the border genomes by ascending index; the noise last, as cluster 0 of
+// size 0.
+static int cmd_dbscan(const Args &a)
+{
+    SelfJoin j(a, "dbscan", true);
+    if (a.num("gpus", 1) > 1) die("command_dbscan(), dbscan runs on one GPU: the core test does not compose from the shards of several (--gpus 1)");
+    if (!a.has("m") || a.num("m", 0) < 1) die("command_dbscan(), minPts must be >= 1\nUse -m to set the minPts (it counts the genome itself)");
+    const uint32_t min_pts = (uint32_t)a.num("m", 1);
+    j.prepare(1, false);
+    const size_t N = j.N;
+    vector<uint32_t> label(N ? N : 1), via(N ? N : 1), degree(N ? N : 1);
+    vector<uint8_t> kind(N ? N : 1);
+    rk_dbscan_stats stats{};
+    const rk_dist_opts o = j.opts(0);
+    j.gpu(0).check(rk_dbscan_rows(j.gpu(0).ctx, j.idx[0], &o, min_pts, label.data(), kind.data(), via.data(), degree.data(), &stats), "rk_dbscan_rows");
+    j.phase_done("density clusters on the host", "density clustering");
+    // a counting sort by (label, kind descending): number[l] and size[l] of the cluster whose label is l
+    vector<uint32_t> number(N, 0), size(N, 0), order(N);
+    vector<size_t> at(N + 1, 0);
+    size_t placed = 0;
+    uint32_t n_clusters = 0;
+    for (size_t i = 0; i < N; i++)
+        if (kind[i]) size[label[i]]++;
+    for (size_t l = 0; l < N; l++) {
+        at[l] = placed;
+        placed += size[l];
+        if (size[l]) number[l] = ++n_clusters;
+    }
+    for (uint8_t k : {(uint8_t)2, (uint8_t)1, (uint8_t)0})
+        for (size_t i = 0; i < N; i++)
+            if (kind[i] == k) order[k ? at[label[i]]++ : placed++] = (uint32_t)i;
+    static const char *const kind_name[3] = {"noise", "border", "core"};
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
+    for (size_t k = 0; k < N; k++) {
+        const uint32_t i = order[k];
+        const uint32_t l = kind[i] ? label[i] : 0;
+        fprintf(fp, "%u\t%u\t%s\t%s\t%u\t%s\n", kind[i] ? number[l] : 0u, kind[i] ? size[l] : 0u, kind_name[kind[i]], j.s.names[i].c_str(), degree[i],
+                kind[i] == 1 ? j.s.names[via[i]].c_str() : "-");
+    }
+    fclose(fp);
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %u density clusters (minPts = %u) of %zu genomes: %u core, %u border, %u noise, from %llu hit records (%llu borderline)\n",
+                stats.n_clusters, min_pts, N, stats.n_core, stats.n_border, stats.n_noise, (unsigned long long)stats.edges, (unsigned long long)stats.borderline);
     j.leave();
 }
 
@@ -1949,7 +2000,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -1957,6 +2008,7 @@ static int usage()
             "  forest -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (minimum spanning forest of alldist's pairs: the single-linkage dendrogram up to -D, one alldist line per edge)\n"
             "  greedy -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--reps FILE] [-L file.shuf] [--device N]   (greedy representatives of alldist's pairs: larger sketch first, a genome joins the nearest earlier representative within -D or becomes one; one GPU)\n"
             "  knn -i in.sketch|genomes.list -o out -N k [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (the k nearest neighbours of every genome among alldist's pairs: one alldist-format line per genome and neighbour, nearest first)\n"
+            "  dbscan -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [-L file.shuf] [--device N]   (density-based clusters of alldist's pairs: a genome with minPts genomes, itself included, within -D is core; clusters are the components of the core genomes, a non-core genome joins its nearest core neighbour's cluster as border, the rest is noise; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -1977,7 +2029,7 @@ int main(int argc, char **argv)
         {"-n", "n"}, {"--leastNumKmer", "n"}, {"-Q", "Q"}, {"--leastQuality", "Q"}, {"-D", "D"}, {"--maxDist", "D"},
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
-        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}};
+        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -1995,7 +2047,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2017,6 +2069,7 @@ int main(int argc, char **argv)
     if (sub == "forest") { cerr << "-----run the subcommand: forest" << endl; return leave(cmd_forest(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "greedy") { cerr << "-----run the subcommand: greedy" << endl; return leave(cmd_greedy(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "knn") { cerr << "-----run the subcommand: knn" << endl; return leave(cmd_knn(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "dbscan") { cerr << "-----run the subcommand: dbscan" << endl; return leave(cmd_dbscan(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
