@@ -25,6 +25,8 @@
  *                             reference's sibling tool; the reference itself has no clustering)
  *   rk_dbscan_rows         <- the same row loop, followed by the DBSCAN its users run over the printed pairs (Ester et al.
  *                             1996; min_pts as scikit-learn's min_samples; the reference itself has no clustering)
+ *   rk_mreach_rows         <- the same row loop, followed by the mutual-reachability spanning forest of HDBSCAN* its users
+ *                             build over the printed pairs (Campello, Moulavi & Sander 2013)
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -116,6 +118,8 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 #define RK_MS_KNN_SELECT 8
 /* rk_dbscan_rows with timing on: hook kernel through label kernel of the last call (0 when the call took the host path). */
 #define RK_MS_DBSCAN 9
+/* rk_mreach_rows with timing on: degree pass through the last Boruvka round of the last call (0 when the call took the host path). */
+#define RK_MS_MREACH 10
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -688,6 +692,70 @@ int rk_dbscan_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
  * NULL when n_hits == 0; via_out and degree_out are optional).  Nothing is written on a refusal. */
 int rk_dbscan_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t min_pts, int metric, uint32_t *labels_out /* n */,
                    uint8_t *kind_out /* n */, uint32_t *via_out /* n, optional */, uint32_t *degree_out /* n, optional */);
+
+/* ---- mutual-reachability forest ---------------------------------------------------- */
+/* The minimum spanning forest of the all-vs-all under MUTUAL-REACHABILITY distance: the HDBSCAN* hierarchy up to -D, the density
+ * counterpart of rk_forest_rows.  Cut at any t <= D it gives the core genomes and the clusters rk_dbscan_rows returns at t, without a
+ * join; with min_pts = 1 it is rk_forest_rows' forest.
+ * Graph.  That of rk_cluster_rows for ALL rows: the pairs `alldist -D d` reports -- rk_dist_rows(ctx, idx, NULL, opts, ...) --, with the
+ * strict `<` on the C library's distance.
+ * Core record.  min_pts >= 1 counts the genome itself, as in rk_dbscan_rows.  Let k = min_pts - 1.  For k >= 1 the core record of v is
+ * the k-th entry of v's neighbour list in the order of rk_knn_rows: ratio descending, compared exactly, then the neighbour's caller
+ * index ascending.  core_dist[v] is that record's dist, recomputed on the host with the C library's log; core_nb[v] is the neighbour.  A
+ * genome with fewer than k incident records has no core record: core_dist[v] = +inf and core_nb[v] = RK_MREACH_NONE; such a genome is
+ * noise at every level <= D and no edge touches it.  For k = 0, core_dist[v] = 0.0 and core_nb[v] = RK_MREACH_NONE for every v.
+ * Weight.  The weight of record e = (a, b) is mw(e) = max(w(e), core_w[a], core_w[b]), where w is the nearness weight of
+ * rk_forest_rows' order (it rises as the ratio common / u falls) and core_w[v] is the w of v's core record, 0 for k = 0 and infinite
+ * for a genome without one.  In doubles this is max(e.dist, core_dist[row], core_dist[col]).
+ * Order of edges.  mw ascending and exact (25/75 ties 20/60), then row ascending, then col ascending (row < col, as a join reports a
+ * pair).  The order is strict, so the forest is unique: the edges Kruskal accepts in this order among the records with finite mw.
+ * *edges_out (library-allocated, rk_free_host) lists them in this order: rk_hit records of the underlying pairs,
+ * at most N - 1 of them, jorc and dist bit for bit the reference's.  The result does not depend on the order of hits or genomes, nor on
+ * the kernel the join took.  core_dist_out (host, N doubles) is required, core_nb_out (host, N) and stats are optional.
+ * The hit records never leave the device (the frame of rk_dbscan_rows: the join through rk_dist_rows_dev with the threshold widened by
+ * 2^-46, the key pass with its small host buffer of RK_CLUSTER_EDGE_CAP borderline records and their slot numbers, both retries).  One
+ * kept borderline edge changes a core distance and with it the weight of edges arbitrarily far away, so the host decides the borderline
+ * records BEFORE anything else and sends the slot numbers of the kept ones back.  Then, for k >= 1, the degrees, a scan, the CSR
+ * adjacency of rk_knn_rows and its wave64 selection, which here keeps the k-th entry alone; one sweep that raises every record's weight
+ * to mw; the Boruvka rounds of rk_forest_rows over mw (at most 2 + ceil(log2 N)); a sort of the forest by (mw, row, col).  PCIe
+ * traffic: 40 bytes per edge and 40 bytes per genome (its core record), the borderline records and a counter per round: never O(hits).
+ * Inside the call, as rk_dist_rows + rk_mreach_hits with the same result (stats.path == 2): min_pts above 65 (k above 64, the lanes of
+ * a wave64), 2^31 hit records or more, and RK_MREACH_DEVICE=0.
+ * The core distances do NOT compose from row shards: row_step > 1 is refused, and so is the join-only index of rk_index_join_shard.
+ * RK_ERR_ARG: triangle != 1, null pointers (core_dist_out, edges_out, n_edges), min_pts == 0, a row shard, a dense report (a threshold
+ * above 1.0), an index rk_dist_rows refuses for a self join, a join-only index.  RK_ERR_UNSUPPORTED: a sketch of 2^30 hashes or more
+ * (the key), what the join answers, and a record outside 0 < common <= u (only sketches that repeat hashes produce such).  An index
+ * without genomes: RK_OK, nothing runs, *edges_out = NULL. */
+#define RK_MREACH_NONE 0xFFFFFFFFu
+typedef struct rk_mreach_stats {
+    uint64_t edges;          /* hit records of the join */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts; /* 2: the host buffer overflowed once */
+    uint32_t rounds;         /* Boruvka rounds, the last (empty) one included; 0 when no record took part */
+    uint32_t n_trees;        /* genomes minus returned edges: components, singletons and genomes without a core record included */
+    uint32_t n_core;         /* genomes with a finite core distance */
+    uint32_t max_degree;     /* most live records at one genome (device path, min_pts >= 2) */
+    uint32_t path;           /* 0 nothing ran, 1 device, 2 rk_dist_rows + rk_mreach_hits inside the call */
+    uint32_t pad_;
+} rk_mreach_stats;           /* 56 bytes */
+int rk_mreach_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint32_t min_pts, double *core_dist_out /* host, N */,
+                   uint32_t *core_nb_out /* host, N, optional */, rk_hit **edges_out, uint64_t *n_edges,
+                   rk_mreach_stats *stats /* optional */);
+/* Host only: the same rule over a hit list the caller already has (`metric` as rk_dist_opts.metric; one record per pair, as a join
+ * reports them).  The edges are the caller's records, unchanged; core_dist is the core record's dist field as the caller gave it.  A
+ * record with row > col counts as the pair (col, row) in the order.  A record without a ratio (u <= 0 or common < 0) weighs more than
+ * every record that has one.  RK_ERR_ARG when a record names a genome >= n or has row == col, for min_pts == 0 and for null pointers
+ * (hits may be NULL when n_hits == 0, core_dist_out when n == 0; core_nb_out is optional). */
+int rk_mreach_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t min_pts, int metric, double *core_dist_out /* n */,
+                   uint32_t *core_nb_out /* n, optional */, rk_hit **edges_out, uint64_t *n_edges);
+/* Host only: the forest cut at t <= D, in the form of rk_dbscan_rows' labels.  Genome v is core at t iff core_dist[v] < t; an edge links
+ * iff max(dist, core_dist[row], core_dist[col]) < t; labels_out[v] = the smallest index of v's component among the core genomes, or
+ * RK_DBSCAN_NOISE for a genome that is not core at t.  This is DBSCAN*: a BORDER genome of rk_dbscan_rows at t is noise here, because
+ * the forest does not hold the edges that would assign it.  The core genomes and their labels are those of rk_dbscan_rows at t with the
+ * same min_pts.  (At t = 0 no genome is core, whatever min_pts: no distance lies below 0.)  RK_ERR_ARG for an edge that names a genome >= n or null pointers (edges may be NULL when n_edges == 0). */
+int rk_mreach_cut(const rk_hit *edges, uint64_t n_edges, const double *core_dist /* n */, uint32_t n, double t, uint32_t *labels_out /* n */);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

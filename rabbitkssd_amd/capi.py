@@ -30,11 +30,12 @@ EXPORTS = [
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
-    "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits",
+    "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
 ]
 
 DBSCAN_NOISE = 0xFFFFFFFF   # RK_DBSCAN_NOISE: label and via of a noise genome
 DBSCAN_KINDS = ("noise", "border", "core")   # kind 0, 1, 2
+MREACH_NONE = 0xFFFFFFFF    # RK_MREACH_NONE: core_nb of a genome without a core record
 
 
 class Params(C.Structure):
@@ -91,6 +92,14 @@ class DbscanStats(C.Structure):
     _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
                 ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("n_core", C.c_uint32), ("n_border", C.c_uint32), ("n_noise", C.c_uint32)]
+
+
+class MreachStats(C.Structure):
+    """rk_mreach_stats: what one rk_mreach_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64),
+                ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("rounds", C.c_uint32),
+                ("n_trees", C.c_uint32), ("n_core", C.c_uint32), ("max_degree", C.c_uint32), ("path", C.c_uint32),
+                ("pad_", C.c_uint32)]
 
 
 class RkError(RuntimeError):
@@ -503,6 +512,24 @@ class Context:
                                     C.byref(st)))
         return labels, kind, via, degree, _stats_dict(st)
 
+    def mreach_rows(self, index, metric, kmer_size, max_dist, min_pts, row_first=0, row_step=1, row_block=0):
+        """the minimum spanning forest of the self join under mutual-reachability distance (rk_mreach_rows): (core_dist, core_nb,
+        edges, stats) -- core_dist[i] = the dist of i's (min_pts - 1)-th nearest record (float64; inf without one, 0.0 at min_pts 1),
+        core_nb[i] = that neighbour or MREACH_NONE (uint32), edges as HIT_DTYPE in the order (mutual-reachability weight, row, col),
+        stats a dict of the MreachStats fields.  min_pts counts the genome itself"""
+        opts = _opts(1, metric, kmer_size, max_dist, row_first, row_step, row_block)
+        core_dist = np.zeros(index.genomes, dtype=np.float64)
+        core_nb = np.zeros(index.genomes, dtype=np.uint32)
+        edges = C.c_void_p()
+        n = C.c_uint64()
+        st = MreachStats()
+        L = lib()
+        L.rk_mreach_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_uint64), C.POINTER(MreachStats)]
+        self.check(L.rk_mreach_rows(self._h, index._h, C.byref(opts), C.c_uint32(min_pts), _ptr(core_dist), _ptr(core_nb), C.byref(edges), C.byref(n),
+                                    C.byref(st)))
+        return core_dist, core_nb, _take_hits(edges, n), _stats_dict(st, MreachStats._fields_[:-1])
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -791,6 +818,38 @@ def dbscan_hits(hits, n, min_pts, metric):
     if rc:
         raise RkError(rc, "rk_dbscan_hits: min_pts is 0, or a record names a genome beyond the number of genomes or one genome twice")
     return labels, kind, via, degree
+
+
+def mreach_hits(hits, n, min_pts, metric):
+    """the mutual-reachability forest of a hit list over n genomes (rk_mreach_hits, host only): (core_dist, core_nb, edges) as
+    Context.mreach_rows gives them, the edges being the caller's records unchanged"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    core_dist = np.zeros(int(n), dtype=np.float64)
+    core_nb = np.zeros(int(n), dtype=np.uint32)
+    edges = C.c_void_p()
+    n_edges = C.c_uint64()
+    L = lib()
+    L.rk_mreach_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_uint64)]
+    rc = L.rk_mreach_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), C.c_uint32(min_pts), int(metric), _ptr(core_dist), _ptr(core_nb),
+                          C.byref(edges), C.byref(n_edges))
+    if rc:
+        raise RkError(rc, "rk_mreach_hits: min_pts is 0, or a record names a genome beyond the number of genomes or one genome twice")
+    return core_dist, core_nb, _take_hits(edges, n_edges)
+
+
+def mreach_cut(edges, core_dist, t):
+    """labels (uint32) of a mutual-reachability forest cut at t (rk_mreach_cut, host only): the smallest index of each component of
+    the genomes that are core at t (core_dist < t), DBSCAN_NOISE for every other genome -- the core labels of dbscan_rows at t"""
+    edges = np.ascontiguousarray(edges, dtype=HIT_DTYPE)
+    core_dist = np.ascontiguousarray(core_dist, dtype=np.float64)
+    labels = np.zeros(len(core_dist), dtype=np.uint32)
+    L = lib()
+    L.rk_mreach_cut.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]
+    rc = L.rk_mreach_cut(_ptr(edges), C.c_uint64(len(edges)), _ptr(core_dist), C.c_uint32(len(core_dist)), C.c_double(t), _ptr(labels))
+    if rc:
+        raise RkError(rc, "rk_mreach_cut: an edge names a genome beyond the number of genomes")
+    return labels
 
 
 def format_hit(name_a, name_b, hit):

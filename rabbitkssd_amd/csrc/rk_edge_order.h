@@ -1,5 +1,5 @@
 // rk_edge_order.h -- the order of hit records by nearness (not part of the public ABI): the keys of rk_edge_stage.h's key pass and of
-// the kernels of rk_forest.hip and rk_greedy.hip that follow it, and the exact order of their host sides.
+// the kernels of rk_forest.hip, rk_greedy.hip, rk_knn.hip and rk_mreach.hip that follow it, and the exact order of their host sides.
 //
 // Order of edges (include/rabbitkssd.h, clusters section): the ratio common / u descending -- u = size0 + size1 - common (metric 0)
 // or min(size0, size1) (metric 1); both distances fall strictly as it rises --, then row ascending, then col ascending.  On the
@@ -53,6 +53,23 @@ struct EdgeLess {
             if (l != r) return l > r;
         }
         return a.row != b.row ? a.row < b.row : a.col < b.col;
+    }
+};
+
+inline uint32_t other_end(const rk_hit &h, uint32_t v) { return h.row == v ? h.col : h.row; }
+
+// the order of genome v's list (rk_knn_rows, the core record of rk_mreach_rows): EdgeLess with the endpoint v fixed -- ratio first,
+// then the neighbour's index
+struct NeighbourLess {
+    int metric;
+    uint32_t v;
+    bool operator()(const rk_hit &a, const rk_hit &b) const
+    {
+        rk_hit x = a, y = b;
+        x.row = y.row = 0;
+        x.col = other_end(a, v);
+        y.col = other_end(b, v);
+        return EdgeLess{metric}(x, y);
     }
 };
 

@@ -11,10 +11,11 @@
 //   stage     rk_edge_stage.h: the self join into a device buffer, its key pass (EdgeStage::key_pass<false>: per record w and
 //             row << 32 | col; a BORDERLINE record and a record outside 0 < common <= u -- multisets: no key -- go to the small host
 //             buffer and are dead on the device), the two retries, the host's decision about the records of that buffer;
-//   rounds    Boruvka: k_match_w (atomic minimum of w per component, both endpoints), k_match_rc (among the records that match
-//             that w, atomic minimum of row << 32 | col), k_link (a record that is the best edge of either of its components is
-//             appended once to the forest buffer, its roots linked with the compare-and-swap hook), k_flatten (label[i] =
-//             root(i), best arrays reset).  The host reads one counter per round and stops when a round appended nothing;
+//   rounds    Boruvka (rk_boruvka.h, shared with rk_mreach.hip): k_match_w (atomic minimum of w per component, both endpoints),
+//             k_match_rc (among the records that match that w, atomic minimum of row << 32 | col), k_link (a record that is the best
+//             edge of either of its components is appended once to the forest buffer, its roots linked with the compare-and-swap
+//             hook), k_flatten (label[i] = root(i), best arrays reset).  The host reads one counter per round and stops when a round
+//             appended nothing;
 //   sort      the <= N - 1 forest records by (w, row, col): two stable radix passes; download;
 //   host      Kruskal over (forest + the records the stage kept), jorc / dist of the result recomputed with the C library's log.
 //
@@ -34,85 +35,9 @@
 #include "rk_union_find.h"
 #include "rk_edge_order.h"
 #include "rk_edge_stage.h"
+#include "rk_boruvka.h"
 
 namespace {
-
-__global__ void k_forest_init(uint32_t *parent, uint32_t *label, unsigned long long *best_w, unsigned long long *best_rc, uint32_t n)
-{
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        parent[i] = i;
-        label[i] = i;
-        best_w[i] = kDead;
-        best_rc[i] = kDead;
-    }
-}
-
-// (In the kernels of the rounds n_hits_dev counts every hit of the join, those beyond `cap` included: they read what was written.)
-// label[] is the round's start: written by k_forest_flatten / k_forest_init, a kernel boundary away.  A record inside one component
-// stays inside it: dead from here on (its own thread is the only one that touches w[e]).
-__global__ void __launch_bounds__(kStageThreads)
-k_forest_match_w(unsigned long long *w, const unsigned long long *rc, const unsigned long long *n_hits_dev, unsigned long long cap,
-                 const uint32_t *label, unsigned long long *best_w)
-{
-    const unsigned long long n_rec = min(*n_hits_dev, cap);
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned long long we = w[e];
-        if (we == kDead) continue;
-        const unsigned long long p = rc[e];
-        const uint32_t la = label[(uint32_t)(p >> 32)], lb = label[(uint32_t)p];
-        if (la == lb) {
-            w[e] = kDead;
-            continue;
-        }
-        min_u64(best_w + la, we);
-        min_u64(best_w + lb, we);
-    }
-}
-
-__global__ void __launch_bounds__(kStageThreads)
-k_forest_match_rc(const unsigned long long *w, const unsigned long long *rc, const unsigned long long *n_hits_dev, unsigned long long cap,
-                  const uint32_t *label, const unsigned long long *best_w, unsigned long long *best_rc)
-{
-    const unsigned long long n_rec = min(*n_hits_dev, cap);
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned long long we = w[e];
-        if (we == kDead) continue;
-        const unsigned long long p = rc[e];
-        const uint32_t la = label[(uint32_t)(p >> 32)], lb = label[(uint32_t)p];
-        if (best_w[la] == we) min_u64(best_rc + la, p);
-        if (best_w[lb] == we) min_u64(best_rc + lb, p);
-    }
-}
-
-// la and lb are the roots of the record's trees at the round's start, so the walk to today's roots starts there
-__global__ void __launch_bounds__(kStageThreads)
-k_forest_link(const rk_hit *hits, unsigned long long *w, const unsigned long long *rc, const unsigned long long *n_hits_dev, unsigned long long cap,
-              const uint32_t *label, const unsigned long long *best_w, const unsigned long long *best_rc, uint32_t *parent, rk_hit *forest,
-              unsigned long long forest_cap, unsigned long long *n_forest)
-{
-    const unsigned long long n_rec = min(*n_hits_dev, cap);
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned long long we = w[e];
-        if (we == kDead) continue;
-        const unsigned long long p = rc[e];
-        const uint32_t la = label[(uint32_t)(p >> 32)], lb = label[(uint32_t)p];
-        const bool best = (best_w[la] == we && best_rc[la] == p) || (best_w[lb] == we && best_rc[lb] == p);
-        if (!best) continue;
-        const unsigned long long at = atomicAdd(n_forest, 1ULL);
-        if (at < forest_cap) forest[at] = hits[e];   // (a forest has at most N - 1 edges; the host checks the counter)
-        w[e] = kDead;
-        p_link(parent, la, lb);
-    }
-}
-
-__global__ void k_forest_flatten(const uint32_t *parent, uint32_t *label, unsigned long long *best_w, unsigned long long *best_rc, uint32_t n)
-{
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        label[i] = p_settled_root(parent, i);
-        best_w[i] = kDead;
-        best_rc[i] = kDead;
-    }
-}
 
 // sort keys of the forest records: pass 0 row << 32 | col, pass 1 w (the radix sort is stable)
 __global__ void k_forest_sort_keys(const rk_hit *forest, unsigned long long n, int metric, int pass, unsigned long long *keys)
@@ -127,20 +52,6 @@ __global__ void k_forest_sort_keys(const rk_hit *forest, unsigned long long n, i
     long long c, u;
     ratio_terms(h.common, h.size0, h.size1, metric, &c, &u);
     keys[i] = ~ratio_key((unsigned long long)c, (unsigned long long)u);   // (only records k_edge_keys gave a key are here)
-}
-
-// Kruskal over edges that are in order already: the accepted ones, in order, compacted to the front.  Returns their number.
-uint64_t kruskal_sorted(rk_hit *e, uint64_t m, uint32_t n)
-{
-    std::vector<uint32_t> parent(n);
-    std::iota(parent.begin(), parent.end(), 0u);
-    uint64_t k = 0;
-    for (uint64_t i = 0; i < m; i++)
-        if (host_union(parent.data(), e[i].row, e[i].col)) {
-            if (k != i) e[k] = e[i];
-            k++;
-        }
-    return k;
 }
 
 bool edges_within(const rk_hit *e, uint64_t m, uint32_t n)

@@ -8,6 +8,7 @@
 //             row << 32 | col; a BORDERLINE record and a record outside 0 < common <= u -- multisets: no key -- go to the small host
 //             buffer and are dead on the device), the two retries;
 //   degree    k_edge_degree: per live record one atomicAdd on deg[row] and one on deg[col] -- behind the stage, whose pass may run twice;
+//   (offsets, fill and the selection's body: rk_knn_select.h, shared with rk_mreach.hip)
 //   offsets   k_knn_offsets writes min(deg, k) and the largest degree; two exclusive scans give the adjacency offsets aoff[] and the
 //             output offsets koff[] (N + 1 words each);
 //   fill      k_knn_fill: per live record and endpoint v the 16-byte entry {w, other << 32 | e} at aoff[v] + atomicAdd(cur + v, 1).
@@ -35,106 +36,23 @@
 #include "rk_dist_plan.h"
 #include "rk_edge_order.h"
 #include "rk_edge_stage.h"
+#include "rk_knn_select.h"
 
 namespace {
 
-constexpr uint32_t kKnnDeviceMax = 64;   // one list slot per lane of a wave64
-constexpr uint32_t kWave = 64;
-
-struct __align__(16) KnnEntry {
-    unsigned long long w, x;   // ~ratio key; neighbour << 32 | record number
-};
-
-// kmin[i] = min(deg[i], k); deg[N] is 0 (the scans then end in the totals); *max_deg: one atomic per wave
-__global__ void __launch_bounds__(kStageThreads)
-k_knn_offsets(const uint32_t *deg, uint32_t *kmin, uint32_t n, uint32_t k, uint32_t *max_deg)
-{
-    uint32_t most = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) {
-        const uint32_t d = deg[i];
-        kmin[i] = min(d, k);
-        most = max(most, d);
-    }
-    for (int d = warpSize / 2; d > 0; d >>= 1) most = max(most, (uint32_t)__shfl_down(most, d));
-    if ((threadIdx.x & (warpSize - 1)) == 0 && most) atomicMax(max_deg, most);
-}
-
-// aoff[v] + cur[v] stays below aoff[v + 1]: the degree pass counted the same live records
-__global__ void __launch_bounds__(kStageThreads)
-k_knn_fill(const unsigned long long *w, const unsigned long long *rc, unsigned long long n_rec, const uint32_t *aoff, uint32_t *cur, KnnEntry *adj)
-{
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_rec; e += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned long long we = w[e];
-        if (we == kDead) continue;
-        const unsigned long long p = rc[e];
-        const uint32_t a = (uint32_t)(p >> 32), b = (uint32_t)p;
-        adj[(unsigned long long)aoff[a] + atomicAdd(cur + a, 1u)] = KnnEntry{we, ((unsigned long long)b << 32) | e};
-        adj[(unsigned long long)aoff[b] + atomicAdd(cur + b, 1u)] = KnnEntry{we, ((unsigned long long)a << 32) | e};
-    }
-}
-
-__device__ __forceinline__ bool entry_less(unsigned long long aw, unsigned long long ax, unsigned long long bw, unsigned long long bx)
-{
-    return aw < bw || (aw == bw && ax < bx);
-}
-
-// the value lane `src` holds, src the same in every lane: two scalar reads, nothing through the LDS crossbar
-__device__ __forceinline__ unsigned long long lane_value(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// 1 <= k <= 64.  Everything the loops branch on is the same in all lanes of a wave (aoff[v], ballots, broadcasts).
+// 1 <= k <= 64: the selection of rk_knn_select.h, then lane l < min(deg, k) writes the record of its entry
 __global__ void __launch_bounds__(kStageThreads)
 k_knn_select(const KnnEntry *adj, const uint32_t *aoff, const uint32_t *koff, const rk_hit *hits, uint32_t n, uint32_t k, rk_hit *out)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t n_waves = (gridDim.x * blockDim.x) / kWave;
-    const int kth = (int)k - 1;
     for (uint32_t v = (blockIdx.x * blockDim.x + threadIdx.x) / kWave; v < n; v += n_waves) {
         const unsigned long long beg = aoff[v], end = aoff[v + 1];
-        unsigned long long bw = kDead, bx = kDead;   // lane l: the l-th best entry so far
-        for (unsigned long long at = beg; at < end; at += kWave) {
-            unsigned long long cw = kDead, cx = kDead;
-            if (at + lane < end) {
-                const KnnEntry c = adj[at + lane];
-                cw = c.w;
-                cx = c.x;
-            }
-            unsigned long long mask = __ballot(entry_less(cw, cx, lane_value(bw, kth), lane_value(bx, kth)));
-            while (mask) {
-                const int src = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const unsigned long long sw = lane_value(cw, src), sx = lane_value(cx, src);
-                if (!entry_less(sw, sx, lane_value(bw, kth), lane_value(bx, kth))) continue;   // an earlier survivor tightened the k-th
-                const uint32_t rank = (uint32_t)__popcll(__ballot(entry_less(bw, bx, sw, sx)));   // < k: lane k - 1 does not precede it
-                const unsigned long long uw = __shfl_up(bw, 1), ux = __shfl_up(bx, 1);
-                if (lane < k && lane >= rank) {
-                    bw = lane == rank ? sw : uw;
-                    bx = lane == rank ? sx : ux;
-                }
-            }
-        }
+        unsigned long long bw, bx;
+        knn_select_wave(adj, beg, end, lane, k, &bw, &bx);
         if (lane < min((unsigned long long)k, end - beg)) out[koff[v] + lane] = hits[(uint32_t)bx];
     }
 }
-
-inline uint32_t other_end(const rk_hit &h, uint32_t v) { return h.row == v ? h.col : h.row; }
-
-// the order of genome v's list: EdgeLess with the endpoint v fixed -- ratio first, then the neighbour's index
-struct NeighbourLess {
-    int metric;
-    uint32_t v;
-    bool operator()(const rk_hit &a, const rk_hit &b) const
-    {
-        rk_hit x = a, y = b;
-        x.row = y.row = 0;
-        x.col = other_end(a, v);
-        y.col = other_end(b, v);
-        return EdgeLess{metric}(x, y);
-    }
-};
 
 // `pool` (records incident to v, any order) -> its first k in the order, one record per neighbour
 void first_k(std::vector<rk_hit> *pool, uint32_t v, uint64_t k, int metric)

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <cstdarg>
@@ -1211,7 +1212,7 @@ static void build_everywhere(GpuSet &set, const SketchSet &s, const string &path
     on_every_gpu(G, [&](size_t g) { idx[g] = build_index(set[g], s, path, g == 0 && write_files); });
 }
 
-// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn, dbscan): the common arguments, the input (a .sketch file, or a
+// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn, dbscan, mreach): the common arguments, the input (a .sketch file, or a
 // genome list that is sketched first), the index on every GPU of the set (the sharded build where it applies, the whole index
 // everywhere otherwise), the reference's phase lines around them and the way out.
 struct SelfJoin {
@@ -1620,6 +1621,81 @@ static int cmd_dbscan(const Args &a)
     j.leave();
 }
 
+// mreach: the minimum spanning forest of alldist's pairs under mutual-reachability distance -- the HDBSCAN* hierarchy up to -D
+// (rk_mreach_rows; the core distance of a genome is the distance of its (minPts - 1)-th nearest pair within -D, the weight of a pair the
+// largest of its own distance and its two genomes' core distances), one forest line per edge in forest order -- lightest first, ties by
+// exact ratio, then by the genomes' indices -- with the mutual-reachability distance as a last column.  --core: one line per genome,
+// name, core distance (- when the genome has fewer than minPts - 1 pairs), the name of the neighbour that sets it (- when none).
+// --cut t --labels FILE: the forest cut at t (rk_mreach_cut) in the layout of cluster, clusters numbered from 1 by their smallest core
+// genome, the genomes that are not core at t last, as cluster 0 of size 0.
+static int cmd_mreach(const Args &a)
+{
+    SelfJoin j(a, "mreach", true);
+    if (a.num("gpus", 1) > 1) die("command_mreach(), mreach runs on one GPU: the core distances do not compose from the shards of several (--gpus 1)");
+    if (!a.has("m") || a.num("m", 0) < 1) die("command_mreach(), minPts must be >= 1\nUse -m to set the minPts (it counts the genome itself)");
+    if (a.has("cut") != a.has("labels")) die("command_mreach(), --cut t and --labels FILE go together");
+    const double cut = a.real("cut", 0.0);
+    if (a.has("cut") && !(cut >= 0.0 && cut <= j.max_dist)) die("command_mreach(), --cut must lie between 0 and maxDist: the forest holds the hierarchy up to -D");
+    const uint32_t min_pts = (uint32_t)a.num("m", 1);
+    j.prepare(1, false);
+    const size_t N = j.N;
+    vector<double> core_dist(N ? N : 1);
+    vector<uint32_t> core_nb(N ? N : 1);
+    rk_hit *edges = nullptr;
+    uint64_t n_edges = 0;
+    rk_mreach_stats stats{};
+    const rk_dist_opts o = j.opts(0);
+    j.gpu(0).check(rk_mreach_rows(j.gpu(0).ctx, j.idx[0], &o, min_pts, core_dist.data(), core_nb.data(), &edges, &n_edges, &stats), "rk_mreach_rows");
+    j.phase_done("mutual-reachability forest on the host", "mutual-reachability forest");
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
+    vector<char> buf(1 << 16);
+    for (uint64_t k = 0; k < n_edges; k++) {
+        const rk_hit &h = edges[k];
+        const string &x = j.s.names[h.col], &y = j.s.names[h.row];   // (the order of an alldist line, src/dist.cpp:233)
+        if (x.size() + y.size() + 128 > buf.size()) die("genome name too long");
+        const int len = rk_format_hit(buf.data(), buf.size(), x.c_str(), y.c_str(), &h);
+        if (len < 1) die("rk_format_hit failed");
+        fwrite(buf.data(), 1, (size_t)len - 1, fp);   // (without its newline)
+        fprintf(fp, "\t%f\n", std::max(h.dist, std::max(core_dist[h.row], core_dist[h.col])));
+    }
+    fclose(fp);
+    if (a.has("core")) {
+        FILE *cp = fopen(a.str("core", "").c_str(), "w");
+        if (!cp) die("cannot write %s", a.str("core", "").c_str());
+        for (size_t i = 0; i < N; i++) {
+            if (std::isinf(core_dist[i])) fprintf(cp, "%s\t-\t", j.s.names[i].c_str());
+            else fprintf(cp, "%s\t%f\t", j.s.names[i].c_str(), core_dist[i]);
+            fprintf(cp, "%s\n", core_nb[i] == RK_MREACH_NONE ? "-" : j.s.names[core_nb[i]].c_str());
+        }
+        fclose(cp);
+    }
+    if (a.has("cut")) {
+        vector<uint32_t> label(N ? N : 1);
+        if (rk_mreach_cut(edges, n_edges, core_dist.data(), (uint32_t)N, cut, label.data()) != 0) die("rk_mreach_cut failed");
+        vector<uint32_t> number(N, 0), size(N, 0);
+        uint32_t n_clusters = 0;
+        for (size_t i = 0; i < N; i++)
+            if (label[i] != RK_DBSCAN_NOISE) size[label[i]]++;
+        for (size_t l = 0; l < N; l++)
+            if (size[l]) number[l] = ++n_clusters;
+        vector<vector<uint32_t>> members(N);   // (a label is its cluster's smallest genome: by label, then by index, is two ascending walks)
+        for (size_t i = 0; i < N; i++)
+            if (label[i] != RK_DBSCAN_NOISE) members[label[i]].push_back((uint32_t)i);
+        FILE *lp = fopen(a.str("labels", "").c_str(), "w");
+        if (!lp) die("cannot write %s", a.str("labels", "").c_str());
+        for (size_t l = 0; l < N; l++)
+            for (uint32_t i : members[l]) fprintf(lp, "%u\t%u\t%s\n", number[l], size[l], j.s.names[i].c_str());
+        for (size_t i = 0; i < N; i++)
+            if (label[i] == RK_DBSCAN_NOISE) fprintf(lp, "0\t0\t%s\n", j.s.names[i].c_str());
+        fclose(lp);
+    }
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %llu mutual-reachability edges (minPts = %u) over %zu genomes, %u with a core distance, from %llu hit records (%llu borderline), %u rounds, path %u\n",
+                (unsigned long long)n_edges, min_pts, N, stats.n_core, (unsigned long long)stats.edges, (unsigned long long)stats.borderline, stats.rounds, stats.path);
+    j.leave();
+}
+
 static int cmd_dist(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("dist needs -r and -q");
@@ -2000,7 +2076,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2009,6 +2085,7 @@ static int usage()
             "  greedy -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--reps FILE] [-L file.shuf] [--device N]   (greedy representatives of alldist's pairs: larger sketch first, a genome joins the nearest earlier representative within -D or becomes one; one GPU)\n"
             "  knn -i in.sketch|genomes.list -o out -N k [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (the k nearest neighbours of every genome among alldist's pairs: one alldist-format line per genome and neighbour, nearest first)\n"
             "  dbscan -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [-L file.shuf] [--device N]   (density-based clusters of alldist's pairs: a genome with minPts genomes, itself included, within -D is core; clusters are the components of the core genomes, a non-core genome joins its nearest core neighbour's cluster as border, the rest is noise; one GPU)\n"
+            "  mreach -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [--core FILE] [--cut t --labels FILE] [-L file.shuf] [--device N]   (minimum spanning forest of alldist's pairs under mutual-reachability distance, the HDBSCAN* hierarchy up to -D: one forest line per edge and its mutual-reachability distance; --core: every genome's core distance and the neighbour that sets it; --cut: the clusters of the core genomes at t <= maxDist, the rest as cluster 0; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -2029,7 +2106,7 @@ int main(int argc, char **argv)
         {"-n", "n"}, {"--leastNumKmer", "n"}, {"-Q", "Q"}, {"--leastQuality", "Q"}, {"-D", "D"}, {"--maxDist", "D"},
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
-        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}};
+        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2047,7 +2124,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2070,6 +2147,7 @@ int main(int argc, char **argv)
     if (sub == "greedy") { cerr << "-----run the subcommand: greedy" << endl; return leave(cmd_greedy(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "knn") { cerr << "-----run the subcommand: knn" << endl; return leave(cmd_knn(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dbscan") { cerr << "-----run the subcommand: dbscan" << endl; return leave(cmd_dbscan(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "mreach") { cerr << "-----run the subcommand: mreach" << endl; return leave(cmd_mreach(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
