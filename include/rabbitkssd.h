@@ -279,6 +279,50 @@ int rk_index_hash_bits(const rk_index *idx);
 /* 1 when rk_index_build took its bucket-sort path (set sketches with 32-bit hashes whose buckets fit the LDS sort),
  * 0 for the general path (device-wide radix sort) or an imported index: lets a harness say which build it timed. */
 int rk_index_built_fast(const rk_index *idx);
+/* Which build rk_index_build / rk_index_build_shard WOULD run for these sketches, under the developer switches of the context
+ * and of the environment as they are now: the knobs, the build's plan and the plan of its first bucket-sort attempt -- host
+ * arithmetic alone, nothing is launched or allocated.  Returns what the plan returns (its refusals included: out[] is then
+ * untouched) and writes RK_PLAN_WORDS words.  A build may still end elsewhere -- its kernels raise flags, attempts are
+ * repeated --: rk_index_build_report says how it did end.  For tests and harnesses (which kernels did I time?). */
+enum {
+    RK_PLAN_FAST_OK = 0,   /* the bucket sort is tried at all (else: the general path, a device-wide radix sort)        */
+    RK_PLAN_TILES_MODE,    /* its first attempt emits tile records (else slice records)                                 */
+    RK_PLAN_SLICES_OK,     /* the key fields and sizes admit slice records                                              */
+    RK_PLAN_TILES_OK,      /* ... tile records                                                                          */
+    RK_PLAN_B,             /* bucket bits                                                                               */
+    RK_PLAN_LOW_BITS,      /* hash bits below the bucket                                                                */
+    RK_PLAN_GB,            /* genome bits of a key                                                                      */
+    RK_PLAN_RB,            /* position bits of a key (slice records)                                                    */
+    RK_PLAN_N_PASS,        /* range passes over the hash space                                                          */
+    RK_PLAN_RANGE_BITS,    /* top hash bits that select a range (shards and passes)                                     */
+    RK_PLAN_PART2,         /* the two-pass partition (coarse + fine) instead of the one scattering pass                 */
+    RK_PLAN_USE_FILTER,    /* a range pass partitions a filtered copy of its hashes                                     */
+    RK_PLAN_SMALL_WGS,     /* the coarse pass in four workgroups of 256 threads per chunk (else one of 1,024)           */
+    RK_PLAN_NARROW,        /* (hash_low, genome) sort keys of 32 bits (else 64)                                         */
+    RK_PLAN_BIG_OK,        /* buckets beyond the in-LDS sort are built slab by slab instead of refusing the bucket sort */
+    RK_PLAN_RELABEL,       /* the genomes are renumbered (rk_index_order)                                               */
+    RK_PLAN_TWO_STREAMS,   /* ... on a stream of its own                                                                */
+    RK_PLAN_EMIT_T,        /* threads per bucket of the emission, as dispatched: 256, 512 or 1024                       */
+    RK_PLAN_KEYS_CAP,      /* keys the buffers of a pass hold                                                           */
+    RK_PLAN_REC_CAP,       /* unsorted tile records the first attempt has room for (0: slice records)                   */
+    RK_PLAN_WORDS
+};
+int rk_index_build_plan(rk_ctx *ctx, const rk_sketches *sketches, int hash_bits, uint32_t shard, uint32_t n_shards, int64_t out[]);
+/* How the build of this index ended: all zeros for an index that was imported, unpacked, broadcast or joined from a shard's
+ * records.  Host bookkeeping of rk_index_build, no device work. */
+enum {
+    RK_REPORT_ATTEMPTS = 0,  /* attempts of the bucket sort (0: the plan went straight to the general path)              */
+    RK_REPORT_KEY_RETRIES,   /* of which repeated because a range pass held more keys than its buffers                   */
+    RK_REPORT_REC_RETRIES,   /* ... because the tile records did not fit                                                 */
+    RK_REPORT_FELL_BACK,     /* 1: tile records were given up for slice records                                          */
+    RK_REPORT_GENERAL,       /* 1: the general path built the index                                                      */
+    RK_REPORT_FLAGS,         /* what the kernels of the last attempt raised: 1 a bucket or a pass beyond its buffer, 2 a
+                                hash outside the hash space                                                              */
+    RK_REPORT_HEAVY,         /* buckets the last attempt left to the slab-by-slab kernel, summed over its passes         */
+    RK_REPORT_PASSES,        /* passes of the last attempt                                                               */
+    RK_REPORT_WORDS
+};
+int rk_index_build_report(const rk_index *idx, uint64_t out[8]);
 /* Which structures of the all-vs-all join the index carries right now, as a bit mask: 1 = slice records (one per (genome,
  * hash) element: rk_near_kernel, rk_dist_kernel), 2 = tile records (one per posting list and pair of 32-genome blocks it
  * touches: rk_tile_kernel), 4 = the tile records came with rk_index_build itself (collections of RK_DIST_TILES_MIN_GENOMES =

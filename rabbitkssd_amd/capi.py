@@ -26,12 +26,17 @@ EXPORTS = [
     "rk_sketches_from_host", "rk_sketches_from_host64", "rk_sketches_download64", "rk_sketches_is64", "rk_sketches_from_dev", "rk_sketches_count", "rk_sketches_total", "rk_sketches_windows",
     "rk_sketches_download", "rk_sketches_hashes_dev", "rk_sketches_off_dev", "rk_sketches_free",
     "rk_index_build", "rk_index_import", "rk_index_export", "rk_index_export_lists", "rk_index_import64", "rk_index_export64", "rk_index_total",
-    "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
+    "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_build_plan", "rk_index_build_report", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
 ]
+
+# the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
+PLAN_WORDS = ("fast_ok", "tiles_mode", "slices_ok", "tiles_ok", "B", "low_bits", "gb", "rb", "n_pass", "range_bits", "part2", "use_filter",
+              "small_wgs", "narrow", "big_ok", "relabel", "two_streams", "emit_t", "keys_cap", "rec_cap")
+REPORT_WORDS = ("attempts", "key_retries", "rec_retries", "fell_back", "general", "flags", "heavy", "passes")
 
 DBSCAN_NOISE = 0xFFFFFFFF   # RK_DBSCAN_NOISE: label and via of a noise genome
 DBSCAN_KINDS = ("noise", "border", "core")   # kind 0, 1, 2
@@ -354,6 +359,15 @@ class Context:
         self.check(lib().rk_index_build(self._h, sketches._h, int(hash_bits_), C.byref(h)))
         return Index(self, h)
 
+    def index_build_plan(self, sketches, hash_bits_, shard=0, n_shards=1):
+        """which build index_build / index_build_shard would run now, as a dict of PLAN_WORDS (rk_index_build_plan: host arithmetic,
+        nothing is launched); raises what the build's plan refuses"""
+        out = (C.c_int64 * len(PLAN_WORDS))()
+        L = lib()
+        L.rk_index_build_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64)]
+        self.check(L.rk_index_build_plan(self._h, sketches._h, int(hash_bits_), int(shard), int(n_shards), out))
+        return {name: int(v) for name, v in zip(PLAN_WORDS, out)}
+
     def index_build_shard(self, sketches, hash_bits_, shard, n_shards):
         """the lists of hash range `shard` of `n_shards` + their tile records grouped by destination shard (rk_index_build_shard)"""
         h = C.c_void_p()
@@ -621,6 +635,15 @@ class Index(_Obj):
         return bool(lib().rk_index_built_fast(self._h))
 
     @property
+    def build_report(self):
+        """how the build of this index ended, as a dict of REPORT_WORDS (rk_index_build_report); zeros for an index not built here"""
+        out = (C.c_uint64 * len(REPORT_WORDS))()
+        L = lib()
+        L.rk_index_build_report.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self.ctx.check(L.rk_index_build_report(self._h, out))
+        return {name: int(v) for name, v in zip(REPORT_WORDS, out)}
+
+    @property
     def products(self):
         """bit mask: 1 slice records, 2 tile records, 4 the tile records came with rk_index_build (rk_index_products)"""
         return int(lib().rk_index_products(self._h))
@@ -688,6 +711,15 @@ class Index(_Obj):
         hashes = np.zeros(self.distinct, dtype=np.uint64)
         counts = np.zeros(self.distinct, dtype=np.uint32)
         self.ctx.check(lib().rk_index_export64(self._h, _ptr(postings), _ptr(hashes), _ptr(counts)))
+        return postings, hashes, counts
+
+    def export_lists(self):
+        """(postings u32[H], hashes u32[U] ascending, counts u32[U]) of an index of 32-bit hashes: the .dict/.index content without
+        the dense array of 2^hash_bits counts (rk_index_export_lists)"""
+        postings = np.zeros(self.total, dtype=np.uint32)
+        hashes = np.zeros(self.distinct, dtype=np.uint32)
+        counts = np.zeros(self.distinct, dtype=np.uint32)
+        self.ctx.check(lib().rk_index_export_lists(self._h, _ptr(postings), _ptr(hashes), _ptr(counts)))
         return postings, hashes, counts
 
     def export(self, want_counts=True):

@@ -1248,6 +1248,8 @@ struct AttemptOutcome {
         Refused             // the kernels raised `flags`, or (flags == 0) the tile records overflowed with no way on: the general path decides
     } what;
     unsigned long long need, flags;
+    unsigned long long heavy;   // buckets the attempt handed to k_bucket_heavy, summed over its passes
+    uint32_t passes;
     BuildResult r;
     TileResult tr;
 };
@@ -1303,13 +1305,22 @@ int bucket_sort_attempt(const BuildCtx &b, Renumbering &rn, const RetryState &rs
     RK_HIP(ctx, hipGetLastError());
     RK_TRY(rn.join());
     unsigned long long n_postings = 0;
-    {   // the one synchronisation of the build: both result records (and the postings of all passes) in one read-back
-        struct { BuildResult r; TileResult t; unsigned long long pass_base[257]; } both;
+    {   // the one synchronisation of the build: both result records, the postings of all passes and -- they lie directly behind, for
+        // rk_index_build_report -- the passes' counts of buckets for k_bucket_heavy (n_big[]) in one read-back
+        struct { BuildResult r; TileResult t; unsigned long long pass_base[257 + 128]; } both;
         static_assert(sizeof(BuildResult) % 8 == 0 && offsetof(decltype(both), pass_base) == sizeof(BuildResult) + sizeof(TileResult), "the records lie back to back");
-        RK_TRY(rk_read_back(ctx, &both, fres, sizeof(BuildResult) + sizeof(TileResult) + ((size_t)a.passes + 1) * 8, st));
+        const size_t big_at = m.z.z_big - m.z.z_pass, words = m.z.z_filt - m.z.z_pass;   // (ZeroedLayout: passes + 1 words, then a u32 per pass; at most 256 passes)
+        RK_TRY(rk_read_back(ctx, &both, fres, sizeof(BuildResult) + sizeof(TileResult) + words * 8, st));
         o->r = both.r;
         o->tr = both.t;
         n_postings = both.pass_base[a.passes];
+        o->heavy = 0;
+        o->passes = a.passes;
+        for (uint32_t pass = 0; pass < a.passes; pass++) {
+            uint32_t n_big;
+            memcpy(&n_big, reinterpret_cast<const char *>(&both.pass_base[big_at]) + (size_t)pass * 4, 4);
+            o->heavy += n_big;
+        }
     }
     const BuildResult &r = o->r;
     const TileResult &tr = o->tr;
@@ -1471,18 +1482,30 @@ int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_
     AttemptOutcome o;
     memset(&o, 0, sizeof o);
     o.what = AttemptOutcome::Refused;
+    uint64_t *const rep = idx->build_report;   // rk_index_build_report
     for (bool again = p.fast_ok(); again;) {
         RK_TRY(bucket_sort_attempt(b, rn, rs, &o));
+        rep[RK_REPORT_ATTEMPTS]++;
         switch (o.what) {
-        case AttemptOutcome::RetryKeysCap: rs.keys_cap_retry = o.need + o.need / 64 + 65536; break;
-        case AttemptOutcome::RetryRecCap: rs.rec_cap_retry = o.need; break;
+        case AttemptOutcome::RetryKeysCap:
+            rs.keys_cap_retry = o.need + o.need / 64 + 65536;
+            rep[RK_REPORT_KEY_RETRIES]++;
+            break;
+        case AttemptOutcome::RetryRecCap:
+            rs.rec_cap_retry = o.need;
+            rep[RK_REPORT_REC_RETRIES]++;
+            break;
         case AttemptOutcome::FallBackToSlices:
             rs.tiles_mode = false;
             drop_blk_min(ctx, idx);
+            rep[RK_REPORT_FELL_BACK] = 1;
             break;
         default: again = false;
         }
     }
+    rep[RK_REPORT_FLAGS] = o.flags;
+    rep[RK_REPORT_HEAVY] = o.heavy;
+    rep[RK_REPORT_PASSES] = o.passes;
     const bool built = o.what == AttemptOutcome::Built;
     if (!built && p.from_keys && (o.flags & kFastBadHash))
         return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_shard_keys: a key outside the wire format (hash bits beyond the shard's range, or a genome id >= %u)", p.N);
@@ -1497,8 +1520,10 @@ int index_build_impl(rk_ctx *ctx, const BuildSource &src, int hash_bits, uint32_
     RK_TRY(rn.enqueue(false));
     RK_TRY(rn.join());
     BuildResult r = built ? o.r : BuildResult{0, 0, 0, 0, 0};
-    if (!built && p.H) RK_TRY(build_general(b, res.p, &r));
-    else if (!p.H) RK_TRY(build_empty(b));
+    if (!built && p.H) {
+        RK_TRY(build_general(b, res.p, &r));
+        rep[RK_REPORT_GENERAL] = 1;
+    } else if (!p.H) RK_TRY(build_empty(b));
     idx->U = r.U;
     idx->n_self = r.n_self;
     idx->slices_refused = p.no_self;
@@ -1686,6 +1711,12 @@ uint64_t rk_index_distinct(const rk_index *idx) { return idx ? idx->U : 0; }
 uint32_t rk_index_genomes(const rk_index *idx) { return idx ? idx->n_ref : 0; }
 int rk_index_hash_bits(const rk_index *idx) { return idx ? idx->hash_bits : 0; }
 int rk_index_built_fast(const rk_index *idx) { return idx && idx->built_fast ? 1 : 0; }
+int rk_index_build_report(const rk_index *idx, uint64_t out[8])
+{
+    if (!idx || !out) return RK_ERR_ARG;
+    for (int i = 0; i < RK_REPORT_WORDS; i++) out[i] = idx->build_report[i];
+    return RK_OK;
+}
 int rk_index_products(const rk_index *idx)
 {
     if (!idx) return 0;
@@ -1754,6 +1785,41 @@ int rk_index_build(rk_ctx *ctx, const rk_sketches *s, int hash_bits, rk_index **
 {
     if (!ctx || !s || !out) return RK_ERR_ARG;
     return settle_streams(ctx, index_build_impl(ctx, source_of(s), hash_bits, 0, 1, out));
+}
+
+int rk_index_build_plan(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint32_t shard, uint32_t n_shards, int64_t out[])
+{
+    if (!ctx) return RK_ERR_ARG;
+    if (!n_shards || n_shards > kRecRegions || (n_shards & (n_shards - 1)) || shard >= n_shards)
+        return rk_fail(ctx, RK_ERR_ARG, "rk_index_build_plan: %u shards (a power of two up to %u), shard %u", n_shards, kRecRegions, shard);
+    if (!s || !out) return RK_ERR_ARG;
+    // exactly what index_build_impl decides before its first launch: the knobs, the plan, the first attempt's plan
+    const BuildKnobs k = read_knobs();
+    BuildPlan p;
+    RK_TRY(plan_build(ctx, source_of(s), hash_bits, shard, n_shards, k, &p));
+    AttemptPlan a;
+    RK_TRY(plan_attempt(ctx, p, k, RetryState{p.tiles_mode}, &a));
+    out[RK_PLAN_FAST_OK] = p.fast_ok();
+    out[RK_PLAN_TILES_MODE] = p.tiles_mode;
+    out[RK_PLAN_SLICES_OK] = p.slices_ok;
+    out[RK_PLAN_TILES_OK] = p.tiles_ok;
+    out[RK_PLAN_B] = p.B;
+    out[RK_PLAN_LOW_BITS] = p.low_bits;
+    out[RK_PLAN_GB] = p.gb;
+    out[RK_PLAN_RB] = p.rb;
+    out[RK_PLAN_N_PASS] = p.n_pass;
+    out[RK_PLAN_RANGE_BITS] = p.range_bits;
+    out[RK_PLAN_PART2] = a.part2;
+    out[RK_PLAN_USE_FILTER] = a.use_filter;
+    out[RK_PLAN_SMALL_WGS] = a.small_wgs;
+    out[RK_PLAN_NARROW] = a.narrow;
+    out[RK_PLAN_BIG_OK] = a.big_ok;
+    out[RK_PLAN_RELABEL] = p.relabel;
+    out[RK_PLAN_TWO_STREAMS] = p.two_streams;
+    out[RK_PLAN_EMIT_T] = with_emit_shape(k.emit_t, a.narrow, [](auto threads, auto) -> int { return decltype(threads)::value; });
+    out[RK_PLAN_KEYS_CAP] = (int64_t)a.keys_cap;
+    out[RK_PLAN_REC_CAP] = (int64_t)a.rec_cap;
+    return RK_OK;
 }
 
 int rk_index_build_shard(rk_ctx *ctx, const rk_sketches *s, int hash_bits, uint32_t shard, uint32_t n_shards, rk_index **out)

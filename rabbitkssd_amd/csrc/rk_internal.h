@@ -205,6 +205,7 @@ struct rk_index {
     uint32_t *d_orig = nullptr;      // u32[n_ref]
     bool relabeled = false;          // d_orig may differ from the identity
     bool built_fast = false;         // built by the bucket-sort path (rk_index_fast.inc)
+    uint64_t build_report[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // rk_index_build_report (RK_REPORT_*): how index_build_impl got there; zeros for an index that was not built here
     uint32_t *d_fb = nullptr;        // fallback list of the near-window self join (rk_dist_near.inc): [0] count, [1] done, [4..] rows;
                                      // allocated on first use; one self join per index in flight at a time
     uint32_t *h_fb_seen = nullptr;   // page-locked host word: rows the last fallback launch found in the list (a hint for the next

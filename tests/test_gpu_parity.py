@@ -608,6 +608,8 @@ def test_a_range_with_more_keys_than_estimated_is_built_again(monkeypatch):
     sk = c.sketches_from_host(h, off)
     idx = c.index_build(sk, 26)
     assert idx.built_fast and idx.products == 6 and idx.total == len(h)
+    report = idx.build_report
+    assert (report["attempts"], report["key_retries"], report["rec_retries"], report["fell_back"], report["general"]) == (2, 1, 0, 0, 0)
     p2, c2 = idx.export()
     assert np.array_equal(p2, postings) and np.array_equal(c2, counts)
     assert_hits_equal(c.dist_rows(idx, None, 1, 0, 20, 0.05)[0], want)
@@ -637,6 +639,7 @@ def test_buckets_beyond_the_lds_sort(monkeypatch, bits, n, m, strains):
     idx = c.index_build(sk, bits)
     old = g.index_build(g.sketches_from_host(h, off), bits)
     assert idx.built_fast and idx.products == 6 and not old.built_fast
+    assert idx.build_report["heavy"] > 0 and idx.build_report["general"] == 0 and old.build_report["general"] == 1
     p2, c2 = idx.export()
     assert np.array_equal(p2, postings) and np.array_equal(c2, counts)
     assert np.array_equal(idx.order, old.order)
@@ -667,6 +670,8 @@ def test_tile_records_that_do_not_fit_fall_back_to_slice_records(monkeypatch):
     c = capi.Context(0)
     idx = c.index_build(c.sketches_from_host(h, off), 26)
     assert idx.products == 1 and idx.built_fast
+    report = idx.build_report
+    assert (report["attempts"], report["rec_retries"], report["fell_back"], report["general"]) == (2, 0, 1, 0)
     p2, c2 = idx.export()
     assert np.array_equal(p2, postings) and np.array_equal(c2, counts)
     assert_hits_equal(c.dist_rows(idx, None, 1, 0, 20, 0.05)[0], want)
