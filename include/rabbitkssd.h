@@ -27,6 +27,9 @@
  *                             1996; min_pts as scikit-learn's min_samples; the reference itself has no clustering)
  *   rk_mreach_rows         <- the same row loop, followed by the mutual-reachability spanning forest of HDBSCAN* its users
  *                             build over the printed pairs (Campello, Moulavi & Sander 2013)
+ *   rk_medoid_rows         <- the same row loop, followed by what its users compute per cluster of any of the above from the
+ *                             printed pairs: the most central member (the representative dRep, GTDB and galah print), the
+ *                             cluster's density and weakest pair, every genome's nearest genome outside its cluster
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -120,6 +123,8 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 #define RK_MS_DBSCAN 9
 /* rk_mreach_rows with timing on: degree pass through the last Boruvka round of the last call (0 when the call took the host path). */
 #define RK_MS_MREACH 10
+/* rk_medoid_rows with timing on: sums sweep through gather kernel of the last call (0 when the call took the host path). */
+#define RK_MS_MEDOID 11
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -800,6 +805,92 @@ int rk_mreach_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, uint32_t min
  * the forest does not hold the edges that would assign it.  The core genomes and their labels are those of rk_dbscan_rows at t with the
  * same min_pts.  (At t = 0 no genome is core, whatever min_pts: no distance lies below 0.)  RK_ERR_ARG for an edge that names a genome >= n or null pointers (edges may be NULL when n_edges == 0). */
 int rk_mreach_cut(const rk_hit *edges, uint64_t n_edges, const double *core_dist /* n */, uint32_t n, double t, uint32_t *labels_out /* n */);
+
+/* ---- medoids and census of a clustering --------------------------------------------- */
+/* What a user does next with the labels of rk_cluster_rows, rk_dbscan_rows, rk_forest_cut, rk_mreach_cut or rep_out of rk_greedy_rows:
+ * pick a representative by centrality (the member with the highest summed similarity to its fellow members, as dRep, GTDB and galah
+ * print it) and check the clustering (how dense a cluster is, its weakest pair, every genome's nearest genome outside its cluster).
+ * All of it is sums and extrema over the hit records, grouped by a label array of N words.
+ * Graph.  The graph of rk_cluster_rows: its edges are the pairs rk_dist_rows(ctx, idx, NULL, opts, ...) would report -- same metric, same
+ * strict threshold (dist < max_dist decided with the C library's log), same row_first / row_step / row_block selection, any index that
+ * call accepts, the join-only index of rk_index_join_shard included.
+ * Labels.  labels[v] (host, rk_index_genomes(idx) = N entries in the caller's genome order): a value below N names v's cluster -- it
+ * need not be a member of that cluster --, RK_MEDOID_NONE (the value of RK_DBSCAN_NOISE) means v is unlabelled; anything else is
+ * RK_ERR_ARG.  The outputs of the five calls above are all of this form.
+ * Inside and leaving.  A record (a, b) is INSIDE iff labels[a] == labels[b] != RK_MEDOID_NONE; otherwise it is LEAVING, for both of its
+ * ends.  An unlabelled genome has only leaving records.
+ * Similarity term.  q(e) = floor(common * 2^32 / u), u as in rk_forest_rows (size0 + size1 - common for metric 0, min(size0, size1) for
+ * metric 1): the jaccard or containment of the record in 32 fractional bits, exact for 0 < common <= u < 2^31.  q <= 2^32, a genome has
+ * fewer than N records and N <= 2^31 is required (RK_ERR_UNSUPPORTED beyond): a genome's sum stays below 2^63.
+ * Per genome v.  in_deg[v] and out_deg[v]: the inside and the leaving records incident to v.  central[v]: the sum of q over v's inside
+ * records -- a pair beyond -D is not reported and contributes 0.  far_in[v]: the inside record incident to v with the SMALLEST ratio
+ * common / u, compared exactly (25/75 ties 20/60); ties go to the smaller neighbour index.  near_out[v]: the leaving record incident to v
+ * with the LARGEST ratio; ties go to the smaller neighbour index -- the first leaving record of v in the order of rk_knn_rows.  The two
+ * record arrays are optional.  Each entry is the hit record as the join reports it (row < col, pad_ 0), jorc and dist recomputed on the
+ * host with the C library's log -- the reference's values bit for bit; an absent record has row = col = RK_MEDOID_NONE and zeros
+ * elsewhere.  The result is unique: it does not depend on the order of hits, the internal genome order, the join kernel or the sharding.
+ * "Medoid" here MAXIMISES SUMMED SIMILARITY over the reported pairs; it does not minimise summed distance.  An unreported pair has a
+ * bound on its similarity from above that is safe to sum (0 for a pair that shares nothing, below the ratio at -D otherwise: counted as
+ * 0) and no distance at all: a sum of distances over the reported pairs alone would favour the member with the FEWEST neighbours.
+ * Per non-empty cluster l (rk_medoid_pick, host work over the per-genome arrays).  size; in_edges: the sum of in_deg over the members,
+ * halved; medoid: the member with the largest central, ties to the smaller caller index (a singleton is its own medoid) and central:
+ * the medoid's; weakest_in: over the members' far_in the record with the smallest ratio, ties to the smaller (row, col); nearest_out:
+ * over the members' near_out the record with the largest ratio, ties to the smaller (row, col) -- both absent without the two record
+ * arrays.  Clusters come by ascending label in *out (library-allocated, rk_free_host; NULL when there is none).
+ * The hit records never leave the device (the frame of rk_dbscan_rows: the join through rk_dist_rows_dev with the threshold widened by
+ * 2^-46, the key pass with its small host buffer of RK_CLUSTER_EDGE_CAP borderline records and their slot numbers, both retries; the host
+ * decides the borderline records BEFORE anything is summed and sends the slot numbers of the kept ones back).  The labels go up once
+ * (4 * N bytes).  Then a sums sweep (per live record two label loads, integer atomic adds on both ends' degree and, inside, on central; a
+ * 64-bit atomic maximum of the weight key at both ends of an inside record, a 64-bit atomic minimum at both ends of a leaving one), a
+ * settle sweep (a 32-bit atomic minimum of the neighbour's index among the records that match a genome's extreme key) and a gather of
+ * the winning records; the last two are skipped when no record array is asked for.  One read-back of 16 * N bytes, 96 * N with the
+ * records, and the borderline records: never O(hits).
+ * Row shards and GPUs compose exactly (sums add, extrema of a union are extrema of the extrema): rk_medoid_merge folds the results of
+ * two DISJOINT record sets -- degrees and central add, far_in keeps the farther record and near_out the nearer in the orders above, an
+ * absent record loses; a record array is written only where both inputs and out have it; out may alias a.
+ * RK_MEDOID_DEVICE=0 answers inside the call as rk_dist_rows + rk_medoid_hits, with the same result.
+ * RK_ERR_ARG: triangle != 1, null pointers (labels, out, out->in_deg, out->out_deg, out->central), a label that is neither below N nor
+ * RK_MEDOID_NONE, a dense report (a threshold above 1.0), an index rk_dist_rows refuses for a self join.  RK_ERR_UNSUPPORTED: a sketch of
+ * 2^30 hashes or more (the key), what the join answers, and a record outside 0 < common <= u -- only sketches that repeat hashes
+ * produce such; q is not defined for them.  Nothing is written on a refusal.  An index without genomes: RK_OK, nothing runs.  stats is
+ * optional. */
+#define RK_MEDOID_NONE 0xFFFFFFFFu
+typedef struct rk_medoid_genomes {   /* the caller's arrays of n entries; far_in / near_out may be NULL */
+    uint32_t *in_deg, *out_deg;
+    uint64_t *central;
+    rk_hit *far_in, *near_out;
+} rk_medoid_genomes;
+typedef struct rk_medoid_cluster {
+    uint32_t label, size, medoid, pad_;
+    uint64_t in_edges, central;      /* inside records of the cluster; central[medoid] */
+    rk_hit weakest_in, nearest_out;
+} rk_medoid_cluster;                 /* 112 bytes */
+typedef struct rk_medoid_stats {
+    uint64_t edges;          /* hit records of the join */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint64_t inside;         /* records of the graph with both ends in one cluster */
+    uint64_t leaving;        /* the others */
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts; /* 2: the host buffer overflowed once */
+} rk_medoid_stats;           /* 48 bytes */
+int rk_medoid_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, const uint32_t *labels /* host, N */, rk_medoid_genomes *out,
+                   rk_medoid_stats *stats /* optional */);
+/* Host only: the same rule over a hit list the caller already has (`metric` as rk_dist_opts.metric; one record per pair, as a join
+ * reports them).  The two records of a genome are the caller's, unchanged but for their orientation: a record with row > col is returned
+ * as the pair (col, row), its sizes swapped with it.  RK_ERR_ARG when a record names a genome >= n or has row == col, for a label that is
+ * neither below n nor RK_MEDOID_NONE and for null pointers (hits may be NULL when n_hits == 0, everything but out when n == 0);
+ * RK_ERR_UNSUPPORTED for a record outside 0 < common <= u and for n above 2^31.  Nothing is written on a refusal. */
+int rk_medoid_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n, const uint32_t *labels /* n */, int metric, rk_medoid_genomes *out);
+/* Host only: folds the results of two disjoint record sets (row shards, GPUs) as described above.  RK_ERR_ARG for null pointers and for
+ * a present record that names a genome >= n, has row >= col or is not incident to the genome whose entry holds it.  Nothing is written
+ * on a refusal. */
+int rk_medoid_merge(const rk_medoid_genomes *a, const rk_medoid_genomes *b, uint32_t n, int metric, rk_medoid_genomes *out);
+/* Host only: the per-cluster records from the per-genome arrays, by ascending label.  g->far_in and g->near_out are needed for
+ * weakest_in and nearest_out alone: without BOTH arrays those two are absent.  RK_ERR_ARG for null pointers (labels and the arrays of g
+ * may be NULL when n == 0) and for a label that is neither below n nor RK_MEDOID_NONE. */
+int rk_medoid_pick(const uint32_t *labels /* n */, const rk_medoid_genomes *g, uint32_t n, int metric, rk_medoid_cluster **out,
+                   uint32_t *n_out);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

@@ -31,6 +31,7 @@ EXPORTS = [
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
+    "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -41,6 +42,10 @@ REPORT_WORDS = ("attempts", "key_retries", "rec_retries", "fell_back", "general"
 DBSCAN_NOISE = 0xFFFFFFFF   # RK_DBSCAN_NOISE: label and via of a noise genome
 DBSCAN_KINDS = ("noise", "border", "core")   # kind 0, 1, 2
 MREACH_NONE = 0xFFFFFFFF    # RK_MREACH_NONE: core_nb of a genome without a core record
+MEDOID_NONE = 0xFFFFFFFF    # RK_MEDOID_NONE: the label of an unlabelled genome, row and col of an absent record
+# rk_medoid_cluster: one record per non-empty cluster (medoid_pick)
+MEDOID_CLUSTER_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("medoid", "<u4"), ("pad", "<u4"), ("in_edges", "<u8"), ("central", "<u8"),
+                                 ("weakest_in", HIT_DTYPE), ("nearest_out", HIT_DTYPE)])
 
 
 class Params(C.Structure):
@@ -105,6 +110,17 @@ class MreachStats(C.Structure):
                 ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32), ("rounds", C.c_uint32),
                 ("n_trees", C.c_uint32), ("n_core", C.c_uint32), ("max_degree", C.c_uint32), ("path", C.c_uint32),
                 ("pad_", C.c_uint32)]
+
+
+class MedoidStats(C.Structure):
+    """rk_medoid_stats: what one rk_medoid_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64), ("inside", C.c_uint64),
+                ("leaving", C.c_uint64), ("join_attempts", C.c_uint32), ("border_attempts", C.c_uint32)]
+
+
+class MedoidGenomes(C.Structure):
+    """rk_medoid_genomes: the caller's per-genome arrays; far_in / near_out may be null"""
+    _fields_ = [("in_deg", C.c_void_p), ("out_deg", C.c_void_p), ("central", C.c_void_p), ("far_in", C.c_void_p), ("near_out", C.c_void_p)]
 
 
 class RkError(RuntimeError):
@@ -176,6 +192,34 @@ def _take_hits(ptr, n):
 def _dbscan_outputs(n):
     """labels, kind, via and degree of n genomes, for the library to fill"""
     return np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+
+
+def _medoid_arrays(n, records=True):
+    """(in_deg, out_deg, central, far_in, near_out) of n genomes for the library to fill; without records the last two are None"""
+    rec = (np.zeros(n, dtype=HIT_DTYPE), np.zeros(n, dtype=HIT_DTYPE)) if records else (None, None)
+    return (np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)) + rec
+
+
+def _medoid_struct(arrays):
+    """rk_medoid_genomes over (in_deg, out_deg, central, far_in, near_out); the arrays must outlive the call"""
+    return MedoidGenomes(*[a.ctypes.data if a is not None else None for a in arrays])
+
+
+def _medoid_given(g, n, what):
+    """a caller's (in_deg, out_deg, central, far_in, near_out) as contiguous arrays of n entries each"""
+    if len(g) != 5:
+        raise ValueError("%s needs (in_deg, out_deg, central, far_in, near_out)" % what)
+    out = tuple(None if a is None else np.ascontiguousarray(a, dtype=t) for a, t in zip(g, (np.uint32, np.uint32, np.uint64, HIT_DTYPE, HIT_DTYPE)))
+    if any(a is None for a in out[:3]) or any(a is not None and a.shape != (int(n),) for a in out):
+        raise ValueError("%s needs arrays of one entry per genome" % what)
+    return out
+
+
+def _medoid_labels(labels, n, what):
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    if labels.shape != (int(n),):
+        raise ValueError("%s needs one label per genome" % what)
+    return labels
 
 
 def _stats_dict(st, fields=None):
@@ -544,6 +588,22 @@ class Context:
                                     C.byref(st)))
         return core_dist, core_nb, _take_hits(edges, n), _stats_dict(st, MreachStats._fields_[:-1])
 
+    def medoid_rows(self, index, metric, kmer_size, max_dist, labels, row_first=0, row_step=1, row_block=0, records=True):
+        """medoids and census of a clustering of the self join (rk_medoid_rows): (in_deg, out_deg, central, far_in, near_out, stats) --
+        labels[i] below the number of genomes names i's cluster, MEDOID_NONE leaves i unlabelled; in_deg / out_deg (uint32) = i's pairs
+        within max_dist inside its cluster and leaving it, central (uint64) = the sum of floor(common * 2^32 / u) over the inside ones,
+        far_in / near_out (HIT_DTYPE, row = col = MEDOID_NONE when absent; None with records=False) = i's farthest inside and nearest
+        leaving pair, stats a dict of the MedoidStats fields"""
+        opts = _opts(1, metric, kmer_size, max_dist, row_first, row_step, row_block)
+        labels = _medoid_labels(labels, index.genomes, "medoid_rows")
+        arrays = _medoid_arrays(index.genomes, records)
+        g = _medoid_struct(arrays)
+        st = MedoidStats()
+        L = lib()
+        L.rk_medoid_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_void_p, C.POINTER(MedoidGenomes), C.POINTER(MedoidStats)]
+        self.check(L.rk_medoid_rows(self._h, index._h, C.byref(opts), _ptr(labels), C.byref(g), C.byref(st)))
+        return arrays + (_stats_dict(st),)
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -882,6 +942,57 @@ def mreach_cut(edges, core_dist, t):
     if rc:
         raise RkError(rc, "rk_mreach_cut: an edge names a genome beyond the number of genomes")
     return labels
+
+
+def medoid_hits(hits, n, labels, metric, records=True):
+    """medoids and census of a clustering of a hit list over n genomes (rk_medoid_hits, host only): (in_deg, out_deg, central, far_in,
+    near_out) as Context.medoid_rows gives them, the records being the caller's (row < col)"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    labels = _medoid_labels(labels, n, "medoid_hits")
+    arrays = _medoid_arrays(int(n), records)
+    g = _medoid_struct(arrays)
+    L = lib()
+    L.rk_medoid_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(MedoidGenomes)]
+    rc = L.rk_medoid_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n), _ptr(labels), int(metric), C.byref(g))
+    if rc:
+        raise RkError(rc, "rk_medoid_hits: a label that names no cluster, a record that names a genome beyond the number of genomes or one genome "
+                          "twice, or a record outside 0 < common <= u")
+    return arrays
+
+
+def medoid_merge(a, b, n, metric):
+    """the results of two disjoint record sets folded (rk_medoid_merge, host only): a and b as (in_deg, out_deg, central, far_in,
+    near_out); a record array the result has only where both have it (None otherwise)"""
+    a = _medoid_given(a, n, "medoid_merge")
+    b = _medoid_given(b, n, "medoid_merge")
+    arrays = _medoid_arrays(int(n))
+    arrays = arrays[:3] + tuple(o if x is not None and y is not None else None for o, x, y in zip(arrays[3:], a[3:], b[3:]))
+    ga, gb, go = _medoid_struct(a), _medoid_struct(b), _medoid_struct(arrays)
+    L = lib()
+    L.rk_medoid_merge.argtypes = [C.POINTER(MedoidGenomes), C.POINTER(MedoidGenomes), C.c_uint32, C.c_int, C.POINTER(MedoidGenomes)]
+    rc = L.rk_medoid_merge(C.byref(ga), C.byref(gb), C.c_uint32(n), int(metric), C.byref(go))
+    if rc:
+        raise RkError(rc, "rk_medoid_merge: a record that is not a pair of the genome whose entry holds it")
+    return arrays
+
+
+def medoid_pick(labels, g, metric):
+    """the per-cluster records of a clustering from its per-genome arrays (rk_medoid_pick, host only): MEDOID_CLUSTER_DTYPE, by
+    ascending label; weakest_in and nearest_out are absent (row = col = MEDOID_NONE) unless g holds both record arrays"""
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    n = len(labels)
+    g = _medoid_given(g, n, "medoid_pick")
+    gs = _medoid_struct(g)
+    out = C.c_void_p()
+    n_out = C.c_uint32()
+    L = lib()
+    L.rk_medoid_pick.argtypes = [C.c_void_p, C.POINTER(MedoidGenomes), C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+    rc = L.rk_medoid_pick(_ptr(labels), C.byref(gs), C.c_uint32(n), int(metric), C.byref(out), C.byref(n_out))
+    if rc:
+        raise RkError(rc, "rk_medoid_pick: a label that names no cluster")
+    buf = C.string_at(out.value, n_out.value * MEDOID_CLUSTER_DTYPE.itemsize) if n_out.value else b""
+    lib().rk_free_host(out)
+    return np.frombuffer(buf, dtype=MEDOID_CLUSTER_DTYPE).copy()
 
 
 def format_hit(name_a, name_b, hit):

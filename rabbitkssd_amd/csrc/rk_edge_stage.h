@@ -1,8 +1,8 @@
-// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip, rk_knn.hip, rk_dbscan.hip and rk_mreach.hip (not
-// part of the public ABI): the self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device
-// may decide.  DESIGN.md 4.6.  The key pass of the last four lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings
+// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip, rk_knn.hip, rk_dbscan.hip, rk_mreach.hip and
+// rk_medoid.hip (not part of the public ABI): the self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device
+// may decide.  DESIGN.md 4.6.  The key pass of all but the first lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings
 // its own.  Two passes over the keyed records that more than one caller runs behind the stage follow it: k_edge_revive (greedy,
-// dbscan, mreach) and k_edge_degree (knn, dbscan, mreach).
+// dbscan, mreach, medoid) and k_edge_degree (knn, dbscan, mreach).
 //
 //   join     rk_dist_rows_dev with the threshold widened by 2^-46 (capped at 1.0: beyond it the public join would turn to the dense
 //            report) appends unordered hit records to a buffer of max(65,536, rows * 64) records; its counter counts every hit,

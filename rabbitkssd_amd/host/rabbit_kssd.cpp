@@ -1212,7 +1212,7 @@ static void build_everywhere(GpuSet &set, const SketchSet &s, const string &path
     on_every_gpu(G, [&](size_t g) { idx[g] = build_index(set[g], s, path, g == 0 && write_files); });
 }
 
-// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn, dbscan, mreach): the common arguments, the input (a .sketch file, or a
+// The frame of the self-join subcommands (alldist, cluster, forest, greedy, knn, dbscan, mreach, medoid): the common arguments, the input (a .sketch file, or a
 // genome list that is sketched first), the index on every GPU of the set (the sharded build where it applies, the whole index
 // everywhere otherwise), the reference's phase lines around them and the way out.
 struct SelfJoin {
@@ -1696,6 +1696,141 @@ static int cmd_mreach(const Args &a)
     j.leave();
 }
 
+// medoid: medoids and census of a clustering of alldist's pairs (rk_medoid_rows on every GPU for its rows, folded with rk_medoid_merge;
+// rk_medoid_pick for the clusters).  The labels come from the same run -- --by cluster (the default; rk_cluster_rows, several GPUs), --by
+// greedy (rk_greedy_rows: a cluster is a representative and its members), --by dbscan -m minPts (rk_dbscan_rows: noise is unlabelled) -- or
+// from --labels FILE: one line per genome in input order, an integer below the number of genomes or - for an unlabelled genome.  One line
+// per genome: cluster number (from 1, clusters by ascending label), cluster size, role (medoid or member), genome name, the pairs of the
+// genome inside its cluster and leaving it, its mean similarity to its fellow members (central / 2^32 / (size - 1)), the name and
+// distance of its nearest genome outside its cluster (- - when it has none within -D); within a cluster the medoid first, then the
+// members by ascending index; the unlabelled genomes last, as cluster 0 of size 0 with role none.  --census: one line per cluster, its
+// number, size, medoid, the pairs inside it, size (size - 1) / 2, its weakest inside pair (two names and the distance) and its
+// nearest leaving pair.
+static int cmd_medoid(const Args &a)
+{
+    SelfJoin j(a, "medoid", true);
+    const string by = a.str("by", "cluster");
+    if (a.has("by") && a.has("labels")) die("command_medoid(), --by and --labels exclude each other: the labels come from one place");
+    if (by != "cluster" && by != "greedy" && by != "dbscan") die("command_medoid(), --by must be cluster, greedy or dbscan");
+    const bool from_file = a.has("labels");
+    if (!from_file && by != "cluster" && a.num("gpus", 1) > 1)
+        die("command_medoid(), --by %s runs on one GPU: the rule does not compose from the shards of several (--gpus 1)", by.c_str());
+    if (!from_file && by == "dbscan" && (!a.has("m") || a.num("m", 0) < 1))
+        die("command_medoid(), minPts must be >= 1\nUse -m to set the minPts (it counts the genome itself)");
+    j.prepare();
+    const size_t G = j.G, N = j.N;
+    vector<uint32_t> label(N ? N : 1, RK_MEDOID_NONE);
+    if (from_file) {
+        std::ifstream in(a.str("labels", ""));
+        if (!in) die("cannot read %s", a.str("labels", "").c_str());
+        string line;
+        size_t seen = 0;
+        while (std::getline(in, line)) {
+            while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+            if (line.empty() && in.peek() == EOF) break;
+            if (seen >= N) die("command_medoid(), %s holds more than the %zu lines of the input", a.str("labels", "").c_str(), N);
+            if (line != "-") {
+                char *end = nullptr;
+                const unsigned long long v = strtoull(line.c_str(), &end, 10);
+                if (line.empty() || *end || line[0] == '-' || line[0] == '+' || v >= N)
+                    die("command_medoid(), line %zu of %s is neither an integer below %zu nor -", seen + 1, a.str("labels", "").c_str(), N);
+                label[seen] = (uint32_t)v;
+            }
+            seen++;
+        }
+        if (seen != N) die("command_medoid(), %s holds %zu lines, the input %zu genomes", a.str("labels", "").c_str(), seen, N);
+    } else if (by == "cluster") {
+        vector<vector<uint32_t>> labels(G, vector<uint32_t>(N ? N : 1));
+        on_every_gpu(G, [&](size_t g) {
+            const rk_dist_opts o = j.opts(g);
+            j.gpu(g).check(rk_cluster_rows(j.gpu(g).ctx, j.idx[g], &o, labels[g].data(), nullptr), "rk_cluster_rows");
+        });
+        for (size_t g = 1; g < G; g++)
+            if (rk_cluster_merge(labels[0].data(), labels[g].data(), (uint32_t)N, labels[0].data()) != 0) die("rk_cluster_merge failed");
+        label = labels[0];
+    } else if (by == "greedy") {
+        rk_hit *links = nullptr;
+        uint64_t n_links = 0;
+        const rk_dist_opts o = j.opts(0);
+        j.gpu(0).check(rk_greedy_rows(j.gpu(0).ctx, j.idx[0], &o, nullptr, label.data(), &links, &n_links, nullptr), "rk_greedy_rows");
+        rk_free_host(links);
+    } else {
+        vector<uint8_t> kind(N ? N : 1);
+        const rk_dist_opts o = j.opts(0);
+        j.gpu(0).check(rk_dbscan_rows(j.gpu(0).ctx, j.idx[0], &o, (uint32_t)a.num("m", 1), label.data(), kind.data(), nullptr, nullptr, nullptr), "rk_dbscan_rows");
+    }
+    // the per-genome sums and records of every GPU's rows, folded into GPU 0's
+    struct Part {
+        vector<uint32_t> in_deg, out_deg;
+        vector<uint64_t> central;
+        vector<rk_hit> far_in, near_out;
+        rk_medoid_genomes g;
+        explicit Part(size_t n) : in_deg(n), out_deg(n), central(n), far_in(n), near_out(n), g{in_deg.data(), out_deg.data(), central.data(), far_in.data(), near_out.data()} {}
+    };
+    vector<std::unique_ptr<Part>> part(G);
+    for (size_t g = 0; g < G; g++) part[g].reset(new Part(N ? N : 1));
+    vector<rk_medoid_stats> stats(G);
+    on_every_gpu(G, [&](size_t g) {
+        const rk_dist_opts o = j.opts(g);
+        j.gpu(g).check(rk_medoid_rows(j.gpu(g).ctx, j.idx[g], &o, label.data(), &part[g]->g, &stats[g]), "rk_medoid_rows");
+    });
+    for (size_t g = 1; g < G; g++)
+        if (rk_medoid_merge(&part[0]->g, &part[g]->g, (uint32_t)N, j.metric, &part[0]->g) != 0) die("rk_medoid_merge failed");
+    const Part &p = *part[0];
+    rk_medoid_cluster *cl = nullptr;
+    uint32_t n_cl = 0;
+    if (rk_medoid_pick(label.data(), &p.g, (uint32_t)N, j.metric, &cl, &n_cl) != 0) die("rk_medoid_pick failed");
+    j.phase_done("medoids on the host", "medoids and census");
+    vector<vector<uint32_t>> members(n_cl);   // by cluster, ascending index
+    {
+        vector<uint32_t> at(N, 0);
+        for (uint32_t k = 0; k < n_cl; k++) at[cl[k].label] = k;
+        for (size_t i = 0; i < N; i++)
+            if (label[i] != RK_MEDOID_NONE) members[at[label[i]]].push_back((uint32_t)i);
+    }
+    FILE *fp = fopen(j.out.c_str(), "w");
+    if (!fp) die("cannot write %s", j.out.c_str());
+    auto genome_line = [&](uint32_t number, uint32_t size, const char *role, uint32_t i) {
+        const double mean = size > 1 ? (double)p.central[i] / 4294967296.0 / (double)(size - 1) : 0.0;
+        fprintf(fp, "%u\t%u\t%s\t%s\t%u\t%u\t%.6f\t", number, size, role, j.s.names[i].c_str(), p.in_deg[i], p.out_deg[i], mean);
+        const rk_hit &h = p.near_out[i];
+        if (h.row == RK_MEDOID_NONE) fprintf(fp, "-\t-\n");
+        else fprintf(fp, "%s\t%f\n", j.s.names[h.row == i ? h.col : h.row].c_str(), h.dist);
+    };
+    for (uint32_t k = 0; k < n_cl; k++) {
+        genome_line(k + 1, cl[k].size, "medoid", cl[k].medoid);
+        for (uint32_t i : members[k])
+            if (i != cl[k].medoid) genome_line(k + 1, cl[k].size, "member", i);
+    }
+    for (size_t i = 0; i < N; i++)
+        if (label[i] == RK_MEDOID_NONE) genome_line(0, 0, "none", (uint32_t)i);
+    fclose(fp);
+    if (a.has("census")) {
+        FILE *cp = fopen(a.str("census", "").c_str(), "w");
+        if (!cp) die("cannot write %s", a.str("census", "").c_str());
+        auto pair = [&](const rk_hit &h) {
+            if (h.row == RK_MEDOID_NONE) fprintf(cp, "\t-\t-\t-");
+            else fprintf(cp, "\t%s\t%s\t%f", j.s.names[h.row].c_str(), j.s.names[h.col].c_str(), h.dist);
+        };
+        for (uint32_t k = 0; k < n_cl; k++) {
+            fprintf(cp, "%u\t%u\t%s\t%llu\t%llu", k + 1, cl[k].size, j.s.names[cl[k].medoid].c_str(), (unsigned long long)cl[k].in_edges,
+                    (unsigned long long)cl[k].size * (cl[k].size - 1) / 2);
+            pair(cl[k].weakest_in);
+            pair(cl[k].nearest_out);
+            fprintf(cp, "\n");
+        }
+        fclose(cp);
+    }
+    if (getenv("RK_TIMING")) {
+        unsigned long long hits = 0, border = 0, inside = 0, leaving = 0;
+        for (size_t g = 0; g < G; g++) { hits += stats[g].edges; border += stats[g].borderline; inside += stats[g].inside; leaving += stats[g].leaving; }
+        fprintf(stderr, "[timing] %u clusters of %zu genomes: %llu pairs inside, %llu leaving, from %llu hit records (%llu borderline)\n", n_cl, N, inside, leaving,
+                hits, border);
+    }
+    rk_free_host(cl);
+    j.leave();
+}
+
 static int cmd_dist(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("dist needs -r and -q");
@@ -2076,7 +2211,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2086,6 +2221,7 @@ static int usage()
             "  knn -i in.sketch|genomes.list -o out -N k [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (the k nearest neighbours of every genome among alldist's pairs: one alldist-format line per genome and neighbour, nearest first)\n"
             "  dbscan -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [-L file.shuf] [--device N]   (density-based clusters of alldist's pairs: a genome with minPts genomes, itself included, within -D is core; clusters are the components of the core genomes, a non-core genome joins its nearest core neighbour's cluster as border, the rest is noise; one GPU)\n"
             "  mreach -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [--core FILE] [--cut t --labels FILE] [-L file.shuf] [--device N]   (minimum spanning forest of alldist's pairs under mutual-reachability distance, the HDBSCAN* hierarchy up to -D: one forest line per edge and its mutual-reachability distance; --core: every genome's core distance and the neighbour that sets it; --cut: the clusters of the core genomes at t <= maxDist, the rest as cluster 0; one GPU)\n"
+            "  medoid -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--by cluster|greedy|dbscan] [-m minPts] [--labels FILE] [--census FILE] [-L file.shuf] [--device N] [--gpus G]   (medoids and census of a clustering of alldist's pairs: per genome its cluster, its role -- the medoid is the member with the highest summed similarity to its fellow members --, its pairs inside the cluster and leaving it, its mean similarity to its fellow members and its nearest genome outside; the labels from --by (default cluster; dbscan needs -m; greedy and dbscan on one GPU) or from --labels: one line per genome, an integer below the number of genomes or -; --census: per cluster its size, medoid, inside pairs of size (size - 1) / 2, weakest inside pair and nearest leaving pair)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -2106,7 +2242,7 @@ int main(int argc, char **argv)
         {"-n", "n"}, {"--leastNumKmer", "n"}, {"-Q", "Q"}, {"--leastQuality", "Q"}, {"-D", "D"}, {"--maxDist", "D"},
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
-        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}};
+        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2124,7 +2260,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2148,6 +2284,7 @@ int main(int argc, char **argv)
     if (sub == "knn") { cerr << "-----run the subcommand: knn" << endl; return leave(cmd_knn(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dbscan") { cerr << "-----run the subcommand: dbscan" << endl; return leave(cmd_dbscan(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "mreach") { cerr << "-----run the subcommand: mreach" << endl; return leave(cmd_mreach(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "medoid") { cerr << "-----run the subcommand: medoid" << endl; return leave(cmd_medoid(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
