@@ -92,11 +92,12 @@ int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, 
     rk_cluster_stats st;
     memset(&st, 0, sizeof st);
     if (stats) *stats = st;
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_cluster_rows clusters a self join: triangle must be 1");
+    const StageNeeds needs{"rk_cluster_rows", nullptr, false};   // (every shard, and the dense report answered below)
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     const uint32_t N = idx->n_ref;
     if (!N) return RK_OK;
     if (!labels_out) return rk_fail(ctx, RK_ERR_ARG, "labels_out is null");
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
     RK_HIP(ctx, hipSetDevice(ctx->device));
     if (rk_dense_mode(opts)) {
         if (!idx->d_selfrange && (idx->slices_refused || idx->H >= (1ULL << 30)))   // (what the join itself answers for a dense report over such an index)
@@ -108,27 +109,25 @@ int rk_cluster_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, 
         return RK_OK;
     }
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_cluster_rows", (size_t)N * 4);   // the tail: the labels
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassOwn, (size_t)N * 4);   // the tail: the labels
+    const TimedSpan span{ctx, RK_MS_CLUSTER_HOOK};
     DevBuf<uint32_t> parent(ctx);
     RK_HIP(ctx, parent.alloc(N));
     hipLaunchKernelGGL(k_cluster_init, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, parent.p, N);
     RK_HIP(ctx, hipGetLastError());
-    if (ctx->timing) ctx->last_ms[RK_MS_CLUSTER_HOOK] = 0.0;
+    span.clear();
     int rc = stage.run([&](int) -> int {
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+        RK_HIP(ctx, span.begin());
         hipLaunchKernelGGL(k_cluster_hook, dim3(grid_for(ctx, stage.cap)), dim3(kStageThreads), 0, stream, stage.hits.p, stage.cnt(),
                            (unsigned long long)stage.cap, parent.p, N, stage.link_below, stage.edges.p, (unsigned long long)stage.edge_cap);
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+        RK_HIP(ctx, span.end());
         RK_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_cluster_flatten, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, parent.p, (uint32_t *)stage.tail(), N);
         RK_HIP(ctx, hipGetLastError());
         return RK_OK;
     });
     if (rc) return rc;
-    if (ctx->timing) {   // (the events of the last pass)
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_CLUSTER_HOOK] = ms;
-    }
+    span.read();   // (the events of the last pass)
     std::vector<rk_hit> kept;
     if ((rc = stage.decide(&kept))) return rc;
     memcpy(labels_out, stage.home_tail(), (size_t)N * 4);

@@ -224,17 +224,15 @@ int rk_dbscan_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
     const uint32_t N = idx->n_ref;
     if (N && (!labels_out || !kind_out)) return rk_fail(ctx, RK_ERR_ARG, "labels_out or kind_out is null");
     if (!min_pts) return rk_fail(ctx, RK_ERR_ARG, "rk_dbscan_rows: min_pts counts the genome itself and must be 1 or more");
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_dbscan_rows works on a self join: triangle must be 1");
-    if (opts->row_step > 1) return rk_fail(ctx, RK_ERR_ARG, "rk_dbscan_rows needs every row: the degrees of a row shard are partial, and the core test does not compose from shards");
-    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_dbscan_rows: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order");
+    const StageNeeds needs{"rk_dbscan_rows", "the degrees of a row shard are partial, and the core test does not compose from shards", true};
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     if (!N) return RK_OK;
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
-    if (!idx->d_postings) return rk_fail(ctx, RK_ERR_ARG, "rk_dbscan_rows: a join-only index (rk_index_join_shard) holds the rows of one shard");
-    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_dbscan_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
-    if (ctx->timing) ctx->last_ms[RK_MS_DBSCAN] = 0.0;
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
+    const TimedSpan span{ctx, RK_MS_DBSCAN};
+    span.clear();
 
     // the same rule over the hit list on the host: the A/B leg of tools/dbscan_probe.py, and a fallback
-    if (const char *sw = getenv("RK_DBSCAN_DEVICE"); sw && atoi(sw) == 0) {
+    if (rk_switched_off("RK_DBSCAN_DEVICE")) {
         rk_hit *hits = nullptr;
         uint64_t n_hits = 0;
         if (int rc = rk_dist_rows(ctx, idx, nullptr, opts, &hits, &n_hits, nullptr)) return rc;
@@ -253,10 +251,8 @@ int rk_dbscan_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
 
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_dbscan_rows", Tail::bytes(N), true);   // with slot numbers; the tail: the results
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassGreedyKeys, Tail::bytes(N));   // with slot numbers; the tail: the results
     stage.tail_in_pass = false;   // (the key pass writes none of them)
-    stage.hits_what = "hit records and their keys";
-    stage.bad_what = "a genome beyond the index or one genome twice";
     DevBuf<unsigned long long> w(ctx), rc_(ctx), best_w(ctx);
     DevBuf<uint32_t> parent(ctx), best_nb(ctx);
     RK_HIP(ctx, parent.alloc(N));
@@ -266,43 +262,26 @@ int rk_dbscan_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
     // the key pass: nothing is counted before the stage is through
     int rc = stage.run([&](int pass) { return stage.key_pass<true>(pass, w, rc_); });
     if (rc) return rc;
-    st.join_attempts = stage.join_attempts;
-    st.border_attempts = stage.pass_attempts;
-    if (stage.n_border >= (1ULL << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_dbscan_rows: %llu borderline records", stage.n_border);
+    stage.stats(&st);
+    // the borderline records, decided before any degree
+    if ((rc = stage.revive(w.p, &st.borderline_kept))) return rc;
     const unsigned long long n_rec = stage.n_hits;
     const unsigned grid = grid_for(ctx, n_rec), vgrid = grid_for(ctx, N);
-    // the borderline records, decided before any degree: the slot numbers of the kept ones go back up
-    {
-        std::vector<rk_hit> kept;
-        std::vector<unsigned long long> kept_slots;
-        if ((rc = stage.decide(&kept, &kept_slots))) return rc;
-        st.borderline_kept = kept.size();
-        if (!kept.empty()) {
-            RK_HIP(ctx, hipMemcpyAsync(stage.slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept_slots is pageable memory)
-            hipLaunchKernelGGL(k_edge_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream,
-                               stage.hits.p, stage.slots.p, (unsigned long long)kept.size(), n_rec, stage.metric, w.p);
-            RK_HIP(ctx, hipGetLastError());
-        }
-    }
     const Tail out(stage.tail(), N);
     RK_HIP(ctx, hipMemsetAsync(out.counts, 0, kOutWords * 8, stream));
     RK_HIP(ctx, hipMemsetAsync(out.deg, 0, (size_t)N * 4, stream));
     hipLaunchKernelGGL(k_dbscan_init, dim3(vgrid), dim3(kStageThreads), 0, stream, parent.p, best_w.p, best_nb.p, N);
     hipLaunchKernelGGL(k_edge_degree, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, out.deg);
     RK_HIP(ctx, hipGetLastError());
-    if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+    RK_HIP(ctx, span.begin());
     hipLaunchKernelGGL(k_dbscan_hook, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, out.deg, min_pts, parent.p, best_w.p);
     hipLaunchKernelGGL(k_dbscan_border, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, out.deg, min_pts, best_w.p, best_nb.p);
     hipLaunchKernelGGL(k_dbscan_labels, dim3(vgrid), dim3(kStageThreads), 0, stream, out.deg, parent.p, best_nb.p, min_pts, N, out.label, out.via, out.kind,
                        out.counts);
     RK_HIP(ctx, hipGetLastError());
-    if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+    RK_HIP(ctx, span.end());
     if ((rc = stage.fetch_home())) return rc;
-    if (ctx->timing) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_DBSCAN] = ms;
-    }
+    span.read();
     const Tail home((void *)stage.home_tail(), N);
     if (home.counts[kOutCore] + home.counts[kOutBorder] + home.counts[kOutNoise] != N || home.counts[kOutClusters] > home.counts[kOutCore])
         return rk_fail(ctx, RK_ERR_HIP, "rk_dbscan_rows: the kinds of %u genomes do not add up (internal error)", N);
@@ -310,8 +289,6 @@ int rk_dbscan_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
     memcpy(kind_out, home.kind, N);
     if (via_out) memcpy(via_out, home.via, (size_t)N * 4);
     if (degree_out) memcpy(degree_out, home.deg, (size_t)N * 4);
-    st.edges = stage.n_hits;
-    st.borderline = stage.n_border;
     st.n_clusters = (uint32_t)home.counts[kOutClusters];
     st.n_core = (uint32_t)home.counts[kOutCore];
     st.n_border = (uint32_t)home.counts[kOutBorder];

@@ -2,7 +2,10 @@
 // rk_medoid.hip (not part of the public ABI): the self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device
 // may decide.  DESIGN.md 4.6.  The key pass of all but the first lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings
 // its own.  Two passes over the keyed records that more than one caller runs behind the stage follow it: k_edge_revive (greedy,
-// dbscan, mreach, medoid) and k_edge_degree (knn, dbscan, mreach).
+// dbscan, mreach, medoid) and k_edge_degree (knn, dbscan, mreach).  So does the host code that every caller would otherwise repeat
+// around the stage: the refusals in front of it (StageNeeds, stage_options, stage_index), EdgeStage::revive (decide, the kept slot
+// numbers back up, k_edge_revive), EdgeStage::beyond_31_bits (the way to a caller's host leg) and EdgeStage::stats; the timed span
+// around a caller's kernels is TimedSpan of rk_internal.h.
 //
 //   join     rk_dist_rows_dev with the threshold widened by 2^-46 (capped at 1.0: beyond it the public join would turn to the dense
 //            report) appends unordered hit records to a buffer of max(65,536, rows * 64) records; its counter counts every hit,
@@ -132,13 +135,43 @@ k_edge_degree(const unsigned long long *w, const unsigned long long *rc, unsigne
     }
 }
 
+// What a call asks in front of the stage, beyond a self join.  The refusals come in two halves, in this order, with the caller's
+// `if (!N) return RK_OK` and whatever it checks itself between them: stage_options (triangle, row shard, dense report), stage_index
+// (rk_self_join_args, join-only index, ratio key).
+struct StageNeeds {
+    const char *who;         // the call's name
+    const char *every_row;   // why the call does not compose from row shards (null: it does).  Such a call has no use for a join-only index either: that holds the rows of one shard
+    bool ratio_key;          // the call orders records by ratio_key: no dense report, no sketch of 2^30 hashes (all but rk_cluster_rows)
+};
+
+inline int stage_options(rk_ctx *ctx, const StageNeeds &needs, const rk_dist_opts *opts)
+{
+    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "%s works on a self join: triangle must be 1", needs.who);
+    if (needs.every_row && opts->row_step > 1) return rk_fail(ctx, RK_ERR_ARG, "%s needs every row: %s", needs.who, needs.every_row);
+    if (needs.ratio_key && rk_dense_mode(opts))
+        return rk_fail(ctx, RK_ERR_ARG, "%s: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order", needs.who);
+    return RK_OK;
+}
+
+inline int stage_index(rk_ctx *ctx, const StageNeeds &needs, const rk_index *idx, const rk_dist_opts *opts)
+{
+    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
+    if (needs.every_row && !idx->d_postings) return rk_fail(ctx, RK_ERR_ARG, "%s: a join-only index (rk_index_join_shard) holds the rows of one shard", needs.who);
+    if (needs.ratio_key && idx->max_ref_size >= (1ULL << 30))
+        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key", needs.who);
+    return RK_OK;
+}
+
+// the first pass a stage will run: the caller's own, key_pass<false>, or key_pass<true> (with the slot numbers of the borderline records)
+enum StagePass { kPassOwn, kPassKeys, kPassGreedyKeys };
+
 struct EdgeStage {
     rk_ctx *ctx;
     const rk_index *idx;
     const rk_dist_opts *exact;   // the caller's options: the threshold the host decides with
     const char *who;             // the caller's name, for the texts that carry it
-    const char *hits_what = "hit records";                // what a capacity's worth of device memory holds, for the text of its refusal
-    const char *bad_what = "a genome beyond the index";   // what the pass counts in kCntBad
+    const char *hits_what;       // what a capacity's worth of device memory holds, for the text of its refusal
+    const char *bad_what;        // what the pass counts in kCntBad
     rk_dist_opts widened;        // the join reports with the widened threshold,
     double link_below;           // the device decides what lies below the narrowed one, the host the rest
     int metric;
@@ -147,16 +180,18 @@ struct EdgeStage {
     DevBuf<rk_edge> edges;
     DevBuf<unsigned long long> slots, block;   // slots: with_slots only.  block: the counters, then the caller's tail
     size_t tail_bytes;
-    bool with_slots;
+    bool with_slots;                           // kPassGreedyKeys
     bool tail_in_pass = true;                  // false: the pass does not write the tail; run() brings the counters home alone and the caller's fetch_home() the tail
     const unsigned char *home = nullptr;       // counters and tail of the last pass in the context's page-locked scratch
     unsigned long long n_hits = 0, n_border = 0;
     uint32_t join_attempts = 0, pass_attempts = 0;   // (pass_attempts: those behind the last join)
 
-    EdgeStage(rk_ctx *c, const rk_index *index, const rk_dist_opts *opts, const char *name, size_t tail = 0, bool want_slots = false)
-        : ctx(c), idx(index), exact(opts), who(name), widened(*opts), link_below(opts->max_dist), metric(opts->metric != 0),
+    EdgeStage(rk_ctx *c, const rk_index *index, const rk_dist_opts *opts, const char *name, StagePass pass, size_t tail = 0)
+        : ctx(c), idx(index), exact(opts), who(name), hits_what(pass == kPassOwn ? "hit records" : "hit records and their keys"),
+          bad_what(pass == kPassGreedyKeys ? "a genome beyond the index or one genome twice" : "a genome beyond the index"),
+          widened(*opts), link_below(opts->max_dist), metric(opts->metric != 0),
           cap(rk_hit_capacity(RowShard(opts, index->n_ref, index->n_ref).n_rows())),   // (the rows of this shard, as rk_dist_rows counts them)
-          edge_cap(kEdgeCapDefault), hits(c), edges(c), slots(c), block(c), tail_bytes(tail), with_slots(want_slots)
+          edge_cap(kEdgeCapDefault), hits(c), edges(c), slots(c), block(c), tail_bytes(tail), with_slots(pass == kPassGreedyKeys)
     {
         if (opts->max_dist > 0.0) {
             widened.max_dist = std::min(opts->max_dist + opts->max_dist * kBorderRel, 1.0);
@@ -232,7 +267,7 @@ struct EdgeStage {
     int key_pass(int k, DevBuf<unsigned long long> &w, DevBuf<unsigned long long> &rc, DevBuf<unsigned long long> *extra = nullptr)
     {
         if (!k && (w.alloc(cap) != hipSuccess || rc.alloc(cap) != hipSuccess || (extra && extra->alloc(cap) != hipSuccess)))
-            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu hit records and their keys on the device", (unsigned long long)cap);
+            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu %s on the device", (unsigned long long)cap, hits_what);
         hipLaunchKernelGGL(k_edge_keys<GREEDY>, dim3(grid_for(ctx, cap)), dim3(kStageThreads), 0, ctx->stream, hits.p, cnt(), (unsigned long long)cap,
                            idx->n_ref, link_below, metric, w.p, rc.p, edges.p, GREEDY ? slots.p : (unsigned long long *)nullptr,
                            (unsigned long long)edge_cap);
@@ -261,6 +296,44 @@ struct EdgeStage {
             for (size_t i = 0; i < kept->size(); i++) (*kept_slots)[i] = slot[(size_t)(*kept)[i].pad_];
         }
         return RK_OK;
+    }
+
+    // decide() for the callers that stage with slot numbers, before their first pass behind the stage: the slot numbers of the records
+    // the host kept go back up and k_edge_revive makes those alive in w (the caller's keys); nothing is copied or launched when none is
+    // kept.  *n_kept: how many were.
+    int revive(unsigned long long *w, uint64_t *n_kept)
+    {
+        // (never in rk_mreach_rows, which goes to the host from 2^31 hits on: n_border <= n_hits)
+        if (n_border >= (1ULL << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: %llu borderline records", who, n_border);
+        std::vector<rk_hit> kept;
+        std::vector<unsigned long long> kept_slots;
+        if (int rc = decide(&kept, &kept_slots)) return rc;
+        *n_kept = kept.size();
+        if (kept.empty()) return RK_OK;
+        RK_HIP(ctx, hipMemcpyAsync(slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (kept_slots is pageable memory)
+        hipLaunchKernelGGL(k_edge_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, ctx->stream, hits.p,
+                           slots.p, (unsigned long long)kept.size(), n_hits, metric, w);
+        RK_HIP(ctx, hipGetLastError());
+        return RK_OK;
+    }
+
+    // run() returned rc with more records than 31-bit record numbers hold, or without the memory for that many: the hit buffer goes
+    // back to the pool, the caller releases its own buffers and takes its host leg
+    bool beyond_31_bits(int rc)
+    {
+        if ((rc && rc != RK_ERR_NOMEM) || n_hits < (1ULL << 31)) return false;
+        hits.reset();
+        return true;
+    }
+
+    // what every caller's stats say about the stage (rk_cluster_stats has its own name for the passes)
+    template <class Stats> void stats(Stats *st) const
+    {
+        st->join_attempts = join_attempts;
+        st->border_attempts = pass_attempts;
+        st->edges = n_hits;
+        st->borderline = n_border;
     }
 };
 

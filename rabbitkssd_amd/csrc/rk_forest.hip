@@ -74,16 +74,14 @@ int rk_forest_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, r
     if (!edges_out || !n_edges) return rk_fail(ctx, RK_ERR_ARG, "edges_out or n_edges is null");
     *edges_out = nullptr;
     *n_edges = 0;
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_forest_rows spans a self join: triangle must be 1");
-    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_forest_rows: a dense report (a threshold above 1.0) has no forest: pairs that share nothing carry no order");
+    const StageNeeds needs{"rk_forest_rows", nullptr, true};
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     const uint32_t N = idx->n_ref;
     if (!N) return RK_OK;
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
-    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_forest_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_forest_rows");
-    stage.hits_what = "hit records and their keys";
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassKeys);
     const int metric = stage.metric;
     const uint64_t forest_cap = N - 1;
     uint32_t max_rounds = 2;   // 2 + ceil(log2 N): the components with an edge left at least halve per round, the last round appends nothing
@@ -105,8 +103,7 @@ int rk_forest_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, r
     // the key pass: nothing is linked before the stage is through
     int rc = stage.run([&](int pass) { return stage.key_pass<false>(pass, w, rc_); });
     if (rc) return rc;
-    st.join_attempts = stage.join_attempts;
-    st.border_attempts = stage.pass_attempts;
+    stage.stats(&st);
     const rk_hit *hits = stage.hits.p;
     const unsigned long long *n_hits_dev = stage.cnt() + kCntHits, cap = stage.cap;
     const unsigned grid = grid_for(ctx, cap);
@@ -166,8 +163,6 @@ int rk_forest_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, r
     if (kept) memcpy(out, all.data(), kept * sizeof(rk_hit));
     *edges_out = out;
     *n_edges = kept;
-    st.edges = stage.n_hits;
-    st.borderline = stage.n_border;
     st.n_trees = N - (uint32_t)kept;
     if (stats) *stats = st;
     return RK_OK;

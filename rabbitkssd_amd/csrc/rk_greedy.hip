@@ -157,19 +157,14 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     *n_links = 0;
     const uint32_t N = idx->n_ref;
     if (!rep_out && N) return rk_fail(ctx, RK_ERR_ARG, "rep_out is null");
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_greedy_rows works on a self join: triangle must be 1");
-    if (opts->row_step > 1) return rk_fail(ctx, RK_ERR_ARG, "rk_greedy_rows needs every row: the greedy rule does not compose from row shards");
-    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_greedy_rows: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order");
+    const StageNeeds needs{"rk_greedy_rows", "the greedy rule does not compose from row shards", true};
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     if (!N) return RK_OK;
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
-    if (!idx->d_postings) return rk_fail(ctx, RK_ERR_ARG, "rk_greedy_rows: a join-only index (rk_index_join_shard) holds the rows of one shard");
-    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_greedy_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_greedy_rows", 0, true);   // with slot numbers
-    stage.hits_what = "hit records and their keys";
-    stage.bad_what = "a genome beyond the index or one genome twice";
-    const int metric = stage.metric;
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassGreedyKeys);   // with slot numbers
+    const TimedSpan span{ctx, RK_MS_GREEDY_ROUNDS};
     const uint64_t max_rounds = (uint64_t)N + 1;   // every round with undecided genomes decides the first of them in rank order
 
     // the priority order, once: 4 * N bytes up (and, without a priority, the sizes and the genome order of the index down)
@@ -209,31 +204,17 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     RK_HIP(ctx, hipStreamSynchronize(stream));   // (rank_h is pageable memory)
     hipLaunchKernelGGL(k_greedy_init, dim3(grid_for(ctx, N)), dim3(kStageThreads), 0, stream, state.p, covered.p, blocked.p, rep.p, best_w.p, best_rc.p, N);
     RK_HIP(ctx, hipGetLastError());
-    if (ctx->timing) ctx->last_ms[RK_MS_GREEDY_ROUNDS] = 0.0;
+    span.clear();
 
     // the key pass: nothing is decided before the stage is through
     int rc = stage.run([&](int pass) { return stage.key_pass<true>(pass, w, rc_, &hl); });
     if (rc) return rc;
-    st.join_attempts = stage.join_attempts;
-    st.border_attempts = stage.pass_attempts;
-    if (stage.n_border >= (1ULL << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_greedy_rows: %llu borderline records", stage.n_border);
+    stage.stats(&st);
+    // the borderline records, decided before any round
+    if ((rc = stage.revive(w.p, &st.borderline_kept))) return rc;
     const rk_hit *hits = stage.hits.p;
     const unsigned long long n_rec = stage.n_hits;
     const unsigned grid = grid_for(ctx, n_rec);
-    // the borderline records, decided before any round: the slot numbers of the kept ones go back up
-    {
-        std::vector<rk_hit> kept;
-        std::vector<unsigned long long> kept_slots;
-        if ((rc = stage.decide(&kept, &kept_slots))) return rc;
-        st.borderline_kept = kept.size();
-        if (!kept.empty()) {
-            RK_HIP(ctx, hipMemcpyAsync(stage.slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept_slots is pageable memory)
-            hipLaunchKernelGGL(k_edge_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream, hits,
-                               stage.slots.p, (unsigned long long)kept.size(), n_rec, metric, w.p);
-            RK_HIP(ctx, hipGetLastError());
-        }
-    }
     std::vector<uint32_t> rep_h(N);
     std::vector<rk_hit> link_h;
     if (stage.n_hits - stage.n_border + st.borderline_kept == 0) {   // no record takes part: no round, every genome its own representative
@@ -242,7 +223,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
         hipLaunchKernelGGL(k_greedy_orient, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, rank.p, hl.p);
         RK_HIP(ctx, hipGetLastError());
         // decision rounds; the host reads the counters of a batch (one round at first: species cliques settle in two or three)
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+        RK_HIP(ctx, span.begin());
         uint64_t rounds = 0;
         bool settled = false;
         while (!settled) {
@@ -267,7 +248,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
             rounds += ran;
         }
         st.rounds = (uint32_t)rounds;
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+        RK_HIP(ctx, span.end());
         // every member to its nearest preceding representative
         hipLaunchKernelGGL(k_greedy_assign<0>, dim3(grid), dim3(kStageThreads), 0, stream, hits, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
         hipLaunchKernelGGL(k_greedy_assign<1>, dim3(grid), dim3(kStageThreads), 0, stream, hits, w.p, rc_.p, n_rec, rank.p, state.p, best_w.p, best_rc.p, rep.p, link.p);
@@ -277,10 +258,7 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
         RK_HIP(ctx, hipMemcpyAsync(rep_h.data(), rep.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
         RK_HIP(ctx, hipMemcpyAsync(link_h.data(), link.p, (size_t)N * sizeof(rk_hit), hipMemcpyDeviceToHost, stream));
         RK_HIP(ctx, hipStreamSynchronize(stream));
-        if (ctx->timing) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_GREEDY_ROUNDS] = ms;
-        }
+        span.read();
     }
     // links in member order (link_h[m] was written iff rep_h[m] != m; without a round there is none)
     uint64_t n_members = 0;
@@ -303,8 +281,6 @@ int rk_greedy_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     }
     *n_links = n_members;
     memcpy(rep_out, rep_h.data(), (size_t)N * 4);
-    st.edges = stage.n_hits;
-    st.borderline = stage.n_border;
     st.n_reps = N - (uint32_t)n_members;
     if (stats) *stats = st;
     return RK_OK;

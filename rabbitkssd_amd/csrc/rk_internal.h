@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -103,6 +104,29 @@ void *rk_pinned_scratch(rk_ctx *ctx, size_t bytes);
             return rk_fail((ctx), RK_ERR_HIP, "%s failed: %s (%s:%d)", #call,               \
                            hipGetErrorString(e__), __FILE__, __LINE__);                     \
     } while (0)
+
+// The timed span of a call (rk_ctx_set_timing): ctx->ev[0] and ctx->ev[1] on ctx->stream around the kernels that count, the time
+// between them in ctx->last_ms[which].  Without timing every operation does nothing, and none synchronises: read() belongs behind
+// a synchronisation of the caller's own.
+struct TimedSpan {
+    rk_ctx *ctx;
+    int which;
+    void clear() const { if (ctx->timing) ctx->last_ms[which] = 0.0; }
+    hipError_t begin() const { return ctx->timing ? hipEventRecord(ctx->ev[0], ctx->stream) : hipSuccess; }
+    hipError_t end() const { return ctx->timing ? hipEventRecord(ctx->ev[1], ctx->stream) : hipSuccess; }
+    void read() const
+    {
+        float ms = 0.f;
+        if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[which] = ms;
+    }
+};
+
+// a developer switch of the environment that is set and says 0: the leg it names is off (RK_DBSCAN_DEVICE=0: the host's rule)
+inline bool rk_switched_off(const char *name)
+{
+    const char *sw = getenv(name);
+    return sw && atoi(sw) == 0;
+}
 
 // owning device pointer from the context's pool; returned to it on scope exit unless release()d.  Work that uses
 // the buffer must be enqueued on ctx->stream (reuse is stream-ordered) or be complete before the scope ends.

@@ -176,13 +176,12 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
     if (!off_out || !nbrs_out || !n_nbrs) return rk_fail(ctx, RK_ERR_ARG, "off_out, nbrs_out or n_nbrs is null");
     *nbrs_out = nullptr;
     *n_nbrs = 0;
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_knn_rows works on a self join: triangle must be 1");
-    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_knn_rows: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order");
+    const StageNeeds needs{"rk_knn_rows", nullptr, true};
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     const uint32_t N = idx->n_ref;
     std::fill(off_out, off_out + (size_t)N + 1, (uint64_t)0);
     if (!N) return RK_OK;
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
-    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_knn_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
     if (!k) return RK_OK;
     const int metric = opts->metric != 0;
 
@@ -202,25 +201,22 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
         if (stats) *stats = st;
         return RK_OK;
     };
-    const char *sw = getenv("RK_KNN_DEVICE");
-    if (k > kKnnDeviceMax || (uint64_t)N * k >= (1ULL << 32) || (sw && atoi(sw) == 0)) return on_the_host();
+    if (k > kKnnDeviceMax || (uint64_t)N * k >= (1ULL << 32) || rk_switched_off("RK_KNN_DEVICE")) return on_the_host();
 
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_knn_rows");
-    stage.hits_what = "hit records and their keys";
-    if (ctx->timing) ctx->last_ms[RK_MS_KNN_SELECT] = 0.0;
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassKeys);
+    const TimedSpan span{ctx, RK_MS_KNN_SELECT};
+    span.clear();
     DevBuf<unsigned long long> w(ctx), rc_(ctx);
     int rc = stage.run([&](int pass) { return stage.key_pass<false>(pass, w, rc_); });
-    if (rc && !(rc == RK_ERR_NOMEM && stage.n_hits >= (1ULL << 31))) return rc;
-    if (stage.n_hits >= (1ULL << 31)) {   // the entries number the records in 31 bits
+    if (stage.beyond_31_bits(rc)) {   // the entries number the records in 31 bits
         w.reset();
         rc_.reset();
-        stage.hits.reset();
         return on_the_host();
     }
-    st.join_attempts = stage.join_attempts;
-    st.border_attempts = stage.pass_attempts;
+    if (rc) return rc;
+    stage.stats(&st);
     st.path = 1;
     const unsigned long long n_rec = stage.n_hits, n_live = n_rec - stage.n_border;
 
@@ -239,7 +235,7 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
         if (adj.alloc(2 * n_live) != hipSuccess || out.alloc(n_out_max) != hipSuccess)
             return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate the adjacency of %llu hit records on the device", n_live);
         const unsigned grid = grid_for(ctx, n_rec), vgrid = grid_for(ctx, (uint64_t)N + 1);
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+        RK_HIP(ctx, span.begin());
         RK_HIP(ctx, hipMemsetAsync(deg.p, 0, ((size_t)N + 1) * 4, stream));
         RK_HIP(ctx, hipMemsetAsync(most.p, 0, 4, stream));
         hipLaunchKernelGGL(k_edge_degree, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, deg.p);
@@ -253,17 +249,14 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
         const unsigned sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((N + waves_per_block - 1) / waves_per_block, (uint64_t)std::max(1, ctx->num_cu) * 16));
         hipLaunchKernelGGL(k_knn_select, dim3(sgrid), dim3(kStageThreads), 0, stream, adj.p, aoff.p, koff.p, stage.hits.p, N, k, out.p);
         RK_HIP(ctx, hipGetLastError());
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+        RK_HIP(ctx, span.end());
         // koff[], then the records it counts
         std::vector<uint32_t> koff_h((size_t)N + 1);
         uint32_t most_h = 0;
         RK_HIP(ctx, hipMemcpyAsync(koff_h.data(), koff.p, koff_h.size() * 4, hipMemcpyDeviceToHost, stream));
         RK_HIP(ctx, hipMemcpyAsync(&most_h, most.p, 4, hipMemcpyDeviceToHost, stream));
         RK_HIP(ctx, hipStreamSynchronize(stream));
-        if (ctx->timing) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_KNN_SELECT] = ms;
-        }
+        span.read();
         st.max_degree = most_h;
         const uint64_t total = koff_h[N];
         if (total > n_out_max) return rk_fail(ctx, RK_ERR_HIP, "rk_knn_rows: %llu neighbour records where %llu are possible (internal error)", (unsigned long long)total, (unsigned long long)n_out_max);
@@ -301,8 +294,6 @@ int rk_knn_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, uint
     }
     if (hand_over(rec, nbrs_out, n_nbrs)) return rk_fail(ctx, RK_ERR_NOMEM, "host allocation of %llu neighbour records failed", (unsigned long long)rec.size());
     memcpy(off_out, off.data(), off.size() * 8);
-    st.edges = stage.n_hits;
-    st.borderline = stage.n_border;
     st.neighbours = rec.size();
     if (stats) *stats = st;
     return RK_OK;

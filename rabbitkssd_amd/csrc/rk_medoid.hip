@@ -368,21 +368,21 @@ int rk_medoid_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     if (!out) return rk_fail(ctx, RK_ERR_ARG, "rk_medoid_rows: out is null");
     if (N && !labels) return rk_fail(ctx, RK_ERR_ARG, "rk_medoid_rows: labels is null");
     if (N && !has_sums(out)) return rk_fail(ctx, RK_ERR_ARG, "rk_medoid_rows: in_deg, out_deg or central of out is null");
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_medoid_rows works on a self join: triangle must be 1");
-    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_medoid_rows: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order");
+    const StageNeeds needs{"rk_medoid_rows", nullptr, true};
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     if (!N) {
         if (stats) *stats = st;
         return RK_OK;
     }
     if (N > (1u << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_medoid_rows: more than 2^31 genomes");
     if (check_labels(labels, N)) return rk_fail(ctx, RK_ERR_ARG, "rk_medoid_rows: a label is neither below the number of genomes nor RK_MEDOID_NONE");
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
-    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_medoid_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
-    if (ctx->timing) ctx->last_ms[RK_MS_MEDOID] = 0.0;
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
+    const TimedSpan span{ctx, RK_MS_MEDOID};
+    span.clear();
     const bool records = out->far_in || out->near_out;
 
     // the same rule over the hit list on the host: the A/B leg of tools/medoid_probe.py, and a fallback
-    if (const char *sw = getenv("RK_MEDOID_DEVICE"); sw && atoi(sw) == 0) {
+    if (rk_switched_off("RK_MEDOID_DEVICE")) {
         rk_hit *hits = nullptr;
         uint64_t n_hits = 0;
         if (int rc = rk_dist_rows(ctx, idx, nullptr, opts, &hits, &n_hits, nullptr)) return rc;
@@ -404,10 +404,8 @@ int rk_medoid_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
 
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_medoid_rows", Tail::bytes(N, records), true);   // with slot numbers; the tail: the results
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassGreedyKeys, Tail::bytes(N, records));   // with slot numbers; the tail: the results
     stage.tail_in_pass = false;   // (the key pass writes none of them)
-    stage.hits_what = "hit records and their keys";
-    stage.bad_what = "a genome beyond the index or one genome twice";
     DevBuf<unsigned long long> w(ctx), rc_(ctx), far_w(ctx), near_w(ctx);
     DevBuf<uint32_t> label(ctx), far_nb(ctx), near_nb(ctx);
     RK_HIP(ctx, label.alloc(N));
@@ -421,31 +419,17 @@ int rk_medoid_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     // the key pass: nothing is summed before the stage is through
     int rc = stage.run([&](int pass) { return stage.key_pass<true>(pass, w, rc_); });
     if (rc) return rc;
-    st.join_attempts = stage.join_attempts;
-    st.border_attempts = stage.pass_attempts;
-    if (stage.n_border >= (1ULL << 31)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_medoid_rows: %llu borderline records", stage.n_border);
+    stage.stats(&st);
+    // the borderline records, decided before any sum
+    if ((rc = stage.revive(w.p, &st.borderline_kept))) return rc;
     const unsigned long long n_rec = stage.n_hits;
     const unsigned grid = grid_for(ctx, n_rec), vgrid = grid_for(ctx, N);
-    // the borderline records, decided before any sum: the slot numbers of the kept ones go back up
-    {
-        std::vector<rk_hit> kept;
-        std::vector<unsigned long long> kept_slots;
-        if ((rc = stage.decide(&kept, &kept_slots))) return rc;
-        st.borderline_kept = kept.size();
-        if (!kept.empty()) {
-            RK_HIP(ctx, hipMemcpyAsync(stage.slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept_slots is pageable memory)
-            hipLaunchKernelGGL(k_edge_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream,
-                               stage.hits.p, stage.slots.p, (unsigned long long)kept.size(), n_rec, stage.metric, w.p);
-            RK_HIP(ctx, hipGetLastError());
-        }
-    }
     const Tail dev(stage.tail(), N);
     RK_HIP(ctx, hipMemsetAsync(dev.central, 0, (size_t)N * 16, stream));   // central and both degrees
     hipLaunchKernelGGL(k_medoid_init, dim3(vgrid), dim3(kStageThreads), 0, stream, far_w.p, near_w.p, far_nb.p, near_nb.p, records ? dev.far_in : (rk_hit *)nullptr,
                        records ? dev.near_out : (rk_hit *)nullptr, N);
     RK_HIP(ctx, hipGetLastError());
-    if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+    RK_HIP(ctx, span.begin());
     hipLaunchKernelGGL(k_medoid_sums, dim3(grid), dim3(kStageThreads), 0, stream, w.p, rc_.p, n_rec, label.p, dev.in_deg, dev.out_deg, dev.central, far_w.p, near_w.p,
                        (int)records);
     if (records) {
@@ -454,12 +438,9 @@ int rk_medoid_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
                            near_nb.p, dev.far_in, dev.near_out);
     }
     RK_HIP(ctx, hipGetLastError());
-    if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+    RK_HIP(ctx, span.end());
     if ((rc = stage.fetch_home())) return rc;
-    if (ctx->timing) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_MEDOID] = ms;
-    }
+    span.read();
     const Tail home((void *)stage.home_tail(), N);
     unsigned long long in_sum = 0, out_sum = 0;
     for (uint32_t v = 0; v < N; v++) {
@@ -482,8 +463,6 @@ int rk_medoid_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, c
     memcpy(out->central, home.central, (size_t)N * 8);
     if (out->far_in) memcpy(out->far_in, home.far_in, (size_t)N * sizeof(rk_hit));
     if (out->near_out) memcpy(out->near_out, home.near_out, (size_t)N * sizeof(rk_hit));
-    st.edges = stage.n_hits;
-    st.borderline = stage.n_border;
     st.inside = in_sum / 2;
     st.leaving = out_sum / 2;
     if (stats) *stats = st;

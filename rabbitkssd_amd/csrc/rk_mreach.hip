@@ -243,14 +243,12 @@ int rk_mreach_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
     const uint32_t N = idx->n_ref;
     if (N && !core_dist_out) return rk_fail(ctx, RK_ERR_ARG, "core_dist_out is null");
     if (!min_pts) return rk_fail(ctx, RK_ERR_ARG, "rk_mreach_rows: min_pts counts the genome itself and must be 1 or more");
-    if (opts->triangle != 1) return rk_fail(ctx, RK_ERR_ARG, "rk_mreach_rows works on a self join: triangle must be 1");
-    if (opts->row_step > 1) return rk_fail(ctx, RK_ERR_ARG, "rk_mreach_rows needs every row: the core distances of a row shard are partial, and the weights do not compose from shards");
-    if (rk_dense_mode(opts)) return rk_fail(ctx, RK_ERR_ARG, "rk_mreach_rows: a dense report (a threshold above 1.0) is not offered: pairs that share nothing carry no order");
+    const StageNeeds needs{"rk_mreach_rows", "the core distances of a row shard are partial, and the weights do not compose from shards", true};
+    if (int rc = stage_options(ctx, needs, opts)) return rc;
     if (!N) return RK_OK;
-    if (int rc = rk_self_join_args(ctx, idx, opts)) return rc;
-    if (!idx->d_postings) return rk_fail(ctx, RK_ERR_ARG, "rk_mreach_rows: a join-only index (rk_index_join_shard) holds the rows of one shard");
-    if (idx->max_ref_size >= (1ULL << 30)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_mreach_rows: a sketch of 2^30 hashes or more is beyond the 62-bit ratio key");
-    if (ctx->timing) ctx->last_ms[RK_MS_MREACH] = 0.0;
+    if (int rc = stage_index(ctx, needs, idx, opts)) return rc;
+    const TimedSpan span{ctx, RK_MS_MREACH};
+    span.clear();
     const int metric = opts->metric != 0;
     const uint32_t k = min_pts - 1;
     const double inf = std::numeric_limits<double>::infinity();
@@ -268,7 +266,7 @@ int rk_mreach_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
         if (out_of_range) {
             rk_free_host(hits);
             return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: %llu hit records lie outside 0 < common <= u (sketches that repeat hashes): they have no place in the order",
-                           "rk_mreach_rows", out_of_range);
+                           needs.who, out_of_range);
         }
         Result r;
         mreach_of_hits(hits, n_hits, N, min_pts, metric, &r);
@@ -283,49 +281,30 @@ int rk_mreach_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
         if (stats) *stats = st;
         return RK_OK;
     };
-    const char *sw = getenv("RK_MREACH_DEVICE");
-    if (k > kKnnDeviceMax || (sw && atoi(sw) == 0)) return on_the_host();
+    if (k > kKnnDeviceMax || rk_switched_off("RK_MREACH_DEVICE")) return on_the_host();
 
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    EdgeStage stage(ctx, idx, opts, "rk_mreach_rows", 0, true);   // with slot numbers
-    stage.hits_what = "hit records and their keys";
-    stage.bad_what = "a genome beyond the index or one genome twice";
+    EdgeStage stage(ctx, idx, opts, needs.who, kPassGreedyKeys);   // with slot numbers
     DevBuf<unsigned long long> w(ctx), rc_(ctx);
     int rc = stage.run([&](int pass) { return stage.key_pass<true>(pass, w, rc_); });
-    if (rc && !(rc == RK_ERR_NOMEM && stage.n_hits >= (1ULL << 31))) return rc;
-    if (stage.n_hits >= (1ULL << 31)) {   // the entries number the records in 31 bits
+    if (stage.beyond_31_bits(rc)) {   // the entries number the records in 31 bits
         w.reset();
         rc_.reset();
-        stage.hits.reset();
         return on_the_host();
     }
-    st.join_attempts = stage.join_attempts;
-    st.border_attempts = stage.pass_attempts;
+    if (rc) return rc;
+    stage.stats(&st);
     st.path = 1;
+    // the borderline records, decided before anything else
+    if ((rc = stage.revive(w.p, &st.borderline_kept))) return rc;
     const unsigned long long n_rec = stage.n_hits;
     const unsigned grid = grid_for(ctx, n_rec), vgrid = grid_for(ctx, (uint64_t)N + 1);
-    // the borderline records, decided before anything else: the slot numbers of the kept ones go back up
-    {
-        std::vector<rk_hit> kept;
-        std::vector<unsigned long long> kept_slots;
-        if ((rc = stage.decide(&kept, &kept_slots))) return rc;
-        st.borderline_kept = kept.size();
-        if (!kept.empty()) {
-            RK_HIP(ctx, hipMemcpyAsync(stage.slots.p, kept_slots.data(), kept_slots.size() * 8, hipMemcpyHostToDevice, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));   // (kept_slots is pageable memory)
-            hipLaunchKernelGGL(k_edge_revive, dim3((unsigned)((kept.size() + kStageThreads - 1) / kStageThreads)), dim3(kStageThreads), 0, stream,
-                               stage.hits.p, stage.slots.p, (unsigned long long)kept.size(), n_rec, stage.metric, w.p);
-            RK_HIP(ctx, hipGetLastError());
-        }
-    }
     const unsigned long long n_live = n_rec - stage.n_border + st.borderline_kept;
-    st.edges = stage.n_hits;
-    st.borderline = stage.n_border;
 
     std::vector<rk_hit> forest_h, core_h;   // the forest in order; per genome its core record (k >= 1)
     if (n_live) {
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
+        RK_HIP(ctx, span.begin());
         DevBuf<uint32_t> core_e(ctx);
         // core records
         if (k) {
@@ -391,7 +370,7 @@ int rk_mreach_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
             settled = now == n_forest;
             n_forest = now;
         }
-        if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
+        RK_HIP(ctx, span.end());
         // the forest in order: by (row, col), then stably by the stored mw
         forest_h.resize(n_forest);
         if (n_forest) {
@@ -417,10 +396,7 @@ int rk_mreach_rows(rk_ctx *ctx, const rk_index *idx, const rk_dist_opts *opts, u
             RK_HIP(ctx, hipMemcpyAsync(core_h.data(), core_rec.p, (size_t)N * sizeof(rk_hit), hipMemcpyDeviceToHost, stream));
         }
         RK_HIP(ctx, hipStreamSynchronize(stream));
-        if (ctx->timing) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_MREACH] = ms;
-        }
+        span.read();
     }
     // the reference's values bit for bit (a record that took part lies below the exact threshold: none is dropped)
     const uint64_t n_forest = forest_h.size();

@@ -1,6 +1,6 @@
-"""What the suites of the self join's consumers share (test_gpu_cluster, test_gpu_forest, test_gpu_greedy, test_gpu_knn): the
-oracle's side of a collection, the device's index of it, and the collections that put a call at the stage's edges.  Everything
-here is built from fixed seeds, the named collections once per session, and nothing a test gets from here is changed by it."""
+"""What the suites of the self join's consumers share (test_gpu_cluster, test_gpu_forest, test_gpu_greedy, test_gpu_knn,
+test_gpu_dbscan, test_gpu_mreach, test_gpu_medoid, and test_gpu_selfjoin_refusals for all seven calls): the oracle's side of a collection, the device's index of
+it, and the collections that put a call at the stage's edges.  Everything here is built from fixed seeds, the named collections once per session, and nothing a test gets from here is changed by it."""
 import os
 
 import numpy as np
