@@ -104,6 +104,11 @@ void *rk_pinned_scratch(rk_ctx *ctx, size_t bytes);
             return rk_fail((ctx), RK_ERR_HIP, "%s failed: %s (%s:%d)", #call,               \
                            hipGetErrorString(e__), __FILE__, __LINE__);                     \
     } while (0)
+#define RK_TRY(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
+
+// the launch shape of the small one-thread-per-element kernels
+constexpr int kThreads = 256;
+inline unsigned blocks_for(uint64_t n, int t = kThreads) { return (unsigned)((n + t - 1) / t); }
 
 // The timed span of a call (rk_ctx_set_timing): ctx->ev[0] and ctx->ev[1] on ctx->stream around the kernels that count, the time
 // between them in ctx->last_ms[which].  Without timing every operation does nothing, and none synchronises: read() belongs behind
@@ -152,6 +157,19 @@ template <class T> struct DevBuf {
         return q;
     }
     operator T *() const { return p; }
+};
+
+// a device array of an object under construction, from the context's pool (the object's free function returns it)
+template <class T> inline int pool_array(rk_ctx *ctx, T **out, size_t n)
+{
+    *out = static_cast<T *>(rk_pool_alloc(ctx, (n ? n : 1) * sizeof(T)));
+    return *out ? RK_OK : rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu bytes on the device", (unsigned long long)(n * sizeof(T)));
+}
+
+// owns a library object while it is put together: every error exit frees it, success takes it out (guard.p = nullptr)
+template <class T, void (*Free)(T *)> struct Owned {
+    T *p;
+    ~Owned() { if (p) Free(p); }
 };
 
 struct rk_filter {
@@ -267,6 +285,19 @@ struct rk_index {
     std::mutex lazy_mu;              // serialises the lazy builders (prefix directory, rank bitmap, list records, sum of
                                      // squares): two host threads may query one index
 };
+
+using IndexGuard = Owned<rk_index, rk_index_free>;
+using SketchesGuard = Owned<rk_sketches, rk_sketches_free>;
+
+// the shape of the prefix directory (rk_index_ensure_dir) from U and hash_bits: every way an index comes to be sets it
+inline void set_dir_shape(rk_index *idx)
+{
+    int dbits = 10;
+    while (dbits < 24 && (1ULL << dbits) < 2 * idx->U) dbits++;
+    if (dbits > idx->hash_bits) dbits = idx->hash_bits;
+    idx->dir_bits = dbits;
+    idx->dir_shift = idx->hash_bits - dbits;
+}
 
 // device-wide primitives behind plain functions (rk_prims.hip, rk_prims_hits.hip: translation units of their own, so that
 // the code objects of the callers stay small -- a code object is loaded when the first kernel of its translation unit runs).

@@ -19,20 +19,11 @@
 // big LDS image variant holds an exact table), and the dr_tuple goes to the genome's candidate region.
 // Per-genome dedup (the reference's unordered_set): one workgroup per genome sorts its region in LDS
 // (k_dedup), a scan and a placement kernel build the CSR; one upload and one read-back per batch.
-#include <cstring>
-
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "rk_internal.h"
-
-#define RK_TRY(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
-template <class T> static int pool_array(rk_ctx *ctx, T **out, size_t n)
-{
-    *out = static_cast<T *>(rk_pool_alloc(ctx, (n ? n : 1) * sizeof(T)));
-    return *out ? RK_OK : rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu bytes on the device", (unsigned long long)(n * sizeof(T)));
-}
 
 namespace {
 
@@ -635,8 +626,6 @@ template <class K> __global__ void k_check_sets(const K *hashes, uint64_t total,
     if (off[lo] != e) *bad = 1;
 }
 
-inline unsigned blocks_for(uint64_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }
-
 // the chunk table of a pass: chunk c belongs to the largest g with first_chunk[g] <= c
 __global__ void k_chunk_table(const GenomeRow *rows, uint32_t n_genomes, uint32_t n_chunks, uint32_t chunk_blocks, ChunkDesc *out)
 {
@@ -680,6 +669,46 @@ void kernel_name(char *buf, size_t cap, int kmer, int out2, bool exact, int img)
     else snprintf(buf, cap, "rk_sketch_kernel<%d, %d, %s, %d>", fixed ? kmer : 0, fixed ? out2 : 0, exact && !img ? "true" : "false", img ? 1 : 0);
 }
 
+// rk_sketches_from_host and rk_sketches_from_host64: one body over the width of the hashes (`arr`: d_hashes or d_hashes64)
+template <class Hash>
+int sketches_from_host(rk_ctx *ctx, const Hash *hashes, const uint64_t *off, uint32_t n, Hash *rk_sketches::*arr, rk_sketches **out)
+{
+    if (!ctx || !off || !out || (!hashes && off[n])) return RK_ERR_ARG;
+    *out = nullptr;
+    for (uint32_t g = 0; g < n; g++)
+        if (off[g + 1] < off[g]) return rk_fail(ctx, RK_ERR_ARG, "offsets must be non-decreasing");
+    if (off[0] != 0) return rk_fail(ctx, RK_ERR_ARG, "off[0] must be 0");
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    rk_sketches *s = new (std::nothrow) rk_sketches;
+    if (!s) return RK_ERR_NOMEM;
+    s->ctx = ctx;
+    s->n = n;
+    s->wide = sizeof(Hash) == 8;
+    s->total = off[n];
+    s->h_off.assign(off, off + n + 1);
+    SketchesGuard guard{s};
+    RK_TRY(pool_array(ctx, &(s->*arr), s->total + 1));
+    RK_TRY(pool_array(ctx, &s->d_off, (size_t)n + 1));
+    if (s->total) RK_HIP(ctx, hipMemcpyAsync(s->*arr, hashes, s->total * sizeof(Hash), hipMemcpyHostToDevice, ctx->stream));
+    RK_HIP(ctx, hipMemcpyAsync(s->d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    RK_TRY(rk_sketches_classify(ctx, s));  // synchronises the stream
+    guard.p = nullptr;
+    *out = s;
+    return RK_OK;
+}
+
+// rk_sketches_download and rk_sketches_download64 behind their refusals: the offsets from the host mirror, the hashes from the device
+template <class Hash> int sketches_download(const rk_sketches *s, const Hash *d_hashes, Hash *hashes, uint64_t *off)
+{
+    rk_ctx *ctx = s->ctx;
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    if (off) memcpy(off, s->h_off.data(), ((size_t)s->n + 1) * 8);
+    if (hashes && s->total) {
+        RK_HIP(ctx, hipMemcpyAsync(hashes, d_hashes, s->total * sizeof(Hash), hipMemcpyDeviceToHost, ctx->stream));
+        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return RK_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -796,30 +825,9 @@ uint64_t rk_sketches_windows(const rk_sketches *s) { return s ? s->windows : 0; 
 const uint32_t *rk_sketches_hashes_dev(const rk_sketches *s) { return s ? s->d_hashes : nullptr; }
 const uint64_t *rk_sketches_off_dev(const rk_sketches *s) { return s ? s->d_off : nullptr; }
 
-int rk_sketches_from_host(rk_ctx *ctx, const uint32_t *hashes, const uint64_t *off, uint32_t n,
-                          rk_sketches **out)
+int rk_sketches_from_host(rk_ctx *ctx, const uint32_t *hashes, const uint64_t *off, uint32_t n, rk_sketches **out)
 {
-    if (!ctx || !off || !out || (!hashes && off[n])) return RK_ERR_ARG;
-    *out = nullptr;
-    for (uint32_t g = 0; g < n; g++)
-        if (off[g + 1] < off[g]) return rk_fail(ctx, RK_ERR_ARG, "offsets must be non-decreasing");
-    if (off[0] != 0) return rk_fail(ctx, RK_ERR_ARG, "off[0] must be 0");
-    RK_HIP(ctx, hipSetDevice(ctx->device));
-    rk_sketches *s = new (std::nothrow) rk_sketches;
-    if (!s) return RK_ERR_NOMEM;
-    s->ctx = ctx;
-    s->n = n;
-    s->total = off[n];
-    s->h_off.assign(off, off + n + 1);
-    struct Guard { rk_sketches *p; ~Guard() { if (p) rk_sketches_free(p); } } guard{s};
-    RK_TRY(pool_array(ctx, &s->d_hashes, s->total + 1));
-    RK_TRY(pool_array(ctx, &s->d_off, (size_t)n + 1));
-    if (s->total) RK_HIP(ctx, hipMemcpyAsync(s->d_hashes, hashes, s->total * 4, hipMemcpyHostToDevice, ctx->stream));
-    RK_HIP(ctx, hipMemcpyAsync(s->d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    RK_TRY(rk_sketches_classify(ctx, s));  // synchronises the stream
-    guard.p = nullptr;
-    *out = s;
-    return RK_OK;
+    return sketches_from_host(ctx, hashes, off, n, &rk_sketches::d_hashes, out);
 }
 
 int rk_sketches_from_dev(rk_ctx *ctx, const uint32_t *hashes_dev, const uint64_t *off_dev, uint32_t n,
@@ -832,7 +840,7 @@ int rk_sketches_from_dev(rk_ctx *ctx, const uint32_t *hashes_dev, const uint64_t
     if (!s) return RK_ERR_NOMEM;
     s->ctx = ctx;
     s->n = n;
-    struct Guard { rk_sketches *p; ~Guard() { if (p) rk_sketches_free(p); } } guard{s};
+    SketchesGuard guard{s};
     s->h_off.resize((size_t)n + 1);
     RK_HIP(ctx, hipMemcpyAsync(s->h_off.data(), off_dev, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -858,56 +866,21 @@ int rk_sketches_is64(const rk_sketches *s) { return s && s->wide ? 1 : 0; }
 
 int rk_sketches_from_host64(rk_ctx *ctx, const uint64_t *hashes, const uint64_t *off, uint32_t n, rk_sketches **out)
 {
-    if (!ctx || !off || !out || (!hashes && off[n])) return RK_ERR_ARG;
-    *out = nullptr;
-    for (uint32_t g = 0; g < n; g++)
-        if (off[g + 1] < off[g]) return rk_fail(ctx, RK_ERR_ARG, "offsets must be non-decreasing");
-    if (off[0] != 0) return rk_fail(ctx, RK_ERR_ARG, "off[0] must be 0");
-    RK_HIP(ctx, hipSetDevice(ctx->device));
-    rk_sketches *s = new (std::nothrow) rk_sketches;
-    if (!s) return RK_ERR_NOMEM;
-    s->ctx = ctx;
-    s->n = n;
-    s->wide = true;
-    s->total = off[n];
-    s->h_off.assign(off, off + n + 1);
-    struct Guard { rk_sketches *p; ~Guard() { if (p) rk_sketches_free(p); } } guard{s};
-    RK_TRY(pool_array(ctx, &s->d_hashes64, s->total + 1));
-    RK_TRY(pool_array(ctx, &s->d_off, (size_t)n + 1));
-    if (s->total) RK_HIP(ctx, hipMemcpyAsync(s->d_hashes64, hashes, s->total * 8, hipMemcpyHostToDevice, ctx->stream));
-    RK_HIP(ctx, hipMemcpyAsync(s->d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    RK_TRY(rk_sketches_classify(ctx, s));
-    guard.p = nullptr;
-    *out = s;
-    return RK_OK;
+    return sketches_from_host(ctx, hashes, off, n, &rk_sketches::d_hashes64, out);
 }
 
 int rk_sketches_download64(const rk_sketches *s, uint64_t *hashes, uint64_t *off)
 {
     if (!s) return RK_ERR_ARG;
-    rk_ctx *ctx = s->ctx;
-    if (!s->wide) return rk_fail(ctx, RK_ERR_ARG, "32-bit sketches: use rk_sketches_download");
-    RK_HIP(ctx, hipSetDevice(ctx->device));
-    if (off) memcpy(off, s->h_off.data(), ((size_t)s->n + 1) * 8);
-    if (hashes && s->total) {
-        RK_HIP(ctx, hipMemcpyAsync(hashes, s->d_hashes64, s->total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return RK_OK;
+    if (!s->wide) return rk_fail(s->ctx, RK_ERR_ARG, "32-bit sketches: use rk_sketches_download");
+    return sketches_download(s, s->d_hashes64, hashes, off);
 }
 
 int rk_sketches_download(const rk_sketches *s, uint32_t *hashes, uint64_t *off)
 {
     if (!s) return RK_ERR_ARG;
-    rk_ctx *ctx = s->ctx;
-    if (s->wide && hashes) return rk_fail(ctx, RK_ERR_ARG, "64-bit sketches: use rk_sketches_download64");
-    RK_HIP(ctx, hipSetDevice(ctx->device));
-    if (off) memcpy(off, s->h_off.data(), ((size_t)s->n + 1) * 8);
-    if (hashes && s->total) {
-        RK_HIP(ctx, hipMemcpyAsync(hashes, s->d_hashes, s->total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return RK_OK;
+    if (s->wide && hashes) return rk_fail(s->ctx, RK_ERR_ARG, "64-bit sketches: use rk_sketches_download64");
+    return sketches_download(s, s->d_hashes, hashes, off);
 }
 
 int rk_sketch_packed_dev(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
@@ -1035,7 +1008,7 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
     s->n = n_genomes;
     s->wide = wide;
     s->is_set = true;  // sorted, distinct
-    struct Guard { rk_sketches *p; ~Guard() { if (p) rk_sketches_free(p); } } guard{s};
+    SketchesGuard guard{s};
     RK_TRY(pool_array(ctx, &s->d_off, (size_t)n_genomes + 1));
     s->h_off.assign((size_t)n_genomes + 1, 0);
 

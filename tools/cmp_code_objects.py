@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer check for refactors of host code: python3 tools/cmp_code_objects.py parent.o branch.o -- compares the gfx950 code objects of two builds of one translation unit, kernel by kernel:
-the set of symbols, every symbol's size, every kernel's metadata (registers, LDS, scratch, spills, kernarg) and code bytes."""
+the set of symbols, every symbol's size, every kernel's metadata (registers, LDS, scratch, spills, kernarg) and code bytes.
+A side may be several objects joined by commas (a unit that was split: parent.o branch.o,branch_new.o): their union is compared."""
 import re, subprocess, sys, os, tempfile
 B = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "")
 def load(o, tag):
@@ -30,7 +31,12 @@ def load(o, tag):
             cur[k] = v
         if cur is not None and k == "name" and v.startswith("_Z"): meta[v] = cur
     return syms, code, meta
-a, b = load(sys.argv[1], "a"), load(sys.argv[2], "b")
+def side(arg, tag):
+    syms, code, meta = {}, {}, {}
+    for o in arg.split(","):
+        for whole, part in zip((syms, code, meta), load(o, tag)): whole.update(part)
+    return syms, code, meta
+a, b = side(sys.argv[1], "a"), side(sys.argv[2], "b")
 bad = 0
 for n in sorted(set(a[0]) | set(b[0])):
     if n not in a[0] or n not in b[0]: print("only on one side:", n); bad += 1
