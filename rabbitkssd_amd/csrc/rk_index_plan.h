@@ -16,9 +16,8 @@ inline int shard_bits_of(uint32_t n_shards)
     return b;
 }
 
-// typed dispatch: f(HT()) with the sketches' hash type, f(K()) with the key type of the bucket sort (32 bits when (hash_low, genome)
+// typed dispatch (with_hash_type: rk_internal.h): f(K()) with the key type of the bucket sort (32 bits when (hash_low, genome)
 // fit them -- also what k_heads_place is instantiated with), f(T, K()) with the emission's block size as well
-template <class F> int with_hash_type(bool wide, F f) { return wide ? f(uint64_t()) : f(uint32_t()); }
 template <class F> int with_key_type(bool narrow, F f) { return narrow ? f(uint32_t()) : f((unsigned long long)0); }
 template <int T> using Threads = std::integral_constant<int, T>;
 template <class F> int with_emit_shape(int emit_t, bool narrow, F f)

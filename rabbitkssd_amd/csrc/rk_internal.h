@@ -203,6 +203,11 @@ struct rk_sketches {
     uint32_t *d_member_seg = nullptr;   // u32[2 * 8 * n]: starts, then counts
 };
 
+// typed dispatch over the width of the hashes: f(HT()) with HT uint32_t or uint64_t, and the hashes of sketches as HT
+template <class F> int with_hash_type(bool wide, F f) { return wide ? f(uint64_t()) : f(uint32_t()); }
+inline uint32_t *&hashes_of(rk_sketches *s, uint32_t) { return s->d_hashes; }
+inline uint64_t *&hashes_of(rk_sketches *s, uint64_t) { return s->d_hashes64; }
+
 struct rk_index {
     rk_ctx *ctx = nullptr;
     uint32_t n_ref = 0;

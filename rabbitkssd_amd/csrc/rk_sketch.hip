@@ -19,16 +19,18 @@
 // big LDS image variant holds an exact table), and the dr_tuple goes to the genome's candidate region.
 // Per-genome dedup (the reference's unordered_set): one workgroup per genome sorts its region in LDS
 // (k_dedup), a scan and a placement kernel build the CSR; one upload and one read-back per batch.
+// Host side of a pass (rk_sketch_packed_dev_ex): its arithmetic -- refusals, chunk length, pass table,
+// grid, buffer layout, candidate regions, retry rule -- is rk_sketch_pass.h (plain C++), the stages here launch what it planned.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "rk_internal.h"
+#include "rk_sketch_pass.h"
 
 namespace {
 
-constexpr int kSketchThreads = 1024;           // 16 waves share one LDS filter image
-constexpr int kWavesPerBlock = kSketchThreads / 64;
+constexpr int kSketchThreads = 64 * kWavesPerBlock;  // 16 waves share one LDS filter image
 // LDS filter image (one workgroup per CU):
 //   The inner 2*half_subk bases of a k-mer sit symmetrically inside it, so the dim_id of
 //   the canonical k-mer (src/sketch.cpp:508-509) is either d_f, the inner bases of the
@@ -68,18 +70,6 @@ template <int IMG> constexpr size_t stage_lds_bytes() { return kWavesPerBlock * 
 static_assert(Img<0>::kFilterLdsBytes + stage_lds_bytes<0>() <= 160 * 1024, "LDS image must fit one CU");
 static_assert(2 * (Img<1>::kFilterLdsBytes + stage_lds_bytes<1>()) <= 160 * 1024, "two small images must fit one CU");
 
-// per-genome row of the pass table (one small upload per pass): where the genome lies in the packed buffer, which
-// chunks (runs of `chunk_blocks` consecutive 1 KiB blocks, one wave each) are its own, and its candidate region
-struct GenomeRow {
-    uint64_t beg;          // byte offset in the packed buffer (multiple of 1024)
-    uint64_t reg_off;      // first slot of the candidate region
-    uint32_t nblk;         // 1 KiB blocks
-    uint32_t first_chunk;  // global index of its first chunk; row[n_genomes].first_chunk = number of chunks
-    uint32_t reg_cap;      // slots in the candidate region
-    uint32_t is_big;       // region beyond the LDS sort capacity: device-wide sort
-};
-static_assert(sizeof(GenomeRow) == 32, "GenomeRow is uploaded as raw bytes");
-
 struct SketchArgs {
     const uint8_t *packed;
     const GenomeRow *rows;
@@ -108,7 +98,6 @@ struct ChunkDesc {
     uint32_t gid;
 };
 static_assert(sizeof(ChunkDesc) == 16, "read as one uint4");
-constexpr uint32_t kTicketGroups = 32, kTicketStride = 32;  // counters, dwords between them
 
 // low 32 bits of the 96-bit string w2:w1:w0 shifted right by sh (0 <= sh < 96); with a compile-time sh this is one
 // v_alignbit_b32
@@ -477,13 +466,13 @@ __global__ __launch_bounds__(kSketchThreads, Img<IMG>::kWavesPerEu) void rk_sket
 // 16 waves per genome: a step of the sort is ~35 dependent instructions per wave, and one wave per SIMD issues them
 // one every few cycles (256 threads: 41 us for 128 genomes of ~1,250 candidates; 1,024: see DESIGN.md 4.1)
 constexpr uint32_t kDedupThreads = 1024;
-constexpr uint32_t kDedupMaxBytes = 64 * 1024;  // LDS sort capacity: 16,384 32-bit or 8,192 64-bit keys
 
 enum : uint32_t { kFlagOverflow = 1 };
 
 struct SketchTail {  // device-side results of one sketch pass, read back in one copy
     unsigned long long windows, flags;
 };
+static_assert(sizeof(SketchTail) == kTailBytes, "the head of the work buffer (PassLayout)");
 
 template <class K>
 __global__ __launch_bounds__(kDedupThreads) void k_dedup(const unsigned long long *cand, const GenomeRow *rows,
@@ -932,6 +921,290 @@ static int dedup_big(rk_ctx *ctx, unsigned long long *region, uint32_t n, int ha
     return RK_OK;
 }
 
+// ---- one sketch pass: rk_sketch_pass.h plans, the stages below launch ------------------------------------------------------
+namespace {
+
+// developer knobs of a pass: read from the environment at the top of EVERY call (tests change RK_SKETCH_CB between calls on one context)
+struct SketchKnobs {
+    uint64_t chunk_blocks;   // RK_SKETCH_CB: the chunk length, 1 .. 2^20 blocks; 0: not set, chunk_length() decides
+    uint32_t prio_turns;     // RK_SCAN2_PRIO (SketchArgs::prio_turns)
+    const char *trace_path;  // RK_SCAN2_TRACE=file: the per-wave trace of the two-stage scan (SketchArgs::trace)
+};
+SketchKnobs read_sketch_knobs()
+{
+    const char *cb = getenv("RK_SKETCH_CB"), *prio = getenv("RK_SCAN2_PRIO");
+    SketchKnobs k;
+    k.chunk_blocks = cb ? clamp_chunk_override(strtoull(cb, nullptr, 10)) : 0;
+    k.prio_turns = prio ? (uint32_t)atoi(prio) : 2u;
+    k.trace_path = getenv("RK_SCAN2_TRACE");
+    return k;
+}
+
+// what a pass owns: its plan, the device buffers with typed views of the work buffer (PassLayout), the sketches it fills and
+// what came home.  Every error exit returns the buffers to the pool and frees the sketches.
+struct SketchPass {
+    rk_ctx *ctx;
+    const rk_filter *f = nullptr;
+    const uint8_t *packed = nullptr;
+    uint32_t min_count = 1;
+    hipStream_t stream = nullptr;
+    int hash_bits = 0;
+    bool wide = false;  // use64 layout
+    SketchKnobs knobs = {};
+    sketch_kernel_t kern = nullptr;
+    PassPlan plan;
+    AttemptLayout lay;  // of the current attempt
+    SketchesGuard s{nullptr};
+    char *pinned = nullptr;  // one upload and one read-back through the pinned scratch
+    DevBuf<GenomeRow> d_rows;
+    DevBuf<ChunkDesc> d_chunks;
+    DevBuf<char> d_work;
+    DevBuf<unsigned long long> cand;
+    DevBuf<char> sorted_out;  // per genome its sorted distinct hashes, at its region's offset
+    SketchTail *d_tail = nullptr;
+    uint64_t *d_off_copy = nullptr;
+    uint32_t *d_gcount = nullptr, *d_usize = nullptr, *d_tickets = nullptr;
+    std::vector<uint32_t> gcount;
+    SketchTail tail{0, 0};
+    bool big_overflow = false;
+    explicit SketchPass(rk_ctx *c) : ctx(c), d_rows(c), d_chunks(c), d_work(c), cand(c), sorted_out(c) {}
+};
+
+int pass_plan(SketchPass &p, const uint64_t *gbeg, const uint64_t *gend, uint32_t n_genomes, uint64_t packed_bytes)
+{
+    const rk_params &P = p.f->params;
+    p.plan = plan_pass(gbeg, gend, n_genomes, packed_bytes, P.drlevel, p.wide ? 8 : 4, p.ctx->num_cu, p.f->img, p.knobs.chunk_blocks);
+    switch (p.plan.rule) {
+    case kPassRange: return rk_fail(p.ctx, p.plan.code, "genome %u: bad packed range", p.plan.bad_genome);
+    case kPassPadding: return rk_fail(p.ctx, p.plan.code, "packed buffer must be padded to a multiple of 1024 bytes");
+    case kPassBlocks: return rk_fail(p.ctx, p.plan.code, "genome %u is too long", p.plan.bad_genome);
+    case kPassCeiling: return rk_fail(p.ctx, p.plan.code, "genome %u is too long for one sketch pass", p.plan.bad_genome);
+    case kPassOk: break;
+    }
+    p.kern = pick_kernel((int)P.kmer_size, 2 * P.half_outctx_len, p.f->exact, p.f->img);
+    if (p.plan.n_chunks && !p.kern) return rk_fail(p.ctx, RK_ERR_UNSUPPORTED, "no scan kernel for this parameter set");
+    return RK_OK;
+}
+
+// device side of the pass: table in, results out; and the sketches object
+int pass_buffers(SketchPass &p)
+{
+    rk_ctx *ctx = p.ctx;
+    const PassLayout &at = p.plan.at;
+    const size_t n = p.plan.n_genomes, pin_bytes = std::max(p.plan.rows.size() * sizeof(GenomeRow), at.res_bytes);
+    p.pinned = static_cast<char *>(rk_pinned_scratch(ctx, pin_bytes));
+    if (!p.pinned) return rk_fail(ctx, RK_ERR_NOMEM, "cannot pin %llu bytes", (unsigned long long)pin_bytes);
+    RK_HIP(ctx, p.d_rows.alloc(p.plan.rows.size()));
+    RK_HIP(ctx, p.d_work.alloc(at.work_bytes));
+    p.d_tail = reinterpret_cast<SketchTail *>(p.d_work.p + at.tail);
+    p.d_off_copy = reinterpret_cast<uint64_t *>(p.d_work.p + at.off);
+    p.d_gcount = reinterpret_cast<uint32_t *>(p.d_work.p + at.gcount);
+    p.d_usize = reinterpret_cast<uint32_t *>(p.d_work.p + at.usize);
+    p.d_tickets = reinterpret_cast<uint32_t *>(p.d_work.p + at.tickets);
+    p.gcount.assign(n, 0);
+
+    rk_sketches *s = new (std::nothrow) rk_sketches;
+    if (!s) return RK_ERR_NOMEM;
+    p.s.p = s;
+    s->ctx = ctx;
+    s->n = p.plan.n_genomes;
+    s->wide = p.wide;
+    s->is_set = true;  // sorted, distinct
+    RK_TRY(pool_array(ctx, &s->d_off, n + 1));
+    s->h_off.assign(n + 1, 0);
+    return RK_OK;
+}
+
+// the candidate regions of this attempt and what is sized by them.  The CSR is allocated for the capacity (distinct hashes <=
+// candidates), so that its placement needs no count on the host: the whole pass runs without an intermediate synchronisation
+template <class H> int pass_layout_regions(SketchPass &p)
+{
+    p.lay = layout_attempt(p.plan.rows, p.plan.n_genomes, p.plan.key_bytes);
+    if (p.cand.alloc(p.lay.total_cap) != hipSuccess || p.sorted_out.alloc(p.lay.total_cap * sizeof(H)) != hipSuccess)
+        return rk_fail(p.ctx, RK_ERR_NOMEM, "cannot allocate %llu candidate slots", (unsigned long long)p.lay.total_cap);
+    H *&hashes = hashes_of(p.s.p, H());
+    rk_pool_free(p.ctx, hashes);
+    hashes = nullptr;
+    return pool_array(p.ctx, &hashes, p.lay.total_cap + 1);
+}
+
+// rk_sketch_last_plan: the record of this attempt (max_candidates follows with the read-back)
+void pass_record(const SketchPass &p, int attempt)
+{
+    const rk_params &P = p.f->params;
+    rk_sketch_plan &r = p.ctx->sketch_plan;
+    r = rk_sketch_plan{};
+    if (p.plan.n_chunks) kernel_name(r.kernel, sizeof(r.kernel), (int)P.kmer_size, 2 * P.half_outctx_len, p.f->exact, p.f->img);
+    r.image = p.f->img;
+    r.exact = p.f->exact ? 1 : 0;
+    r.chunk_blocks = p.plan.chunk_blocks;
+    r.n_chunks = p.plan.n_chunks;
+    r.grid = p.plan.grid;
+    r.n_groups = p.plan.n_groups;
+    r.attempts = (uint32_t)attempt + 1;
+    r.n_big = p.lay.n_big;
+    r.max_reg_cap = p.lay.max_reg_cap;
+    p.ctx->sketch_plan_set = true;
+}
+
+int pass_upload(SketchPass &p)
+{
+    const size_t rows_bytes = p.plan.rows.size() * sizeof(GenomeRow);
+    memcpy(p.pinned, p.plan.rows.data(), rows_bytes);
+    RK_HIP(p.ctx, hipMemcpyAsync(p.d_rows.p, p.pinned, rows_bytes, hipMemcpyHostToDevice, p.stream));
+    RK_HIP(p.ctx, hipMemsetAsync(p.d_work.p, 0, p.plan.at.work_bytes, p.stream));
+    return RK_OK;
+}
+
+SketchArgs scan_args(const SketchPass &p)
+{
+    const rk_params &P = p.f->params;
+    SketchArgs a;
+    a.packed = p.packed;
+    a.rows = p.d_rows.p;
+    a.n_genomes = p.plan.n_genomes;
+    a.n_chunks = p.plan.n_chunks;
+    a.chunk_blocks = p.plan.chunk_blocks;
+    a.filter_image = p.f->d_bitmap;
+    a.table = p.f->d_table;
+    a.tupmask = P.tupmask;
+    a.undomask0 = P.undomask0;
+    a.undomask1 = P.undomask1;
+    a.kmer = (int32_t)P.kmer_size;
+    a.out2 = 2 * P.half_outctx_len;
+    a.dim_bits = 4 * P.half_subk;
+    a.hi_shift = std::max(0, 4 * P.half_subk - (p.f->img ? Img<1>::kBitsB : Img<0>::kBitsB));  // unused by the two-stage scan
+    a.dim_start = P.dim_start;
+    a.dim_end = P.dim_end;
+    a.dr_shift = 4 * P.drlevel;
+    a.und1_shift = (int32_t)P.kmer_size * 2 - P.half_outctx_len * 4;
+    a.cand = p.cand.p;
+    a.gcount = p.d_gcount;
+    a.n_windows = &p.d_tail->windows;
+    a.tickets = p.d_tickets;
+    a.n_groups = p.plan.n_groups;
+    a.chunks = p.d_chunks.p;
+    a.prio_turns = p.knobs.prio_turns;
+    a.trace = nullptr;
+    return a;
+}
+
+// the chunk table, then the scan between the two timing events; the developer trace (RK_SCAN2_TRACE) around it
+int pass_scan(SketchPass &p)
+{
+    if (!p.plan.n_chunks) return RK_OK;
+    rk_ctx *ctx = p.ctx;
+    const uint32_t grid = p.plan.grid;
+    RK_HIP(ctx, p.d_chunks.alloc(p.plan.n_chunks));
+    hipLaunchKernelGGL(k_chunk_table, dim3(blocks_for(p.plan.n_chunks)), dim3(256), 0, p.stream, p.d_rows.p, p.plan.n_genomes, p.plan.n_chunks,
+                       p.plan.chunk_blocks, p.d_chunks.p);
+    SketchArgs a = scan_args(p);
+    DevBuf<unsigned long long> d_trace(ctx);
+    if (p.knobs.trace_path && p.f->img == 2) {
+        RK_HIP(ctx, d_trace.alloc((size_t)grid * kWavesPerBlock * 8));
+        RK_HIP(ctx, hipMemsetAsync(d_trace.p, 0, (size_t)grid * kWavesPerBlock * 64, p.stream));
+        a.trace = d_trace.p;
+    }
+    if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], p.stream));
+    hipLaunchKernelGGL(p.kern, dim3(grid), dim3(kSketchThreads), 0, p.stream, a);
+    if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], p.stream));
+    RK_HIP(ctx, hipGetLastError());
+    if (a.trace) {
+        std::vector<unsigned long long> h((size_t)grid * kWavesPerBlock * 8);
+        RK_HIP(ctx, hipMemcpyAsync(h.data(), a.trace, h.size() * 8, hipMemcpyDeviceToHost, p.stream));
+        RK_HIP(ctx, hipStreamSynchronize(p.stream));
+        if (FILE *fp = fopen(p.knobs.trace_path, "wb")) { fwrite(h.data(), 8, h.size(), fp); fclose(fp); }
+    }
+    return RK_OK;
+}
+
+// per-genome dedup in LDS; with the sizes and the placement below: three launches, no host round trip
+template <class H> int pass_dedup(SketchPass &p)
+{
+    if (!p.plan.n_genomes) return RK_OK;
+    if (p.lay.small_lds > 48 * 1024)
+        RK_HIP(p.ctx, hipFuncSetAttribute((const void *)k_dedup<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.small_lds));
+    hipLaunchKernelGGL(k_dedup<H>, dim3(p.plan.n_genomes), dim3(kDedupThreads), p.lay.small_lds, p.stream, p.cand.p, p.d_rows.p, p.d_gcount,
+                       p.min_count, (H *)p.sorted_out.p, p.d_usize, p.d_tail);
+    RK_HIP(p.ctx, hipGetLastError());
+    return RK_OK;
+}
+
+// 3 Gb genomes: their regions exceed the LDS sort; needs their candidate counts on the host
+template <class H> int pass_big_genomes(SketchPass &p)
+{
+    p.big_overflow = false;
+    if (!p.lay.any_big) return RK_OK;
+    rk_ctx *ctx = p.ctx;
+    const std::vector<GenomeRow> &rows = p.plan.rows;
+    const uint32_t n_genomes = p.plan.n_genomes;
+    RK_HIP(ctx, hipMemcpyAsync(p.gcount.data(), p.d_gcount, (size_t)n_genomes * 4, hipMemcpyDeviceToHost, p.stream));
+    RK_HIP(ctx, hipStreamSynchronize(p.stream));
+    for (uint32_t g = 0; g < n_genomes && !p.big_overflow; g++) p.big_overflow = rows[g].is_big && p.gcount[g] > rows[g].reg_cap;
+    for (uint32_t g = 0; g < n_genomes && !p.big_overflow; g++) {
+        if (!rows[g].is_big) continue;
+        uint32_t nu = 0;
+        RK_TRY(dedup_big<H>(ctx, p.cand.p + rows[g].reg_off, p.gcount[g], p.hash_bits, p.min_count, (H *)p.sorted_out.p + rows[g].reg_off, &nu, p.stream));
+        memcpy(p.pinned, &nu, 4);
+        RK_HIP(ctx, hipMemcpyAsync(p.d_usize + g, p.pinned, 4, hipMemcpyHostToDevice, p.stream));
+        RK_HIP(ctx, hipStreamSynchronize(p.stream));  // the pinned word is reused
+    }
+    return RK_OK;
+}
+
+// sizes -> offsets, then every genome's hashes to their place in the CSR
+template <class H> int pass_place(SketchPass &p)
+{
+    rk_sketches *s = p.s.p;
+    hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(1024), 0, p.stream, p.d_usize, p.plan.n_genomes, s->d_off, p.d_off_copy);
+    if (p.plan.n_genomes)
+        hipLaunchKernelGGL(k_csr_place<H>, dim3(p.plan.n_genomes), dim3(256), 0, p.stream, (const H *)p.sorted_out.p, p.d_rows.p, p.d_usize, s->d_off,
+                           hashes_of(s, H()));
+    RK_HIP(p.ctx, hipGetLastError());
+    return RK_OK;
+}
+
+// the one read-back of the common case: window count, offsets, candidate counts (for the retry)
+int pass_read_back(SketchPass &p)
+{
+    const PassLayout &at = p.plan.at;
+    const size_t n = p.plan.n_genomes;
+    RK_HIP(p.ctx, hipMemcpyAsync(p.pinned, p.d_work.p, at.res_bytes, hipMemcpyDeviceToHost, p.stream));
+    RK_HIP(p.ctx, hipStreamSynchronize(p.stream));
+    memcpy(&p.tail, p.pinned + at.tail, sizeof(p.tail));
+    memcpy(p.s.p->h_off.data(), p.pinned + at.off, (n + 1) * 8);
+    if (n) memcpy(p.gcount.data(), p.pinned + at.gcount, n * 4);
+    return RK_OK;
+}
+
+template <class H> int pass_attempt(SketchPass &p, int attempt)
+{
+    RK_TRY(pass_layout_regions<H>(p));
+    pass_record(p, attempt);
+    RK_TRY(pass_upload(p));
+    RK_TRY(pass_scan(p));
+    RK_TRY(pass_dedup<H>(p));
+    RK_TRY(pass_big_genomes<H>(p));
+    RK_TRY(pass_place<H>(p));
+    return pass_read_back(p);
+}
+
+rk_sketches *pass_finish(SketchPass &p)
+{
+    rk_ctx *ctx = p.ctx;
+    rk_sketches *s = p.s.p;
+    if (ctx->timing && p.plan.n_chunks) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_SKETCH_KERNEL] = ms;
+    }
+    s->windows = p.tail.windows;
+    s->total = s->h_off[s->n];
+    for (uint32_t g = 0; g < s->n; g++) s->max_size = std::max<uint64_t>(s->max_size, s->h_off[g + 1] - s->h_off[g]);
+    p.s.p = nullptr;
+    return s;
+}
+}  // namespace
+
 extern "C" {
 
 int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
@@ -941,240 +1214,26 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
     if (!ctx || !f || !out || (!packed_dev && packed_bytes) || ((!gbeg || !gend) && n_genomes))
         return RK_ERR_ARG;
     *out = nullptr;
-    hipStream_t stream = (hipStream_t)stream_v;
     RK_HIP(ctx, hipSetDevice(ctx->device));
-    const rk_params &P = f->params;
-    const int hash_bits = rk_hash_bits(&P);
-    const bool wide = hash_bits > 32;  // use64 layout
-    const size_t key_bytes = wide ? 8 : 4;
-
-    // ---- the pass table: one row per genome (one wave walks one chunk of `cb` consecutive 1 KiB blocks)
-    uint64_t total_blocks = 0;
-    for (uint32_t g = 0; g < n_genomes; g++) {
-        if (gend[g] < gbeg[g] || (gbeg[g] & 1023) || gend[g] > packed_bytes)
-            return rk_fail(ctx, RK_ERR_ARG, "genome %u: bad packed range", g);
-        if (((gend[g] + 1023) & ~1023ULL) > packed_bytes && gend[g] > gbeg[g])
-            return rk_fail(ctx, RK_ERR_ARG, "packed buffer must be padded to a multiple of 1024 bytes");
-        if (((gend[g] - gbeg[g] + 1023) >> 10) > 0x7FFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "genome %u is too long", g);
-        total_blocks += (gend[g] - gbeg[g] + 1023) >> 10;
-    }
-    // Chunk length: (nearly) the smallest for which there are at most two chunks per wave (2 workgroups of 16 waves per CU).
-    // The waves run at the same speed, so the kernel lasts ceil(chunks / waves) chunks whatever the order they are
-    // handed out in: 2.4 chunks per wave cost three rounds (measured: 32 blocks 0.242 ms, 38 blocks 0.211 ms on
-    // 128 x 5 Mb); and a chunk has a fixed cost (its genome's row, the 32 bases before it, the last partial rounds
-    // of its queues), so more and shorter chunks are slower too (20 blocks: 0.245 ms).
-    // (a genome adds at most one partial chunk: total / len + n_genomes bounds the count from above)
-    const uint64_t wave_slots = (uint64_t)ctx->num_cu * 2 * kWavesPerBlock, limit = 2 * wave_slots;
-    uint64_t cb = n_genomes < limit ? (total_blocks + (limit - n_genomes) - 1) / (limit - n_genomes) : (total_blocks + limit - 1) / limit;
-    cb = std::min<uint64_t>(1u << 20, std::max<uint64_t>(16, cb));
-    if (getenv("RK_SKETCH_CB")) cb = std::min<uint64_t>(1u << 20, std::max<uint64_t>(1, strtoull(getenv("RK_SKETCH_CB"), nullptr, 10)));
-    std::vector<GenomeRow> rows((size_t)n_genomes + 1);
-    uint64_t n_chunks64 = 0;
-    for (uint32_t g = 0; g < n_genomes; g++) {
-        GenomeRow &r = rows[g];
-        r.beg = gbeg[g];
-        r.nblk = (uint32_t)((gend[g] - gbeg[g] + 1023) >> 10);
-        r.first_chunk = (uint32_t)n_chunks64;
-        n_chunks64 += (r.nblk + cb - 1) / cb;
-        // candidate region: expected survivors = windows / 16^drlevel; x2 + slack, exact retry on overflow
-        const uint64_t want = 2 * ((gend[g] - gbeg[g]) >> (4 * P.drlevel)) + 192;
-        if (want > 0xFFFFFFF0ULL || n_chunks64 > 0xFFFFFFF0ULL)
-            return rk_fail(ctx, RK_ERR_UNSUPPORTED, "genome %u is too long for one sketch pass", g);
-        r.reg_cap = (uint32_t)want;
-    }
-    const uint32_t n_chunks = (uint32_t)n_chunks64;
-    rows[n_genomes] = GenomeRow{0, 0, 0, n_chunks, 0, 0};
-
-    // device side of the pass: table in, results out -- one upload and one read-back through the pinned scratch
-    const size_t rows_bytes = rows.size() * sizeof(GenomeRow);
-    const size_t res_bytes = sizeof(SketchTail) + ((size_t)n_genomes + 1) * 8 + (size_t)n_genomes * 4;  // tail | off | gcount
-    char *pinned = static_cast<char *>(rk_pinned_scratch(ctx, std::max(rows_bytes, res_bytes)));
-    if (!pinned) return rk_fail(ctx, RK_ERR_NOMEM, "cannot pin %llu bytes", (unsigned long long)std::max(rows_bytes, res_bytes));
-    DevBuf<GenomeRow> d_rows(ctx);
-    DevBuf<ChunkDesc> d_chunks(ctx);
-    DevBuf<char> d_res(ctx);  // tail | off | gcount (read back) | per-genome sketch sizes: cleared with ONE fill per pass
-    const size_t tickets_off = (res_bytes + (size_t)n_genomes * 4 + 127) & ~(size_t)127;
-    const size_t work_bytes = tickets_off + kTicketGroups * kTicketStride * 4;  // ... | the scan kernel's ticket counters
-    RK_HIP(ctx, d_rows.alloc(rows.size()));
-    RK_HIP(ctx, d_res.alloc(work_bytes));
-    SketchTail *d_tail = reinterpret_cast<SketchTail *>(d_res.p);
-    uint64_t *d_off_copy = reinterpret_cast<uint64_t *>(d_res.p + sizeof(SketchTail));
-    uint32_t *d_gcount = reinterpret_cast<uint32_t *>(d_res.p + sizeof(SketchTail) + ((size_t)n_genomes + 1) * 8);
-    struct { uint32_t *p; } d_usize{d_gcount + n_genomes};
-
-    rk_sketches *s = new (std::nothrow) rk_sketches;
-    if (!s) return RK_ERR_NOMEM;
-    s->ctx = ctx;
-    s->n = n_genomes;
-    s->wide = wide;
-    s->is_set = true;  // sorted, distinct
-    SketchesGuard guard{s};
-    RK_TRY(pool_array(ctx, &s->d_off, (size_t)n_genomes + 1));
-    s->h_off.assign((size_t)n_genomes + 1, 0);
-
-    sketch_kernel_t kern = pick_kernel((int)P.kmer_size, 2 * P.half_outctx_len, f->exact, f->img);
-    DevBuf<unsigned long long> cand(ctx);
-    DevBuf<char> sorted_out(ctx);
-    std::vector<uint32_t> gcount(n_genomes, 0);
-    SketchTail tail{0, 0};
-    rk_sketch_plan &plan = ctx->sketch_plan;  // rk_sketch_last_plan
-    plan = rk_sketch_plan{};
-    plan.image = f->img;
-    plan.exact = f->exact ? 1 : 0;
-    plan.chunk_blocks = (uint32_t)cb;
-    plan.n_chunks = n_chunks;
-    ctx->sketch_plan_set = true;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        plan.attempts = (uint32_t)attempt + 1;
-        plan.n_big = plan.max_candidates = plan.max_reg_cap = 0;
-        uint64_t total_cap = 0;
-        size_t small_lds = key_bytes;
-        bool any_big = false;
-        for (uint32_t g = 0; g < n_genomes; g++) {
-            rows[g].reg_off = total_cap;
-            total_cap += rows[g].reg_cap;
-            size_t p2 = 1;
-            while (p2 < rows[g].reg_cap) p2 <<= 1;
-            rows[g].is_big = p2 * key_bytes > kDedupMaxBytes;
-            plan.max_reg_cap = std::max(plan.max_reg_cap, rows[g].reg_cap);
-            if (rows[g].is_big) { any_big = true; plan.n_big++; }
-            else small_lds = std::max(small_lds, p2 * key_bytes);
-        }
-        if (cand.alloc(total_cap) != hipSuccess || sorted_out.alloc(total_cap * key_bytes) != hipSuccess)
-            return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu candidate slots", (unsigned long long)total_cap);
-        // the CSR is allocated for the capacity (distinct hashes <= candidates), so that its placement needs no
-        // count on the host: the whole pass runs without an intermediate synchronisation
-        if (wide) { rk_pool_free(ctx, s->d_hashes64); s->d_hashes64 = nullptr; RK_TRY(pool_array(ctx, &s->d_hashes64, total_cap + 1)); }
-        else { rk_pool_free(ctx, s->d_hashes); s->d_hashes = nullptr; RK_TRY(pool_array(ctx, &s->d_hashes, total_cap + 1)); }
-        memcpy(pinned, rows.data(), rows_bytes);
-        RK_HIP(ctx, hipMemcpyAsync(d_rows.p, pinned, rows_bytes, hipMemcpyHostToDevice, stream));
-        RK_HIP(ctx, hipMemsetAsync(d_res.p, 0, work_bytes, stream));
-        if (n_chunks) {
-            SketchArgs a;
-            a.packed = packed_dev;
-            a.rows = d_rows.p;
-            a.n_genomes = n_genomes;
-            a.n_chunks = n_chunks;
-            a.chunk_blocks = (uint32_t)cb;
-            a.filter_image = f->d_bitmap;
-            a.table = f->d_table;
-            a.tupmask = P.tupmask;
-            a.dim_bits = 4 * P.half_subk;
-            a.hi_shift = std::max(0, 4 * P.half_subk - (f->img ? Img<1>::kBitsB : Img<0>::kBitsB));  // unused by the two-stage scan
-            a.undomask0 = P.undomask0;
-            a.undomask1 = P.undomask1;
-            a.kmer = (int32_t)P.kmer_size;
-            a.out2 = 2 * P.half_outctx_len;
-            a.dim_start = P.dim_start;
-            a.dim_end = P.dim_end;
-            a.dr_shift = 4 * P.drlevel;
-            a.und1_shift = (int32_t)P.kmer_size * 2 - P.half_outctx_len * 4;
-            a.cand = cand.p;
-            a.gcount = d_gcount;
-            a.n_windows = &d_tail->windows;
-            const uint32_t want = (n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-            // persistent: as many workgroups as the LDS image admits per CU (two; one with the 144 KiB image), the filter
-            // image staged once per workgroup; chunks by table and ticket (chunk_range)
-            uint32_t grid = std::min<uint32_t>(want, (uint32_t)ctx->num_cu * (f->img ? 2u : 1u));
-            RK_HIP(ctx, d_chunks.alloc(n_chunks));
-            hipLaunchKernelGGL(k_chunk_table, dim3(blocks_for(n_chunks)), dim3(256), 0, stream, d_rows.p, n_genomes, n_chunks, (uint32_t)cb, d_chunks.p);
-            a.chunks = d_chunks.p;
-            a.n_groups = std::max(1u, std::min(grid / 16, kTicketGroups));
-            if (a.n_groups > 1) grid -= grid % (8 * a.n_groups);
-            a.tickets = reinterpret_cast<uint32_t *>(d_res.p + tickets_off);
-            a.prio_turns = getenv("RK_SCAN2_PRIO") ? (uint32_t)atoi(getenv("RK_SCAN2_PRIO")) : 2u;
-            a.trace = nullptr;
-            DevBuf<unsigned long long> d_trace(ctx);
-            const char *trace_path = getenv("RK_SCAN2_TRACE");
-            if (trace_path && f->img == 2) {
-                RK_HIP(ctx, d_trace.alloc((size_t)grid * kWavesPerBlock * 8));
-                RK_HIP(ctx, hipMemsetAsync(d_trace.p, 0, (size_t)grid * kWavesPerBlock * 64, stream));
-                a.trace = d_trace.p;
-            }
-            if (!kern) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "no scan kernel for this parameter set");
-            kernel_name(plan.kernel, sizeof(plan.kernel), (int)P.kmer_size, 2 * P.half_outctx_len, f->exact, f->img);
-            plan.grid = grid;
-            plan.n_groups = a.n_groups;
-            if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kSketchThreads), 0, stream, a);
-            if (ctx->timing) RK_HIP(ctx, hipEventRecord(ctx->ev[1], stream));
-            RK_HIP(ctx, hipGetLastError());
-            if (a.trace) {
-                std::vector<unsigned long long> h((size_t)grid * kWavesPerBlock * 8);
-                RK_HIP(ctx, hipMemcpyAsync(h.data(), a.trace, h.size() * 8, hipMemcpyDeviceToHost, stream));
-                RK_HIP(ctx, hipStreamSynchronize(stream));
-                if (FILE *fp = fopen(trace_path, "wb")) { fwrite(h.data(), 8, h.size(), fp); fclose(fp); }
-            }
-        }
-        if (n_genomes) {
-            // ---- per-genome dedup in LDS, sizes -> offsets, CSR placement: three launches, no host round trip
-            if (wide) {
-                if (small_lds > 48 * 1024)
-                    RK_HIP(ctx, hipFuncSetAttribute((const void *)k_dedup<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds));
-                hipLaunchKernelGGL(k_dedup<uint64_t>, dim3(n_genomes), dim3(kDedupThreads), small_lds, stream, cand.p, d_rows.p,
-                                   d_gcount, min_count, (uint64_t *)sorted_out.p, d_usize.p, d_tail);
-            } else {
-                if (small_lds > 48 * 1024)
-                    RK_HIP(ctx, hipFuncSetAttribute((const void *)k_dedup<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds));
-                hipLaunchKernelGGL(k_dedup<uint32_t>, dim3(n_genomes), dim3(kDedupThreads), small_lds, stream, cand.p, d_rows.p,
-                                   d_gcount, min_count, (uint32_t *)sorted_out.p, d_usize.p, d_tail);
-            }
-            RK_HIP(ctx, hipGetLastError());
-        }
-        bool big_overflow = false;
-        if (any_big) {  // 3 Gb genomes: their regions exceed the LDS sort; needs their candidate counts on the host
-            RK_HIP(ctx, hipMemcpyAsync(gcount.data(), d_gcount, (size_t)n_genomes * 4, hipMemcpyDeviceToHost, stream));
-            RK_HIP(ctx, hipStreamSynchronize(stream));
-            for (uint32_t g = 0; g < n_genomes && !big_overflow; g++) big_overflow = rows[g].is_big && gcount[g] > rows[g].reg_cap;
-            for (uint32_t g = 0; g < n_genomes && !big_overflow; g++) {
-                if (!rows[g].is_big) continue;
-                uint32_t nu = 0;
-                if (wide)
-                    RK_TRY(dedup_big<uint64_t>(ctx, cand.p + rows[g].reg_off, gcount[g], hash_bits, min_count,
-                                               (uint64_t *)sorted_out.p + rows[g].reg_off, &nu, stream));
-                else
-                    RK_TRY(dedup_big<uint32_t>(ctx, cand.p + rows[g].reg_off, gcount[g], hash_bits, min_count,
-                                               (uint32_t *)sorted_out.p + rows[g].reg_off, &nu, stream));
-                memcpy(pinned, &nu, 4);
-                RK_HIP(ctx, hipMemcpyAsync(d_usize.p + g, pinned, 4, hipMemcpyHostToDevice, stream));
-                RK_HIP(ctx, hipStreamSynchronize(stream));  // the pinned word is reused
-            }
-        }
-        hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(1024), 0, stream, d_usize.p, n_genomes, s->d_off, d_off_copy);
-        if (n_genomes) {
-            if (wide)
-                hipLaunchKernelGGL(k_csr_place<uint64_t>, dim3(n_genomes), dim3(256), 0, stream, (const uint64_t *)sorted_out.p,
-                                   d_rows.p, d_usize.p, s->d_off, s->d_hashes64);
-            else
-                hipLaunchKernelGGL(k_csr_place<uint32_t>, dim3(n_genomes), dim3(256), 0, stream, (const uint32_t *)sorted_out.p,
-                                   d_rows.p, d_usize.p, s->d_off, s->d_hashes);
-        }
-        RK_HIP(ctx, hipGetLastError());
-        // ---- the one read-back of the common case: window count, offsets, candidate counts (for the retry)
-        RK_HIP(ctx, hipMemcpyAsync(pinned, d_res.p, res_bytes, hipMemcpyDeviceToHost, stream));
-        RK_HIP(ctx, hipStreamSynchronize(stream));
-        memcpy(&tail, pinned, sizeof(tail));
-        memcpy(s->h_off.data(), pinned + sizeof(SketchTail), ((size_t)n_genomes + 1) * 8);
-        if (n_genomes) memcpy(gcount.data(), pinned + sizeof(SketchTail) + ((size_t)n_genomes + 1) * 8, (size_t)n_genomes * 4);
-        bool overflow = big_overflow || (tail.flags & kFlagOverflow) != 0;
-        for (uint32_t g = 0; g < n_genomes; g++) plan.max_candidates = std::max(plan.max_candidates, gcount[g]);
-        for (uint32_t g = 0; g < n_genomes; g++)
-            if (gcount[g] > rows[g].reg_cap) {
-                overflow = true;
-                rows[g].reg_cap = gcount[g];  // exact on the second pass
-            }
-        if (!overflow) break;
+    SketchPass p(ctx);
+    p.f = f;
+    p.packed = packed_dev;
+    p.min_count = min_count;
+    p.stream = (hipStream_t)stream_v;
+    p.hash_bits = rk_hash_bits(&f->params);
+    p.wide = p.hash_bits > 32;
+    p.knobs = read_sketch_knobs();
+    RK_TRY(pass_plan(p, gbeg, gend, n_genomes, packed_bytes));
+    RK_TRY(pass_buffers(p));
+    for (int attempt = 0;; attempt++) {
+        RK_TRY(with_hash_type(p.wide, [&](auto ht) -> int { return pass_attempt<decltype(ht)>(p, attempt); }));
+        const bool overflowed = p.big_overflow || (p.tail.flags & kFlagOverflow) != 0;
+        const RetryOutcome r = retry_rule(p.plan.rows, n_genomes, p.gcount.data(), overflowed);
+        ctx->sketch_plan.max_candidates = r.max_candidates;
+        if (!r.again) break;
         if (attempt == 1) return rk_fail(ctx, RK_ERR_CAPACITY, "candidate overflow persisted");
     }
-    if (ctx->timing && n_chunks) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->last_ms[RK_MS_SKETCH_KERNEL] = ms;
-    }
-    s->windows = tail.windows;
-    s->total = s->h_off[n_genomes];
-    for (uint32_t g = 0; g < n_genomes; g++) s->max_size = std::max<uint64_t>(s->max_size, s->h_off[g + 1] - s->h_off[g]);
-    guard.p = nullptr;
-    *out = s;
+    *out = pass_finish(p);
     return RK_OK;
 }
 
@@ -1232,11 +1291,11 @@ static int check_sets(rk_ctx *ctx, rk_sketches *s, bool *ascending)
     RK_HIP(ctx, bad.alloc(1));
     RK_HIP(ctx, hipMemsetAsync(bad.p, 0, 4, ctx->stream));
     if (s->n && s->total > 1) {
-        const unsigned blocks = blocks_for(s->total - 1);
-        if (s->wide)
-            hipLaunchKernelGGL(k_check_sets<uint64_t>, dim3(blocks), dim3(256), 0, ctx->stream, s->d_hashes64, s->total, s->d_off, s->n, bad.p);
-        else
-            hipLaunchKernelGGL(k_check_sets<uint32_t>, dim3(blocks), dim3(256), 0, ctx->stream, s->d_hashes, s->total, s->d_off, s->n, bad.p);
+        RK_TRY(with_hash_type(s->wide, [&](auto ht) -> int {
+            hipLaunchKernelGGL(k_check_sets<decltype(ht)>, dim3(blocks_for(s->total - 1)), dim3(256), 0, ctx->stream, hashes_of(s, ht), s->total,
+                               s->d_off, s->n, bad.p);
+            return RK_OK;
+        }));
         RK_HIP(ctx, hipGetLastError());
     }
     uint32_t b = 0;
@@ -1261,21 +1320,18 @@ int rk_sketches_classify(rk_ctx *ctx, rk_sketches *s)
     RK_TRY(check_sets(ctx, s, &ascending));
     if (!ascending && s->total < 0xFFFFFFFFULL) {
         const unsigned int n = (unsigned int)s->total;
-        if (s->wide) {
-            DevBuf<uint64_t> sorted(ctx);
+        RK_TRY(with_hash_type(s->wide, [&](auto ht) -> int {
+            using H = decltype(ht);
+            H *&hashes = hashes_of(s, ht);
+            DevBuf<H> sorted(ctx);
             RK_HIP(ctx, sorted.alloc(s->total + 1));
-            RK_TRY(rk_prim_segmented_sort_u64(ctx, s->d_hashes64, sorted.p, n, s->n, s->d_off, ctx->stream));
+            if constexpr (sizeof(H) == 8) RK_TRY(rk_prim_segmented_sort_u64(ctx, hashes, sorted.p, n, s->n, s->d_off, ctx->stream));
+            else RK_TRY(rk_prim_segmented_sort_u32(ctx, hashes, sorted.p, n, s->n, s->d_off, ctx->stream));
             RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            rk_pool_free(ctx, s->d_hashes64);
-            s->d_hashes64 = sorted.release();
-        } else {
-            DevBuf<uint32_t> sorted(ctx);
-            RK_HIP(ctx, sorted.alloc(s->total + 1));
-            RK_TRY(rk_prim_segmented_sort_u32(ctx, s->d_hashes, sorted.p, n, s->n, s->d_off, ctx->stream));
-            RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            rk_pool_free(ctx, s->d_hashes);
-            s->d_hashes = sorted.release();
-        }
+            rk_pool_free(ctx, hashes);
+            hashes = sorted.release();
+            return RK_OK;
+        }));
         RK_TRY(check_sets(ctx, s, &ascending));  // still not strictly ascending: some genome repeats a hash
     }
     s->is_set = ascending;

@@ -213,6 +213,29 @@ def test_many_genomes_with_empty_ones_between(n):
         ctx.close()
 
 
+def test_calls_that_scan_nothing():
+    """no genomes, and genomes of no bytes: no chunk, so no scan kernel -- the record says kernel "" and grid 0 -- while the sizes,
+    offsets and the read-back still run; then empty genomes around one of 1,025 bytes"""
+    ps = sr.param_set(8, 5, 2)
+    rng = np.random.default_rng(5)
+    empty = (np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64))   # a genome without records
+    ctx = capi.Context(0)
+    try:
+        for genomes in ([], [empty, one(np.zeros(0, dtype=np.uint8)), empty]):
+            sk, plan = sketch(ctx, ps, genomes)
+            assert (plan["kernel"], plan["grid"], plan["n_chunks"], plan["attempts"]) == ("", 0, 0, 1)
+            gh, goff = sk.download()
+            assert sk.count == len(genomes) and len(goff) == len(genomes) + 1 and not np.any(goff) and len(gh) == 0
+            assert sk.windows == 0 and sk.total == 0
+        genomes = [empty, empty, one(sr.dense(ps, rng, 1025 // ps.k + 1)[:1025]), empty]
+        wants = oracle_sets(ps, genomes)
+        assert [len(h) > 0 for h, _ in wants] == [False, False, True, False]
+        plan = run(ctx, ps, genomes, wants=wants)
+        assert (plan["n_chunks"], plan["grid"], plan["attempts"]) == (1, 1, 1) and plan["kernel"] != ""
+    finally:
+        ctx.close()
+
+
 def test_more_genomes_than_twice_the_wave_slots():
     """the second branch of the chunk-length formula (n_genomes >= 2 * wave slots)"""
     ps = sr.param_set(8, 5, 2)
