@@ -30,6 +30,9 @@
  *   rk_medoid_rows         <- the same row loop, followed by what its users compute per cluster of any of the above from the
  *                             printed pairs: the most central member (the representative dRep, GTDB and galah print), the
  *                             cluster's density and weakest pair, every genome's nearest genome outside its cluster
+ *   rk_assign_rows         <- row loop of index_dist     src/dist.cpp:560-692 (without -N), followed by what its users do
+ *                             with the printed pairs of new genomes against a clustered collection: the cluster of the
+ *                             nearest labelled reference, its support, the runner-up cluster, novelty
  *
  * Conventions
  *   - plain C types only; every call returns 0 on success or a negative rk_status and
@@ -125,6 +128,8 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4]);
 #define RK_MS_MREACH 10
 /* rk_medoid_rows with timing on: sums sweep through gather kernel of the last call (0 when the call took the host path). */
 #define RK_MS_MEDOID 11
+/* rk_assign_rows with timing on: first sweep through gather kernel of the last call (0 when the call took the host path). */
+#define RK_MS_ASSIGN 12
 void rk_ctx_set_timing(rk_ctx *ctx, int on);
 /* A process that makes ONE pass (a command-line tool) says so: the library then keeps work on the host where the device path
  * would first have to load a code object that costs more than it saves on a single call (today: ordering up to 2^18 hit
@@ -891,6 +896,72 @@ int rk_medoid_merge(const rk_medoid_genomes *a, const rk_medoid_genomes *b, uint
  * may be NULL when n == 0) and for a label that is neither below n nor RK_MEDOID_NONE. */
 int rk_medoid_pick(const uint32_t *labels /* n */, const rk_medoid_genomes *g, uint32_t n, int metric, rk_medoid_cluster **out,
                    uint32_t *n_out);
+
+/* ---- placement of query genomes into a labelled collection --------------------------- */
+/* What a user does next with a clustered collection and NEW genomes: for each query, which cluster it belongs to, how well supported
+ * that placement is, which cluster is the runner-up, whether the genome is novel.  All of it is sums and extrema over the hit records
+ * of the QUERY join, grouped by a label array of N words.
+ * Graph.  The records rk_dist_rows(ctx, idx, queries, opts, ...) would report with triangle = 0 -- same metric, the reference's NON-strict
+ * threshold (dist <= max_dist decided with the C library's log), same row_first / row_step / row_block selection of QUERY rows.  A
+ * record has row = query, col = reference, size0 = |reference|, size1 = |query|.
+ * Labels.  labels[r] (host, rk_index_genomes(idx) = N entries in the caller's reference order): a value below N names r's cluster,
+ * RK_ASSIGN_NONE (the value of RK_DBSCAN_NOISE) means r is unlabelled; anything else is RK_ERR_ARG.  The outputs of rk_cluster_rows,
+ * rk_dbscan_rows, rk_forest_cut, rk_mreach_cut and rep_out of rk_greedy_rows are all of this form; for DBSCAN "predict" the caller sets
+ * the non-core genomes to RK_ASSIGN_NONE.  An unlabelled reference is counted but never anchors a query.
+ * Per selected query q.  n_within[q]: q's records.  n_labelled[q]: those whose reference is labelled.  nearest[q]: the record of q's
+ * nearest LABELLED reference in the order of rk_knn_rows restricted to q: the ratio common / u descending, compared exactly (25/75 ties
+ * 20/60), then the reference's caller index ascending; u as in rk_forest_rows (size0 + size1 - common for metric 0, min(size0, size1)
+ * for metric 1).  label[q] = labels[nearest[q].col], or RK_ASSIGN_NONE when q has no labelled record: such a q is NOVEL.  n_same[q]: q's
+ * records whose reference carries label[q] -- the support of the placement (0 for a novel q).  runner_up[q]: the nearest record of q,
+ * in the same order, whose reference is labelled with a label OTHER than label[q] -- how ambiguous the placement is; absent when
+ * there is none.  An absent record (nearest of a novel q, a missing runner-up) has row = col = RK_ASSIGN_NONE and zeros elsewhere, as
+ * rk_medoid_rows writes them.
+ * Records.  The two record arrays are optional.  A present record is the hit as the join reports it (pad_ 0), jorc and dist recomputed
+ * on the host with the C library's log -- the reference's values bit for bit.
+ * The result is unique: it does not depend on the order of hits, the internal genome order or the query kernel the join took.
+ * Entries of unselected query rows are NOT WRITTEN, and a query's result depends on its own records alone: row shards and GPUs
+ * compose by writing into one set of arrays, no merge call is needed.  (Sharding by REFERENCES is not offered: n_same does not compose.)
+ * The hit records never leave the device (the frame of rk_medoid_rows over the query join: rk_dist_rows_dev with the threshold widened
+ * by 2^-46, the key pass with its small host buffer of RK_CLUSTER_EDGE_CAP borderline records and their slot numbers, both retries; the
+ * host decides the borderline records with `<=` BEFORE anything is counted and sends the slot numbers of the kept ones back).  The
+ * labels go up once (4 * N bytes).  Then: a first sweep (integer atomic adds on n_within and n_labelled, a 64-bit atomic minimum of
+ * the weight key of a labelled record at its query), a settle sweep (a 32-bit atomic minimum of the reference's index among the records
+ * that match their query's key), one thread per query for label[q], a second sweep (the add on n_same, the 64-bit minimum among the
+ * other labels), its settle sweep and a gather of the winning records; the 64-bit minimum of the second sweep, its settle sweep and the
+ * gather are skipped when no record array is asked for.  One read-back of 16 * Q bytes, 96 * Q with the records, and the borderline
+ * records: never O(hits).
+ * RK_ASSIGN_DEVICE=0 answers inside the call as rk_dist_rows + rk_assign_hits, with the same result; so does a join of 2^31 records or more.
+ * RK_ERR_ARG: triangle != 0, queries == NULL, null pointers (labels, out, out->label, out->n_within, out->n_labelled, out->n_same), a
+ * label that is neither below N nor RK_ASSIGN_NONE, a dense report (triangle = 0: a threshold of 1.0 or above), an index without posting
+ * lists (the join-only index of rk_index_join_shard, a shard of a sharded build), what rk_dist_rows refuses for explicit queries.
+ * RK_ERR_UNSUPPORTED: a reference or query sketch of 2^30 hashes or more (the key), what the join answers, and a record outside
+ * 0 < common <= u -- only sketches that repeat hashes produce such; they have no place in the order.  Nothing is written on a refusal.
+ * No queries: RK_OK, nothing runs.  An index without genomes: RK_OK, no join runs, every selected query is novel.  stats is optional. */
+#define RK_ASSIGN_NONE 0xFFFFFFFFu
+typedef struct rk_assign_queries {   /* the caller's arrays of Q = rk_sketches_count(queries) entries; nearest / runner_up may be NULL */
+    uint32_t *label, *n_within, *n_labelled, *n_same;
+    rk_hit *nearest, *runner_up;
+} rk_assign_queries;
+typedef struct rk_assign_stats {
+    uint64_t edges;          /* hit records of the join */
+    uint64_t borderline;     /* of which sent to the host */
+    uint64_t borderline_kept;
+    uint32_t join_attempts;  /* 2: the hit buffer overflowed once */
+    uint32_t border_attempts; /* 2: the host buffer overflowed once */
+    uint32_t placed;         /* selected queries with a label */
+    uint32_t novel;          /* selected queries without */
+    uint32_t ambiguous;      /* placed queries with a runner-up (n_labelled > n_same) */
+    uint32_t sweeps;         /* sweeps over the records behind the stage: 5 with a record array, 3 without, 0 on the host path */
+} rk_assign_stats;           /* 48 bytes */
+int rk_assign_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_dist_opts *opts, const uint32_t *labels /* host, N */,
+                   rk_assign_queries *out, rk_assign_stats *stats /* optional */);
+/* Host only: the same rule over a hit list the caller already has (row = query below n_query, col = reference below n_ref; `metric` as
+ * rk_dist_opts.metric; one record per pair, as a join reports them).  EVERY entry of the n_query rows is written; the records are the
+ * caller's, unchanged.  RK_ERR_ARG when a record names a query >= n_query or a reference >= n_ref, for a label that is neither below
+ * n_ref nor RK_ASSIGN_NONE and for null pointers (hits may be NULL when n_hits == 0, labels when n_ref == 0, the arrays of out when
+ * n_query == 0); RK_ERR_UNSUPPORTED for a record outside 0 < common <= u.  Nothing is written on a refusal. */
+int rk_assign_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n_query, uint32_t n_ref, const uint32_t *labels /* n_ref */, int metric,
+                   rk_assign_queries *out);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

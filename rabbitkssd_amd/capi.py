@@ -31,7 +31,7 @@ EXPORTS = [
     "rk_index_free", "rk_index_blob_bytes", "rk_index_pack_dev", "rk_index_unpack_dev", "rk_index_broadcast", "rk_dist_rows", "rk_dist_rows_dev", "rk_topn_rows", "rk_dist_topn", "rk_format_hit",
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
-    "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick",
+    "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -43,6 +43,7 @@ DBSCAN_NOISE = 0xFFFFFFFF   # RK_DBSCAN_NOISE: label and via of a noise genome
 DBSCAN_KINDS = ("noise", "border", "core")   # kind 0, 1, 2
 MREACH_NONE = 0xFFFFFFFF    # RK_MREACH_NONE: core_nb of a genome without a core record
 MEDOID_NONE = 0xFFFFFFFF    # RK_MEDOID_NONE: the label of an unlabelled genome, row and col of an absent record
+ASSIGN_NONE = 0xFFFFFFFF    # RK_ASSIGN_NONE: the label of an unlabelled reference and of a novel query, row and col of an absent record
 # rk_medoid_cluster: one record per non-empty cluster (medoid_pick)
 MEDOID_CLUSTER_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("medoid", "<u4"), ("pad", "<u4"), ("in_edges", "<u8"), ("central", "<u8"),
                                  ("weakest_in", HIT_DTYPE), ("nearest_out", HIT_DTYPE)])
@@ -121,6 +122,18 @@ class MedoidStats(C.Structure):
 class MedoidGenomes(C.Structure):
     """rk_medoid_genomes: the caller's per-genome arrays; far_in / near_out may be null"""
     _fields_ = [("in_deg", C.c_void_p), ("out_deg", C.c_void_p), ("central", C.c_void_p), ("far_in", C.c_void_p), ("near_out", C.c_void_p)]
+
+
+class AssignStats(C.Structure):
+    """rk_assign_stats: what one rk_assign_rows call did"""
+    _fields_ = [("edges", C.c_uint64), ("borderline", C.c_uint64), ("borderline_kept", C.c_uint64), ("join_attempts", C.c_uint32),
+                ("border_attempts", C.c_uint32), ("placed", C.c_uint32), ("novel", C.c_uint32), ("ambiguous", C.c_uint32), ("sweeps", C.c_uint32)]
+
+
+class AssignQueries(C.Structure):
+    """rk_assign_queries: the caller's per-query arrays; nearest / runner_up may be null"""
+    _fields_ = [("label", C.c_void_p), ("n_within", C.c_void_p), ("n_labelled", C.c_void_p), ("n_same", C.c_void_p), ("nearest", C.c_void_p),
+                ("runner_up", C.c_void_p)]
 
 
 class RkError(RuntimeError):
@@ -213,6 +226,25 @@ def _medoid_given(g, n, what):
     if any(a is None for a in out[:3]) or any(a is not None and a.shape != (int(n),) for a in out):
         raise ValueError("%s needs arrays of one entry per genome" % what)
     return out
+
+
+def _assign_arrays(q, records=True, out=None):
+    """(label, n_within, n_labelled, n_same, nearest, runner_up) of q queries for the library to fill -- the caller's `out` (row shards
+    and GPUs write into one set: the entries of unselected rows stay as they are) or new ones; without records the last two are None"""
+    if out is not None:
+        if len(out) != 6 or any(a is None for a in out[:4]):
+            raise ValueError("out needs (label, n_within, n_labelled, n_same, nearest, runner_up)")
+        for a, t in zip(out, (np.uint32,) * 4 + (HIT_DTYPE,) * 2):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == t and a.shape == (int(q),) and a.flags.c_contiguous and a.flags.writeable):
+                raise ValueError("out needs writable contiguous arrays of one entry per query")
+        return tuple(out)
+    rec = (np.zeros(q, dtype=HIT_DTYPE), np.zeros(q, dtype=HIT_DTYPE)) if records else (None, None)
+    return tuple(np.zeros(q, dtype=np.uint32) for _ in range(4)) + rec
+
+
+def _assign_struct(arrays):
+    """rk_assign_queries over the six arrays; they must outlive the call"""
+    return AssignQueries(*[a.ctypes.data if a is not None else None for a in arrays])
 
 
 def _medoid_labels(labels, n, what):
@@ -604,6 +636,23 @@ class Context:
         self.check(L.rk_medoid_rows(self._h, index._h, C.byref(opts), _ptr(labels), C.byref(g), C.byref(st)))
         return arrays + (_stats_dict(st),)
 
+    def assign_rows(self, index, queries, metric, kmer_size, max_dist, labels, records=True, row_first=0, row_step=1, row_block=0, out=None):
+        """placement of query sketches into a labelled collection (rk_assign_rows): (label, n_within, n_labelled, n_same, nearest,
+        runner_up, stats) -- labels[r] below the number of references names r's cluster, ASSIGN_NONE leaves r unlabelled; per query
+        label (uint32; ASSIGN_NONE: novel), its records within max_dist, those to a labelled reference, those to references of its label,
+        nearest / runner_up (HIT_DTYPE, row = col = ASSIGN_NONE when absent; None with records=False) = its nearest labelled reference
+        and the nearest one of another label, stats a dict of the AssignStats fields.  Only the entries of the selected query rows are
+        written: `out` (six arrays as returned) lets row shards and GPUs write into one set"""
+        opts = _opts(0, metric, kmer_size, max_dist, row_first, row_step, row_block)
+        labels = _medoid_labels(labels, index.genomes, "assign_rows")
+        arrays = _assign_arrays(queries.count if queries is not None else 0, records, out)
+        g = _assign_struct(arrays)
+        st = AssignStats()
+        L = lib()
+        L.rk_assign_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DistOpts), C.c_void_p, C.POINTER(AssignQueries), C.POINTER(AssignStats)]
+        self.check(L.rk_assign_rows(self._h, index._h, queries._h if queries is not None else None, C.byref(opts), _ptr(labels), C.byref(g), C.byref(st)))
+        return arrays + (_stats_dict(st),)
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -957,6 +1006,22 @@ def medoid_hits(hits, n, labels, metric, records=True):
     if rc:
         raise RkError(rc, "rk_medoid_hits: a label that names no cluster, a record that names a genome beyond the number of genomes or one genome "
                           "twice, or a record outside 0 < common <= u")
+    return arrays
+
+
+def assign_hits(hits, n_query, n_ref, labels, metric, records=True):
+    """placement over a hit list of n_query queries against n_ref references (rk_assign_hits, host only): (label, n_within, n_labelled,
+    n_same, nearest, runner_up) as Context.assign_rows gives them, every row written, the records being the caller's"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    labels = _medoid_labels(labels, n_ref, "assign_hits")
+    arrays = _assign_arrays(int(n_query), records)
+    g = _assign_struct(arrays)
+    L = lib()
+    L.rk_assign_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(AssignQueries)]
+    rc = L.rk_assign_hits(_ptr(hits), C.c_uint64(len(hits)), C.c_uint32(n_query), C.c_uint32(n_ref), _ptr(labels), int(metric), C.byref(g))
+    if rc:
+        raise RkError(rc, "rk_assign_hits: a label that names no cluster, a record that names a query or a reference beyond their number, "
+                          "or a record outside 0 < common <= u")
     return arrays
 
 

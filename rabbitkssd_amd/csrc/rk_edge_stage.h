@@ -1,5 +1,5 @@
-// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip, rk_knn.hip, rk_dbscan.hip, rk_mreach.hip and
-// rk_medoid.hip (not part of the public ABI): the self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device
+// rk_edge_stage.h -- the first stage of rk_cluster.hip, rk_forest.hip, rk_greedy.hip, rk_knn.hip, rk_dbscan.hip, rk_mreach.hip,
+// rk_medoid.hip and -- over a QUERY join: EdgeStage::queries, with a key pass of its own -- rk_assign.hip (not part of the public ABI): the self join into a device buffer and one pass over its records that tells the BORDERLINE ones from those the device
 // may decide.  DESIGN.md 4.6.  The key pass of all but the first lives here too (k_edge_keys, EdgeStage::key_pass); rk_cluster.hip brings
 // its own.  Two passes over the keyed records that more than one caller runs behind the stage follow it: k_edge_revive (greedy,
 // dbscan, mreach, medoid) and k_edge_degree (knn, dbscan, mreach).  So does the host code that every caller would otherwise repeat
@@ -16,7 +16,7 @@
 //   retries  more hits than the buffer holds: the join again with the exact count, every counter reset; more borderline records than
 //            theirs holds: the pass alone again, the borderline counter reset.  Each at most once;
 //   decide   the borderline records come home and rk_host_exact_distances (the C library's log, the reference's strict `<` of
-//            src/dist.cpp:232) keeps or drops each.
+//            src/dist.cpp:232; the non-strict `<=` of :624 for a query join) keeps or drops each.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -168,6 +168,8 @@ enum StagePass { kPassOwn, kPassKeys, kPassGreedyKeys };
 struct EdgeStage {
     rk_ctx *ctx;
     const rk_index *idx;
+    const rk_sketches *queries;  // null: the self join (all callers but rk_assign_rows); else the rows are these queries
+    uint32_t n_rows;             // rows of the join: genomes of the index, or queries
     const rk_dist_opts *exact;   // the caller's options: the threshold the host decides with
     const char *who;             // the caller's name, for the texts that carry it
     const char *hits_what;       // what a capacity's worth of device memory holds, for the text of its refusal
@@ -186,15 +188,17 @@ struct EdgeStage {
     unsigned long long n_hits = 0, n_border = 0;
     uint32_t join_attempts = 0, pass_attempts = 0;   // (pass_attempts: those behind the last join)
 
-    EdgeStage(rk_ctx *c, const rk_index *index, const rk_dist_opts *opts, const char *name, StagePass pass, size_t tail = 0)
-        : ctx(c), idx(index), exact(opts), who(name), hits_what(pass == kPassOwn ? "hit records" : "hit records and their keys"),
-          bad_what(pass == kPassGreedyKeys ? "a genome beyond the index or one genome twice" : "a genome beyond the index"),
+    EdgeStage(rk_ctx *c, const rk_index *index, const rk_dist_opts *opts, const char *name, StagePass pass, size_t tail = 0, const rk_sketches *qs = nullptr)
+        : ctx(c), idx(index), queries(qs), n_rows(qs ? qs->n : index->n_ref), exact(opts), who(name),
+          hits_what(pass == kPassOwn ? "hit records" : "hit records and their keys"),
+          bad_what(qs ? "a query or a reference beyond their number" : pass == kPassGreedyKeys ? "a genome beyond the index or one genome twice" : "a genome beyond the index"),
           widened(*opts), link_below(opts->max_dist), metric(opts->metric != 0),
-          cap(rk_hit_capacity(RowShard(opts, index->n_ref, index->n_ref).n_rows())),   // (the rows of this shard, as rk_dist_rows counts them)
+          cap(rk_hit_capacity(RowShard(opts, n_rows, n_rows).n_rows())),   // (the rows of this shard, as rk_dist_rows counts them)
           edge_cap(kEdgeCapDefault), hits(c), edges(c), slots(c), block(c), tail_bytes(tail), with_slots(pass == kPassGreedyKeys)
     {
         if (opts->max_dist > 0.0) {
-            widened.max_dist = std::min(opts->max_dist + opts->max_dist * kBorderRel, 1.0);
+            // (a query join turns dense AT 1.0, the self join beyond it: rk_dense_mode)
+            widened.max_dist = std::min(opts->max_dist + opts->max_dist * kBorderRel, qs ? std::nextafter(1.0, 0.0) : 1.0);
             link_below = opts->max_dist - opts->max_dist * kBorderRel;
         }
         if (const char *e = getenv("RK_CLUSTER_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
@@ -222,7 +226,7 @@ struct EdgeStage {
         for (int attempt = 0; attempt < 2; attempt++) {
             if (hits.alloc(cap) != hipSuccess) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu %s on the device", (unsigned long long)cap, hits_what);
             RK_HIP(ctx, hipMemsetAsync(block.p, 0, kCntWords * 8, stream));
-            if (int rc = rk_dist_rows_dev(ctx, idx, nullptr, &widened, hits.p, cap, (uint64_t *)(block.p + kCntHits), stream)) return rc;
+            if (int rc = rk_dist_rows_dev(ctx, idx, queries, &widened, hits.p, cap, (uint64_t *)(block.p + kCntHits), stream)) return rc;
             join_attempts++;
             pass_attempts = 0;
             for (int k = 0; k < 2; k++) {

@@ -1696,6 +1696,30 @@ static int cmd_mreach(const Args &a)
     j.leave();
 }
 
+// --labels FILE of medoid and assign: one line per genome of the clustered input in its order, an integer below their number N or - for
+// an unlabelled genome (label[i] stays RK_MEDOID_NONE); dies in the name of `cmd` on anything else
+static void read_labels(const string &path, size_t N, const char *cmd, vector<uint32_t> &label)
+{
+    std::ifstream in(path);
+    if (!in) die("cannot read %s", path.c_str());
+    string line;
+    size_t seen = 0;
+    while (std::getline(in, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty() && in.peek() == EOF) break;
+        if (seen >= N) die("command_%s(), %s holds more than the %zu lines of the input", cmd, path.c_str(), N);
+        if (line != "-") {
+            char *end = nullptr;
+            const unsigned long long v = strtoull(line.c_str(), &end, 10);
+            if (line.empty() || *end || line[0] == '-' || line[0] == '+' || v >= N)
+                die("command_%s(), line %zu of %s is neither an integer below %zu nor -", cmd, seen + 1, path.c_str(), N);
+            label[seen] = (uint32_t)v;
+        }
+        seen++;
+    }
+    if (seen != N) die("command_%s(), %s holds %zu lines, the input %zu genomes", cmd, path.c_str(), seen, N);
+}
+
 // medoid: medoids and census of a clustering of alldist's pairs (rk_medoid_rows on every GPU for its rows, folded with rk_medoid_merge;
 // rk_medoid_pick for the clusters).  The labels come from the same run -- --by cluster (the default; rk_cluster_rows, several GPUs), --by
 // greedy (rk_greedy_rows: a cluster is a representative and its members), --by dbscan -m minPts (rk_dbscan_rows: noise is unlabelled) -- or
@@ -1721,24 +1745,7 @@ static int cmd_medoid(const Args &a)
     const size_t G = j.G, N = j.N;
     vector<uint32_t> label(N ? N : 1, RK_MEDOID_NONE);
     if (from_file) {
-        std::ifstream in(a.str("labels", ""));
-        if (!in) die("cannot read %s", a.str("labels", "").c_str());
-        string line;
-        size_t seen = 0;
-        while (std::getline(in, line)) {
-            while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
-            if (line.empty() && in.peek() == EOF) break;
-            if (seen >= N) die("command_medoid(), %s holds more than the %zu lines of the input", a.str("labels", "").c_str(), N);
-            if (line != "-") {
-                char *end = nullptr;
-                const unsigned long long v = strtoull(line.c_str(), &end, 10);
-                if (line.empty() || *end || line[0] == '-' || line[0] == '+' || v >= N)
-                    die("command_medoid(), line %zu of %s is neither an integer below %zu nor -", seen + 1, a.str("labels", "").c_str(), N);
-                label[seen] = (uint32_t)v;
-            }
-            seen++;
-        }
-        if (seen != N) die("command_medoid(), %s holds %zu lines, the input %zu genomes", a.str("labels", "").c_str(), seen, N);
+        read_labels(a.str("labels", ""), N, "medoid", label);
     } else if (by == "cluster") {
         vector<vector<uint32_t>> labels(G, vector<uint32_t>(N ? N : 1));
         on_every_gpu(G, [&](size_t g) {
@@ -1914,6 +1921,146 @@ static int cmd_dist(const Args &a)
         rk_index_free(idx[g]);
     }
     return 0;
+}
+
+// assign: placement of the queries into the clustered references (rk_assign_rows).  The reference index is replicated on every GPU as
+// dist --gpus does; every GPU places the query rows dealt to it (blocks of 32, round-robin) and writes them into ONE set of arrays: a
+// query's result depends on its own records alone, so nothing is merged.  The references' labels come from --labels FILE (the format of
+// medoid --labels) or from --by on the same index with the same -D and -M: cluster (the default; rk_cluster_rows, its rows dealt to the
+// GPUs), greedy (rk_greedy_rows) or dbscan -m minPts (rk_dbscan_rows; the non-core references become unlabelled: DBSCAN's "predict"), the
+// last two on the first GPU.  One line per query in input order: its name, the name of the genome whose index is its label, the nearest
+// labelled reference's name, common|size0|size1, jorc and dist as dist prints them, its references of that label, its labelled
+// references and all its references within -D, the name of the runner-up cluster and the distance of its nearest member (- -
+// without one); a novel query has - in the five fields behind its name.  --novel: the names of the novel queries.
+static int cmd_assign(const Args &a)
+{
+    if (!a.has("r") || !a.has("q")) die("assign needs -r and -q");
+    if (!a.has("D")) die("command_assign(), assign needs -D: the distance within which a reference anchors a query");
+    const double max_dist = a.real("D", 1.0);
+    if (max_dist < 0.0) die("command_assign(), maxDist must be > 0\nUse -D to set the maxDist");
+    if (!(max_dist < 1.0)) die("command_assign(), maxDist must stay below 1.0: at 1.0 every reference is within -D of every query (a dense report), and pairs that share nothing carry no order");
+    const string by = a.str("by", "cluster");
+    if (a.has("by") && a.has("labels")) die("command_assign(), --by and --labels exclude each other: the labels come from one place");
+    if (by != "cluster" && by != "greedy" && by != "dbscan") die("command_assign(), --by must be cluster, greedy or dbscan");
+    const bool from_file = a.has("labels");
+    if (!from_file && by == "dbscan" && (!a.has("m") || a.num("m", 0) < 1))
+        die("command_assign(), minPts must be >= 1\nUse -m to set the minPts (it counts the genome itself)");
+    const string out = a.str("o", "result.out");
+    const int metric = a.num("M", 0);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), a.num("gpus", 1), a.has("same-device"));
+    const double t_cmd0 = get_sec();
+    SketchSet ref, qry;
+    string ref_path, qry_path;
+    {   // .sketch inputs are read while the runtime starts
+        string err;
+        if (is_sketch_file(a.str("r", ""))) {
+            ref_path = a.str("r", "");
+            if (!read_sketches(ref_path, ref, err)) die("readSketches(), %s", err.c_str());
+        }
+        if (is_sketch_file(a.str("q", ""))) {
+            qry_path = a.str("q", "");
+            if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
+        }
+    }
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), false, a, threads, ref, ref_path);
+    cerr << "the ref_sketch size is: " << ref.size() << endl;
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), true, a, threads, qry, qry_path);
+    if (qry.info.id != ref.info.id)
+        die("command_assign(), the sketch infos between reference and query files are not match\n"
+            "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    const size_t G = set.size(), N = ref.size(), Q = qry.size();
+    vector<uint32_t> label(N ? N : 1, RK_ASSIGN_NONE);
+    if (from_file) read_labels(a.str("labels", ""), N, "assign", label);   // (before the index: a bad file costs no build)
+    const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
+    vector<rk_index *> idx(G, nullptr);
+    build_everywhere(set, ref, ref_path, missing, idx);
+    stamp("index built");
+    const double t1 = get_sec();
+    cerr << "===================time of read index and offset sketch file is: " << t1 - t_cmd0 << endl;
+    cerr << "=====total: " << Q << endl;
+    auto opts_of = [&](size_t g, int triangle) {   // GPU g's rows: of the self join that labels the references, or of the queries
+        rk_dist_opts o{};
+        o.triangle = triangle;
+        o.metric = metric;
+        o.kmer_size = 2 * ref.info.half_k;
+        o.max_dist = max_dist;
+        if (G > 1) {
+            o.row_first = (uint32_t)g;
+            o.row_step = (uint32_t)G;
+            o.row_block = kRowBlock;
+        }
+        return o;
+    };
+    if (!from_file && N) {
+        if (by == "cluster") {
+            vector<vector<uint32_t>> labels(G, vector<uint32_t>(N));
+            on_every_gpu(G, [&](size_t g) {
+                const rk_dist_opts o = opts_of(g, 1);
+                set[g].check(rk_cluster_rows(set[g].ctx, idx[g], &o, labels[g].data(), nullptr), "rk_cluster_rows");
+            });
+            for (size_t g = 1; g < G; g++)
+                if (rk_cluster_merge(labels[0].data(), labels[g].data(), (uint32_t)N, labels[0].data()) != 0) die("rk_cluster_merge failed");
+            label = labels[0];
+        } else {
+            rk_dist_opts o = opts_of(0, 1);
+            o.row_first = 0;   // every row on the first GPU: neither rule composes from shards
+            o.row_step = 1;
+            o.row_block = 0;
+            if (by == "greedy") {
+                rk_hit *links = nullptr;
+                uint64_t n_links = 0;
+                set[0].check(rk_greedy_rows(set[0].ctx, idx[0], &o, nullptr, label.data(), &links, &n_links, nullptr), "rk_greedy_rows");
+                rk_free_host(links);
+            } else {
+                vector<uint8_t> kind(N);
+                set[0].check(rk_dbscan_rows(set[0].ctx, idx[0], &o, (uint32_t)a.num("m", 1), label.data(), kind.data(), nullptr, nullptr, nullptr), "rk_dbscan_rows");
+                for (size_t i = 0; i < N; i++)
+                    if (kind[i] != 2) label[i] = RK_ASSIGN_NONE;   // only a core reference anchors a query
+            }
+        }
+        stamp("references labelled");
+    }
+    // one set of arrays for all GPUs: each writes the entries of its rows
+    const size_t Qa = Q ? Q : 1;
+    vector<uint32_t> q_label(Qa, RK_ASSIGN_NONE), n_within(Qa, 0), n_labelled(Qa, 0), n_same(Qa, 0);
+    vector<rk_hit> nearest(Qa), runner_up(Qa);
+    rk_assign_queries res{q_label.data(), n_within.data(), n_labelled.data(), n_same.data(), nearest.data(), runner_up.data()};
+    vector<rk_assign_stats> stats(G);
+    on_every_gpu(G, [&](size_t g) {
+        Gpu &dev = set[g];
+        rk_sketches *qs = upload(dev, qry);
+        const rk_dist_opts o = opts_of(g, 0);
+        dev.check(rk_assign_rows(dev.ctx, idx[g], qs, &o, label.data(), &res, &stats[g]), "rk_assign_rows");
+        rk_sketches_free(qs);
+    });
+    stamp("queries placed");
+    cerr << "===================time of multiple threads distance computing and placement is: " << get_sec() - t1 << endl;
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    FILE *np = nullptr;
+    if (a.has("novel") && !(np = fopen(a.str("novel", "").c_str(), "w"))) die("cannot write %s", a.str("novel", "").c_str());
+    for (size_t q = 0; q < Q; q++) {
+        const rk_hit &h = nearest[q], &s = runner_up[q];
+        if (q_label[q] == RK_ASSIGN_NONE) {
+            fprintf(fp, "%s\t-\t-\t-\t-\t-\t%u\t%u\t%u\t-\t-\n", qry.names[q].c_str(), n_same[q], n_labelled[q], n_within[q]);
+            if (np) fprintf(np, "%s\n", qry.names[q].c_str());
+            continue;
+        }
+        fprintf(fp, "%s\t%s\t%s\t%d|%d|%d\t%f\t%f\t%u\t%u\t%u\t", qry.names[q].c_str(), ref.names[q_label[q]].c_str(), ref.names[h.col].c_str(), h.common, h.size0,
+                h.size1, h.jorc, h.dist, n_same[q], n_labelled[q], n_within[q]);
+        if (s.row == RK_ASSIGN_NONE) fprintf(fp, "-\t-\n");
+        else fprintf(fp, "%s\t%f\n", ref.names[label[s.col]].c_str(), s.dist);
+    }
+    fclose(fp);
+    if (np) fclose(np);
+    if (getenv("RK_TIMING")) {
+        unsigned long long hits = 0, border = 0, placed = 0, novel = 0, ambiguous = 0;
+        for (size_t g = 0; g < G; g++) { hits += stats[g].edges; border += stats[g].borderline; placed += stats[g].placed; novel += stats[g].novel; ambiguous += stats[g].ambiguous; }
+        fprintf(stderr, "[timing] %zu queries against %zu references: %llu placed (%llu with a runner-up), %llu novel, from %llu hit records (%llu borderline)\n", Q, N,
+                placed, ambiguous, novel, hits, border);
+    }
+    SelfJoin::leave();
 }
 
 // test helper: the text writer alone (no GPU): `_format alldist|dist names.txt hits.bin out pieces threads`;
@@ -2211,7 +2358,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2222,6 +2369,7 @@ static int usage()
             "  dbscan -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [-L file.shuf] [--device N]   (density-based clusters of alldist's pairs: a genome with minPts genomes, itself included, within -D is core; clusters are the components of the core genomes, a non-core genome joins its nearest core neighbour's cluster as border, the rest is noise; one GPU)\n"
             "  mreach -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [--core FILE] [--cut t --labels FILE] [-L file.shuf] [--device N]   (minimum spanning forest of alldist's pairs under mutual-reachability distance, the HDBSCAN* hierarchy up to -D: one forest line per edge and its mutual-reachability distance; --core: every genome's core distance and the neighbour that sets it; --cut: the clusters of the core genomes at t <= maxDist, the rest as cluster 0; one GPU)\n"
             "  medoid -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--by cluster|greedy|dbscan] [-m minPts] [--labels FILE] [--census FILE] [-L file.shuf] [--device N] [--gpus G]   (medoids and census of a clustering of alldist's pairs: per genome its cluster, its role -- the medoid is the member with the highest summed similarity to its fellow members --, its pairs inside the cluster and leaving it, its mean similarity to its fellow members and its nearest genome outside; the labels from --by (default cluster; dbscan needs -m; greedy and dbscan on one GPU) or from --labels: one line per genome, an integer below the number of genomes or -; --census: per cluster its size, medoid, inside pairs of size (size - 1) / 2, weakest inside pair and nearest leaving pair)\n"
+            "  assign -r ref.sketch|list -q qry.sketch|list -D maxDist [-M 0|1] (--labels FILE | --by cluster|greedy|dbscan -m minPts) -o out [--novel FILE] [--gpus G] [--device N]   (placement of the queries into the clustered references: per query the cluster of its nearest labelled reference within -D, that reference's dist line, the query's references of that cluster, labelled and all within -D, and the runner-up cluster with its distance; - when novel; -D below 1.0; the labels from --labels -- one line per reference, an integer below their number or - -- or from --by on the same index (default cluster; dbscan needs -m and leaves non-core references unlabelled; greedy and dbscan on the first GPU); --novel: the names of the unplaced queries)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -2242,7 +2390,7 @@ int main(int argc, char **argv)
         {"-n", "n"}, {"--leastNumKmer", "n"}, {"-Q", "Q"}, {"--leastQuality", "Q"}, {"-D", "D"}, {"--maxDist", "D"},
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
-        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}};
+        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2260,7 +2408,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2285,6 +2433,7 @@ int main(int argc, char **argv)
     if (sub == "dbscan") { cerr << "-----run the subcommand: dbscan" << endl; return leave(cmd_dbscan(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "mreach") { cerr << "-----run the subcommand: mreach" << endl; return leave(cmd_mreach(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "medoid") { cerr << "-----run the subcommand: medoid" << endl; return leave(cmd_medoid(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "assign") { cerr << "-----run the subcommand: assign" << endl; return leave(cmd_assign(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
