@@ -963,6 +963,67 @@ int rk_assign_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
 int rk_assign_hits(const rk_hit *hits, uint64_t n_hits, uint32_t n_query, uint32_t n_ref, const uint32_t *labels /* n_ref */, int metric,
                    rk_assign_queries *out);
 
+/* ---- pan, core and marker sketches per cluster --------------------------------------- */
+/* What turns a labelled collection back into sketches: per cluster the union of its members' sketches (its pan sketch), the hashes
+ * every member holds (its core sketch), the hashes no genome outside it holds (its markers) -- the reference's `union` and `sub`
+ * (src/subCommand.cpp:307-543, :545-794) for every cluster at once, from the posting lists alone: no join, no distance.
+ * Labels.  labels[v] (host, rk_index_genomes(idx) = N entries in the caller's genome order): a value below N names v's cluster (it need
+ * not be a member of it), RK_GROUP_NONE (the value of RK_DBSCAN_NOISE) means v is unlabelled; anything else is RK_ERR_ARG.  The GROUPS
+ * are the labels in use by ascending label, K of them; m_l = the genomes that carry l (one with an empty sketch counts).
+ * Rule (integers only).  For a hash h: c_l(h) = the DISTINCT genomes labelled l whose sketch holds h (a sketch that repeats h counts
+ * once), t(h) = the distinct genomes that hold h, unlabelled ones included.  h is in the sketch of group l iff c_l(h) >= min_count and
+ * c_l(h) * share_den >= share_num * m_l (64-bit products) and, with only = 1, c_l(h) == t(h): every holder carries l -- an unlabelled
+ * holder is outside every cluster and defeats it.  pan {0,1,1,0}, core {1,1,1,0}, majority {1,2,1,0}, markers {0,1,1,1}.
+ * Result.  *out: K sketches by ascending label, each strictly ascending, of the hash width of the index, device-resident and
+ * library-owned (rk_sketches_free): it goes straight into rk_index_build, rk_dist_rows, rk_dist_topn, rk_assign_rows.  A group without a
+ * hash is an empty sketch.  group_label_out / group_size_out: K entries each, the label and m_l (rk_free_host).  The result is unique:
+ * it does not depend on the internal genome order, on how the index came to be or on the path taken.
+ * Accepted: every index that carries posting lists, built (rk_index_build) or imported (rk_index_import, rk_index_import64).
+ * The host computes need[g] = max(min_count, ceil(share_num * m / share_den)); 4 * N + 4 * K bytes go up, the counters and 8 * (K + 1)
+ * bytes of offsets come back, never the postings.  On the device (rk_group.hip): the group numbers in internal order, then per posting
+ * list by its length -- up to lane_max postings one lane, up to wave_max one wave, beyond that a workgroup that streams the list in
+ * chunks of `chunk` postings into an LDS table of table_groups groups; a list with more groups than the table holds is SPILLED: its
+ * raw keys are sorted and run-length counted.  A (group, list) that passes appends one 64-bit key; the keys are sorted, the offsets of
+ * the groups found, the hashes gathered.  When the key buffer (or the spill buffer) overflows, the call runs once more with the exact
+ * count (attempts = 2); RK_GROUP_CAP / RK_GROUP_SPILL_CAP (developer switches) set the first capacities.
+ * RK_GROUP_DEVICE=0 answers inside the call as export + rk_group_lists + rk_sketches_from_host(64), with the same result.
+ * RK_ERR_ARG: null pointers, a label that names nothing, share_den == 0, share_num > share_den, min_count == 0, only > 1, an index
+ * without posting lists (the join-only index of rk_index_join_shard), one hash range of a sharded build.  RK_ERR_UNSUPPORTED: more than
+ * 2^31 genomes.  Nothing is written on a refusal.  No genomes, or no labelled genome: RK_OK, nothing runs, *out = NULL, *n_groups = 0,
+ * the two arrays NULL.  stats is optional. */
+#define RK_GROUP_NONE 0xFFFFFFFFu
+#define RK_MS_GROUP 13          /* rk_group_sketches: the first list kernel through the gather of the hashes; 0 on the host path */
+typedef struct rk_group_rule {
+    uint32_t share_num, share_den;  /* 0 <= num <= den, den >= 1 */
+    uint32_t min_count;             /* >= 1 */
+    uint32_t only;                  /* 0 or 1 */
+} rk_group_rule;
+typedef struct rk_group_stats {
+    uint64_t lists;          /* posting lists = distinct hashes of the index */
+    uint64_t postings;
+    uint64_t kept;           /* (group, hash) pairs of the result = rk_sketches_total(*out) */
+    uint64_t lane_lists;     /* lists of up to lane_max postings: one lane each */
+    uint64_t wave_lists;     /* lists of up to wave_max postings: one wave each */
+    uint64_t block_lists;    /* longer lists: one workgroup each, streamed in chunks (the spilled ones included) */
+    uint64_t spilled;        /* of which with more than table_groups groups: counted by sort + run lengths */
+    uint32_t labelled;       /* genomes with a label */
+    uint32_t groups;         /* K */
+    uint32_t attempts;       /* 2: the key buffer or the spill buffer overflowed once; 0 when nothing ran or on the host path */
+    uint32_t path;           /* 0 nothing ran, 1 device, 2 host */
+    uint32_t lane_max, wave_max, table_groups, chunk;   /* the constants of the list kernels (every path fills them) */
+} rk_group_stats;            /* 88 bytes */
+int rk_group_sketches(rk_ctx *ctx, const rk_index *idx, const uint32_t *labels /* host, N */, const rk_group_rule *rule, rk_sketches **out,
+                      uint32_t **group_label_out, uint32_t **group_size_out, uint32_t *n_groups, rk_group_stats *stats /* optional */);
+/* Host only: the same rule over posting lists as rk_index_export_lists / rk_index_export64 return them (the lists back to back in
+ * `postings`, their lengths in `counts`; genome ids below n_genomes in any order within a list, repeats allowed and counted once).  Per
+ * group the INDICES of the kept lists, ascending: kept_out[off_out[g] .. off_out[g + 1]) -- blind to the hash width, the caller maps an
+ * index to its hash.  off_out has K + 1 entries; kept_out, group_label_out and group_size_out are NULL when they would be empty; all
+ * four are the library's (rk_free_host).  RK_ERR_ARG for a posting >= n_genomes, a bad label or rule, null pointers (postings / counts
+ * may be NULL when n_lists is 0 or every list is empty, labels when n_genomes is 0).  Nothing is written on a refusal. */
+int rk_group_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, uint32_t n_genomes, const uint32_t *labels /* n_genomes */,
+                   const rk_group_rule *rule, uint64_t **off_out /* K + 1 */, uint64_t **kept_out, uint32_t **group_label_out, uint32_t **group_size_out,
+                   uint32_t *n_groups);
+
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,
                   const rk_hit *hit);

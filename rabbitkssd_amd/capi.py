@@ -32,6 +32,7 @@ EXPORTS = [
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
     "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
+    "rk_group_sketches", "rk_group_lists",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -44,6 +45,8 @@ DBSCAN_KINDS = ("noise", "border", "core")   # kind 0, 1, 2
 MREACH_NONE = 0xFFFFFFFF    # RK_MREACH_NONE: core_nb of a genome without a core record
 MEDOID_NONE = 0xFFFFFFFF    # RK_MEDOID_NONE: the label of an unlabelled genome, row and col of an absent record
 ASSIGN_NONE = 0xFFFFFFFF    # RK_ASSIGN_NONE: the label of an unlabelled reference and of a novel query, row and col of an absent record
+GROUP_NONE = 0xFFFFFFFF     # RK_GROUP_NONE: the label of an unlabelled genome (rk_group_sketches, rk_group_lists)
+MS_GROUP = 13               # RK_MS_GROUP: the timed span of rk_group_sketches (Context.last_ms)
 # rk_medoid_cluster: one record per non-empty cluster (medoid_pick)
 MEDOID_CLUSTER_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("medoid", "<u4"), ("pad", "<u4"), ("in_edges", "<u8"), ("central", "<u8"),
                                  ("weakest_in", HIT_DTYPE), ("nearest_out", HIT_DTYPE)])
@@ -134,6 +137,36 @@ class AssignQueries(C.Structure):
     """rk_assign_queries: the caller's per-query arrays; nearest / runner_up may be null"""
     _fields_ = [("label", C.c_void_p), ("n_within", C.c_void_p), ("n_labelled", C.c_void_p), ("n_same", C.c_void_p), ("nearest", C.c_void_p),
                 ("runner_up", C.c_void_p)]
+
+
+class GroupRule(C.Structure):
+    """rk_group_rule: a hash is in a group's sketch iff c >= min_count, c * share_den >= share_num * m and, with only, c == t"""
+    _fields_ = [("share_num", C.c_uint32), ("share_den", C.c_uint32), ("min_count", C.c_uint32), ("only", C.c_uint32)]
+
+
+GROUP_RULES = {"pan": (0, 1, 1, 0), "core": (1, 1, 1, 0), "majority": (1, 2, 1, 0), "markers": (0, 1, 1, 1)}
+
+
+class GroupStats(C.Structure):
+    """rk_group_stats: what one rk_group_sketches call did"""
+    _fields_ = [("lists", C.c_uint64), ("postings", C.c_uint64), ("kept", C.c_uint64), ("lane_lists", C.c_uint64), ("wave_lists", C.c_uint64),
+                ("block_lists", C.c_uint64), ("spilled", C.c_uint64), ("labelled", C.c_uint32), ("groups", C.c_uint32), ("attempts", C.c_uint32),
+                ("path", C.c_uint32), ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("table_groups", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+def group_rule(rule):
+    """a GroupRule from a name of GROUP_RULES, a (share_num, share_den, min_count, only) tuple or a GroupRule"""
+    if isinstance(rule, GroupRule):
+        return rule
+    return GroupRule(*[int(x) for x in (GROUP_RULES[rule] if isinstance(rule, str) else rule)])
+
+
+def _take_array(ptr, n, dtype):
+    """takes over a host array the library returned (NULL when empty): copied out, then freed"""
+    dtype = np.dtype(dtype)
+    buf = C.string_at(ptr.value, int(n) * dtype.itemsize) if ptr.value and n else b""
+    lib().rk_free_host(ptr)
+    return np.frombuffer(buf, dtype=dtype).copy()
 
 
 class RkError(RuntimeError):
@@ -653,6 +686,23 @@ class Context:
         self.check(L.rk_assign_rows(self._h, index._h, queries._h if queries is not None else None, C.byref(opts), _ptr(labels), C.byref(g), C.byref(st)))
         return arrays + (_stats_dict(st),)
 
+    def group_sketches(self, index, labels, rule="pan"):
+        """one sketch per cluster of a labelled collection (rk_group_sketches): (sketches, group_label, group_size, stats) -- labels[v]
+        below the number of genomes names v's cluster, GROUP_NONE leaves v unlabelled; the groups are the labels in use by ascending
+        label; `rule` a name of GROUP_RULES (pan, core, majority, markers), a (share_num, share_den, min_count, only) tuple or a
+        GroupRule.  sketches: a device-resident Sketches of one strictly ascending sketch per group (None without a labelled genome),
+        group_label / group_size (uint32) the label and the number of genomes of each group, stats a dict of the GroupStats fields"""
+        labels = _medoid_labels(labels, index.genomes, "group_sketches")
+        r = group_rule(rule)
+        h, gl, gs = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        k = C.c_uint32()
+        st = GroupStats()
+        L = lib()
+        L.rk_group_sketches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GroupRule), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(GroupStats)]
+        self.check(L.rk_group_sketches(self._h, index._h, _ptr(labels), C.byref(r), C.byref(h), C.byref(gl), C.byref(gs), C.byref(k), C.byref(st)))
+        return (Sketches(self, h) if h.value else None), _take_array(gl, k.value, np.uint32), _take_array(gs, k.value, np.uint32), _stats_dict(st)
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -1023,6 +1073,30 @@ def assign_hits(hits, n_query, n_ref, labels, metric, records=True):
         raise RkError(rc, "rk_assign_hits: a label that names no cluster, a record that names a query or a reference beyond their number, "
                           "or a record outside 0 < common <= u")
     return arrays
+
+
+def group_lists(postings, counts, n_genomes, labels, rule="pan"):
+    """the rule of Context.group_sketches over exported posting lists (rk_group_lists, host only): (off, kept, group_label, group_size) --
+    the lists back to back in `postings` with their lengths in `counts` (Index.export_lists / export64), genome ids in any order within
+    a list, repeats counted once; kept[off[g]:off[g + 1]] (uint64) = the indices of the lists group g keeps, ascending"""
+    postings = np.ascontiguousarray(postings, dtype=np.uint32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if int(counts.sum(dtype=np.uint64)) != len(postings):
+        raise ValueError("group_lists: the counts do not add up to the postings")
+    labels = _medoid_labels(labels, n_genomes, "group_lists")
+    r = group_rule(rule)
+    off, kept, gl, gs = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    k = C.c_uint32()
+    L = lib()
+    L.rk_group_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(GroupRule), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+    rc = L.rk_group_lists(_ptr(postings) if len(postings) else None, _ptr(counts) if len(counts) else None, C.c_uint64(len(counts)), C.c_uint32(n_genomes),
+                          _ptr(labels) if n_genomes else None, C.byref(r), C.byref(off), C.byref(kept), C.byref(gl), C.byref(gs), C.byref(k))
+    if rc:
+        raise RkError(rc, "rk_group_lists: a label that names no cluster, a posting beyond the number of genomes, or a rule outside "
+                          "share_num <= share_den, share_den >= 1, min_count >= 1, only <= 1")
+    off = _take_array(off, k.value + 1, np.uint64)
+    return off, _take_array(kept, int(off[-1]), np.uint64), _take_array(gl, k.value, np.uint32), _take_array(gs, k.value, np.uint32)
 
 
 def medoid_merge(a, b, n, metric):

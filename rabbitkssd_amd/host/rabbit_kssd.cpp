@@ -1838,6 +1838,111 @@ static int cmd_medoid(const Args &a)
     j.leave();
 }
 
+// group: one sketch per cluster of a labelled collection (rk_group_sketches): its pan sketch (--pan, the default: the union of its
+// members' sketches), its core sketch (--core: the hashes every member holds), the hashes at least P of Q of its members hold (--share
+// P/Q), each with --min-count C (at least C members hold it) and --only (no genome outside the cluster holds it: its markers).  The
+// labels come from --labels FILE (as medoid reads them) or from --by cluster|greedy|dbscan on the index this command builds anyway
+// (default cluster at -D 0.05; dbscan with -m, default 5, leaves noise unlabelled).  out.sketch carries the input's info header and one
+// sketch per cluster by ascending label, named after the member with the smallest index; --map: one line per cluster -- number from 1,
+// label, genomes, hashes kept, name.  One GPU.
+static int cmd_group(const Args &a)
+{
+    if (!a.has("o")) die("group needs -i and -o");
+    SelfJoin j(a, "group", true);
+    if (a.has("by") && a.has("labels")) die("command_group(), --by and --labels exclude each other: the labels come from one place");
+    const string by = a.str("by", "cluster");
+    if (by != "cluster" && by != "greedy" && by != "dbscan") die("command_group(), --by must be cluster, greedy or dbscan");
+    if (a.num("gpus", 1) != 1) die("command_group(), group runs on one GPU (--gpus 1)");
+    if ((int)a.has("pan") + (int)a.has("core") + (int)a.has("share") > 1) die("command_group(), --pan, --core and --share exclude each other");
+    rk_group_rule rule{0, 1, 1, a.has("only") ? 1u : 0u};
+    if (a.has("core")) rule.share_num = 1;
+    if (a.has("share")) {
+        const string sh = a.str("share", "");
+        char *end = nullptr;
+        const unsigned long long p = strtoull(sh.c_str(), &end, 10);
+        const unsigned long long q = *end == '/' && end != sh.c_str() ? strtoull(end + 1, &end, 10) : 0;
+        if (*end || !q || p > q || q > 0xFFFFFFFFULL || sh[0] == '-' || sh[0] == '+') die("command_group(), --share needs P/Q with 0 <= P <= Q and Q >= 1");
+        rule.share_num = (uint32_t)p;
+        rule.share_den = (uint32_t)q;
+    }
+    if (a.has("min-count")) {
+        if (a.num("min-count", 0) < 1) die("command_group(), --min-count must be >= 1");
+        rule.min_count = (uint32_t)a.num("min-count", 1);
+    }
+    const bool from_file = a.has("labels");
+    const int min_pts = a.num("m", 5);
+    if (!from_file && by == "dbscan" && min_pts < 1) die("command_group(), minPts must be >= 1\nUse -m to set the minPts (it counts the genome itself)");
+    const double by_dist = a.real("D", 0.05);
+    if (!from_file && 1.0 <= by_dist) die("command_group(), maxDist of --by must be below 1.0");
+    j.prepare(1, false);
+    const size_t N = j.N;
+    Gpu &gpu = j.gpu(0);
+    vector<uint32_t> label(N ? N : 1, RK_GROUP_NONE);
+    if (from_file) {
+        read_labels(a.str("labels", ""), N, "group", label);
+    } else {
+        rk_dist_opts o = j.opts(0);
+        o.max_dist = by_dist;
+        if (by == "cluster") {
+            gpu.check(rk_cluster_rows(gpu.ctx, j.idx[0], &o, label.data(), nullptr), "rk_cluster_rows");
+        } else if (by == "greedy") {
+            rk_hit *links = nullptr;
+            uint64_t n_links = 0;
+            gpu.check(rk_greedy_rows(gpu.ctx, j.idx[0], &o, nullptr, label.data(), &links, &n_links, nullptr), "rk_greedy_rows");
+            rk_free_host(links);
+        } else {
+            vector<uint8_t> kind(N ? N : 1);
+            gpu.check(rk_dbscan_rows(gpu.ctx, j.idx[0], &o, (uint32_t)min_pts, label.data(), kind.data(), nullptr, nullptr, nullptr), "rk_dbscan_rows");
+        }
+    }
+    if (getenv("RK_TIMING")) rk_ctx_set_timing(gpu.ctx, 1);
+    rk_sketches *grouped = nullptr;
+    uint32_t *group_label = nullptr, *group_size = nullptr, K = 0;
+    rk_group_stats stats;
+    gpu.check(rk_group_sketches(gpu.ctx, j.idx[0], label.data(), &rule, &grouped, &group_label, &group_size, &K, &stats), "rk_group_sketches");
+    SketchSet out;
+    out.info = j.s.info;
+    out.off.assign((size_t)K + 1, 0);
+    if (grouped) {
+        if (out.wide()) {
+            out.hashes64.resize(rk_sketches_total(grouped));
+            gpu.check(rk_sketches_download64(grouped, out.hashes64.data(), out.off.data()), "rk_sketches_download64");
+        } else {
+            out.hashes.resize(rk_sketches_total(grouped));
+            gpu.check(rk_sketches_download(grouped, out.hashes.data(), out.off.data()), "rk_sketches_download");
+        }
+    }
+    j.phase_done("group sketches on the host", "grouping");
+    {   // a group is named after its member with the smallest index
+        vector<uint32_t> at(N ? N : 1, 0);
+        for (uint32_t k = 0; k < K; k++) at[group_label[k]] = k;
+        out.names.assign(K, string());
+        vector<uint8_t> named(K ? K : 1, 0);
+        for (size_t i = 0; i < N; i++)
+            if (label[i] != RK_GROUP_NONE && !named[at[label[i]]]) {
+                named[at[label[i]]] = 1;
+                out.names[at[label[i]]] = j.s.names[i];
+            }
+    }
+    string err;
+    if (!save_sketches(j.out, out, err)) die("%s", err.c_str());
+    if (a.has("map")) {
+        FILE *mp = fopen(a.str("map", "").c_str(), "w");
+        if (!mp) die("cannot write %s", a.str("map", "").c_str());
+        for (uint32_t k = 0; k < K; k++)
+            fprintf(mp, "%u\t%u\t%u\t%llu\t%s\n", k + 1, group_label[k], group_size[k], (unsigned long long)(out.off[k + 1] - out.off[k]), out.names[k].c_str());
+        fclose(mp);
+    }
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %u group sketches of %u labelled genomes (%zu in all): %llu hashes kept from %llu lists (%llu by lane, %llu by wave, %llu by workgroup, %llu spilled), "
+                        "%u attempt(s), path %u, %.3f ms on the device\n", K, stats.labelled, N, (unsigned long long)stats.kept, (unsigned long long)stats.lists,
+                (unsigned long long)stats.lane_lists, (unsigned long long)stats.wave_lists, (unsigned long long)stats.block_lists, (unsigned long long)stats.spilled,
+                stats.attempts, stats.path, rk_ctx_last_ms(gpu.ctx, RK_MS_GROUP));
+    rk_free_host(group_label);
+    rk_free_host(group_size);
+    j.leave();
+}
+
 static int cmd_dist(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("dist needs -r and -q");
@@ -2358,7 +2463,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2370,6 +2475,7 @@ static int usage()
             "  mreach -i in.sketch|genomes.list -o out -m minPts [-D maxDist] [-M 0|1] [--core FILE] [--cut t --labels FILE] [-L file.shuf] [--device N]   (minimum spanning forest of alldist's pairs under mutual-reachability distance, the HDBSCAN* hierarchy up to -D: one forest line per edge and its mutual-reachability distance; --core: every genome's core distance and the neighbour that sets it; --cut: the clusters of the core genomes at t <= maxDist, the rest as cluster 0; one GPU)\n"
             "  medoid -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--by cluster|greedy|dbscan] [-m minPts] [--labels FILE] [--census FILE] [-L file.shuf] [--device N] [--gpus G]   (medoids and census of a clustering of alldist's pairs: per genome its cluster, its role -- the medoid is the member with the highest summed similarity to its fellow members --, its pairs inside the cluster and leaving it, its mean similarity to its fellow members and its nearest genome outside; the labels from --by (default cluster; dbscan needs -m; greedy and dbscan on one GPU) or from --labels: one line per genome, an integer below the number of genomes or -; --census: per cluster its size, medoid, inside pairs of size (size - 1) / 2, weakest inside pair and nearest leaving pair)\n"
             "  assign -r ref.sketch|list -q qry.sketch|list -D maxDist [-M 0|1] (--labels FILE | --by cluster|greedy|dbscan -m minPts) -o out [--novel FILE] [--gpus G] [--device N]   (placement of the queries into the clustered references: per query the cluster of its nearest labelled reference within -D, that reference's dist line, the query's references of that cluster, labelled and all within -D, and the runner-up cluster with its distance; - when novel; -D below 1.0; the labels from --labels -- one line per reference, an integer below their number or - -- or from --by on the same index (default cluster; dbscan needs -m and leaves non-core references unlabelled; greedy and dbscan on the first GPU); --novel: the names of the unplaced queries)\n"
+            "  group -i in.sketch|genomes.list (--labels FILE | --by cluster|greedy|dbscan [-D 0.05] [-M 0|1] [-m 5]) [--pan | --core | --share P/Q] [--min-count C] [--only] -o out.sketch [--map FILE] [--device N]   (one sketch per cluster: --pan, the default, the union of its members' sketches; --core the hashes every member holds; --share P/Q those at least P of Q of its members hold; --min-count C: at least C members hold it; --only: no genome outside the cluster holds it -- its markers; the labels as medoid takes them; out.sketch: one sketch per cluster by ascending label, named after its first member; --map: per cluster its number, label, genomes, hashes kept and name; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -2390,7 +2496,8 @@ int main(int argc, char **argv)
         {"-n", "n"}, {"--leastNumKmer", "n"}, {"-Q", "Q"}, {"--leastQuality", "Q"}, {"-D", "D"}, {"--maxDist", "D"},
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
-        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"}};
+        {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"},
+        {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2408,7 +2515,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2434,6 +2541,7 @@ int main(int argc, char **argv)
     if (sub == "mreach") { cerr << "-----run the subcommand: mreach" << endl; return leave(cmd_mreach(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "medoid") { cerr << "-----run the subcommand: medoid" << endl; return leave(cmd_medoid(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "assign") { cerr << "-----run the subcommand: assign" << endl; return leave(cmd_assign(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "group") { cerr << "-----run the subcommand: group" << endl; return leave(cmd_group(parse_args(argc, argv, 2, alias, {"pan", "core", "only"}))); }   // (--core is a flag here, a file of mreach)
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
