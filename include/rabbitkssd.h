@@ -1024,6 +1024,77 @@ int rk_group_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_
                    const rk_group_rule *rule, uint64_t **off_out /* K + 1 */, uint64_t **kept_out, uint32_t **group_label_out, uint32_t **group_size_out,
                    uint32_t *n_groups);
 
+/* ---- decomposing queries into references --------------------------------------------- */
+/* rk_gather_rows: which references explain a query sketch, in what order, and how much each adds beyond the ones already chosen -- the
+ * greedy minimum set cover (sourmash `gather`) of every selected query over the references of an index, in integers only.  Sketches are
+ * taken as SETS: an index whose references repeat a hash and queries that repeat a hash are RK_ERR_UNSUPPORTED.
+ * Per selected query q with hash set S: matched[q] = the hashes of S that have a posting list; common(r) = |S n R_r|; n_cand[q] = the
+ * references with common(r) >= min_new.  Rounds: M_0 = the matched hashes of S; in round t, rem_t(r) = |M_t n R_r| over the references
+ * not yet picked; the pick is the reference with the largest rem_t, ties to the smaller CALLER's reference index; the rounds end when
+ * that maximum is below min_new or when t = max_picks (0: no limit); otherwise M_{t+1} = M_t \ R_pick.  One record per pick:
+ * rank = t, common = the original overlap, fresh = rem_t(pick), left = |M_{t+1}|, the two sketch sizes.  covered[q] = the sum of fresh.
+ * off_out (host, Q + 1 entries, every one written; an unselected row is empty) delimits the picks of each query in *picks_out
+ * (library-allocated, rk_free_host; NULL when there is none), which come in (query, rank) order.  matched_out / n_cand_out / covered_out
+ * (host, Q entries each): only the entries of the selected rows (row_first / row_step / row_block as in rk_dist_opts) are written.
+ * The result is unique: it does not depend on the internal genome order, on how the index came to be (built or imported), on batches,
+ * on shards or on the path taken.  With min_new = 1 and max_picks = 0, covered == matched for every query.  A query's result depends on
+ * its own hashes alone: row shards compose by concatenation, no merge call is needed.
+ * On the device (rk_gather.hip), per batch of query rows whose counter rows fit RK_GATHER_BATCH_BYTES (default 1 GiB; at least one row):
+ * the counter rows of the query join (stage A of rk_dist_topn) become the mutable rem; the candidates (ref, common) with common >= min_new
+ * and the matched posting lists are compacted per batch; then two kernels per round over the whole batch: one workgroup per live row
+ * takes the maximum of (rem, -ref) over the row's candidates and appends the pick, then every live matched list of a live row looks for
+ * the winner by binary search (a list ascends in internal genome id) and, on a hit, dies and takes 1 off rem of every genome it names
+ * (relaxed agent-scope integer adds) -- by one lane up to lane_max postings, by one wave up to wave_max, by the workgroup beyond.  The
+ * host reads the number of live rows every sync_every rounds and launches nothing once it is 0; the live lists are compacted when
+ * fewer than half survive.  One read-back carries 32 picks + 12 Q + 8 (Q + 1) bytes; counter rows and postings never leave the device.
+ * RK_GATHER_DEVICE=0 answers inside the call as export + rk_gather_lists, with the same result; stats->path says which leg ran.
+ * RK_ERR_ARG: null pointers, min_new == 0, an index without posting lists (the join-only index of rk_index_join_shard, one hash range of
+ * a sharded build), queries and index of different hash widths.  RK_ERR_UNSUPPORTED: sketches that repeat a hash, and an index of
+ * 2^31 - 1 postings or more (as rk_dist_rows answers explicit queries).  Nothing is written on a refusal.  No query: RK_OK, nothing runs.
+ * An index without genomes: RK_OK, every row empty. */
+#define RK_MS_GATHER 14         /* rk_gather_rows: the counts of the first batch through the last compaction of picks; 0 on the host path */
+typedef struct rk_gather_opts {
+    uint32_t min_new;        /* >= 1: a pick adds at least this many hashes that no earlier pick held */
+    uint32_t max_picks;      /* picks per query at most; 0: no limit */
+    uint32_t row_first, row_step, row_block;   /* the row shard, as in rk_dist_opts (0 0 0: every query) */
+} rk_gather_opts;            /* 20 bytes */
+typedef struct rk_gather_pick {
+    uint32_t query, ref;     /* the query row and the CALLER's reference index */
+    uint32_t rank;           /* t: the round of the pick, from 0 */
+    uint32_t common;         /* |S n R_ref|, the original overlap */
+    uint32_t fresh;          /* rem_t(ref): matched hashes of the query that no earlier pick held */
+    uint32_t left;           /* |M_{t+1}|: matched hashes still unexplained after this pick */
+    uint32_t size_ref, size_query;
+} rk_gather_pick;            /* 32 bytes */
+typedef struct rk_gather_stats {
+    uint64_t picks, candidates, matched;   /* sums over the selected rows */
+    uint64_t decrements;     /* postings of the lists that died on a winner (device leg); the lists of a row's LAST pick are not walked when nothing is left */
+    uint64_t lane_lists, wave_lists, block_lists;   /* lists that died, by who walked them (device leg) */
+    uint64_t rows_per_batch;
+    uint32_t path;           /* 0 nothing ran, 1 the device, 2 the host (RK_GATHER_DEVICE=0) */
+    uint32_t rows;           /* selected rows */
+    uint32_t batches;
+    uint32_t rounds;         /* the most picks of any row: the rounds that did work */
+    uint32_t launched_rounds;   /* rounds the host launched, all batches; at most sync_every - 1 more per batch than the batch needed, plus the one that retires */
+    uint32_t launches;       /* kernels of this unit the host launched */
+    uint32_t read_backs;     /* synchronising reads of the counters */
+    uint32_t compactions;    /* of the live lists */
+    uint32_t lane_max, wave_max, sync_every, threads;   /* the constants of the round kernels (every path fills them) */
+} rk_gather_stats;           /* 112 bytes */
+int rk_gather_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_gather_opts *opts, uint64_t *off_out /* host, Q + 1 */,
+                   rk_gather_pick **picks_out, uint64_t *n_picks, uint32_t *matched_out /* host, Q */, uint32_t *n_cand_out /* host, Q */,
+                   uint32_t *covered_out /* host, Q */, rk_gather_stats *stats /* optional */);
+/* Host only: the same rule over posting lists as rk_index_export_lists / rk_index_export64 return them (reference ids below n_ref in
+ * any order within a list, repeats counted once) -- blind to the hash width: per query i the indices of the lists its hashes hit,
+ * strictly ascending, are q_lists[q_off[i] .. q_off[i + 1]).  ref_sizes (n_ref) and query_sizes (n_query) only fill the records.  The
+ * outputs are those of rk_gather_rows.  RK_ERR_ARG: null pointers (postings / counts may be NULL without lists, q_lists when no query
+ * hits a list, the size arrays and the per-query outputs when their number is 0), min_new == 0, offsets that do not ascend from 0, a
+ * list index >= n_lists or out of order, a posting >= n_ref.  Nothing is written on a refusal. */
+int rk_gather_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off /* n_query + 1 */,
+                    const uint64_t *q_lists, uint32_t n_query, uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes,
+                    const rk_gather_opts *opts, uint64_t *off_out /* n_query + 1 */, rk_gather_pick **picks_out, uint64_t *n_picks,
+                    uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *covered_out);
+
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,
                   const rk_hit *hit);

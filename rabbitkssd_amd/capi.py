@@ -32,7 +32,7 @@ EXPORTS = [
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
     "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
-    "rk_group_sketches", "rk_group_lists",
+    "rk_group_sketches", "rk_group_lists", "rk_gather_rows", "rk_gather_lists",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -47,6 +47,10 @@ MEDOID_NONE = 0xFFFFFFFF    # RK_MEDOID_NONE: the label of an unlabelled genome,
 ASSIGN_NONE = 0xFFFFFFFF    # RK_ASSIGN_NONE: the label of an unlabelled reference and of a novel query, row and col of an absent record
 GROUP_NONE = 0xFFFFFFFF     # RK_GROUP_NONE: the label of an unlabelled genome (rk_group_sketches, rk_group_lists)
 MS_GROUP = 13               # RK_MS_GROUP: the timed span of rk_group_sketches (Context.last_ms)
+MS_GATHER = 14              # RK_MS_GATHER: the timed span of rk_gather_rows (Context.last_ms)
+# rk_gather_pick: one record per pick of rk_gather_rows / rk_gather_lists
+GATHER_PICK_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("rank", "<u4"), ("common", "<u4"), ("fresh", "<u4"), ("left", "<u4"),
+                              ("size_ref", "<u4"), ("size_query", "<u4")])
 # rk_medoid_cluster: one record per non-empty cluster (medoid_pick)
 MEDOID_CLUSTER_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("medoid", "<u4"), ("pad", "<u4"), ("in_edges", "<u8"), ("central", "<u8"),
                                  ("weakest_in", HIT_DTYPE), ("nearest_out", HIT_DTYPE)])
@@ -152,6 +156,19 @@ class GroupStats(C.Structure):
     _fields_ = [("lists", C.c_uint64), ("postings", C.c_uint64), ("kept", C.c_uint64), ("lane_lists", C.c_uint64), ("wave_lists", C.c_uint64),
                 ("block_lists", C.c_uint64), ("spilled", C.c_uint64), ("labelled", C.c_uint32), ("groups", C.c_uint32), ("attempts", C.c_uint32),
                 ("path", C.c_uint32), ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("table_groups", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+class GatherOpts(C.Structure):
+    """rk_gather_opts: a pick adds at least min_new hashes, at most max_picks picks per query (0: no limit), the row shard"""
+    _fields_ = [("min_new", C.c_uint32), ("max_picks", C.c_uint32), ("row_first", C.c_uint32), ("row_step", C.c_uint32), ("row_block", C.c_uint32)]
+
+
+class GatherStats(C.Structure):
+    """rk_gather_stats: what one rk_gather_rows call did"""
+    _fields_ = [("picks", C.c_uint64), ("candidates", C.c_uint64), ("matched", C.c_uint64), ("decrements", C.c_uint64), ("lane_lists", C.c_uint64),
+                ("wave_lists", C.c_uint64), ("block_lists", C.c_uint64), ("rows_per_batch", C.c_uint64), ("path", C.c_uint32), ("rows", C.c_uint32),
+                ("batches", C.c_uint32), ("rounds", C.c_uint32), ("launched_rounds", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32),
+                ("compactions", C.c_uint32), ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("sync_every", C.c_uint32), ("threads", C.c_uint32)]
 
 
 def group_rule(rule):
@@ -703,6 +720,30 @@ class Context:
         self.check(L.rk_group_sketches(self._h, index._h, _ptr(labels), C.byref(r), C.byref(h), C.byref(gl), C.byref(gs), C.byref(k), C.byref(st)))
         return (Sketches(self, h) if h.value else None), _take_array(gl, k.value, np.uint32), _take_array(gs, k.value, np.uint32), _stats_dict(st)
 
+    def gather_rows(self, index, queries, min_new=1, max_picks=0, row_first=0, row_step=1, row_block=0, out=None):
+        """the references that explain each query sketch, greedily (rk_gather_rows): (off, picks, matched, n_cand, covered, stats) -- per
+        round the reference that holds most of the query's hashes no earlier pick held (ties: the smaller index), until fewer than
+        min_new are added or max_picks (0: no limit) are made.  picks (GATHER_PICK_DTYPE) in (query, rank) order, those of query q at
+        picks[off[q]:off[q + 1]] (off: uint64, Q + 1); matched / n_cand / covered (uint32, Q): the query's hashes that have a posting
+        list, the references sharing at least min_new hashes, the sum of fresh.  Only the entries of the selected query rows are
+        written: `out` (matched, n_cand, covered as returned) lets row shards write into one set; their picks concatenate"""
+        q = queries.count if queries is not None else 0
+        if out is None:
+            out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(3))
+        elif len(out) != 3 or any(not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.shape == (q,) and a.flags.c_contiguous and a.flags.writeable)
+                                  for a in out):
+            raise ValueError("out needs (matched, n_cand, covered): writable contiguous uint32 arrays of one entry per query")
+        o = GatherOpts(int(min_new), int(max_picks), int(row_first), int(row_step), int(row_block))
+        off = np.zeros(q + 1, dtype=np.uint64)
+        picks, n = C.c_void_p(), C.c_uint64()
+        st = GatherStats()
+        L = lib()
+        L.rk_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GatherOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GatherStats)]
+        self.check(L.rk_gather_rows(self._h, index._h, queries._h if queries is not None else None, C.byref(o), _ptr(off), C.byref(picks), C.byref(n),
+                                    _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(st)))
+        return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + tuple(out) + (_stats_dict(st),)
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -1097,6 +1138,38 @@ def group_lists(postings, counts, n_genomes, labels, rule="pan"):
                           "share_num <= share_den, share_den >= 1, min_count >= 1, only <= 1")
     off = _take_array(off, k.value + 1, np.uint64)
     return off, _take_array(kept, int(off[-1]), np.uint64), _take_array(gl, k.value, np.uint32), _take_array(gs, k.value, np.uint32)
+
+
+def gather_lists(postings, counts, q_off, q_lists, n_ref, ref_sizes, query_sizes, min_new=1, max_picks=0, row_first=0, row_step=1, row_block=0):
+    """the rule of Context.gather_rows over exported posting lists (rk_gather_lists, host only): (off, picks, matched, n_cand, covered) --
+    the lists back to back in `postings` with their lengths in `counts` (Index.export_lists / export64), reference ids in any order
+    within a list, repeats counted once; q_lists[q_off[i]:q_off[i + 1]] = the indices of the lists query i's hashes hit, ascending"""
+    postings = np.ascontiguousarray(postings, dtype=np.uint32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if int(counts.sum(dtype=np.uint64)) != len(postings):
+        raise ValueError("gather_lists: the counts do not add up to the postings")
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    q_lists = np.ascontiguousarray(q_lists, dtype=np.uint64)
+    ref_sizes = np.ascontiguousarray(ref_sizes, dtype=np.uint32)
+    query_sizes = np.ascontiguousarray(query_sizes, dtype=np.uint32)
+    q = len(query_sizes)
+    if len(q_off) != q + 1 or len(ref_sizes) != int(n_ref) or (q and int(q_off[-1]) != len(q_lists)):
+        raise ValueError("gather_lists needs one size per reference and query and q_off of one entry more than the queries, ending at len(q_lists)")
+    o = GatherOpts(int(min_new), int(max_picks), int(row_first), int(row_step), int(row_block))
+    off = np.zeros(q + 1, dtype=np.uint64)
+    out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(3))
+    picks, n = C.c_void_p(), C.c_uint64()
+    L = lib()
+    L.rk_gather_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                  C.POINTER(GatherOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.rk_gather_lists(_ptr(postings) if len(postings) else None, _ptr(counts) if len(counts) else None, C.c_uint64(len(counts)), _ptr(q_off),
+                           _ptr(q_lists) if len(q_lists) else None, C.c_uint32(q), C.c_uint32(n_ref), _ptr(ref_sizes) if n_ref else None,
+                           _ptr(query_sizes) if q else None, C.byref(o), _ptr(off), C.byref(picks), C.byref(n), _ptr(out[0]) if q else None,
+                           _ptr(out[1]) if q else None, _ptr(out[2]) if q else None)
+    if rc:
+        raise RkError(rc, "rk_gather_lists: min_new == 0, offsets that do not ascend from 0, a list index beyond the lists or out of order, "
+                          "or a posting beyond the number of references")
+    return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + out
 
 
 def medoid_merge(a, b, n, metric):

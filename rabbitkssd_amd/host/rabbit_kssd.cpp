@@ -2168,6 +2168,78 @@ static int cmd_assign(const Args &a)
     SelfJoin::leave();
 }
 
+// gather: which references explain each query sketch (rk_gather_rows): per round the reference that holds most of the query's hashes
+// no earlier pick held -- the greedy minimum set cover, a metagenome's decomposition.  One line per pick:
+// query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref.
+static int cmd_gather(const Args &a)
+{
+    if (!a.has("r") || !a.has("q")) die("gather needs -r and -q");
+    if (a.num("gpus", 1) != 1) die("command_gather(), gather runs on one GPU (--gpus 1)");
+    if (a.has("min-new") && a.num("min-new", 1) < 1) die("command_gather(), --min-new must be >= 1");
+    if (a.has("max-picks") && a.num("max-picks", 0) < 0) die("command_gather(), --max-picks must be >= 0 (0: no limit)");
+    const string out = a.str("o", "result.out");
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), 1, false);
+    SketchSet ref, qry;
+    string ref_path, qry_path;
+    {   // .sketch inputs are read while the runtime starts
+        string err;
+        if (is_sketch_file(a.str("r", ""))) {
+            ref_path = a.str("r", "");
+            if (!read_sketches(ref_path, ref, err)) die("readSketches(), %s", err.c_str());
+        }
+        if (is_sketch_file(a.str("q", ""))) {
+            qry_path = a.str("q", "");
+            if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
+        }
+    }
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), false, a, threads, ref, ref_path);
+    cerr << "the ref_sketch size is: " << ref.size() << endl;
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), true, a, threads, qry, qry_path);
+    if (qry.info.id != ref.info.id)
+        die("command_gather(), the sketch infos between reference and query files are not match\n"
+            "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    const size_t N = ref.size(), Q = qry.size();
+    const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
+    vector<rk_index *> idx(1, nullptr);
+    build_everywhere(set, ref, ref_path, missing, idx);
+    stamp("index built");
+    cerr << "=====total: " << Q << endl;
+    const rk_gather_opts o{(uint32_t)a.num("min-new", 1), (uint32_t)a.num("max-picks", 0), 0, 0, 0};
+    vector<uint64_t> off(Q + 1, 0);
+    vector<uint32_t> matched(Q ? Q : 1, 0), n_cand(Q ? Q : 1, 0), covered(Q ? Q : 1, 0);
+    rk_gather_pick *picks = nullptr;
+    uint64_t n_picks = 0;
+    rk_gather_stats stats;
+    rk_sketches *qs = upload(set[0], qry);
+    set[0].check(rk_gather_rows(set[0].ctx, idx[0], qs, &o, off.data(), &picks, &n_picks, matched.data(), n_cand.data(), covered.data(), &stats), "rk_gather_rows");
+    rk_sketches_free(qs);
+    stamp("queries decomposed");
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    for (uint64_t k = 0; k < n_picks; k++) {
+        const rk_gather_pick &p = picks[k];
+        fprintf(fp, "%s\t%s\t%u\t%u|%u|%u\t%u\t%f\t%f\n", qry.names[p.query].c_str(), ref.names[p.ref].c_str(), p.rank, p.common, p.size_ref, p.size_query, p.fresh,
+                (double)p.fresh / (double)p.size_query, (double)p.common / (double)p.size_ref);
+    }
+    fclose(fp);
+    if (a.has("summary")) {
+        FILE *sp = fopen(a.str("summary", "").c_str(), "w");
+        if (!sp) die("cannot write %s", a.str("summary", "").c_str());
+        for (size_t q = 0; q < Q; q++)
+            fprintf(sp, "%s\t%llu\t%u\t%u\t%u\t%llu\n", qry.names[q].c_str(), (unsigned long long)(qry.off[q + 1] - qry.off[q]), matched[q], covered[q], n_cand[q],
+                    (unsigned long long)(off[q + 1] - off[q]));
+        fclose(sp);
+    }
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %zu queries against %zu references: %llu picks of %llu candidates in %u rounds (%u launched, %u batches, %u read-backs), %llu lists died "
+                        "(%llu by lane, %llu by wave, %llu by workgroup), path %u\n", Q, N, (unsigned long long)stats.picks, (unsigned long long)stats.candidates, stats.rounds,
+                stats.launched_rounds, stats.batches, stats.read_backs, (unsigned long long)(stats.lane_lists + stats.wave_lists + stats.block_lists),
+                (unsigned long long)stats.lane_lists, (unsigned long long)stats.wave_lists, (unsigned long long)stats.block_lists, stats.path);
+    rk_free_host(picks);
+    SelfJoin::leave();
+}
+
 // test helper: the text writer alone (no GPU): `_format alldist|dist names.txt hits.bin out pieces threads`;
 // hits.bin = rk_hit records sorted by (row, col), dealt to `pieces` parts in blocks of 32 rows like --gpus does
 static int cmd_format(int argc, char **argv)
@@ -2463,7 +2535,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert merge info\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2476,6 +2548,7 @@ static int usage()
             "  medoid -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--by cluster|greedy|dbscan] [-m minPts] [--labels FILE] [--census FILE] [-L file.shuf] [--device N] [--gpus G]   (medoids and census of a clustering of alldist's pairs: per genome its cluster, its role -- the medoid is the member with the highest summed similarity to its fellow members --, its pairs inside the cluster and leaving it, its mean similarity to its fellow members and its nearest genome outside; the labels from --by (default cluster; dbscan needs -m; greedy and dbscan on one GPU) or from --labels: one line per genome, an integer below the number of genomes or -; --census: per cluster its size, medoid, inside pairs of size (size - 1) / 2, weakest inside pair and nearest leaving pair)\n"
             "  assign -r ref.sketch|list -q qry.sketch|list -D maxDist [-M 0|1] (--labels FILE | --by cluster|greedy|dbscan -m minPts) -o out [--novel FILE] [--gpus G] [--device N]   (placement of the queries into the clustered references: per query the cluster of its nearest labelled reference within -D, that reference's dist line, the query's references of that cluster, labelled and all within -D, and the runner-up cluster with its distance; - when novel; -D below 1.0; the labels from --labels -- one line per reference, an integer below their number or - -- or from --by on the same index (default cluster; dbscan needs -m and leaves non-core references unlabelled; greedy and dbscan on the first GPU); --novel: the names of the unplaced queries)\n"
             "  group -i in.sketch|genomes.list (--labels FILE | --by cluster|greedy|dbscan [-D 0.05] [-M 0|1] [-m 5]) [--pan | --core | --share P/Q] [--min-count C] [--only] -o out.sketch [--map FILE] [--device N]   (one sketch per cluster: --pan, the default, the union of its members' sketches; --core the hashes every member holds; --share P/Q those at least P of Q of its members hold; --min-count C: at least C members hold it; --only: no genome outside the cluster holds it -- its markers; the labels as medoid takes them; out.sketch: one sketch per cluster by ascending label, named after its first member; --map: per cluster its number, label, genomes, hashes kept and name; one GPU)\n"
+            "  gather -r ref.sketch|list -q qry.sketch|list [--min-new 1] [--max-picks 0] -o out [--summary FILE] [--device N]   (which references explain each query, greedily: per round the reference that holds most of the query's hashes no earlier pick held, ties to the earlier reference, until a pick would add fewer than --min-new hashes or --max-picks are made; one line per pick: query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref; --summary: per query its name, size, hashes some reference holds, hashes the picks explain, references sharing at least --min-new hashes, picks; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -2497,7 +2570,8 @@ int main(int argc, char **argv)
         {"-M", "M"}, {"--metric", "M"}, {"-N", "N"}, {"--neighborN_max", "N"}, {"-r", "r"}, {"--reference", "r"},
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
         {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"},
-        {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"}};
+        {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"},
+        {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--summary", "summary"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2515,7 +2589,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2542,6 +2616,7 @@ int main(int argc, char **argv)
     if (sub == "medoid") { cerr << "-----run the subcommand: medoid" << endl; return leave(cmd_medoid(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "assign") { cerr << "-----run the subcommand: assign" << endl; return leave(cmd_assign(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "group") { cerr << "-----run the subcommand: group" << endl; return leave(cmd_group(parse_args(argc, argv, 2, alias, {"pan", "core", "only"}))); }   // (--core is a flag here, a file of mreach)
+    if (sub == "gather") { cerr << "-----run the subcommand: gather" << endl; return leave(cmd_gather(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
