@@ -46,6 +46,9 @@ MREACH_NONE = 0xFFFFFFFF    # RK_MREACH_NONE: core_nb of a genome without a core
 MEDOID_NONE = 0xFFFFFFFF    # RK_MEDOID_NONE: the label of an unlabelled genome, row and col of an absent record
 ASSIGN_NONE = 0xFFFFFFFF    # RK_ASSIGN_NONE: the label of an unlabelled reference and of a novel query, row and col of an absent record
 GROUP_NONE = 0xFFFFFFFF     # RK_GROUP_NONE: the label of an unlabelled genome (rk_group_sketches, rk_group_lists)
+# RK_MS_TOPN_*: the stages of the last rk_dist_topn (Context.last_ms, timing on): counting kernel, selection kernel, candidates' sort
+# + download, host finish in ms; MS_TOPN_CANDIDATES is no time but the number of candidate records the selection kernel emitted
+MS_TOPN_COUNTS, MS_TOPN_SELECT, MS_TOPN_DOWNLOAD, MS_TOPN_HOST, MS_TOPN_CANDIDATES = 1, 2, 3, 4, 5
 MS_GROUP = 13               # RK_MS_GROUP: the timed span of rk_group_sketches (Context.last_ms)
 MS_GATHER = 14              # RK_MS_GATHER: the timed span of rk_gather_rows (Context.last_ms)
 # rk_gather_pick: one record per pick of rk_gather_rows / rk_gather_lists

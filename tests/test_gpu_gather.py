@@ -360,6 +360,34 @@ def test_row_shards_concatenate_to_the_whole(ctx, block):
     assert both.tobytes() == whole[1].tobytes() and all(np.array_equal(a, b) for a, b in zip(out, whole[2:]))
 
 
+@pytest.mark.parametrize("sliced", [False, True])
+@pytest.mark.parametrize("rows_per_batch", [1, 3])
+def test_shards_with_a_partial_last_block_in_batches(ctx, monkeypatch, rows_per_batch, sliced):
+    """23 rows in blocks of 4 dealt to 3 shards: block 5 (rows 20 .. 22) is partial and belongs to shard 2.  Batches of one row, and of
+    three (a batch boundary inside every block), of rk_distq_counts(slot_base, n_slots) -- also over the sliced membership pass, which
+    the later batches of a call reuse."""
+    refs, queries, bits = clades(False)
+    queries, want = queries[:23], wanted(False, 1, 0)[:23]
+    idx = index_of(ctx, refs, False, bits)
+    qs = queries_of(ctx, queries)
+    row_bytes = 12 * len(refs) + 16 * max(len(q) for q in queries) + 64   # rk_gather.hip: counter row, candidates, items twice, state
+    plain_name = ctx.dist_kernel_name(idx, qs, 0, 0, 20, 1.0)
+    for first in range(3):
+        shard = dict(row_first=first, row_step=3, row_block=4)
+        one, st = gathered(ctx, idx, qs, refs, queries, want=want, **shard)
+        assert st["batches"] == 1 and st["rows"] == (8, 8, 7)[first] == st["rows_per_batch"]
+        monkeypatch.setenv("RK_GATHER_BATCH_BYTES", str(rows_per_batch * row_bytes + row_bytes // 2))
+        if sliced:
+            monkeypatch.setenv("RK_DISTQ_SLICED", "1")
+            assert ctx.dist_kernel_name(idx, qs, 0, 0, 20, 1.0) != plain_name   # the pre-resolved look-up is what runs
+        many, st = gathered(ctx, idx, qs, refs, queries, want=want, **shard)
+        assert st["rows_per_batch"] == rows_per_batch and st["batches"] == -(-st["rows"] // rows_per_batch) >= 3
+        assert result_bytes(many) == result_bytes(one) and len(many[1]) > 8
+        monkeypatch.delenv("RK_GATHER_BATCH_BYTES")
+        monkeypatch.delenv("RK_DISTQ_SLICED", raising=False)
+    assert ga.selected_rows(23, 2, 3, 4)[-3:] == [20, 21, 22]
+
+
 def test_host_leg_gives_the_same_bytes(ctx, monkeypatch):
     for wide in (False, True):
         refs, queries, bits = clades(wide)
