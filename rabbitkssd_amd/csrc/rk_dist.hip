@@ -407,9 +407,10 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 || THREADS == 768) ? 6 : 4
                         continue;
                     }
                     uint32_t at = atomicAdd(&s_ncand[ccur], n);
-                    // a quad whose cells do not all fit stays in the row (and is not cleared): the walk below finds it
+                    // a quad whose cells do not all fit stays in the row; the walk below may find only such quads, so one that
+                    // fits is cleared whether or not the rows are kept clean
                     const bool fits = at + n <= kCandCap;
-                    if (keep_clean && fits) z4s[q] = make_uint4(0, 0, 0, 0);
+                    if ((FILTER || keep_clean) && fits) z4s[q] = make_uint4(0, 0, 0, 0);
                     const bool in_b = PAIR && cq >= row_b_cell;
                     const uint32_t erow = in_b ? row_b : row_a;
                     const uint32_t eq = (uint32_t)(in_b ? qsize_b : qsize_a);
@@ -481,9 +482,10 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 || THREADS == 768) ? 6 : 4
                         continue;
                     }
                     uint32_t at = atomicAdd(&s_ncand[par], n);
-                    // a quad whose cells do not all fit stays in the row (and is not cleared): the walk below finds it
+                    // a quad whose cells do not all fit stays in the row; the walk below may find only such quads, so one that
+                    // fits is cleared whether or not the rows are kept clean
                     const bool fits = at + n <= kCandCap;
-                    if (keep_clean && fits) z4s[q] = make_uint4(0, 0, 0, 0);
+                    if ((FILTER || keep_clean) && fits) z4s[q] = make_uint4(0, 0, 0, 0);
 #pragma unroll
                     for (int wi = 0; wi < 4; wi++) {
 #pragma unroll

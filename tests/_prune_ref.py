@@ -290,6 +290,9 @@ SITE_PAD = 200                         # jaccard: a genome that holds fewer hash
 SITE_STRIDE = 80
 
 
+FAMILY = 20                            # more than a cell list of 16 entries holds
+
+
 def site_counts(metric):
     """(floor_common of a site's row, first_reportable of a relative)"""
     D = SITE_D[metric]
@@ -300,7 +303,7 @@ def site_counts(metric):
 def site_min_ref_size(kind, metric):
     """the smallest sketch: containment collections hold nothing below a row's 1,000 hashes (the bound of every row is built
     from it); jaccard: the far genome of floor_common - 1 hashes, or the padded one of the loud collection"""
-    return SITE_Q if metric else min(site_counts(0)[0] - 1, SITE_PAD if kind == "loud" else SITE_Q)
+    return SITE_Q if metric else min(site_counts(0)[0] - 1, SITE_PAD if kind in ("loud", "family") else SITE_Q)
 
 
 def site_specs(kind, metric):
@@ -322,7 +325,10 @@ def site_specs(kind, metric):
     ]
     if metric:
         loud.append((0, 3 * SITE_Q, [(33, fr, 0)]))
-    return {"quiet": quiet, "edge": quiet + loud[:1], "loud": quiet + loud}[kind]
+    # a far family: FAMILY genomes behind the window with first_reportable hashes of the row each -- the row falls back and
+    # brings that many cells into the fallback's cell list
+    family = [(0, SITE_Q, [(33 + i, fr, 0) for i in range(FAMILY)])]
+    return {"quiet": quiet, "edge": quiet + loud[:1], "loud": quiet + loud, "family": quiet + loud + family}[kind]
 
 
 @functools.lru_cache(maxsize=None)

@@ -19,56 +19,20 @@ import math
 import numpy as np
 import pytest
 
-from rabbitkssd_amd import capi
-
+import _gpu_join as gj
 import _prune_ref as pr
+from _gpu_join import assert_hits_equal, make_ctx, pairs_of
 
 pytestmark = pytest.mark.gpu
 K = pr.K
-CREATION = ("RK_INDEX_RELABEL", "RK_DIST_TILES", "RK_INDEX_TILES", "RK_DIST_NEAR", "RK_DIST_NEAR_UW", "RK_DIST_PAIR",
-            "RK_DIST_BAND_MIN_ROWS", "RK_DIST_LDS_KB")
-
-
-def make_ctx(monkeypatch, env, relabel=False):
-    """a context with these developer switches (they are read when it is created) and, unless `relabel`, the caller's order"""
-    env = dict(env)
-    if not relabel:
-        env["RK_INDEX_RELABEL"] = "0"
-    for k in CREATION:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        assert k in CREATION
-        monkeypatch.setenv(k, v)
-    ctx = capi.Context(0)
-    for k in env:
-        monkeypatch.delenv(k)
-    return ctx
-
-
-def assert_hits_equal(mine, want):
-    """as tests/test_gpu_parity.py: integers equal, jorc and dist bit for bit (rk_dist_rows)"""
-    assert len(mine) == len(want), (len(mine), len(want))
-    for f in ("row", "col", "common", "size0", "size1"):
-        assert np.array_equal(mine[f], want[f]), f
-    assert np.array_equal(mine["jorc"], want["jorc"])
-    assert np.array_equal(mine["dist"], want["dist"])
 
 
 def join(ctx, idx, metric, D, **shard):
-    return ctx.dist_rows(idx, None, 1, metric, K, D, **shard)[0]
+    return gj.join(ctx, idx, metric, D, K, **shard)
 
 
 def assert_shards(ctx, idx, metric, D, want, shards):
-    for step, block in shards:
-        parts = [join(ctx, idx, metric, D, row_first=r, row_step=step, row_block=block) for r in range(step)]
-        for r, p in enumerate(parts):
-            assert np.all(idx.shard_of(p, step, block) == r)
-        merged = np.concatenate(parts)
-        assert_hits_equal(merged[np.lexsort((merged["col"], merged["row"]))], want)
-
-
-def pairs_of(hits):
-    return set(zip(hits["row"].tolist(), hits["col"].tolist()))
+    gj.assert_shards(ctx, idx, metric, D, K, want, shards)
 
 
 def build(ctx, key):

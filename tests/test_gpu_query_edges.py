@@ -5,7 +5,6 @@ rk_dist_rows, within 1e-12 through rk_dist_rows_dev.  Every case asserts the ker
 reference, the property it was built for; sizes make that property hold by arithmetic (the whole LDS is 160 KiB), not by
 the planner's constants."""
 import functools
-import math
 import os
 
 import numpy as np
@@ -15,14 +14,15 @@ import torch
 from oracle import oracle as ok
 from rabbitkssd_amd import capi
 
+import _gpu_join as gj
 import _query_ref as qr
+from _gpu_join import REC, check_dev
+from _rows_ref import min_common      # (the row-level reject is the same expression in rk_distq_kernel and rk_dist_kernel)
 
 pytestmark = pytest.mark.gpu
 K = 20
 LDS_BYTES = 160 * 1024     # all the LDS of a CU: a counter row above it cannot be one tile
 CORES = min(16, os.cpu_count() or 1)
-REC = capi.HIT_DTYPE.itemsize
-GUARD = 4096               # bytes of a known pattern behind every device hit buffer
 
 
 def make_ctx(relabel):
@@ -53,24 +53,7 @@ def upload(ctx, h, off):
 
 
 def dev_records(ctx, idx, qs, triangle, metric, D, cap, **shard):
-    """(*n_hits_dev, the min(n, cap) records by (row, col)) of rk_dist_rows_dev; the guard behind the buffer must be untouched"""
-    buf = torch.full((cap * REC + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    ctx.dist_rows_dev(idx, triangle, metric, K, D, buf.data_ptr(), cap, cnt.data_ptr(),
-                      stream=torch.cuda.current_stream().cuda_stream, queries=qs, **shard)
-    torch.cuda.synchronize()
-    n = int(cnt.item())
-    raw = buf.cpu().numpy()
-    assert np.all(raw[cap * REC:] == 0xA5), "bytes behind hits_cap were written"
-    got = np.frombuffer(raw[: min(n, cap) * REC].tobytes(), dtype=capi.HIT_DTYPE)
-    return n, got[np.lexsort((got["col"], got["row"]))]
-
-
-def check_dev(dev, want):
-    assert len(dev) == len(want)
-    for f in ("row", "col", "common", "size0", "size1", "pad", "jorc"):
-        assert np.array_equal(dev[f], want[f]), f
-    assert np.max(np.abs(dev["dist"] - want["dist"]), initial=0.0) <= 1e-12
+    return gj.dev_records(ctx, idx, qs, triangle, metric, D, K, cap, **shard)
 
 
 def check_both(ctx, idx, qs, want, triangle, metric, D, wdense=None, **shard):
@@ -442,14 +425,6 @@ def epilogue_data():
     return bits, rh, roff, qh, qoff, np.flatnonzero(kinds == 0)
 
 
-def min_common(metric, D, qsize, min_ref_size):
-    """the row-level reject of rk_distq_kernel: cells below it never enter the candidate list"""
-    t = math.exp(-K * D)
-    min_jorc = (t if metric else t / (2.0 - t)) * (1.0 - 1e-6)
-    lb = min(qsize, min_ref_size) if metric else qsize
-    return max(1, int(math.floor(min_jorc * lb)))
-
-
 @pytest.mark.parametrize("leg", ["identity", "shipped"])
 def test_sparse_epilogue_overflows_its_list_and_its_stage(ctxs, leg):
     """More than 256 candidate cells in a unit (families of 257..260 references leave a quad that fits the list partly or not
@@ -500,10 +475,4 @@ def test_device_hits_over_capacity(ctxs, D):
         assert len(want) > 100000 and (D < 1 or len(want) == nq * n_ref)
         cap = len(want) // 3
         n, got = dev_records(ctx, idx, qs, 0, metric, D, cap)       # (asserts the guard)
-        assert n == len(want) and len(got) == cap
-        wkey = want["row"].astype(np.int64) * n_ref + want["col"]
-        gkey = got["row"].astype(np.int64) * n_ref + got["col"]
-        assert len(np.unique(gkey)) == cap                          # no record twice
-        at = np.searchsorted(wkey, gkey)
-        assert np.all(at < len(wkey)) and np.array_equal(wkey[np.minimum(at, len(wkey) - 1)], gkey)
-        check_dev(got, want[at])
+        gj.assert_capped_records(n, got, want, cap, n_ref)
