@@ -50,7 +50,8 @@ def build(force=False, verbose=False):
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs)
     # host tool (C++ above the C ABI): rabbit_kssd with the reference's command line
     host_src = os.path.join(HERE, "host", "rabbit_kssd.cpp")
-    host_deps = [host_src, os.path.join(HERE, "host", "formats.hpp"), os.path.join(ROOT, "include", "rabbitkssd.h"), LIB]
+    host_deps = [host_src, os.path.join(HERE, "host", "formats.hpp"), os.path.join(HERE, "host", "sketch_input.hpp"),
+                 os.path.join(ROOT, "include", "rabbitkssd.h"), LIB]
     if force or _newer(TOOL, host_deps):
         # plain g++: the host side sees only the C ABI (no HIP headers, no device pass)
         run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), host_src, "-o", TOOL,

@@ -407,6 +407,35 @@ class RecordReader {
         return r;
     }
 
+    // The FASTA line walk of everything that parses a text piece by piece (parse_packed_parallel below, the streamed
+    // readers of sketch_input.hpp).  t[0, n) starts at a line start.  What it contributes to the packed layout: every
+    // header line starts a record (one 0x00 separator, except for the file's first: `starts_file` and at t[0]), every
+    // other non-empty line its characters.  w == nullptr counts only.  bad: a '+' or '@' line (FASTQ) or a line that
+    // ends in '\r' -- not a text for this walk, whatever was written is to be discarded.
+    struct Lines { uint64_t bytes = 0, headers = 0; bool bad = false; };
+    static Lines walk_fasta_lines(const uint8_t *t, size_t n, bool starts_file, uint8_t *w)
+    {
+        Lines r;
+        size_t pos = 0;
+        while (pos < n) {
+            const uint8_t c = t[pos];
+            const size_t e = (size_t)(line_end(t + pos, t + n) - t);
+            if (c == '>') {
+                if (!(starts_file && pos == 0)) { if (w) *w++ = 0; r.bytes++; }   // (a window never spans records, src/sketch.cpp:487-488)
+                r.headers++;
+            } else if (c == '+' || c == '@') {
+                r.bad = true;
+                return r;
+            } else if (e > pos) {
+                if (t[e - 1] == '\r') { r.bad = true; return r; }
+                if (w) { memcpy(w, t + pos, e - pos); w += e - pos; }
+                r.bytes += e - pos;
+            }
+            pos = e + 1;
+        }
+        return r;
+    }
+
     // Big plain FASTA files (one 3 Gb genome is a single list entry): the buffer is cut into
     // `threads` pieces at line starts -- kseq looks for '>' only at the start of a line
     // (src/kseq.h:192-196), so a piece needs no context -- each piece counts its packed bytes, a
@@ -430,38 +459,11 @@ class RecordReader {
             const uint8_t *e = line_end(b + p, b + n);
             cut[i] = e < b + n ? (size_t)(e - b) + 1 : n;
         }
-        struct Piece { uint64_t bytes = 0, headers = 0; bool bad = false; };
-        std::vector<Piece> pc(T);
-        // what a piece contributes: every header line starts a record (a separator, except for the
-        // file's first), every other non-empty line its characters
-        auto walk = [&](size_t i, uint8_t *to) {
-            Piece &q = pc[i];
-            size_t pos = cut[i];
-            const size_t end = cut[i + 1];
-            uint8_t *w = to;
-            uint64_t bytes = 0, headers = 0;
-            while (pos < end) {
-                const uint8_t c = b[pos];
-                const size_t e = (size_t)(line_end(b + pos, b + end) - b);
-                if (c == '>') {
-                    if (pos != start) { if (w) *w++ = 0; bytes++; }
-                    headers++;
-                } else if (c == '+' || c == '@') {
-                    q.bad = true;
-                    return;
-                } else if (e > pos) {
-                    if (b[e - 1] == '\r') { q.bad = true; return; }
-                    if (w) { memcpy(w, b + pos, e - pos); w += e - pos; }
-                    bytes += e - pos;
-                }
-                pos = e + 1;
-            }
-            q.bytes = bytes;
-            q.headers = headers;
-        };
+        std::vector<Lines> pc(T);
         auto run = [&](uint8_t *const *targets) {
             std::vector<std::thread> pool;
-            for (size_t i = 0; i < T; i++) pool.emplace_back([&, i]() { walk(i, targets ? targets[i] : nullptr); });
+            for (size_t i = 0; i < T; i++)
+                pool.emplace_back([&, i]() { pc[i] = walk_fasta_lines(b + cut[i], cut[i + 1] - cut[i], i == 0, targets ? targets[i] : nullptr); });
             for (auto &th : pool) th.join();
         };
         run(nullptr);

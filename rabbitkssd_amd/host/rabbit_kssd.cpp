@@ -22,16 +22,14 @@
 #include <atomic>
 #include <cerrno>
 #include <cmath>
-#include <condition_variable>
-#include <deque>
 #include <cstdarg>
 #include <iostream>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <thread>
 
 #include "formats.hpp"
+#include "sketch_input.hpp"
 #include "rabbitkssd.h"
 
 using namespace rkhost;
@@ -83,450 +81,6 @@ struct Gpu {
         if (rc) die("%s failed (%d): %s", what, rc, rk_last_error(ctx));
     }
 };
-
-// ---- one big plain FASTA file, streamed (the role of src/sketch.cpp:380-450: RabbitFX chunks of a big file go to the
-// consumers while the producer is still reading) --------------------------------------------------------------------
-// A 3 Gb genome used to be read completely, parsed in two passes into ordinary memory and only then uploaded
-// (0.71 s + 0.09 s).  Now the file is mapped and cut into pieces at line starts; parser threads turn piece after piece
-// into the packed layout -- ONE pass, straight into a small ring of page-locked buffers -- and the calling thread
-// uploads every finished piece to its own slot of the device buffer while the others are still being parsed.  A piece
-// starts with the last k-1 bases in front of it (unless a header line lies between), so that every window is seen
-// exactly once: by the piece it ENDS in.  Slots are sized for the piece's file bytes (newlines become padding: zero
-// bytes, which the kernel treats like any invalid base), so no piece has to know how much the pieces before it shrank.
-// Returns false -- nothing done -- for inputs this path does not take (FASTQ, '\r' line ends, no header at the start):
-// the caller falls back to the whole-file path.
-static bool sketch_big_fasta_streamed(Gpu &gpu, const rk_filter *flt, const string &path, int kmer, int threads, uint32_t min_count,
-                                      void *stream, rk_sketches **sk_out, bool timing)
-{
-    const double t0 = get_sec();
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return false;
-    struct stat st;
-    if (fstat(fd, &st) || st.st_size < 64) { close(fd); return false; }
-    const size_t sz = (size_t)st.st_size;
-    const uint8_t *b = (const uint8_t *)mmap(nullptr, sz, PROT_READ, MAP_PRIVATE, fd, 0);
-    close(fd);
-    if (b == MAP_FAILED) return false;
-    (void)madvise((void *)b, sz, MADV_SEQUENTIAL);
-    struct Unmap { const uint8_t *p; size_t n; ~Unmap() { munmap((void *)p, n); } } unmap{b, sz};
-    if (b[0] != '>') return false;   // (kseq skips to the first header: leave odd files to the serial reader)
-
-    size_t piece = (size_t)(getenv("RK_BIG_PIECE_MB") ? std::max(1, atoi(getenv("RK_BIG_PIECE_MB"))) : 32) << 20;
-    if (getenv("RK_BIG_PIECE_KB")) piece = (size_t)std::max(1, atoi(getenv("RK_BIG_PIECE_KB"))) << 10;   // tests
-    vector<size_t> cut{0};
-    while (cut.back() < sz) {
-        size_t p = std::min(sz, cut.back() + piece);
-        if (p < sz) {
-            const void *e = memchr(b + p, '\n', sz - p);
-            p = e ? (size_t)((const uint8_t *)e - b) + 1 : sz;
-        }
-        cut.push_back(p);
-    }
-    const size_t n_pieces = cut.size() - 1;
-    vector<uint64_t> slot_off(n_pieces + 1, 0);
-    uint64_t max_slot = 0;
-    for (size_t i = 0; i < n_pieces; i++) {
-        const uint64_t cap = ((cut[i + 1] - cut[i]) + (uint64_t)kmer + 2 + 1023) & ~1023ULL;   // prefix + separator + the piece
-        slot_off[i + 1] = slot_off[i] + cap;
-        max_slot = std::max(max_slot, cap);
-    }
-    const uint64_t dev_bytes = slot_off[n_pieces];
-    const int n_ring = (int)std::min<size_t>(n_pieces, (size_t)std::max(2, std::min(threads, 8)));
-    vector<uint8_t *> ring((size_t)n_ring, nullptr);
-    void *d_buf = nullptr;
-    gpu.check(rk_dev_alloc(gpu.ctx, dev_bytes, &d_buf), "rk_dev_alloc");
-    for (int j = 0; j < n_ring; j++) gpu.check(rk_pinned_alloc(gpu.ctx, max_slot, (void **)&ring[(size_t)j]), "rk_pinned_alloc");
-    if (timing) fprintf(stderr, "[timing] big file: %zu piece(s), %d x %.1f MB page-locked + %.1f MB device: %.3f s\n", n_pieces, n_ring,
-                        max_slot / 1e6, dev_bytes / 1e6, get_sec() - t0);
-
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<int> free_slots;
-    std::deque<std::pair<size_t, int>> ready;   // (piece, ring slot)
-    for (int j = 0; j < n_ring; j++) free_slots.push_back(j);
-    std::atomic<size_t> next_piece{0};
-    std::atomic<bool> bad{false};
-
-    // the last k-1 bases in front of position `pos` (a line start), unless a header line lies between: walked backwards
-    // line by line.  Returns the number of bases written to the END of tmp[0 .. k-1).
-    auto bases_before = [&](size_t pos, uint8_t *tmp, size_t need) -> size_t {
-        size_t got = 0;
-        size_t le = pos;   // one past the newline that ends the line being looked at
-        while (got < need && le > 0) {
-            const size_t nl = le - 1;   // b[nl] == '\n'
-            const void *q = nl ? memrchr(b, '\n', nl) : nullptr;
-            const size_t ls = q ? (size_t)((const uint8_t *)q - b) + 1 : 0;
-            if (b[ls] == '>') return got;   // a record starts here: nothing in front of it belongs to the windows of this piece
-            if (b[ls] == '+' || b[ls] == '@') { bad = true; return 0; }
-            for (size_t c = nl; c > ls && got < need; c--) tmp[need - 1 - got++] = b[c - 1];
-            le = ls;
-        }
-        return got;
-    };
-    auto parse_piece = [&](size_t i, uint8_t *dst) {
-        const uint64_t cap = slot_off[i + 1] - slot_off[i];
-        uint8_t *w = dst;
-        if (i > 0) {
-            uint8_t tmp[64];
-            const size_t need = (size_t)std::min(63, kmer - 1);
-            const size_t got = bases_before(cut[i], tmp, need);
-            memcpy(w, tmp + (need - got), got);
-            w += got;
-        }
-        size_t pos = cut[i];
-        const size_t end = cut[i + 1];
-        while (pos < end) {
-            const void *q = memchr(b + pos, '\n', end - pos);
-            const size_t e = q ? (size_t)((const uint8_t *)q - b) : end;
-            const uint8_t c = b[pos];
-            if (c == '>') {
-                if (pos != 0) *w++ = 0;   // record separator (a window never spans records, src/sketch.cpp:487-488)
-            } else if (c == '+' || c == '@') {
-                bad = true;
-                return;
-            } else if (e > pos) {
-                if (b[e - 1] == '\r') { bad = true; return; }
-                memcpy(w, b + pos, e - pos);
-                w += e - pos;
-            }
-            pos = e + 1;
-        }
-        memset(w, 0, (size_t)(dst + cap - w));   // padding: invalid bases
-    };
-
-    vector<std::thread> pool;
-    const int nt = (int)std::min<size_t>(n_pieces, (size_t)std::max(1, threads));
-    for (int t = 0; t < nt; t++)
-        pool.emplace_back([&]() {
-            for (;;) {
-                const size_t i = next_piece.fetch_add(1);
-                if (i >= n_pieces) return;
-                int j;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !free_slots.empty(); });
-                    j = free_slots.front();
-                    free_slots.pop_front();
-                }
-                if (!bad) parse_piece(i, ring[(size_t)j]);
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ready.emplace_back(i, j);
-                }
-                cv.notify_all();
-            }
-        });
-    // this thread: every finished piece to its slot of the device buffer, while the others are parsed
-    for (size_t done = 0; done < n_pieces; done++) {
-        std::pair<size_t, int> pj;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty(); });
-            pj = ready.front();
-            ready.pop_front();
-        }
-        if (!bad) {
-            gpu.check(rk_upload_async(gpu.ctx, (uint8_t *)d_buf + slot_off[pj.first], ring[(size_t)pj.second],
-                                      slot_off[pj.first + 1] - slot_off[pj.first], stream), "rk_upload_async");
-            gpu.check(rk_stream_sync(gpu.ctx, stream), "rk_stream_sync");
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            free_slots.push_back(pj.second);
-        }
-        cv.notify_all();
-    }
-    for (auto &th : pool) th.join();
-    const double t1 = get_sec();
-    bool ok = !bad;
-    if (ok) {
-        const uint64_t gbeg = 0, gend = dev_bytes;
-        gpu.check(rk_sketch_packed_dev_ex(gpu.ctx, flt, (const uint8_t *)d_buf, dev_bytes, &gbeg, &gend, 1, min_count, stream, sk_out),
-                  "rk_sketch_packed_dev_ex");
-    }
-    if (timing) fprintf(stderr, "[timing] big file: parse + upload of %.1f MB (overlapped, %d thread(s)): %.3f s, sketch kernels: %.3f s\n",
-                        sz / 1e6, nt, t1 - t0, get_sec() - t1);
-    for (int j = 0; j < n_ring; j++) rk_pinned_free(ring[(size_t)j]);
-    rk_dev_free(d_buf);
-    return ok;
-}
-
-
-// ---- one big gzip'ed file, or one big FASTQ file, streamed (the role of src/sketch.cpp:380-450 and :658-737: the
-// RabbitFX producer hands chunks of FA / FQ_SE records to the consumers while it is still reading) -------------------
-// Such a file used to be inflated and parsed completely before its upload.  Now a reader thread (gzread: plain, gzip'ed
-// and multi-member files alike) fills text pieces of ~32 MB, each cut where the parser of a piece needs no context: a
-// FASTQ piece ends in front of a record (an '@' line whose next line but one starts with '+'; RecordReader::parse_packed
-// -- kseq semantics, quality gate -- parses it like a file of its own), a FASTA piece at a line start and carries the
-// last k-1 bases of the text in front of it unless a header line lies between (as sketch_big_fasta_streamed).  Parser
-// threads turn pieces into the packed layout in a ring of page-locked buffers, the calling thread uploads them to
-// consecutive slots of a device buffer that doubles when the inflated size outgrows it, and ONE sketch call over the
-// whole buffer follows (so -n, the minimum number of occurrences, counts over the whole file).
-// Returns false -- nothing done -- for inputs this path does not take ('\r' line ends in FASTA, multi-line FASTQ records
-// longer than a piece, a file that starts without a header): the caller falls back to the whole-file path.
-static bool sketch_big_sequential(Gpu &gpu, const rk_filter *flt, const string &path, bool fastq, int least_qual, int kmer, int threads,
-                                  uint32_t min_count, void *stream, rk_sketches **sk_out, bool timing)
-{
-    const double t0 = get_sec();
-    gzFile fp = gzopen(path.c_str(), "r");
-    if (!fp) return false;
-    gzbuffer(fp, 1 << 20);
-    size_t piece = (size_t)(getenv("RK_BIG_PIECE_MB") ? std::max(1, atoi(getenv("RK_BIG_PIECE_MB"))) : 32) << 20;
-    if (getenv("RK_BIG_PIECE_KB")) piece = (size_t)std::max(1, atoi(getenv("RK_BIG_PIECE_KB"))) << 10;   // tests
-    const size_t need = (size_t)std::min(63, kmer - 1);
-    struct Piece {
-        RawBuf text;
-        size_t len = 0;
-        uint8_t prefix[64];
-        size_t n_prefix = 0;
-        bool first = false;
-        uint64_t dev_off = 0, cap = 0;
-    };
-    const int n_ring = std::max(2, std::min(threads, 4));
-    const uint64_t slot_cap = ((uint64_t)piece * 2 + (uint64_t)kmer + 2 + 1024 + 1023) & ~1023ULL;   // (a piece holds at most 2 x `piece` text bytes)
-    vector<uint8_t *> ring((size_t)n_ring, nullptr);
-    for (int j = 0; j < n_ring; j++) gpu.check(rk_pinned_alloc(gpu.ctx, slot_cap, (void **)&ring[(size_t)j]), "rk_pinned_alloc");
-    struct stat st;
-    uint64_t dev_cap = 256ull << 20;
-    if (stat(path.c_str(), &st) == 0) dev_cap = std::max<uint64_t>(dev_cap, (uint64_t)st.st_size * (ends_with(path, ".gz") ? 4 : 1) + (64ull << 20));
-    if (getenv("RK_BIG_DEV_MB")) dev_cap = (uint64_t)std::max(1, atoi(getenv("RK_BIG_DEV_MB"))) << 20;   // tests: force the growth
-    dev_cap = (dev_cap + 1023) & ~1023ULL;
-    void *d_buf = nullptr;
-    gpu.check(rk_dev_alloc(gpu.ctx, dev_cap, &d_buf), "rk_dev_alloc");
-
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::unique_ptr<Piece>> todo;              // read, not yet parsed
-    std::deque<std::pair<std::unique_ptr<Piece>, int>> ready;   // parsed into ring slot
-    std::deque<int> free_slots;
-    for (int j = 0; j < n_ring; j++) free_slots.push_back(j);
-    bool eof = false;
-    std::atomic<bool> bad{false};
-    size_t n_pieces_read = 0, n_parsed = 0;
-    uint64_t text_bytes = 0;
-
-    // where a text may be cut so that what follows parses on its own: returns the length of the part to keep
-    auto cut_point = [&](const uint8_t *b, size_t n) -> size_t {
-        if (fastq) {
-            // the last '@' line start whose next line but one starts with '+' (a quality line may start with '@' too: the
-            // line after ITS next is a sequence line, never '+')
-            size_t pos = n;
-            for (int tries = 0; tries < 4096 && pos > 0; tries++) {
-                const void *q = memrchr(b, '\n', pos - 1);
-                const size_t ls = q ? (size_t)((const uint8_t *)q - b) + 1 : 0;
-                if (b[ls] == '@') {
-                    const void *e1 = memchr(b + ls, '\n', n - ls);
-                    const void *e2 = e1 ? memchr((const uint8_t *)e1 + 1, '\n', n - ((const uint8_t *)e1 + 1 - b)) : nullptr;
-                    if (e2 && (size_t)((const uint8_t *)e2 + 1 - b) < n && ((const uint8_t *)e2)[1] == '+') {
-                        // ... and, so that a quality line that starts with '@' inside a MULTI-line record (two lines further on: another
-                        // quality line starting with '+': both are valid Phred characters) is not taken for a record start: the
-                        // candidate's sequence line and its quality line have the same length (a four-line record; a multi-line file
-                        // offers no such candidate and takes the whole-file path)
-                        const uint8_t *p3 = (const uint8_t *)e2 + 1;
-                        const void *e3 = memchr(p3, '\n', n - (size_t)(p3 - b));
-                        const uint8_t *p4 = e3 ? (const uint8_t *)e3 + 1 : nullptr;
-                        const void *e4 = p4 ? memchr(p4, '\n', n - (size_t)(p4 - b)) : nullptr;
-                        if (e4) {
-                            auto len = [](const uint8_t *a, const void *e) { size_t l = (size_t)((const uint8_t *)e - a); return l && a[l - 1] == '\r' ? l - 1 : l; };
-                            if (len((const uint8_t *)e1 + 1, e2) == len(p4, e4)) return ls;
-                        }
-                    }
-                }
-                if (ls == 0) break;
-                pos = ls;   // (the newline before this line start is at ls - 1)
-                if (pos == 0) break;
-            }
-            return 0;
-        }
-        const void *q = memrchr(b, '\n', n);
-        return q ? (size_t)((const uint8_t *)q - b) + 1 : 0;
-    };
-    // FASTA: the last k-1 bases of a text that ends at a line start, unless a header line lies between
-    auto tail_bases = [&](const uint8_t *b, size_t n, const uint8_t *older, size_t n_older, uint8_t *out) -> size_t {
-        uint8_t tmp[64];
-        size_t got = 0;
-        auto walk = [&](const uint8_t *t, size_t len) -> bool {   // false: stop (a header line, or enough)
-            size_t le = len;
-            while (got < need && le > 0) {
-                const size_t nl = le - 1;
-                const void *q = nl ? memrchr(t, '\n', nl) : nullptr;
-                const size_t ls = q ? (size_t)((const uint8_t *)q - t) + 1 : 0;
-                if (t[ls] == '>') return false;
-                for (size_t c = nl; c > ls && got < need; c--) tmp[need - 1 - got++] = t[c - 1];
-                le = ls;
-            }
-            return got < need;
-        };
-        if (walk(b, n) && older)   // (`older`: the bases in front of this text, no line structure)
-            for (size_t c = n_older; c > 0 && got < need; c--) tmp[need - 1 - got++] = older[c - 1];
-        memcpy(out, tmp + (need - got), got);
-        return got;
-    };
-
-    std::thread reader([&]() {
-        std::unique_ptr<Piece> cur(new Piece);
-        cur->text.resize(2 * piece + (1u << 20));
-        cur->first = true;
-        uint8_t carry_prefix[64];
-        size_t n_carry_prefix = 0;
-        for (;;) {
-            // fill the current piece up to `piece` bytes beyond what it already holds
-            bool end = false;
-            while (cur->len < piece) {
-                const int r = gzread(fp, cur->text.data() + cur->len, (unsigned)std::min<size_t>(piece - cur->len, 1u << 30));
-                if (r <= 0) { end = true; break; }
-                cur->len += (size_t)r;
-            }
-            if (cur->first && cur->len && cur->text.data()[0] != (fastq ? '@' : '>')) { bad = true; end = true; cur->len = 0; }
-            std::unique_ptr<Piece> next(new Piece);
-            if (!end) {
-                const size_t keep = cut_point(cur->text.data(), cur->len);
-                if (keep == 0) { bad = true; end = true; cur->len = 0; }   // no cut point inside a piece: not a file for this path
-                else {
-                    next->text.resize(2 * piece + (1u << 20));
-                    next->len = cur->len - keep;
-                    memcpy(next->text.data(), cur->text.data() + keep, next->len);
-                    cur->len = keep;
-                }
-            }
-            if (!fastq) {
-                memcpy(cur->prefix, carry_prefix, n_carry_prefix);
-                cur->n_prefix = cur->first ? 0 : n_carry_prefix;
-                // (a piece with fewer than k-1 bases of its own hands the bases in front of it on)
-                if (cur->len) n_carry_prefix = tail_bases(cur->text.data(), cur->len, cur->prefix, cur->n_prefix, carry_prefix);
-            }
-            if (cur->len) {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return todo.size() < (size_t)n_ring || bad; });   // (bounded: the reader runs at most n_ring pieces ahead)
-                text_bytes += cur->len;
-                n_pieces_read++;
-                todo.push_back(std::move(cur));
-                lk.unlock();
-                cv.notify_all();
-            }
-            if (end) break;
-            cur = std::move(next);
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            eof = true;
-        }
-        cv.notify_all();
-    });
-
-    auto parse_piece = [&](Piece &pc, uint8_t *dst) -> uint64_t {   // returns the bytes written (padded to 1 KiB by the caller)
-        uint8_t *w = dst;
-        const uint8_t *b = pc.text.data();
-        if (fastq) {
-            const RecordReader::Packed pk = RecordReader::parse_packed(b, pc.len, w, slot_cap - 1024, least_qual);
-            if (pk.overflow) { bad = true; return 0; }
-            w += pk.bytes;
-            *w++ = 0;   // the next piece starts a new record
-            return (uint64_t)(w - dst);
-        }
-        memcpy(w, pc.prefix, pc.n_prefix);
-        w += pc.n_prefix;
-        size_t pos = 0;
-        while (pos < pc.len) {
-            const void *q = memchr(b + pos, '\n', pc.len - pos);
-            const size_t e = q ? (size_t)((const uint8_t *)q - b) : pc.len;
-            const uint8_t c = b[pos];
-            if (c == '>') {
-                if (!(pc.first && pos == 0)) *w++ = 0;   // record separator (a window never spans records, src/sketch.cpp:487-488)
-            } else if (c == '+' || c == '@') {
-                bad = true;
-                return 0;
-            } else if (e > pos) {
-                if (b[e - 1] == '\r') { bad = true; return 0; }
-                memcpy(w, b + pos, e - pos);
-                w += e - pos;
-            }
-            pos = e + 1;
-        }
-        return (uint64_t)(w - dst);
-    };
-    vector<std::thread> pool;
-    const int nt = std::max(1, std::min(threads, n_ring));
-    for (int t = 0; t < nt; t++)
-        pool.emplace_back([&]() {
-            for (;;) {
-                std::unique_ptr<Piece> pc;
-                int j;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return (!todo.empty() && !free_slots.empty()) || (eof && todo.empty()); });
-                    if (todo.empty()) return;
-                    pc = std::move(todo.front());
-                    todo.pop_front();
-                    j = free_slots.front();
-                    free_slots.pop_front();
-                }
-                cv.notify_all();
-                uint64_t bytes = bad ? 0 : parse_piece(*pc, ring[(size_t)j]);
-                const uint64_t cap = (bytes + 1023) & ~1023ULL;
-                memset(ring[(size_t)j] + bytes, 0, (size_t)(cap - bytes));   // padding: invalid bases
-                pc->cap = cap;
-                pc->text.resize(0);
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ready.emplace_back(std::move(pc), j);
-                }
-                cv.notify_all();
-            }
-        });
-    // this thread: every parsed piece to the next free stretch of the device buffer (the order of the pieces in the buffer
-    // does not matter to a FASTQ file -- every record is a record --, but it does to FASTA: a piece carries the bases in
-    // front of it, so pieces may go in any order as long as each is followed by padding, which they are)
-    uint64_t dev_used = 0;
-    for (;;) {
-        std::pair<std::unique_ptr<Piece>, int> pj;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty() || (eof && todo.empty() && n_parsed == n_pieces_read); });
-            if (ready.empty()) break;
-            pj = std::move(ready.front());
-            ready.pop_front();
-            n_parsed++;
-        }
-        if (!bad && pj.first->cap) {
-            if (dev_used + pj.first->cap > dev_cap) {   // the inflated file outgrew the buffer: twice the size, copy, go on
-                const uint64_t bigger = std::max(dev_cap * 2, dev_used + pj.first->cap);
-                void *d_new = nullptr;
-                gpu.check(rk_dev_alloc(gpu.ctx, bigger, &d_new), "rk_dev_alloc");
-                gpu.check(rk_dev_copy_async(gpu.ctx, d_new, d_buf, dev_used, stream), "rk_dev_copy_async");
-                gpu.check(rk_stream_sync(gpu.ctx, stream), "rk_stream_sync");
-                rk_dev_free(d_buf);
-                d_buf = d_new;
-                dev_cap = bigger;
-            }
-            gpu.check(rk_upload_async(gpu.ctx, (uint8_t *)d_buf + dev_used, ring[(size_t)pj.second], pj.first->cap, stream), "rk_upload_async");
-            gpu.check(rk_stream_sync(gpu.ctx, stream), "rk_stream_sync");
-            dev_used += pj.first->cap;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            free_slots.push_back(pj.second);
-        }
-        cv.notify_all();
-    }
-    reader.join();
-    for (auto &th : pool) th.join();
-    gzclose(fp);
-    const double t1 = get_sec();
-    bool ok = !bad;
-    if (ok) {
-        const uint64_t gbeg = 0, gend = dev_used;
-        gpu.check(rk_sketch_packed_dev_ex(gpu.ctx, flt, (const uint8_t *)d_buf, dev_used, &gbeg, &gend, 1, min_count, stream, sk_out),
-                  "rk_sketch_packed_dev_ex");
-    }
-    if (timing) fprintf(stderr, "[timing] big file (sequential reader): %zu piece(s), %.1f MB of text, %.1f MB packed, read + parse + upload "
-                        "(overlapped, %d parser thread(s)): %.3f s, sketch kernels: %.3f s\n", n_pieces_read, text_bytes / 1e6, dev_used / 1e6, nt,
-                        t1 - t0, get_sec() - t1);
-    for (int j = 0; j < n_ring; j++) rk_pinned_free(ring[(size_t)j]);
-    rk_dev_free(d_buf);
-    return ok;
-}
-
 
 // HIP runtime start-up (hipInit: 150-190 ms on an MI355X box) is the largest single item of a short alldist/dist run:
 // it starts on a thread of its own while the main thread reads the .sketch files
@@ -603,254 +157,209 @@ static bool list_is_fastq(const vector<string> &files)
     return n_fq > 0;
 }
 
-static void sketch_list(Gpu &gpu, const string &list, bool is_query, const Shuf &shuf, int threads,
-                        SketchSet &out, const string &out_path_in, const FastqOpts &fq = FastqOpts())
-{
-    const double t0 = get_sec();
-    rk_params P;
-    if (rk_params_init(shuf.k, shuf.subk, shuf.drlevel, &P))
-        die("the half_subk - drlevel should at least 3 (half_subk=%d drlevel=%d), half_k >= half_subk, half_subk < 8",
-            shuf.subk, shuf.drlevel);  // src/common.cpp:37
-    rk_filter *flt = nullptr;
-    gpu.check(rk_filter_create(gpu.ctx, &P, shuf.table.data(), &flt), "rk_filter_create");
-    if (getenv("RK_TIMING")) fprintf(stderr, "[timing] rk_filter_create: %.3f s\n", get_sec() - t0);
-
-    const vector<string> files = read_list(list);
-    cerr << "the total fileNumber is: " << files.size() << endl;
-    out = SketchSet();
-    out.info.half_k = shuf.k;
-    out.info.half_subk = shuf.subk;
-    out.info.drlevel = shuf.drlevel;
-    out.names = files;
-    out.off.assign(1, 0);
-
-    // ---- streaming pipeline (the role of src/sketch.cpp:318-460's producer/consumer threads) ----
-    // Files are grouped into batches that fit one page-locked staging buffer.  The parser
-    // threads write every genome straight into its 1 KiB-aligned slot of the staging buffer
-    // in the packed layout of rk_sketch_packed_dev (no intermediate copy); a GPU thread
-    // uploads the batch, runs the sketch kernels and downloads the hashes while the parser
-    // threads already fill the other staging buffer.
-    struct Slot {
-        uint64_t off = 0, cap = 0;  // position / capacity in the staging buffer
-        uint64_t len = 0;           // packed bytes written
-        bool overflow = false;      // the size estimate was too small (multi-member .gz): slow path
-    };
-    struct Batch {
-        size_t first = 0, last = 0;  // files [first, last)
-        uint64_t bytes = 0;          // staging bytes used
-        bool pageable = false;       // one oversized file: staged in ordinary memory
-        bool streamed = false;       // ... or, a plain FASTA file, streamed piece by piece (sketch_big_fasta_streamed)
-        vector<Slot> slots;
-    };
-    // upper bound of a file's packed size: a plain file cannot expand; a .gz member stores its
-    // length mod 2^32 in the trailer
-    auto packed_bound = [](const string &f) -> uint64_t {
-        struct stat st;
-        if (stat(f.c_str(), &st)) die("cannot open the genome file: %s", f.c_str());
-        uint64_t sz = (uint64_t)st.st_size;
-        FILE *fp = fopen(f.c_str(), "rb");
-        if (!fp) die("cannot open the genome file: %s", f.c_str());
-        unsigned char m[2] = {0, 0}, tail[4];
-        if (fread(m, 1, 2, fp) == 2 && m[0] == 0x1f && m[1] == 0x8b && sz >= 18 && !fseek(fp, -4, SEEK_END) &&
-            fread(tail, 1, 4, fp) == 4) {
-            const uint64_t isize = (uint64_t)tail[0] | ((uint64_t)tail[1] << 8) | ((uint64_t)tail[2] << 16) |
-                                   ((uint64_t)tail[3] << 24);
-            sz = std::max<uint64_t>(isize, sz);
-        }
-        fclose(fp);
-        return sz;
-    };
-    vector<uint64_t> bound(files.size());
-    uint64_t total_bound = 0, max_bound = 0;
-    for (size_t i = 0; i < files.size(); i++) {
-        bound[i] = ((packed_bound(files[i]) + 1 + 1023) & ~1023ULL);
-        total_bound += bound[i];
-        max_bound = std::max(max_bound, bound[i]);
-    }
-    // staging buffers: two, an eighth of the input each (uploads and kernels overlap the parsing of the next batch), between
-    // 64 and 256 MiB -- page-locking costs 0.2 s per GB and releasing 0.13 s per GB (measured: 2 x 1 GiB for 1,000 x 5 Mb
-    // were 0.42 + 0.27 s of a 1.4 s run whose parsing, uploads and kernels take 0.2 s).  A file bigger than the staging
-    // buffer gets a batch of its own: a plain FASTA file is streamed in pieces through a ring of small page-locked buffers
-    // (sketch_big_fasta_streamed), anything else is parsed into ordinary memory (page-locking and releasing 3 GB costs 0.9 s,
-    // the slower upload 0.2 s).
-    uint64_t stage_bytes = std::min<uint64_t>(256ull << 20, std::max<uint64_t>(64ull << 20, total_bound / 8));
-    if (getenv("RK_STAGE_MB")) stage_bytes = std::max<uint64_t>(1, (uint64_t)atoll(getenv("RK_STAGE_MB"))) << 20;
-    stage_bytes = (stage_bytes + 1023) & ~1023ULL;
-    const uint64_t dev_bytes = std::max(stage_bytes, max_bound);
-    vector<Batch> batches;
-    for (size_t i = 0; i < files.size();) {
-        Batch bt;
-        bt.first = i;
-        uint64_t pos = 0;
-        if (bound[i] > stage_bytes) {  // oversized: alone, pageable staging
-            Slot sl;
-            sl.cap = bound[i];
-            bt.slots.push_back(sl);
-            bt.last = i + 1;
-            bt.bytes = bound[i];
-            bt.pageable = true;
-            batches.push_back(std::move(bt));
-            i++;
-            continue;
-        }
-        while (i < files.size() && pos + bound[i] <= stage_bytes) {
-            Slot sl;
-            sl.off = pos;
-            sl.cap = bound[i];
-            bt.slots.push_back(sl);
-            pos += bound[i];
-            i++;
-        }
-        bt.last = i;
-        bt.bytes = pos;
-        batches.push_back(std::move(bt));
-    }
-
+// ---- streaming pipeline (the role of src/sketch.cpp:318-460's producer/consumer threads) ----
+// Files are grouped into batches that fit one page-locked staging buffer (the plan: sketch_input.hpp).  The parser
+// threads write every genome straight into its 1 KiB-aligned slot of the staging buffer in the packed layout of
+// rk_sketch_packed_dev (no intermediate copy); a GPU thread uploads the batch, runs the sketch kernels and downloads the
+// hashes while the parser threads already fill the other staging buffer.  A file bigger than the staging buffer gets a
+// batch of its own and is streamed piece by piece (sketch_streamed), or, with RK_BIG_WHOLE or where the streamed
+// readers decline, parsed whole into ordinary memory.
+struct ListSketcher {
+    Gpu &gpu;
+    const rk_filter *flt;
+    const vector<string> &files;
+    const Shuf &shuf;
+    const int threads;
+    const FastqOpts &fq;
+    SketchSet &out;
     const bool timing = getenv("RK_TIMING") != nullptr;
-    const double t_alloc = get_sec();
-    const int n_buf = batches.size() > 1 ? 2 : 1;
+    uint64_t total_windows = 0;
+
+    // the plan
+    uint64_t stage_bytes = 0, dev_bytes = 0;
+    vector<Batch> batches;
+    // the buffers
+    int n_buf = 0;
     uint8_t *stage[2] = {nullptr, nullptr};
     void *dev[2] = {nullptr, nullptr};
     void *stream = nullptr;
-    gpu.check(rk_stream_create(gpu.ctx, &stream), "rk_stream_create");
-    bool need_pinned = false;
-    for (const Batch &bt : batches) need_pinned |= !bt.pageable;
-    for (int k = 0; k < n_buf; k++) {
-        if (need_pinned) gpu.check(rk_pinned_alloc(gpu.ctx, stage_bytes, (void **)&stage[k]), "rk_pinned_alloc");
-        gpu.check(rk_dev_alloc(gpu.ctx, dev_bytes, &dev[k]), "rk_dev_alloc");
+    RawBuf big_stage;  // pageable staging of an oversized file
+    // hand-over of filled staging buffers to the GPU thread: (batch, buffer), in list order; buffer b is stage[b] and dev[b]
+    // (two slots also where a single batch has n_buf == 1: slots come out in order, and one batch only ever takes slot 0)
+    PieceRing<size_t> staging{2, 1};
+
+    uint32_t min_count() const { return (uint32_t)std::max(1, fq.least_num); }
+
+    void plan()
+    {
+        vector<uint64_t> bound(files.size());
+        uint64_t total_bound = 0, max_bound = 0;
+        for (size_t i = 0; i < files.size(); i++) {
+            uint64_t packed = 0;
+            if (!packed_bound(files[i], packed)) die("cannot open the genome file: %s", files[i].c_str());
+            bound[i] = slot_bound(packed);
+            total_bound += bound[i];
+            max_bound = std::max(max_bound, bound[i]);
+        }
+        stage_bytes = stage_size(total_bound);
+        dev_bytes = std::max(stage_bytes, max_bound);
+        batches = plan_batches(bound, stage_bytes);
     }
 
-    if (timing) fprintf(stderr, "[timing] %d staging buffer(s) of %.1f MB pinned + device: %.3f s\n", n_buf, stage_bytes / 1e6, get_sec() - t_alloc);
-    RawBuf big_stage;  // pageable staging of an oversized file
-    // hand-over of filled staging buffers to the GPU thread
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t filled = 0, consumed = 0;  // batches parsed / batches whose staging buffer is free again
-    uint64_t total_windows = 0;
-    string gpu_error;
+    void alloc_buffers()
+    {
+        const double t_alloc = get_sec();
+        n_buf = batches.size() > 1 ? 2 : 1;
+        gpu.check(rk_stream_create(gpu.ctx, &stream), "rk_stream_create");
+        bool need_pinned = false;
+        for (const Batch &bt : batches) need_pinned |= !bt.pageable;
+        for (int k = 0; k < n_buf; k++) {
+            if (need_pinned) gpu.check(rk_pinned_alloc(gpu.ctx, stage_bytes, (void **)&stage[k]), "rk_pinned_alloc");
+            gpu.check(rk_dev_alloc(gpu.ctx, dev_bytes, &dev[k]), "rk_dev_alloc");
+        }
+        if (timing) fprintf(stderr, "[timing] %d staging buffer(s) of %.1f MB pinned + device: %.3f s\n", n_buf, stage_bytes / 1e6, get_sec() - t_alloc);
+    }
+    void free_buffers()
+    {
+        // the page-locked buffers go back to the system while the sketches are saved and the index is built (unpinning is
+        // kernel work that needs nothing from this thread)
+        const double t_free = get_sec();
+        for (int k = 0; k < n_buf; k++) rk_dev_free(dev[k]);
+        rk_stream_destroy(stream);
+        // (detached: the GPU subcommands leave through _exit once their output is on disk)
+        std::thread([st0 = stage[0], st1 = stage[1], timing = timing, t_free] {
+            rk_pinned_free(st0);
+            rk_pinned_free(st1);
+            if (timing) fprintf(stderr, "[timing] staging buffers released (in the background): %.3f s\n", get_sec() - t_free);
+        }).detach();
+    }
 
-    auto slow_path = [&](size_t file_idx, rk_sketches **sk) {  // whole file through rk_sketch_batch_ex
+    // ---- results: a sketches object of n genomes into (hashes, offsets), once for both hash widths
+    SketchSet download(rk_sketches *sk, uint32_t n)
+    {
+        SketchSet d;
+        d.off.resize((size_t)n + 1);
+        if (out.wide()) {
+            d.hashes64.resize(rk_sketches_total(sk));
+            gpu.check(rk_sketches_download64(sk, d.hashes64.data(), d.off.data()), "rk_sketches_download64");
+        } else {
+            d.hashes.resize(rk_sketches_total(sk));
+            gpu.check(rk_sketches_download(sk, d.hashes.data(), d.off.data()), "rk_sketches_download");
+        }
+        total_windows += rk_sketches_windows(sk);
+        return d;
+    }
+    void append(const SketchSet &d, uint32_t first, uint32_t last)   // genomes [first, last) of a download
+    {
+        if (out.wide()) out.hashes64.insert(out.hashes64.end(), d.hashes64.begin() + d.off[first], d.hashes64.begin() + d.off[last]);
+        else out.hashes.insert(out.hashes.end(), d.hashes.begin() + d.off[first], d.hashes.begin() + d.off[last]);
+        for (uint32_t i = first; i < last; i++) out.off.push_back(out.off.back() + (d.off[i + 1] - d.off[i]));
+    }
+    void slow_path(size_t file_idx, rk_sketches **sk)  // whole file through rk_sketch_batch_ex
+    {
         vector<uint8_t> seq, qual;
         vector<uint64_t> rec_off, genome_rec{0};
         if (!RecordReader::read_file(files[file_idx], seq, rec_off, fq.fastq ? &qual : nullptr))
             die("cannot open the genome file: %s", files[file_idx].c_str());
         if (rec_off.empty()) rec_off.push_back(0);
         genome_rec.push_back(rec_off.size() - 1);
-        gpu.check(rk_sketch_batch_ex(gpu.ctx, flt, seq.data(), fq.fastq ? qual.data() : nullptr, fq.least_qual,
-                                     (uint32_t)std::max(1, fq.least_num), rec_off.data(), rec_off.size() - 1,
-                                     genome_rec.data(), 1, sk), "rk_sketch_batch_ex");
-    };
-    auto append_sketches = [&](rk_sketches *sk, uint32_t n) {
-        vector<uint64_t> off((size_t)n + 1);
-        const uint64_t b0 = out.total();
-        if (out.wide()) {
-            vector<uint64_t> h(rk_sketches_total(sk));
-            gpu.check(rk_sketches_download64(sk, h.data(), off.data()), "rk_sketches_download64");
-            out.hashes64.insert(out.hashes64.end(), h.begin(), h.end());
-        } else {
-            vector<uint32_t> h(rk_sketches_total(sk));
-            gpu.check(rk_sketches_download(sk, h.data(), off.data()), "rk_sketches_download");
-            out.hashes.insert(out.hashes.end(), h.begin(), h.end());
+        gpu.check(rk_sketch_batch_ex(gpu.ctx, flt, seq.data(), fq.fastq ? qual.data() : nullptr, fq.least_qual, min_count(), rec_off.data(),
+                                     rec_off.size() - 1, genome_rec.data(), 1, sk), "rk_sketch_batch_ex");
+    }
+    // rare: the genomes of a batch whose slots overflowed take the slow path, spliced in in list order
+    void append_spliced(const Batch &bt, rk_sketches *sk)
+    {
+        const uint32_t nb = (uint32_t)(bt.last - bt.first);
+        const SketchSet d = download(sk, nb);
+        for (uint32_t i = 0; i < nb; i++) {
+            if (!bt.slots[i].overflow) { append(d, i, i + 1); continue; }
+            rk_sketches *one = nullptr;
+            slow_path(bt.first + i, &one);
+            append(download(one, 1), 0, 1);
+            rk_sketches_free(one);
         }
-        total_windows += rk_sketches_windows(sk);
-        for (size_t i = 1; i <= n; i++) out.off.push_back(b0 + off[i]);
-    };
+    }
 
-    std::thread gpu_thread([&]() {
-        for (size_t k = 0; k < batches.size(); k++) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return filled > k; });
-            }
-            Batch &bt = batches[k];
-            const int bi = (int)(k % (size_t)n_buf);
-            const uint32_t nb = (uint32_t)(bt.last - bt.first);
-            vector<uint64_t> gbeg(nb), gend(nb);
-            bool any_overflow = false;
-            for (uint32_t i = 0; i < nb; i++) {
-                gbeg[i] = bt.slots[i].off;
-                gend[i] = bt.slots[i].off + (bt.slots[i].overflow ? 0 : bt.slots[i].len);
-                any_overflow |= bt.slots[i].overflow;
-            }
-            rk_sketches *sk = nullptr;
-            const double t_gpu = get_sec();
-            if (bt.streamed) {
-                const bool plain_fasta = !fq.fastq && !ends_with(files[bt.first], ".gz");
-                const bool done = plain_fasta
-                    ? sketch_big_fasta_streamed(gpu, flt, files[bt.first], 2 * shuf.k, threads, (uint32_t)std::max(1, fq.least_num), stream, &sk, timing)
-                    : sketch_big_sequential(gpu, flt, files[bt.first], fq.fastq, fq.fastq ? fq.least_qual : 0, 2 * shuf.k, threads,
-                                            (uint32_t)std::max(1, fq.least_num), stream, &sk, timing);
-                if (!done) slow_path(bt.first, &sk);   // not a file these paths take ('\r' line ends, odd records): the serial reader
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    consumed = k + 1;
-                }
-                cv.notify_all();
-                append_sketches(sk, 1);
-                rk_sketches_free(sk);
-                cerr << "finshed sketching: " << bt.last << " genomes" << endl;
-                continue;
-            }
-            gpu.check(rk_upload_async(gpu.ctx, dev[bi], bt.pageable ? big_stage.data() : stage[bi], bt.bytes, stream),
-                      "rk_upload_async");
-            gpu.check(rk_sketch_packed_dev_ex(gpu.ctx, flt, (const uint8_t *)dev[bi], bt.bytes, gbeg.data(), gend.data(),
-                                              nb, (uint32_t)std::max(1, fq.least_num), stream, &sk),
-                      "rk_sketch_packed_dev_ex");
-            if (timing) fprintf(stderr, "[timing] batch %zu: upload + sketch of %.1f MB: %.3f s\n", k, bt.bytes / 1e6, get_sec() - t_gpu);
-            {   // the call above synchronised the stream: the staging buffer can be refilled
-                std::lock_guard<std::mutex> lk(mu);
-                consumed = k + 1;
-            }
-            cv.notify_all();
-            if (!any_overflow) {
-                append_sketches(sk, nb);
-            } else {  // rare: splice the slow-path genomes in, keeping list order
-                vector<uint64_t> off((size_t)nb + 1);
-                vector<uint32_t> h32;
-                vector<uint64_t> h64;
-                if (out.wide()) { h64.resize(rk_sketches_total(sk)); gpu.check(rk_sketches_download64(sk, h64.data(), off.data()), "rk_sketches_download64"); }
-                else { h32.resize(rk_sketches_total(sk)); gpu.check(rk_sketches_download(sk, h32.data(), off.data()), "rk_sketches_download"); }
-                total_windows += rk_sketches_windows(sk);
-                for (uint32_t i = 0; i < nb; i++) {
-                    if (bt.slots[i].overflow) {
-                        rk_sketches *one = nullptr;
-                        slow_path(bt.first + i, &one);
-                        append_sketches(one, 1);
-                        rk_sketches_free(one);
-                    } else {
-                        if (out.wide()) out.hashes64.insert(out.hashes64.end(), h64.begin() + off[i], h64.begin() + off[i + 1]);
-                        else out.hashes.insert(out.hashes.end(), h32.begin() + off[i], h32.begin() + off[i + 1]);
-                        out.off.push_back(out.off.back() + (off[i + 1] - off[i]));
-                    }
-                }
-            }
-            rk_sketches_free(sk);
-            cerr << "finshed sketching: " << bt.last << " genomes" << endl;
+    // ---- one big file, streamed.  What the readers of sketch_input.hpp need of the GPU: a ring of page-locked buffers, one upload
+    // and one synchronisation per piece, a device buffer that is copied when it grows, ONE sketch call over the complete buffer.
+    struct GpuSink : InputSink {
+        ListSketcher &job;
+        rk_sketches **sk_out;
+        void *d_buf = nullptr;
+        double kernel_sec = 0;
+        GpuSink(ListSketcher &j, rk_sketches **out) : job(j), sk_out(out) {}
+        ~GpuSink() { rk_dev_free(d_buf); }
+        uint8_t *ring_alloc(uint64_t bytes) override
+        {
+            uint8_t *p = nullptr;
+            job.gpu.check(rk_pinned_alloc(job.gpu.ctx, bytes, (void **)&p), "rk_pinned_alloc");
+            return p;
         }
-    });
+        void ring_free(uint8_t *p) override { rk_pinned_free(p); }
+        void grow(uint64_t cap, uint64_t used) override
+        {
+            void *d_new = nullptr;
+            job.gpu.check(rk_dev_alloc(job.gpu.ctx, cap, &d_new), "rk_dev_alloc");
+            if (used) {
+                job.gpu.check(rk_dev_copy_async(job.gpu.ctx, d_new, d_buf, used, job.stream), "rk_dev_copy_async");
+                job.gpu.check(rk_stream_sync(job.gpu.ctx, job.stream), "rk_stream_sync");
+            }
+            rk_dev_free(d_buf);
+            d_buf = d_new;
+        }
+        void put(uint64_t off, const uint8_t *src, uint64_t bytes) override
+        {
+            job.gpu.check(rk_upload_async(job.gpu.ctx, (uint8_t *)d_buf + off, src, bytes, job.stream), "rk_upload_async");
+            job.gpu.check(rk_stream_sync(job.gpu.ctx, job.stream), "rk_stream_sync");
+        }
+        void complete(uint64_t used) override
+        {
+            const double t = get_sec();
+            const uint64_t gbeg = 0, gend = used;
+            job.gpu.check(rk_sketch_packed_dev_ex(job.gpu.ctx, job.flt, (const uint8_t *)d_buf, used, &gbeg, &gend, 1, job.min_count(), job.stream,
+                                                  sk_out), "rk_sketch_packed_dev_ex");
+            kernel_sec = get_sec() - t;
+        }
+    };
+    // A plain FASTA file is mapped and cut at line starts, anything else (gzip'ed, FASTQ) read sequentially.  Returns false --
+    // nothing done -- for a file the streamed readers do not take ('\r' line ends, odd records).
+    bool sketch_streamed(const string &path, rk_sketches **sk)
+    {
+        GpuSink sink(*this, sk);
+        StreamStats st;
+        const int kmer = 2 * shuf.k;
+        const bool mapped = !fq.fastq && !ends_with(path, ".gz");
+        const bool ok = mapped ? stream_mapped_fasta(path, kmer, threads, big_piece_bytes(), sink, st)
+                               : stream_sequential(path, fq.fastq, fq.fastq ? fq.least_qual : 0, kmer, threads, big_piece_bytes(),
+                                                   sequential_dev_cap(path), sink, st);
+        if (timing && st.ring && mapped) {
+            fprintf(stderr, "[timing] big file: %zu piece(s), %d x %.1f MB page-locked + %.1f MB device: %.3f s\n", st.pieces, st.ring,
+                    st.slot_bytes / 1e6, st.dev_bytes / 1e6, st.alloc_sec);
+            fprintf(stderr, "[timing] big file: parse + upload of %.1f MB (overlapped, %d thread(s)): %.3f s, sketch kernels: %.3f s\n",
+                    st.text_bytes / 1e6, st.parsers, st.stream_sec, sink.kernel_sec);
+        } else if (timing && st.ring)
+            fprintf(stderr, "[timing] big file (sequential reader): %zu piece(s), %.1f MB of text, %.1f MB packed, read + parse + upload "
+                    "(overlapped, %d parser thread(s)): %.3f s, sketch kernels: %.3f s\n", st.pieces, st.text_bytes / 1e6, st.used / 1e6, st.parsers,
+                    st.stream_sec, sink.kernel_sec);
+        return ok;
+    }
 
-    for (size_t k = 0; k < batches.size(); k++) {
-        {   // wait until the GPU thread has released this staging buffer
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return k < (size_t)n_buf || consumed + (size_t)n_buf > k; });
-        }
+    // ---- the parser stage of batch k (the calling thread and its pool)
+    void parse_batch(size_t k)
+    {
+        const int slot = staging.acquire();   // the GPU thread has released this staging buffer
         Batch &bt = batches[k];
         if (bt.pageable && !getenv("RK_BIG_WHOLE")) {
             // a big file: the GPU thread streams it piece by piece (read / inflate, parse, upload and kernels overlap)
             bt.streamed = true;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                filled = k + 1;
-            }
-            cv.notify_all();
-            continue;
+            staging.publish(k, slot);
+            return;
         }
-        if (bt.pageable) {  // its own buffer; the previous oversized batch must be uploaded first
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return consumed == k; });
+        if (bt.pageable) {  // its own buffer; the previous oversized batch must be uploaded first: the other buffer is free too
+            staging.release(staging.acquire());
             big_stage.resize(bt.bytes);
         }
-        uint8_t *base = bt.pageable ? big_stage.data() : stage[k % (size_t)n_buf];
+        uint8_t *base = bt.pageable ? big_stage.data() : stage[slot];
         const size_t nb = bt.last - bt.first;
         const double t_parse = get_sec();
         std::atomic<size_t> next_file{0};
@@ -884,24 +393,77 @@ static void sketch_list(Gpu &gpu, const string &list, bool is_query, const Shuf 
         for (auto &th : pool) th.join();
         if (timing) fprintf(stderr, "[timing] batch %zu: read + parse of %zu file(s) on %d thread(s): %.3f s\n", k, nb, nt, get_sec() - t_parse);
         if (failed >= 0) die("cannot open the genome file: %s", files[bt.first + (size_t)failed].c_str());
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            filled = k + 1;
-        }
-        cv.notify_all();
+        staging.publish(k, slot);
     }
-    gpu_thread.join();
-    // the page-locked buffers go back to the system while the sketches are saved and the index is built (unpinning is
-    // kernel work that needs nothing from this thread)
-    const double t_free = get_sec();
-    for (int k = 0; k < n_buf; k++) rk_dev_free(dev[k]);
-    rk_stream_destroy(stream);
-    // (detached: the GPU subcommands leave through _exit once their output is on disk)
-    std::thread([st0 = stage[0], st1 = stage[1], timing, t_free] {
-        rk_pinned_free(st0);
-        rk_pinned_free(st1);
-        if (timing) fprintf(stderr, "[timing] staging buffers released (in the background): %.3f s\n", get_sec() - t_free);
-    }).detach();
+
+    // ---- the GPU stage of batch k (the GPU thread)
+    void gpu_batch(size_t k, int bi)
+    {
+        Batch &bt = batches[k];
+        const uint32_t nb = (uint32_t)(bt.last - bt.first);
+        rk_sketches *sk = nullptr;
+        bool any_overflow = false;
+        if (bt.streamed) {
+            if (!sketch_streamed(files[bt.first], &sk)) slow_path(bt.first, &sk);   // the serial reader
+        } else {
+            vector<uint64_t> gbeg(nb), gend(nb);
+            for (uint32_t i = 0; i < nb; i++) {
+                gbeg[i] = bt.slots[i].off;
+                gend[i] = bt.slots[i].off + (bt.slots[i].overflow ? 0 : bt.slots[i].len);
+                any_overflow |= bt.slots[i].overflow;
+            }
+            const double t_gpu = get_sec();
+            gpu.check(rk_upload_async(gpu.ctx, dev[bi], bt.pageable ? big_stage.data() : stage[bi], bt.bytes, stream), "rk_upload_async");
+            gpu.check(rk_sketch_packed_dev_ex(gpu.ctx, flt, (const uint8_t *)dev[bi], bt.bytes, gbeg.data(), gend.data(), nb, min_count(),
+                                              stream, &sk), "rk_sketch_packed_dev_ex");
+            if (timing) fprintf(stderr, "[timing] batch %zu: upload + sketch of %.1f MB: %.3f s\n", k, bt.bytes / 1e6, get_sec() - t_gpu);
+        }
+        staging.release(bi);   // the call above synchronised the stream: the staging buffer can be refilled
+        if (any_overflow) append_spliced(bt, sk);
+        else append(download(sk, nb), 0, nb);
+        rk_sketches_free(sk);
+        cerr << "finshed sketching: " << bt.last << " genomes" << endl;
+    }
+
+    void run()
+    {
+        plan();
+        alloc_buffers();
+        std::thread gpu_thread([&]() {
+            size_t k = 0;
+            int slot = 0;
+            while (staging.take(k, slot)) gpu_batch(k, slot);
+        });
+        for (size_t k = 0; k < batches.size(); k++) parse_batch(k);
+        staging.producer_done();
+        gpu_thread.join();
+        free_buffers();
+    }
+};
+
+static void sketch_list(Gpu &gpu, const string &list, const Shuf &shuf, int threads, SketchSet &out, const string &out_path_in,
+                        const FastqOpts &fq = FastqOpts())
+{
+    const double t0 = get_sec();
+    rk_params P;
+    if (rk_params_init(shuf.k, shuf.subk, shuf.drlevel, &P))
+        die("the half_subk - drlevel should at least 3 (half_subk=%d drlevel=%d), half_k >= half_subk, half_subk < 8",
+            shuf.subk, shuf.drlevel);  // src/common.cpp:37
+    rk_filter *flt = nullptr;
+    gpu.check(rk_filter_create(gpu.ctx, &P, shuf.table.data(), &flt), "rk_filter_create");
+    if (getenv("RK_TIMING")) fprintf(stderr, "[timing] rk_filter_create: %.3f s\n", get_sec() - t0);
+
+    const vector<string> files = read_list(list);
+    cerr << "the total fileNumber is: " << files.size() << endl;
+    out = SketchSet();
+    out.info.half_k = shuf.k;
+    out.info.half_subk = shuf.subk;
+    out.info.drlevel = shuf.drlevel;
+    out.names = files;
+    out.off.assign(1, 0);
+
+    ListSketcher job{gpu, flt, files, shuf, threads, fq, out};
+    job.run();
     rk_filter_free(flt);
 
     string out_path = out_path_in;
@@ -909,9 +471,8 @@ static void sketch_list(Gpu &gpu, const string &list, bool is_query, const Shuf 
     string err;
     if (!save_sketches(out_path, out, err)) die("%s", err.c_str());
     cerr << "save the sketches into: " << out_path << endl;
-    cerr << "===================time of sketching " << files.size() << " genomes (" << total_windows
+    cerr << "===================time of sketching " << files.size() << " genomes (" << job.total_windows
          << " k-mers) is: " << get_sec() - t0 << endl;
-    (void)is_query;
 }
 
 static rk_sketches *upload(Gpu &gpu, const SketchSet &s)
@@ -1105,7 +666,7 @@ static void write_hits(const string &out, const vector<HitPart> &parts, bool all
     cerr << "===================time of merge the subFiles into final files is: " << get_sec() - t0 << endl;
 }
 
-static void load_or_sketch(Gpu &gpu, const string &input, bool is_query, const Args &a, int threads, SketchSet &s,
+static void load_or_sketch(Gpu &gpu, const string &input, const Args &a, int threads, SketchSet &s,
                            string &sketch_path)
 {
     string err;
@@ -1126,7 +687,7 @@ static void load_or_sketch(Gpu &gpu, const string &input, bool is_query, const A
     cerr << "---read the shuffle file: " << shuf_file << endl;
     if (!read_shuf(shuf_file, shuf, err)) die("read_shuffle_dim(), %s", err.c_str());
     sketch_path = input + ".sketch";
-    sketch_list(gpu, input, is_query, shuf, threads, s, sketch_path, fq);
+    sketch_list(gpu, input, shuf, threads, s, sketch_path, fq);
 }
 
 static int cmd_shuffle(const Args &a)
@@ -1163,7 +724,7 @@ static int cmd_sketch(const Args &a)
     fq.least_num = a.num("n", 1);
     SketchSet s;
     string out_path = out;
-    sketch_list(gpu, in, is_query, shuf, threads, s, out_path, fq);
+    sketch_list(gpu, in, shuf, threads, s, out_path, fq);
     if (!is_sketch_file(out_path)) out_path += ".sketch";
     if (!is_query) rk_index_free(build_index(gpu, s, out_path, true));
     return 0;
@@ -1294,7 +855,7 @@ void SelfJoin::build()
         if (!read_sketches(sketch_path, s, err)) die("readSketches(), %s", err.c_str());
     }
     Gpu &gpu = set[0];
-    if (sketch_path.empty()) load_or_sketch(gpu, a.str("i", ""), false, a, threads, s, sketch_path);
+    if (sketch_path.empty()) load_or_sketch(gpu, a.str("i", ""), a, threads, s, sketch_path);
     stamp("sketches read");
     // the .dict/.index pair is (re)written only if missing (src/subCommand.cpp:165-169); the
     // device index is always rebuilt from the sketches: faster than reading the 2^bits array
@@ -1970,9 +1531,9 @@ static int cmd_dist(const Args &a)
         }
     }
     Gpu &gpu = set[0];
-    if (ref_path.empty()) load_or_sketch(gpu, a.str("r", ""), false, a, threads, ref, ref_path);
+    if (ref_path.empty()) load_or_sketch(gpu, a.str("r", ""), a, threads, ref, ref_path);
     cerr << "the ref_sketch size is: " << ref.size() << endl;
-    if (qry_path.empty()) load_or_sketch(gpu, a.str("q", ""), true, a, threads, qry, qry_path);
+    if (qry_path.empty()) load_or_sketch(gpu, a.str("q", ""), a, threads, qry, qry_path);
     if (qry.info.id != ref.info.id)  // src/subCommand.cpp:297-301
         die("command_dist(), the sketch infos between reference and query files are not match\n"
             "try to use the same shuffle file to generate sketches of the reference and query datasets");
@@ -2068,9 +1629,9 @@ static int cmd_assign(const Args &a)
             if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
         }
     }
-    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), false, a, threads, ref, ref_path);
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), a, threads, ref, ref_path);
     cerr << "the ref_sketch size is: " << ref.size() << endl;
-    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), true, a, threads, qry, qry_path);
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), a, threads, qry, qry_path);
     if (qry.info.id != ref.info.id)
         die("command_assign(), the sketch infos between reference and query files are not match\n"
             "try to use the same shuffle file to generate sketches of the reference and query datasets");
@@ -2193,9 +1754,9 @@ static int cmd_gather(const Args &a)
             if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
         }
     }
-    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), false, a, threads, ref, ref_path);
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), a, threads, ref, ref_path);
     cerr << "the ref_sketch size is: " << ref.size() << endl;
-    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), true, a, threads, qry, qry_path);
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), a, threads, qry, qry_path);
     if (qry.info.id != ref.info.id)
         die("command_gather(), the sketch infos between reference and query files are not match\n"
             "try to use the same shuffle file to generate sketches of the reference and query datasets");

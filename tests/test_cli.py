@@ -420,6 +420,113 @@ def test_cli_big_gzip_and_fastq_files_are_streamed(tmp_path):
 
 
 @pytest.mark.gpu
+def test_cli_every_input_path_of_sketch_in_one_small_list(tmp_path):
+    """Every path of the sketch host pipeline at once, at sizes of a few MB (RK_STAGE_MB=1: staging buffers of 1 MiB): genomes of
+    300 KB in several batches, a three-member .fa.gz whose trailer understates its size (its slot overflows: the whole-file path,
+    spliced back in list order), a 3 MB plain FASTA file (mapped, in pieces of 64 KB), a 3 MB .fa.gz (read sequentially into a device
+    buffer that starts at 1 MiB and grows), and a FASTQ list with a 3 MB .fq under -Q / -n.  Every hash set is the oracle's, and the
+    FASTA list's .sketch is byte-identical to the whole-file run's (RK_BIG_WHOLE=1)."""
+    import gzip
+    from rabbitkssd_amd import synth
+    k, s, l = 8, 5, 2
+    shuf = tmp_path / "L2K8.shuf"
+    run(["shuffle", "-k", k, "-s", s, "-l", l, "-o", shuf])
+    param, table = ok.init_param(k, s, l), ok.shuffle_table(k, s, l)
+    rng = np.random.default_rng(31)
+    lut = np.frombuffer(b"ACGTacgtN", dtype=np.uint8)
+
+    def records(total):
+        """(records, text): records of every size in lines of 60 / 61 / 200 columns, N runs, an empty line now and then"""
+        recs, text, size = [], [], 0
+        while size < total:
+            n = int(rng.choice([1, 15, 16, 17, 300, 5000, 200_000]))
+            codes = rng.integers(0, 8, n, dtype=np.uint8)
+            if n > 1000:
+                a = int(rng.integers(0, n - 100))
+                codes[a:a + int(rng.integers(1, 90))] = 8
+            bases = lut[codes]
+            recs.append(bases)
+            width = int(rng.choice([60, 61, 200]))
+            body = bases.tobytes()
+            lines = [body[i:i + width] for i in range(0, n, width)]
+            if rng.random() < 0.2:
+                lines.insert(len(lines) // 2, b"")
+            text.append(b">r%d c\n" % len(recs) + b"\n".join(lines) + b"\n")
+            size += n
+        return recs, b"".join(text)
+
+    files, seqs = [], []
+    for name, bases in synth.clade_genome_set(7, 300_000):
+        p = tmp_path / (name + ".fa")
+        p.write_bytes(synth.fasta_text(name, bases))
+        files.append(str(p))
+        seqs.append([bases])
+    recs, text = records(900_000)                                     # three members, the last one the smallest
+    c1, c2 = len(text) // 2, len(text) - 1000
+    p = tmp_path / "members.fa.gz"
+    p.write_bytes(gzip.compress(text[:c1], 1, mtime=0) + gzip.compress(text[c1:c2], 1, mtime=0) + gzip.compress(text[c2:], 1, mtime=0))
+    assert p.stat().st_size < (1 << 20) - 1024 and p.stat().st_size < sum(len(r) for r in recs)    # fits a batch, overflows its slot
+    files.insert(4, str(p))
+    seqs.insert(4, recs)
+    recs, text = records(3_000_000)
+    p = tmp_path / "big.fa"
+    p.write_bytes(text)
+    files.insert(2, str(p))
+    seqs.insert(2, recs)
+    recs, text = records(3_000_000)
+    p = tmp_path / "bigz.fa.gz"
+    p.write_bytes(gzip.compress(text, 1, mtime=0))
+    files.append(str(p))
+    seqs.append(recs)
+    lst = tmp_path / "fa.list"
+    lst.write_text("".join(f + "\n" for f in files))
+    env = dict(os.environ, RK_STAGE_MB="1", RK_BIG_PIECE_KB="64", RK_BIG_DEV_MB="1", RK_TIMING="1")
+    p = subprocess.run([TOOL, "sketch", "-i", str(lst), "-L", str(shuf), "-o", str(tmp_path / "st"), "-t", "6", "-q"], cwd=tmp_path, env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    err = p.stderr.decode()
+    assert "big file: " in err and "big file (sequential reader):" in err and err.count(": upload + sketch of") >= 3   # both readers, several batches
+    assert int(err.split("big file: ")[1].split(" piece(s)")[0]) > 40
+    _, names, h, off = ok.read_sketches32(str(tmp_path / "st.sketch"))
+    assert names == files
+    for g, recs in enumerate(seqs):
+        rec_off = np.concatenate([[0], np.cumsum([len(r) for r in recs])]).astype(np.uint64)
+        want = ok.sketch_records(param, table, np.concatenate(recs), rec_off)
+        assert np.array_equal(h[int(off[g]):int(off[g + 1])].astype(np.uint64), want), files[g]
+    p = subprocess.run([TOOL, "sketch", "-i", str(lst), "-L", str(shuf), "-o", str(tmp_path / "wh"), "-t", "6", "-q"], cwd=tmp_path,
+                       env=dict(env, RK_BIG_WHOLE="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    assert b"big file" not in p.stderr
+    assert (tmp_path / "wh.sketch").read_bytes() == (tmp_path / "st.sketch").read_bytes()
+    # ---- FASTQ: 150-base reads, every read twice, quality lines that start like a header line; -Q 36 -n 2 and the defaults
+    n_reads = 10_000
+    codes = rng.integers(0, 4, (n_reads, 150), dtype=np.uint8)
+    codes[rng.random((n_reads, 150)) < 0.001] = 8
+    codes[n_reads // 2:] = codes[: n_reads - n_reads // 2]
+    reads = lut[codes]
+    quals = rng.integers(33, 75, (n_reads, 150), dtype=np.uint8)
+    quals[::7, 0] = ord("@")
+    fq_text = b"".join(b"@read%d/1\n" % i + reads[i].tobytes() + b"\n+\n" + quals[i].tobytes() + b"\n" for i in range(n_reads))
+    assert len(fq_text) > (3 << 20)
+    fq = tmp_path / "reads.fq"
+    fq.write_bytes(fq_text)
+    smallq = tmp_path / "small.fq"
+    smallq.write_bytes(b"@q\nACGTACGTACGTACGTACGTAAAACCCCGGGGTTTT\n+\nIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII\n")
+    lst = tmp_path / "fq.list"
+    lst.write_text("%s\n%s\n" % (smallq, fq))
+    off_q = np.arange(n_reads + 1, dtype=np.uint64) * 150
+    for least_qual, least_num in ((0, 1), (36, 2)):
+        want = ok.sketch_records_fastq(param, table, reads.reshape(-1), quals.reshape(-1), off_q, least_qual, least_num)
+        assert len(want) > 100
+        p = subprocess.run([TOOL, "sketch", "-i", str(lst), "-L", str(shuf), "-o", str(tmp_path / "fq"), "-t", "6", "-q", "-Q", str(least_qual),
+                            "-n", str(least_num)], cwd=tmp_path, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        assert b"big file (sequential reader):" in p.stderr
+        _, names, h, off = ok.read_sketches32(str(tmp_path / "fq.sketch"))
+        assert np.array_equal(h[int(off[1]):int(off[2])].astype(np.uint64), want), (least_qual, least_num)
+
+
+@pytest.mark.gpu
 def test_cli_dist_matches_reference_text(tmp_path):
     d = os.path.join(GOLDEN, "dist")
     man = json.load(open(os.path.join(d, "manifest.json")))
