@@ -1095,6 +1095,57 @@ int rk_gather_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n
                     const rk_gather_opts *opts, uint64_t *off_out /* n_query + 1 */, rk_gather_pick **picks_out, uint64_t *n_picks,
                     uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *covered_out);
 
+/* ---- filtering query sketches by an index ------------------------------------------------ */
+/* rk_sketches_mask: every query sketch without (or with only) the hashes that the references of an index hold -- the reference's `sub`
+ * ("subtract the reference sketch from the query sketches") and three relatives, on the device, in integers only.
+ * For a query hash h, c(h) = the length of h's posting list in the index, 0 when it has none: a hash at or beyond 2^hash_bits of the
+ * index has no list; a reference sketch that repeats a hash lengthens the list, exactly as it counts in rk_dist_rows; for set sketches
+ * c(h) is the number of references that hold h.  h survives iff min_refs <= c(h) <= max_refs:
+ *   {0, 0}            the reference's `sub`: the hashes no reference holds;
+ *   {1, UINT32_MAX}   the intersection: the hashes at least one reference holds;
+ *   {0, m}            without the hashes more than m references hold ("stop words");
+ *   {m, UINT32_MAX}   only the hashes at least m references hold.
+ * *out (library-owned, rk_sketches_free) has as many sketches as the queries, in their order, and their hash width; each holds its
+ * surviving hashes in the order a device-resident sketch has them: ascending, repeats kept with their multiplicity.  A sketch that
+ * loses everything stays, as an empty sketch.  The object is a sketches object like any other (rk_index_build, rk_dist_rows,
+ * rk_dist_topn, rk_assign_rows, rk_gather_rows, rk_sketches_download / download64); rk_sketches_windows() of it is 0.
+ * The result is unique: it does not depend on the internal genome order, on how the index came to be (built or imported) or on the leg.
+ * On the device (rk_mask.hip), flat over all query hashes in tiles of tile_hashes, never one workgroup per sketch: the flag kernel looks
+ * every hash up (the bucket of the prefix directory, then a binary search among the distinct hashes), applies the band to the length of
+ * its list and writes one 64-bit keep word per 64 hashes and the tile's count; an exclusive scan of the tile counts (scan_blocks
+ * blocks); the scatter kernel re-reads hashes and keep words and writes every survivor at tile prefix + kept bits before it (order
+ * preserved, no atomics); the offsets kernel computes off_out[g] = the survivors before off_in[g] from the same words.  No kernel waits
+ * for another workgroup.  One read-back brings the n + 1 offsets and the counters.
+ * RK_MASK_DEVICE=0 answers inside the call as export + rk_mask_lists + rk_sketches_from_host(64), with the same result; stats->path
+ * says which leg ran.
+ * RK_ERR_ARG: null pointers, min_refs > max_refs, queries and index of different hash widths, an index without all posting lists (the
+ * join-only index of rk_index_join_shard, one hash range of a sharded build).  Nothing is written on a refusal.  No query sketch:
+ * RK_OK, *out = NULL, nothing runs.  An index without genomes or without hashes is legal: every c(h) is 0. */
+#define RK_MS_MASK 15           /* rk_sketches_mask: the flag kernel through the offsets kernel of the last call; 0 on the host leg */
+typedef struct rk_mask_rule {
+    uint32_t min_refs, max_refs;   /* h survives iff min_refs <= c(h) <= max_refs */
+} rk_mask_rule;                    /* 8 bytes */
+typedef struct rk_mask_stats {
+    uint64_t hashes, kept, matched;   /* query hashes in, out, and those with c(h) > 0 */
+    uint64_t tiles;                   /* tiles of the flag / scatter kernels: ceil(hashes / tile_hashes) */
+    uint32_t emptied;                 /* non-empty sketches that end empty */
+    uint32_t path;                    /* 0 nothing ran, 1 the device, 2 the host (RK_MASK_DEVICE=0) */
+    uint32_t tile_hashes, scan_blocks, threads;   /* hashes of a tile, blocks of the scan of the tile counts, threads of a workgroup:
+                                                     constants / geometry, filled on every path that ran */
+    uint32_t pad_;
+} rk_mask_stats;                      /* 56 bytes */
+int rk_sketches_mask(rk_ctx *ctx, const rk_sketches *queries, const rk_index *idx, const rk_mask_rule *rule, rk_sketches **out,
+                     rk_mask_stats *stats /* optional */);
+/* Host only, no context: the same rule over the distinct hashes and list lengths as rk_index_export_lists / rk_index_export64 return them
+ * (list_hashes strictly ascending: uint32 when wide == 0, uint64 otherwise, like q_hashes).  The hashes of query i are
+ * q_hashes[q_off[i] .. q_off[i + 1]), in ANY order; the survivors keep their order.  *hashes_out (rk_free_host; NULL when nothing
+ * survives) holds them back to back, off_out (caller's, n_query + 1) delimits them.  stats (optional): hashes, kept, matched, emptied.
+ * RK_ERR_ARG: null pointers (q_hashes may be NULL without hashes, list_hashes / counts without lists), min_refs > max_refs, offsets
+ * that do not ascend from 0, list hashes that do not strictly ascend.  Nothing is written on a refusal. */
+int rk_mask_lists(const void *q_hashes, int wide, const uint64_t *q_off /* n_query + 1 */, uint32_t n_query, const void *list_hashes,
+                  const uint32_t *counts, uint64_t n_lists, const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out /* n_query + 1 */,
+                  rk_mask_stats *stats /* optional */);
+
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,
                   const rk_hit *hit);

@@ -32,7 +32,7 @@ EXPORTS = [
     "rk_cluster_rows", "rk_cluster_merge", "rk_forest_rows", "rk_forest_merge", "rk_forest_cut", "rk_greedy_rows", "rk_greedy_hits",
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
     "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
-    "rk_group_sketches", "rk_group_lists", "rk_gather_rows", "rk_gather_lists",
+    "rk_group_sketches", "rk_group_lists", "rk_gather_rows", "rk_gather_lists", "rk_sketches_mask", "rk_mask_lists",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -51,6 +51,8 @@ GROUP_NONE = 0xFFFFFFFF     # RK_GROUP_NONE: the label of an unlabelled genome (
 MS_TOPN_COUNTS, MS_TOPN_SELECT, MS_TOPN_DOWNLOAD, MS_TOPN_HOST, MS_TOPN_CANDIDATES = 1, 2, 3, 4, 5
 MS_GROUP = 13               # RK_MS_GROUP: the timed span of rk_group_sketches (Context.last_ms)
 MS_GATHER = 14              # RK_MS_GATHER: the timed span of rk_gather_rows (Context.last_ms)
+MS_MASK = 15                # RK_MS_MASK: the timed span of rk_sketches_mask (Context.last_ms)
+MASK_MAX = 0xFFFFFFFF       # UINT32_MAX: no upper bound of a MaskRule
 # rk_gather_pick: one record per pick of rk_gather_rows / rk_gather_lists
 GATHER_PICK_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("rank", "<u4"), ("common", "<u4"), ("fresh", "<u4"), ("left", "<u4"),
                               ("size_ref", "<u4"), ("size_query", "<u4")])
@@ -172,6 +174,17 @@ class GatherStats(C.Structure):
                 ("wave_lists", C.c_uint64), ("block_lists", C.c_uint64), ("rows_per_batch", C.c_uint64), ("path", C.c_uint32), ("rows", C.c_uint32),
                 ("batches", C.c_uint32), ("rounds", C.c_uint32), ("launched_rounds", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32),
                 ("compactions", C.c_uint32), ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("sync_every", C.c_uint32), ("threads", C.c_uint32)]
+
+
+class MaskRule(C.Structure):
+    """rk_mask_rule: a query hash survives iff min_refs <= the length of its posting list <= max_refs"""
+    _fields_ = [("min_refs", C.c_uint32), ("max_refs", C.c_uint32)]
+
+
+class MaskStats(C.Structure):
+    """rk_mask_stats: what one rk_sketches_mask / rk_mask_lists call did"""
+    _fields_ = [("hashes", C.c_uint64), ("kept", C.c_uint64), ("matched", C.c_uint64), ("tiles", C.c_uint64), ("emptied", C.c_uint32),
+                ("path", C.c_uint32), ("tile_hashes", C.c_uint32), ("scan_blocks", C.c_uint32), ("threads", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 def group_rule(rule):
@@ -747,6 +760,21 @@ class Context:
                                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(st)))
         return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + tuple(out) + (_stats_dict(st),)
 
+    def sketches_mask(self, queries, index, min_refs=0, max_refs=0):
+        """the query sketches with only the hashes that between min_refs and max_refs references of the index hold (rk_sketches_mask):
+        (sketches, stats) -- (0, 0) subtracts the index from the queries like the reference's `sub`, (1, MASK_MAX) intersects, (0, m)
+        drops the hashes more than m references hold, (m, MASK_MAX) keeps those at least m hold.  sketches: a device-resident Sketches
+        of as many sketches as the queries, in their order, survivors ascending with their repeats (None without a query sketch);
+        stats a dict of the MaskStats fields"""
+        r = MaskRule(int(min_refs), int(max_refs))
+        h = C.c_void_p()
+        st = MaskStats()
+        L = lib()
+        L.rk_sketches_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MaskRule), C.POINTER(C.c_void_p), C.POINTER(MaskStats)]
+        self.check(L.rk_sketches_mask(self._h, queries._h if queries is not None else None, index._h if index is not None else None, C.byref(r),
+                                      C.byref(h), C.byref(st)))
+        return (Sketches(self, h) if h.value else None), _stats_dict(st)
+
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
                       n_hits_dev_ptr, row_first=0, row_step=1, stream=0, row_block=0, queries=None):
         opts = _opts(triangle, metric, kmer_size, max_dist, row_first, row_step, row_block)
@@ -1173,6 +1201,35 @@ def gather_lists(postings, counts, q_off, q_lists, n_ref, ref_sizes, query_sizes
         raise RkError(rc, "rk_gather_lists: min_new == 0, offsets that do not ascend from 0, a list index beyond the lists or out of order, "
                           "or a posting beyond the number of references")
     return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + out
+
+
+def mask_lists(q_hashes, q_off, list_hashes, counts, min_refs=0, max_refs=0):
+    """the rule of Context.sketches_mask over exported lists (rk_mask_lists, host only): (hashes, off, stats) -- list_hashes the distinct
+    hashes of the index, strictly ascending, and counts the lengths of their posting lists (Index.export_lists / export64); q_hashes
+    (uint32 or uint64: its dtype decides the width) in any order within a sketch; the survivors of query i, in its order, are
+    hashes[off[i]:off[i + 1]]"""
+    q_hashes = np.ascontiguousarray(q_hashes)
+    if q_hashes.dtype not in (np.uint32, np.uint64):
+        raise ValueError("mask_lists needs uint32 or uint64 query hashes")
+    list_hashes = np.ascontiguousarray(list_hashes, dtype=q_hashes.dtype)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    if len(q_off) < 1 or len(counts) != len(list_hashes) or int(q_off[-1]) > len(q_hashes):
+        raise ValueError("mask_lists needs one count per list hash and offsets that end within the query hashes")
+    q = len(q_off) - 1
+    r = MaskRule(int(min_refs), int(max_refs))
+    off = np.zeros(q + 1, dtype=np.uint64)
+    h = C.c_void_p()
+    st = MaskStats()
+    L = lib()
+    L.rk_mask_lists.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MaskRule),
+                                C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(MaskStats)]
+    rc = L.rk_mask_lists(_ptr(q_hashes) if len(q_hashes) else None, int(q_hashes.dtype == np.uint64), _ptr(q_off), C.c_uint32(q),
+                         _ptr(list_hashes) if len(counts) else None, _ptr(counts) if len(counts) else None, C.c_uint64(len(counts)), C.byref(r),
+                         C.byref(h), _ptr(off), C.byref(st))
+    if rc:
+        raise RkError(rc, "rk_mask_lists: min_refs above max_refs, offsets that do not ascend from 0, or list hashes that do not strictly ascend")
+    return _take_array(h, int(off[-1]), q_hashes.dtype), off, _stats_dict(st)
 
 
 def medoid_merge(a, b, n, metric):

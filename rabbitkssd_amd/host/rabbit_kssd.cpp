@@ -1729,9 +1729,99 @@ static int cmd_assign(const Args &a)
     SelfJoin::leave();
 }
 
+// the sketches of `qry` on the device with only the hashes that between rule.min_refs and rule.max_refs sketches of `ref` hold
+// (rk_sketches_mask); NULL without a query sketch.  The index of `ref` is built for the call, and written next to ref_path when asked.
+static rk_sketches *masked_queries(GpuSet &set, const SketchSet &ref, const string &ref_path, bool write_files, const SketchSet &qry, const rk_mask_rule &rule,
+                                   rk_mask_stats *stats)
+{
+    vector<rk_index *> idx(1, nullptr);
+    build_everywhere(set, ref, ref_path, write_files, idx);
+    rk_sketches *qs = upload(set[0], qry), *out = nullptr;
+    set[0].check(rk_sketches_mask(set[0].ctx, qs, idx[0], &rule, &out, stats), "rk_sketches_mask");
+    rk_sketches_free(qs);
+    rk_index_free(idx[0]);
+    return out;
+}
+
+// mask: the query sketches with only the hashes that between --min-refs and --max-refs reference sketches hold (rk_sketches_mask).
+// --keep absent (the default, {0, 0}) writes the sketches `sub` writes, with the hashes of every sketch ascending; --keep present
+// ({1, no limit}) the intersection.  out.sketch: the queries' info and names, one sketch per query in input order.
+static int cmd_mask(const Args &a)
+{
+    if (!a.has("r") || !a.has("q") || !a.has("o")) die("mask needs -r, -q and -o");
+    if (a.num("gpus", 1) != 1) die("command_mask(), mask runs on one GPU (--gpus 1)");
+    if (a.has("keep") && (a.has("min-refs") || a.has("max-refs"))) die("command_mask(), --keep and --min-refs / --max-refs exclude each other");
+    const string keep = a.str("keep", "absent");
+    if (keep != "absent" && keep != "present") die("command_mask(), --keep must be absent or present");
+    rk_mask_rule rule{0, 0};
+    if (keep == "present") rule = rk_mask_rule{1, 0xFFFFFFFFu};
+    if (a.has("min-refs") || a.has("max-refs")) {
+        auto bound = [&](const char *key, uint32_t otherwise) {
+            if (!a.has(key)) return otherwise;
+            const string v = a.str(key, "");
+            char *end = nullptr;
+            const unsigned long long x = strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] == '-' || v[0] == '+' || x > 0xFFFFFFFFULL) die("command_mask(), --%s needs an integer from 0 to 4294967295", key);
+            return (uint32_t)x;
+        };
+        rule.min_refs = bound("min-refs", 0u);
+        rule.max_refs = bound("max-refs", 0xFFFFFFFFu);
+        if (rule.min_refs > rule.max_refs) die("command_mask(), --min-refs must not exceed --max-refs");
+    }
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), 1, false);
+    SketchSet ref, qry;
+    string ref_path, qry_path;
+    {   // .sketch inputs are read while the runtime starts
+        string err;
+        if (is_sketch_file(a.str("r", ""))) {
+            ref_path = a.str("r", "");
+            if (!read_sketches(ref_path, ref, err)) die("readSketches(), %s", err.c_str());
+        }
+        if (is_sketch_file(a.str("q", ""))) {
+            qry_path = a.str("q", "");
+            if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
+        }
+    }
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), a, threads, ref, ref_path);
+    cerr << "the ref_sketch size is: " << ref.size() << endl;
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), a, threads, qry, qry_path);
+    if (qry.info.id != ref.info.id)
+        die("command_mask(), the sketch infos between reference and query files are not match\n"
+            "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    // the .dict/.index pair next to the reference is (re)written only if missing, as dist does
+    const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
+    if (getenv("RK_TIMING")) rk_ctx_set_timing(set[0].ctx, 1);
+    rk_mask_stats stats;
+    rk_sketches *kept = masked_queries(set, ref, ref_path, missing, qry, rule, &stats);
+    stamp("queries masked");
+    SketchSet out;
+    out.info = qry.info;
+    out.names = qry.names;
+    out.off.assign(qry.size() + 1, 0);
+    if (kept) {
+        if (out.wide()) {
+            out.hashes64.resize(rk_sketches_total(kept));
+            set[0].check(rk_sketches_download64(kept, out.hashes64.data(), out.off.data()), "rk_sketches_download64");
+        } else {
+            out.hashes.resize(rk_sketches_total(kept));
+            set[0].check(rk_sketches_download(kept, out.hashes.data(), out.off.data()), "rk_sketches_download");
+        }
+        rk_sketches_free(kept);
+    }
+    string err;
+    if (!save_sketches(a.str("o", ""), out, err)) die("%s", err.c_str());
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %zu queries against %zu references: %llu of %llu hashes kept (%llu have a posting list), %u sketches emptied, %llu tiles, %u scan block(s), "
+                        "path %u, %.3f ms on the device\n", qry.size(), ref.size(), (unsigned long long)stats.kept, (unsigned long long)stats.hashes,
+                (unsigned long long)stats.matched, stats.emptied, (unsigned long long)stats.tiles, stats.scan_blocks, stats.path, rk_ctx_last_ms(set[0].ctx, RK_MS_MASK));
+    SelfJoin::leave();
+}
+
 // gather: which references explain each query sketch (rk_gather_rows): per round the reference that holds most of the query's hashes
 // no earlier pick held -- the greedy minimum set cover, a metagenome's decomposition.  One line per pick:
 // query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref.
+// --sub host.sketch: the queries lose the hashes of host.sketch on the device first (rk_sketches_mask {0, 0}): the cover of what `sub` would leave.
 static int cmd_gather(const Args &a)
 {
     if (!a.has("r") || !a.has("q")) die("gather needs -r and -q");
@@ -1772,7 +1862,20 @@ static int cmd_gather(const Args &a)
     rk_gather_pick *picks = nullptr;
     uint64_t n_picks = 0;
     rk_gather_stats stats;
-    rk_sketches *qs = upload(set[0], qry);
+    rk_sketches *qs = nullptr;
+    vector<uint64_t> q_off = qry.off;   // the sizes of the queries as they are covered
+    if (a.has("sub")) {
+        const string host_path = a.str("sub", "");
+        if (!is_sketch_file(host_path)) die("command_gather(), %s is not sketch file, --sub needs a sketch file", host_path.c_str());
+        SketchSet host;
+        string err;
+        if (!read_sketches(host_path, host, err)) die("readSketches(), %s", err.c_str());
+        if (host.info.id != qry.info.id) die("command_gather(), the sketch infos between the --sub sketches and the query sketches are not same");
+        qs = masked_queries(set, host, host_path, false, qry, rk_mask_rule{0, 0}, nullptr);
+        if (qs) set[0].check(rk_sketches_download(qs, nullptr, q_off.data()), "rk_sketches_download");
+        stamp("queries masked");
+    }
+    if (!qs) qs = upload(set[0], qry);
     set[0].check(rk_gather_rows(set[0].ctx, idx[0], qs, &o, off.data(), &picks, &n_picks, matched.data(), n_cand.data(), covered.data(), &stats), "rk_gather_rows");
     rk_sketches_free(qs);
     stamp("queries decomposed");
@@ -1788,7 +1891,7 @@ static int cmd_gather(const Args &a)
         FILE *sp = fopen(a.str("summary", "").c_str(), "w");
         if (!sp) die("cannot write %s", a.str("summary", "").c_str());
         for (size_t q = 0; q < Q; q++)
-            fprintf(sp, "%s\t%llu\t%u\t%u\t%u\t%llu\n", qry.names[q].c_str(), (unsigned long long)(qry.off[q + 1] - qry.off[q]), matched[q], covered[q], n_cand[q],
+            fprintf(sp, "%s\t%llu\t%u\t%u\t%u\t%llu\n", qry.names[q].c_str(), (unsigned long long)(q_off[q + 1] - q_off[q]), matched[q], covered[q], n_cand[q],
                     (unsigned long long)(off[q + 1] - off[q]));
         fclose(sp);
     }
@@ -2096,7 +2199,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert merge info\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert merge info mask\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2109,12 +2212,13 @@ static int usage()
             "  medoid -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [--by cluster|greedy|dbscan] [-m minPts] [--labels FILE] [--census FILE] [-L file.shuf] [--device N] [--gpus G]   (medoids and census of a clustering of alldist's pairs: per genome its cluster, its role -- the medoid is the member with the highest summed similarity to its fellow members --, its pairs inside the cluster and leaving it, its mean similarity to its fellow members and its nearest genome outside; the labels from --by (default cluster; dbscan needs -m; greedy and dbscan on one GPU) or from --labels: one line per genome, an integer below the number of genomes or -; --census: per cluster its size, medoid, inside pairs of size (size - 1) / 2, weakest inside pair and nearest leaving pair)\n"
             "  assign -r ref.sketch|list -q qry.sketch|list -D maxDist [-M 0|1] (--labels FILE | --by cluster|greedy|dbscan -m minPts) -o out [--novel FILE] [--gpus G] [--device N]   (placement of the queries into the clustered references: per query the cluster of its nearest labelled reference within -D, that reference's dist line, the query's references of that cluster, labelled and all within -D, and the runner-up cluster with its distance; - when novel; -D below 1.0; the labels from --labels -- one line per reference, an integer below their number or - -- or from --by on the same index (default cluster; dbscan needs -m and leaves non-core references unlabelled; greedy and dbscan on the first GPU); --novel: the names of the unplaced queries)\n"
             "  group -i in.sketch|genomes.list (--labels FILE | --by cluster|greedy|dbscan [-D 0.05] [-M 0|1] [-m 5]) [--pan | --core | --share P/Q] [--min-count C] [--only] -o out.sketch [--map FILE] [--device N]   (one sketch per cluster: --pan, the default, the union of its members' sketches; --core the hashes every member holds; --share P/Q those at least P of Q of its members hold; --min-count C: at least C members hold it; --only: no genome outside the cluster holds it -- its markers; the labels as medoid takes them; out.sketch: one sketch per cluster by ascending label, named after its first member; --map: per cluster its number, label, genomes, hashes kept and name; one GPU)\n"
-            "  gather -r ref.sketch|list -q qry.sketch|list [--min-new 1] [--max-picks 0] -o out [--summary FILE] [--device N]   (which references explain each query, greedily: per round the reference that holds most of the query's hashes no earlier pick held, ties to the earlier reference, until a pick would add fewer than --min-new hashes or --max-picks are made; one line per pick: query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref; --summary: per query its name, size, hashes some reference holds, hashes the picks explain, references sharing at least --min-new hashes, picks; one GPU)\n"
+            "  gather -r ref.sketch|list -q qry.sketch|list [--min-new 1] [--max-picks 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references explain each query, greedily: per round the reference that holds most of the query's hashes no earlier pick held, ties to the earlier reference, until a pick would add fewer than --min-new hashes or --max-picks are made; one line per pick: query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref; --summary: per query its name, size, hashes some reference holds, hashes the picks explain, references sharing at least --min-new hashes, picks; --sub: the queries first lose every hash a sketch of host.sketch holds, on the device -- the cover of what sub would write; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
             "  union   -i in.sketch -o out.sketch\n"
             "  sub     --rs ref.sketch --qs qry.sketch -o out.sketch\n"
+            "  mask    -r ref.sketch|list -q qry.sketch|list [--keep absent|present | --min-refs A --max-refs B] -o out.sketch [--device N]   (the query sketches with only the hashes that at least A and at most B reference sketches hold, hashes ascending: --keep absent, the default, is A = B = 0 -- the sketches sub writes, computed on the device; --keep present is A = 1 without B -- the intersection; --max-refs B alone drops the hashes more than B references hold, --min-refs A alone keeps those at least A hold; one GPU)\n"
             "  convert -i kssd_dir -o out[.sketch] [-q]   |   convert --reverse -i in.sketch -o kssd_dir\n";
     return 1;
 }
@@ -2132,7 +2236,8 @@ int main(int argc, char **argv)
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
         {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"},
         {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"},
-        {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--summary", "summary"}};
+        {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--summary", "summary"}, {"--sub", "sub"},
+        {"--keep", "keep"}, {"--min-refs", "min-refs"}, {"--max-refs", "max-refs"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2150,7 +2255,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather" || sub == "mask") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2178,6 +2283,7 @@ int main(int argc, char **argv)
     if (sub == "assign") { cerr << "-----run the subcommand: assign" << endl; return leave(cmd_assign(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "group") { cerr << "-----run the subcommand: group" << endl; return leave(cmd_group(parse_args(argc, argv, 2, alias, {"pan", "core", "only"}))); }   // (--core is a flag here, a file of mreach)
     if (sub == "gather") { cerr << "-----run the subcommand: gather" << endl; return leave(cmd_gather(parse_args(argc, argv, 2, alias, {}))); }
+    if (sub == "mask") { cerr << "-----run the subcommand: mask" << endl; return leave(cmd_mask(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
