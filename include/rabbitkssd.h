@@ -1146,6 +1146,109 @@ int rk_mask_lists(const void *q_hashes, int wide, const uint64_t *q_off /* n_que
                   const uint32_t *counts, uint64_t n_lists, const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out /* n_query + 1 */,
                   rk_mask_stats *stats /* optional */);
 
+/* ---- taxonomic classification by per-hash LCA -------------------------------------------- */
+/* rk_lca_rows: per query sketch the tally of the lowest common ancestors of its hashes in a taxonomy over the references -- the rule of
+ * Kraken and of sourmash `lca classify` / `summarize`, on the device, in integers only.
+ * Taxonomy: parent[0 .. n_taxa) (host); parent[t] == t marks the root, of which there is exactly one; every other node reaches it by
+ * following parent.  Node ids are the caller's: no order, no depth bound.  taxa[0 .. N) (host) names the node of every reference in the
+ * CALLER's genome order, RK_LCA_NONE leaves a reference unlabelled.
+ * Per hash h with a posting list: lca(h) = the lowest common ancestor of the taxa of its labelled holders (a genome that repeats h is a
+ * holder like any other; an unlabelled holder is ignored -- unlike rk_group_sketches `only`, where it defeats the hash); undefined when
+ * no holder is labelled.
+ * Per selected query row q (row_first / row_step / row_block as in rk_gather_opts), every ELEMENT of the sketch counting, a repeated
+ * hash as often as it occurs (as in rk_sketches_mask):
+ *   matched[q]      the elements with a posting list (a hash at or beyond 2^hash_bits of the index has none);
+ *   unlabelled[q]   the matched elements whose lca is undefined;
+ *   the tally       the records {taxon, direct} with direct > 0 = the matched elements with lca == taxon, by ascending caller node id:
+ *                   (*counts_out)[off_out[q] .. off_out[q + 1]).  sum(direct) + unlabelled[q] == matched[q].
+ * off_out (host, Q + 1) is written in full (an unselected row is empty); *counts_out is the library's (rk_free_host; NULL when there is
+ * no record); matched_out / unlabelled_out (host, Q entries each): only the entries of the selected rows are written.  The result is
+ * unique: it does not depend on the internal genome order, on how the index came to be (built or imported), on how the nodes are
+ * numbered (the records map onto each other), on tiles, shards or the leg.  A row depends on its own elements alone: row shards
+ * concatenate, no merge call is needed.
+ * Accepted: every index that carries all posting lists, built or imported.  Traffic: 16 * n_taxa + 4 * N bytes go up; the counters,
+ * 8 * (Q + 1) bytes of offsets, 8 * Q bytes of the two per-row counts and 8 bytes per record come back, never a hash, a posting or the
+ * taxon of a list.
+ * On the device (rk_lca.hip), one stream: the host validates the taxonomy and numbers it in preorder (iterative, children by ascending
+ * id); the preorder id of every genome's taxon in internal genome order; per posting list the smallest and the largest preorder id of
+ * its labelled postings -- the LCA of a set is the LCA of these two -- and one climb from the smaller, by list length: one lane up to
+ * lane_max postings, one wave up to wave_max, a workgroup that streams chunks of `chunk` postings beyond; then flat over all query
+ * elements in tiles of tile_hashes, never one workgroup per sketch: the look-up (the bucket of the prefix directory, a binary search),
+ * the row of the element (a binary search among the query offsets), a tile-local table of table_slots slots in LDS keyed by
+ * row << 32 | taxon, one reservation per tile for its partial records; these sorted, equal keys summed, offsets taken.  No kernel
+ * waits for another workgroup.  When the partial records outgrow their buffer the query pass runs once more with the exact count
+ * (attempts = 2).  The host synchronises for the counters, for the offsets and per-row counts, and for the records.
+ * RK_LCA_DEVICE=0 answers inside the call as export + look-up + rk_lca_lists, with the same result; stats->path says which leg ran.
+ * RK_ERR_ARG: null pointers, n_taxa == 0, no root or two, a parent >= n_taxa, a cycle, a taxon that is neither < n_taxa nor
+ * RK_LCA_NONE, queries and index of different hash widths, an index without all posting lists (the join-only index of
+ * rk_index_join_shard, one hash range of a sharded build).  RK_ERR_UNSUPPORTED: n_taxa or N at 2^31 or more, a query sketch of 2^32
+ * elements or more.  Nothing is written on a refusal.  No query sketch: RK_OK, nothing runs.  An index without genomes, without hashes
+ * or without a labelled genome is legal: every tally is empty, matched is still counted. */
+#define RK_LCA_NONE 0xFFFFFFFFu /* taxa[]: an unlabelled reference; rk_lca_called: no call */
+#define RK_MS_LCA 16            /* rk_lca_rows: k_lca_taxa through the fold of the last call; 0 on the host leg */
+typedef struct rk_lca_opts {
+    uint32_t row_first, row_step, row_block;   /* the row shard, as in rk_gather_opts (0 0 0: every query) */
+} rk_lca_opts;                  /* 12 bytes */
+typedef struct rk_lca_count {
+    uint32_t taxon, direct;     /* the caller's node id; the matched elements of the query whose lca is this node (> 0) */
+} rk_lca_count;                 /* 8 bytes */
+typedef struct rk_lca_rule {
+    uint32_t min_count;         /* >= 1: a record counts from this many elements on */
+    uint32_t conf_num, conf_den;   /* the confidence conf_num / conf_den in [0, 1]: conf_num <= conf_den, conf_den >= 1 */
+    uint32_t denom;             /* the denominator of the confidence: 0 the retained elements, 1 the size of the query sketch */
+} rk_lca_rule;                  /* 16 bytes */
+typedef struct rk_lca_called {
+    uint32_t taxon;             /* the call, RK_LCA_NONE when the root fails too or nothing is retained */
+    uint32_t candidate;         /* the LCA of the retained nodes of maximal score (RK_LCA_NONE: nothing retained) */
+    uint32_t clade;             /* clade(taxon); clade(root) when there is no call */
+    uint32_t score;             /* the maximal score */
+    uint32_t retained;          /* the sum of direct over the retained records */
+    uint32_t n_taxa;            /* the retained records */
+} rk_lca_called;                /* 24 bytes */
+typedef struct rk_lca_stats {
+    uint64_t lists, postings;   /* posting lists and postings of the index */
+    uint64_t lane_lists, wave_lists, block_lists;   /* lists by the class of their length (lane_max, wave_max) */
+    uint64_t elements;          /* query elements of the selected rows */
+    uint64_t matched, unlabelled, records;   /* summed over the selected rows */
+    uint64_t partials;          /* (row, taxon, count) records the tiles emitted (device leg) */
+    uint64_t tiles;             /* tiles of the query pass: ceil(all query elements / tile_hashes) */
+    uint32_t longest_climb;     /* the most parent steps one list took from its smallest preorder id to its lca (device leg) */
+    uint32_t path;              /* 0 nothing ran, 1 the device, 2 the host (RK_LCA_DEVICE=0, rk_lca_lists) */
+    uint32_t attempts;          /* runs of the query pass: 2 after an overflow of the partial records */
+    uint32_t rows;              /* selected rows */
+    uint32_t lane_max, wave_max, chunk, tile_hashes, table_slots, threads;   /* constants, filled on every path that ran */
+} rk_lca_stats;                 /* 128 bytes */
+int rk_lca_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const uint32_t *taxa /* N */, const uint32_t *parent /* n_taxa */,
+                uint32_t n_taxa, const rk_lca_opts *opts, uint64_t *off_out /* Q + 1 */, rk_lca_count **counts_out, uint64_t *n_counts,
+                uint32_t *matched_out /* Q */, uint32_t *unlabelled_out /* Q */, rk_lca_stats *stats /* optional */);
+/* Host only, no context: the same rule over posting lists as rk_index_export_lists / rk_index_export64 return them (reference ids below
+ * n_ref in any order within a list, a repeated id a holder like any other) -- blind to the hash width: per query i the indices of the
+ * lists its elements hit, ascending, repeats allowed, one per matched element, are q_lists[q_off[i] .. q_off[i + 1]).  The LCA of a
+ * list is folded pairwise by depth and parent steps; nothing is numbered in preorder: the two legs do not share their algorithm.  The
+ * outputs are those of rk_lca_rows.  RK_ERR_ARG: null pointers (postings / counts may be NULL without lists, q_lists when no element hits
+ * a list, taxa when n_ref is 0, the per-query outputs when n_query is 0), a bad taxonomy or taxon as above, offsets that do not ascend
+ * from 0, a list index >= n_lists or out of order, a posting >= n_ref.  RK_ERR_UNSUPPORTED as above.  Nothing is written on a refusal. */
+int rk_lca_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off /* n_query + 1 */,
+                 const uint64_t *q_lists, uint32_t n_query, uint32_t n_ref, const uint32_t *taxa /* n_ref */, const uint32_t *parent /* n_taxa */,
+                 uint32_t n_taxa, const rk_lca_opts *opts, uint64_t *off_out /* n_query + 1 */, rk_lca_count **counts_out, uint64_t *n_counts,
+                 uint32_t *matched_out, uint32_t *unlabelled_out, rk_lca_stats *stats /* optional */);
+/* Host only, no context: the call on the tally of every query (counts[off[q] .. off[q + 1]), as rk_lca_rows returns them; any order
+ * within a query, every taxon at most once), the taxonomy and a rule.
+ *   retained    the records with direct >= min_count; `retained` = the sum of their direct;
+ *   clade(t)    the sum of retained direct over the subtree of t;  score(t) the sum over the path from the root to t;
+ *   candidate   the LCA of the retained nodes of maximal score (Kraken's root-to-leaf rule with its tie rule);
+ *   climb       from the candidate to the parent while clade(t) * conf_den < conf_num * D, D = retained (denom 0) or query_sizes[q]
+ *               (denom 1); the first node that passes is the call; RK_LCA_NONE when the root fails too or nothing is retained.
+ * {m, 1, 1, 0} is sourmash `lca classify --threshold m` (the LCA of every retained taxon), {1, 0, 1, *} Kraken without confidence.
+ * called_out (host, n_query records); clade_out (optional, host, off[n_query] entries): clade(taxon) of every tally record, parallel
+ * to counts.  RK_ERR_ARG: null pointers (counts may be NULL without records, query_sizes unless denom is 1), a bad taxonomy,
+ * a record's taxon >= n_taxa or twice in a query, offsets that do not ascend from 0, min_count == 0, conf_den == 0, conf_num > conf_den,
+ * denom > 1.  RK_ERR_UNSUPPORTED: a query whose direct counts add up to 2^32 or more (clade, score and retained are 32 bits wide; a
+ * tally of rk_lca_rows cannot).  Nothing is written on a refusal. */
+int rk_lca_call(const rk_lca_count *counts, const uint64_t *off /* n_query + 1 */, uint32_t n_query, const uint32_t *query_sizes /* n_query */,
+                const uint32_t *parent /* n_taxa */, uint32_t n_taxa, const rk_lca_rule *rule, rk_lca_called *called_out /* n_query */,
+                uint32_t *clade_out /* optional */);
+
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,
                   const rk_hit *hit);

@@ -33,6 +33,7 @@ EXPORTS = [
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
     "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
     "rk_group_sketches", "rk_group_lists", "rk_gather_rows", "rk_gather_lists", "rk_sketches_mask", "rk_mask_lists",
+    "rk_lca_rows", "rk_lca_lists", "rk_lca_call",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -53,6 +54,11 @@ MS_GROUP = 13               # RK_MS_GROUP: the timed span of rk_group_sketches (
 MS_GATHER = 14              # RK_MS_GATHER: the timed span of rk_gather_rows (Context.last_ms)
 MS_MASK = 15                # RK_MS_MASK: the timed span of rk_sketches_mask (Context.last_ms)
 MASK_MAX = 0xFFFFFFFF       # UINT32_MAX: no upper bound of a MaskRule
+MS_LCA = 16                 # RK_MS_LCA: the timed span of rk_lca_rows (Context.last_ms)
+LCA_NONE = 0xFFFFFFFF       # RK_LCA_NONE: the taxon of an unlabelled reference; no call
+# rk_lca_count: one record of a query's tally; rk_lca_called: the call on it
+LCA_COUNT_DTYPE = np.dtype([("taxon", "<u4"), ("direct", "<u4")])
+LCA_CALLED_DTYPE = np.dtype([("taxon", "<u4"), ("candidate", "<u4"), ("clade", "<u4"), ("score", "<u4"), ("retained", "<u4"), ("n_taxa", "<u4")])
 # rk_gather_pick: one record per pick of rk_gather_rows / rk_gather_lists
 GATHER_PICK_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("rank", "<u4"), ("common", "<u4"), ("fresh", "<u4"), ("left", "<u4"),
                               ("size_ref", "<u4"), ("size_query", "<u4")])
@@ -185,6 +191,26 @@ class MaskStats(C.Structure):
     """rk_mask_stats: what one rk_sketches_mask / rk_mask_lists call did"""
     _fields_ = [("hashes", C.c_uint64), ("kept", C.c_uint64), ("matched", C.c_uint64), ("tiles", C.c_uint64), ("emptied", C.c_uint32),
                 ("path", C.c_uint32), ("tile_hashes", C.c_uint32), ("scan_blocks", C.c_uint32), ("threads", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class LcaOpts(C.Structure):
+    """rk_lca_opts: the row shard, as in GatherOpts (0 0 0: every query)"""
+    _fields_ = [("row_first", C.c_uint32), ("row_step", C.c_uint32), ("row_block", C.c_uint32)]
+
+
+class LcaRule(C.Structure):
+    """rk_lca_rule: a record counts from min_count elements on; the call climbs while clade / D < conf_num / conf_den, D the retained
+    elements (denom 0) or the size of the query sketch (denom 1)"""
+    _fields_ = [("min_count", C.c_uint32), ("conf_num", C.c_uint32), ("conf_den", C.c_uint32), ("denom", C.c_uint32)]
+
+
+class LcaStats(C.Structure):
+    """rk_lca_stats: what one rk_lca_rows / rk_lca_lists call did"""
+    _fields_ = [("lists", C.c_uint64), ("postings", C.c_uint64), ("lane_lists", C.c_uint64), ("wave_lists", C.c_uint64), ("block_lists", C.c_uint64),
+                ("elements", C.c_uint64), ("matched", C.c_uint64), ("unlabelled", C.c_uint64), ("records", C.c_uint64), ("partials", C.c_uint64),
+                ("tiles", C.c_uint64), ("longest_climb", C.c_uint32), ("path", C.c_uint32), ("attempts", C.c_uint32), ("rows", C.c_uint32),
+                ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("chunk", C.c_uint32), ("tile_hashes", C.c_uint32), ("table_slots", C.c_uint32),
+                ("threads", C.c_uint32)]
 
 
 def group_rule(rule):
@@ -760,6 +786,35 @@ class Context:
                                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(st)))
         return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + tuple(out) + (_stats_dict(st),)
 
+    def lca_rows(self, index, queries, taxa, parent, row_first=0, row_step=1, row_block=0, out=None):
+        """the tally of per-hash lowest common ancestors of each query sketch (rk_lca_rows): (off, counts, matched, unlabelled, stats) --
+        parent (uint32, one entry per node of the taxonomy, the root names itself), taxa (uint32, one node or LCA_NONE per reference in
+        the caller's order).  counts (LCA_COUNT_DTYPE) by ascending node id, those of query q at counts[off[q]:off[q + 1]] (off: uint64,
+        Q + 1); matched / unlabelled (uint32, Q): the query's elements with a posting list, and those whose list has no labelled holder.
+        Only the entries of the selected query rows are written: `out` (matched, unlabelled as returned) lets row shards write into
+        one set; their records concatenate"""
+        q = queries.count if queries is not None else 0
+        if out is None:
+            out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(2))
+        elif len(out) != 2 or any(not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.shape == (q,) and a.flags.c_contiguous and a.flags.writeable)
+                                  for a in out):
+            raise ValueError("out needs (matched, unlabelled): writable contiguous uint32 arrays of one entry per query")
+        taxa = np.ascontiguousarray(taxa, dtype=np.uint32)
+        parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        if index is not None and len(taxa) != index.genomes:
+            raise ValueError("lca_rows needs one taxon per reference of the index")
+        o = LcaOpts(int(row_first), int(row_step), int(row_block))
+        off = np.zeros(q + 1, dtype=np.uint64)
+        recs, n = C.c_void_p(), C.c_uint64()
+        st = LcaStats()
+        L = lib()
+        L.rk_lca_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(LcaOpts), C.c_void_p,
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(LcaStats)]
+        self.check(L.rk_lca_rows(self._h, index._h if index is not None else None, queries._h if queries is not None else None,
+                                 _ptr(taxa) if len(taxa) else None, _ptr(parent) if len(parent) else None, C.c_uint32(len(parent)), C.byref(o), _ptr(off),
+                                 C.byref(recs), C.byref(n), _ptr(out[0]) if q else None, _ptr(out[1]) if q else None, C.byref(st)))
+        return (off, _take_array(recs, n.value, LCA_COUNT_DTYPE)) + tuple(out) + (_stats_dict(st),)
+
     def sketches_mask(self, queries, index, min_refs=0, max_refs=0):
         """the query sketches with only the hashes that between min_refs and max_refs references of the index hold (rk_sketches_mask):
         (sketches, stats) -- (0, 0) subtracts the index from the queries like the reference's `sub`, (1, MASK_MAX) intersects, (0, m)
@@ -1201,6 +1256,68 @@ def gather_lists(postings, counts, q_off, q_lists, n_ref, ref_sizes, query_sizes
         raise RkError(rc, "rk_gather_lists: min_new == 0, offsets that do not ascend from 0, a list index beyond the lists or out of order, "
                           "or a posting beyond the number of references")
     return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + out
+
+
+def lca_lists(postings, counts, q_off, q_lists, taxa, parent, row_first=0, row_step=1, row_block=0):
+    """the rule of Context.lca_rows over exported posting lists (rk_lca_lists, host only): (off, counts, matched, unlabelled, stats) --
+    the lists back to back in `postings` with their lengths in `counts` (Index.export_lists / export64), reference ids in any order
+    within a list; q_lists[q_off[i]:q_off[i + 1]] = the indices of the lists query i's elements hit, ascending, one per matched
+    element; taxa one node or LCA_NONE per reference"""
+    postings = np.ascontiguousarray(postings, dtype=np.uint32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if int(counts.sum(dtype=np.uint64)) != len(postings):
+        raise ValueError("lca_lists: the counts do not add up to the postings")
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    q_lists = np.ascontiguousarray(q_lists, dtype=np.uint64)
+    taxa = np.ascontiguousarray(taxa, dtype=np.uint32)
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    if len(q_off) < 1 or int(q_off[-1]) != len(q_lists):
+        raise ValueError("lca_lists needs q_off of one entry more than the queries, ending at len(q_lists)")
+    q = len(q_off) - 1
+    o = LcaOpts(int(row_first), int(row_step), int(row_block))
+    off = np.zeros(q + 1, dtype=np.uint64)
+    out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(2))
+    recs, n = C.c_void_p(), C.c_uint64()
+    st = LcaStats()
+    L = lib()
+    L.rk_lca_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                               C.POINTER(LcaOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(LcaStats)]
+    rc = L.rk_lca_lists(_ptr(postings) if len(postings) else None, _ptr(counts) if len(counts) else None, C.c_uint64(len(counts)), _ptr(q_off),
+                        _ptr(q_lists) if len(q_lists) else None, C.c_uint32(q), C.c_uint32(len(taxa)), _ptr(taxa) if len(taxa) else None,
+                        _ptr(parent) if len(parent) else None, C.c_uint32(len(parent)), C.byref(o), _ptr(off), C.byref(recs), C.byref(n),
+                        _ptr(out[0]) if q else None, _ptr(out[1]) if q else None, C.byref(st))
+    if rc:
+        raise RkError(rc, "rk_lca_lists: a taxonomy without exactly one root, with a parent beyond the nodes or a cycle, a taxon that is no node, "
+                          "offsets that do not ascend from 0, a list index beyond the lists or out of order, or a posting beyond the references")
+    return (off, _take_array(recs, n.value, LCA_COUNT_DTYPE)) + out + (_stats_dict(st),)
+
+
+def lca_call(counts, off, parent, rule=(1, 0, 1, 0), query_sizes=None, clades=False):
+    """the call on the tallies of Context.lca_rows / lca_lists (rk_lca_call, host only): called (LCA_CALLED_DTYPE, one record per query),
+    or (called, clade) with clades=True -- clade (uint32) the retained elements under the taxon of every record, parallel to counts.
+    rule = (min_count, conf_num, conf_den, denom): (m, 1, 1, 0) is the LCA of every taxon with at least m elements, (1, 0, 1, 0) the
+    root-to-leaf maximum; denom 1 measures the confidence against query_sizes"""
+    counts = np.ascontiguousarray(counts, dtype=LCA_COUNT_DTYPE)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    if len(off) < 1 or int(off[-1]) != len(counts):
+        raise ValueError("lca_call needs off of one entry more than the queries, ending at len(counts)")
+    q = len(off) - 1
+    if query_sizes is not None:
+        query_sizes = np.ascontiguousarray(query_sizes, dtype=np.uint32)
+        if len(query_sizes) != q:
+            raise ValueError("lca_call needs one size per query")
+    r = rule if isinstance(rule, LcaRule) else LcaRule(*[int(x) for x in rule])
+    called = np.zeros(q, dtype=LCA_CALLED_DTYPE)
+    clade = np.zeros(len(counts), dtype=np.uint32) if clades else None
+    L = lib()
+    L.rk_lca_call.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(LcaRule), C.c_void_p, C.c_void_p]
+    rc = L.rk_lca_call(_ptr(counts) if len(counts) else None, _ptr(off), C.c_uint32(q), _ptr(query_sizes) if query_sizes is not None and q else None,
+                       _ptr(parent) if len(parent) else None, C.c_uint32(len(parent)), C.byref(r), _ptr(called) if q else None,
+                       _ptr(clade) if clades else None)
+    if rc:
+        raise RkError(rc, "rk_lca_call: a bad rule or taxonomy, a record's taxon beyond the nodes or twice in a query, or offsets that do not ascend from 0")
+    return (called, clade) if clades else called
 
 
 def mask_lists(q_hashes, q_off, list_hashes, counts, min_refs=0, max_refs=0):

@@ -1904,6 +1904,193 @@ static int cmd_gather(const Args &a)
     SelfJoin::leave();
 }
 
+// --taxonomy FILE of lca: one line per node, id<TAB>parent id[<TAB>name]; ids are arbitrary non-negative integers (NCBI taxids work),
+// the root names itself.  The nodes become dense numbers by ascending id: id[] ascending, parent[] in node numbers, name[] ("" without).
+struct Taxonomy {
+    vector<unsigned long long> id;
+    vector<uint32_t> parent;
+    vector<string> name;
+    // the node number of an id, or -1
+    long long node_of(unsigned long long x) const
+    {
+        const auto it = std::lower_bound(id.begin(), id.end(), x);
+        return it != id.end() && *it == x ? (long long)(it - id.begin()) : -1;
+    }
+};
+
+static bool parse_id(const string &s, unsigned long long &out)
+{
+    // digits only (strtoull would take white space and a sign), and no more than 64 bits hold
+    if (s.empty() || s.size() > 20 || s.find_first_not_of("0123456789") != string::npos) return false;
+    errno = 0;
+    out = strtoull(s.c_str(), nullptr, 10);
+    return errno == 0;
+}
+
+static void read_taxonomy(const string &path, Taxonomy &t)
+{
+    std::ifstream in(path);
+    if (!in) die("cannot read %s", path.c_str());
+    struct Row { unsigned long long id, parent; string name; };
+    vector<Row> rows;
+    string line;
+    size_t n = 0;
+    while (std::getline(in, line)) {
+        n++;
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        const size_t t1 = line.find('\t'), t2 = t1 == string::npos ? string::npos : line.find('\t', t1 + 1);
+        Row r;
+        if (t1 == string::npos || !parse_id(line.substr(0, t1), r.id) || !parse_id(line.substr(t1 + 1, t2 == string::npos ? string::npos : t2 - t1 - 1), r.parent))
+            die("command_lca(), line %zu of %s is not id<TAB>parent id[<TAB>name] with non-negative integers", n, path.c_str());
+        if (t2 != string::npos) r.name = line.substr(t2 + 1);
+        rows.push_back(r);
+    }
+    if (rows.empty()) die("command_lca(), %s holds no node", path.c_str());
+    if (rows.size() >= 0x80000000ULL) die("command_lca(), %s holds 2^31 nodes or more", path.c_str());
+    std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.id < b.id; });
+    for (size_t k = 1; k < rows.size(); k++)
+        if (rows[k].id == rows[k - 1].id) die("command_lca(), %s names the node %llu twice", path.c_str(), rows[k].id);
+    for (const Row &r : rows) {
+        t.id.push_back(r.id);
+        t.name.push_back(r.name);
+    }
+    size_t roots = 0;
+    for (const Row &r : rows) {
+        const long long p = t.node_of(r.parent);
+        if (p < 0) die("command_lca(), the parent %llu of node %llu is no node of %s", r.parent, r.id, path.c_str());
+        t.parent.push_back((uint32_t)p);
+        roots += r.parent == r.id;
+    }
+    if (roots != 1) die("command_lca(), %s holds %zu roots (a node that names itself as its parent): exactly one is needed", path.c_str(), roots);
+}
+
+// --taxa FILE of lca: one line per reference in input order, an id of the taxonomy or - for an unlabelled reference
+static void read_taxa(const string &path, size_t N, const Taxonomy &t, vector<uint32_t> &taxa)
+{
+    std::ifstream in(path);
+    if (!in) die("cannot read %s", path.c_str());
+    string line;
+    size_t seen = 0;
+    while (std::getline(in, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty() && in.peek() == EOF) break;
+        if (seen >= N) die("command_lca(), %s holds more than the %zu lines of the input", path.c_str(), N);
+        if (line != "-") {
+            unsigned long long v = 0;
+            const long long node = parse_id(line, v) ? t.node_of(v) : -1;
+            if (node < 0) die("command_lca(), line %zu of %s is neither an id of the taxonomy nor -", seen + 1, path.c_str());
+            taxa[seen] = (uint32_t)node;
+        }
+        seen++;
+    }
+    if (seen != N) die("command_lca(), %s holds %zu lines, the input %zu genomes", path.c_str(), seen, N);
+}
+
+// lca: every query classified by the per-hash lowest common ancestor in a taxonomy over the references (rk_lca_rows, rk_lca_call).
+// One line per query: name, called id or -, its name, candidate id, clade, retained, matched, unlabelled, sketch size.
+// --summary: one line per record of a query's tally: query, id, name, direct, clade.
+static int cmd_lca(const Args &a)
+{
+    if (!a.has("r") || !a.has("q") || !a.has("o") || !a.has("taxonomy") || !a.has("taxa")) die("lca needs -r, -q, --taxonomy, --taxa and -o");
+    if (a.num("gpus", 1) != 1) die("command_lca(), lca runs on one GPU (--gpus 1)");
+    rk_lca_rule rule{1, 0, 1, 0};
+    if (a.has("min-count")) {
+        unsigned long long v = 0;
+        if (!parse_id(a.str("min-count", ""), v) || v < 1 || v > 0xFFFFFFFFULL) die("command_lca(), --min-count needs an integer from 1 to 4294967295");
+        rule.min_count = (uint32_t)v;
+    }
+    if (a.has("confidence")) {
+        const string c = a.str("confidence", "");
+        const size_t slash = c.find('/');
+        unsigned long long p = 0, q = 0;
+        if (slash == string::npos || !parse_id(c.substr(0, slash), p) || !parse_id(c.substr(slash + 1), q) || !q || p > q || q > 0xFFFFFFFFULL)
+            die("command_lca(), --confidence needs P/Q with 0 <= P <= Q and Q >= 1");
+        rule.conf_num = (uint32_t)p;
+        rule.conf_den = (uint32_t)q;
+    }
+    const string of = a.str("of", "labelled");
+    if (of != "labelled" && of != "sketch") die("command_lca(), --of must be labelled or sketch");
+    rule.denom = of == "sketch";
+    Taxonomy tax;
+    read_taxonomy(a.str("taxonomy", ""), tax);
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), 1, false);
+    SketchSet ref, qry;
+    string ref_path, qry_path;
+    {   // .sketch inputs are read while the runtime starts
+        string err;
+        if (is_sketch_file(a.str("r", ""))) {
+            ref_path = a.str("r", "");
+            if (!read_sketches(ref_path, ref, err)) die("readSketches(), %s", err.c_str());
+        }
+        if (is_sketch_file(a.str("q", ""))) {
+            qry_path = a.str("q", "");
+            if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
+        }
+    }
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), a, threads, ref, ref_path);
+    cerr << "the ref_sketch size is: " << ref.size() << endl;
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), a, threads, qry, qry_path);
+    if (qry.info.id != ref.info.id)
+        die("command_lca(), the sketch infos between reference and query files are not match\n"
+            "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    const size_t N = ref.size(), Q = qry.size();
+    vector<uint32_t> taxa(N ? N : 1, RK_LCA_NONE);
+    read_taxa(a.str("taxa", ""), N, tax, taxa);
+    const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
+    vector<rk_index *> idx(1, nullptr);
+    build_everywhere(set, ref, ref_path, missing, idx);
+    stamp("index built");
+    if (getenv("RK_TIMING")) rk_ctx_set_timing(set[0].ctx, 1);
+    const rk_lca_opts o{0, 0, 0};
+    vector<uint64_t> off(Q + 1, 0);
+    vector<uint32_t> matched(Q ? Q : 1, 0), unlabelled(Q ? Q : 1, 0), sizes(Q ? Q : 1, 0);
+    for (size_t q = 0; q < Q; q++) sizes[q] = (uint32_t)(qry.off[q + 1] - qry.off[q]);
+    rk_lca_count *counts = nullptr;
+    uint64_t n_counts = 0;
+    rk_lca_stats stats;
+    rk_sketches *qs = upload(set[0], qry);
+    set[0].check(rk_lca_rows(set[0].ctx, idx[0], qs, taxa.data(), tax.parent.data(), (uint32_t)tax.parent.size(), &o, off.data(), &counts, &n_counts, matched.data(),
+                             unlabelled.data(), &stats), "rk_lca_rows");
+    rk_sketches_free(qs);
+    stamp("queries classified");
+    vector<rk_lca_called> called(Q ? Q : 1);
+    vector<uint32_t> clade(n_counts ? n_counts : 1, 0);
+    if (rk_lca_call(counts, off.data(), (uint32_t)Q, sizes.data(), tax.parent.data(), (uint32_t)tax.parent.size(), &rule, called.data(), clade.data()) != 0)
+        die("rk_lca_call failed");
+    FILE *fp = fopen(a.str("o", "").c_str(), "w");
+    if (!fp) die("cannot write %s", a.str("o", "").c_str());
+    for (size_t q = 0; q < Q; q++) {
+        const rk_lca_called &c = called[q];
+        fprintf(fp, "%s\t", qry.names[q].c_str());
+        if (c.taxon == RK_LCA_NONE) fprintf(fp, "-\t-\t");
+        else fprintf(fp, "%llu\t%s\t", tax.id[c.taxon], tax.name[c.taxon].c_str());
+        if (c.candidate == RK_LCA_NONE) fprintf(fp, "-");
+        else fprintf(fp, "%llu", tax.id[c.candidate]);
+        fprintf(fp, "\t%u\t%u\t%u\t%u\t%u\n", c.clade, c.retained, matched[q], unlabelled[q], sizes[q]);
+    }
+    fclose(fp);
+    if (a.has("summary")) {
+        FILE *sp = fopen(a.str("summary", "").c_str(), "w");
+        if (!sp) die("cannot write %s", a.str("summary", "").c_str());
+        for (size_t q = 0; q < Q; q++)
+            for (uint64_t k = off[q]; k < off[q + 1]; k++)
+                fprintf(sp, "%s\t%llu\t%s\t%u\t%u\n", qry.names[q].c_str(), tax.id[counts[k].taxon], tax.name[counts[k].taxon].c_str(), counts[k].direct, clade[k]);
+        fclose(sp);
+    }
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %zu queries against %zu references under %zu nodes: %llu of %llu elements matched (%llu without a labelled holder), %llu records from "
+                        "%llu partial records of %llu tiles, %llu lists (%llu by lane, %llu by wave, %llu by workgroup), longest climb %u, attempts %u, path %u, "
+                        "%.3f ms on the device\n", Q, N, tax.parent.size(), (unsigned long long)stats.matched, (unsigned long long)stats.elements,
+                (unsigned long long)stats.unlabelled, (unsigned long long)stats.records, (unsigned long long)stats.partials, (unsigned long long)stats.tiles,
+                (unsigned long long)stats.lists, (unsigned long long)stats.lane_lists, (unsigned long long)stats.wave_lists, (unsigned long long)stats.block_lists,
+                stats.longest_climb, stats.attempts, stats.path, rk_ctx_last_ms(set[0].ctx, RK_MS_LCA));
+    rk_free_host(counts);
+    rk_index_free(idx[0]);
+    SelfJoin::leave();
+}
+
 // test helper: the text writer alone (no GPU): `_format alldist|dist names.txt hits.bin out pieces threads`;
 // hits.bin = rk_hit records sorted by (row, col), dealt to `pieces` parts in blocks of 32 rows like --gpus does
 static int cmd_format(int argc, char **argv)
@@ -2199,7 +2386,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert merge info mask\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert merge lca info mask\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2219,6 +2406,7 @@ static int usage()
             "  union   -i in.sketch -o out.sketch\n"
             "  sub     --rs ref.sketch --qs qry.sketch -o out.sketch\n"
             "  mask    -r ref.sketch|list -q qry.sketch|list [--keep absent|present | --min-refs A --max-refs B] -o out.sketch [--device N]   (the query sketches with only the hashes that at least A and at most B reference sketches hold, hashes ascending: --keep absent, the default, is A = B = 0 -- the sketches sub writes, computed on the device; --keep present is A = 1 without B -- the intersection; --max-refs B alone drops the hashes more than B references hold, --min-refs A alone keeps those at least A hold; one GPU)\n"
+            "  lca     -r ref.sketch|list -q qry.sketch|list --taxonomy FILE --taxa FILE [--min-count 1] [--confidence P/Q] [--of labelled|sketch] -o out [--summary FILE] [-L file.shuf] [--device N]   (every query classified by the lowest common ancestors of its hashes: a hash of the references carries the LCA of the taxa of the references that hold it, a query is the tally of those; --taxonomy: one line per node, id<TAB>parent id[<TAB>name], the root names itself; --taxa: one line per reference, an id of the taxonomy or -; the call is the LCA of the taxa with the highest root-to-node sum among those with at least --min-count hashes, moved towards the root until its clade holds P/Q of the hashes that carry a taxon, or with --of sketch of the whole sketch; one line per query: name, called id or -, its name, candidate id, clade, retained, matched, unlabelled, sketch size; --summary: per query and taxon its id, name, hashes and clade; one GPU)\n"
             "  convert -i kssd_dir -o out[.sketch] [-q]   |   convert --reverse -i in.sketch -o kssd_dir\n";
     return 1;
 }
@@ -2237,7 +2425,8 @@ int main(int argc, char **argv)
         {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"},
         {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"},
         {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--summary", "summary"}, {"--sub", "sub"},
-        {"--keep", "keep"}, {"--min-refs", "min-refs"}, {"--max-refs", "max-refs"}};
+        {"--keep", "keep"}, {"--min-refs", "min-refs"}, {"--max-refs", "max-refs"},
+        {"--taxonomy", "taxonomy"}, {"--taxa", "taxa"}, {"--confidence", "confidence"}, {"--of", "of"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
     if (sub == "_layout") {  // test helper: the on-disk structs of this tool, in the format of `ref_driver layout`
@@ -2255,7 +2444,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather" || sub == "mask") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather" || sub == "mask" || sub == "lca") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2284,6 +2473,7 @@ int main(int argc, char **argv)
     if (sub == "group") { cerr << "-----run the subcommand: group" << endl; return leave(cmd_group(parse_args(argc, argv, 2, alias, {"pan", "core", "only"}))); }   // (--core is a flag here, a file of mreach)
     if (sub == "gather") { cerr << "-----run the subcommand: gather" << endl; return leave(cmd_gather(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "mask") { cerr << "-----run the subcommand: mask" << endl; return leave(cmd_mask(parse_args(argc, argv, 2, alias, {}))); }
+    if (sub == "lca") { cerr << "-----run the subcommand: lca" << endl; return leave(cmd_lca(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
