@@ -1249,6 +1249,85 @@ int rk_lca_call(const rk_lca_count *counts, const uint64_t *off /* n_query + 1 *
                 const uint32_t *parent /* n_taxa */, uint32_t n_taxa, const rk_lca_rule *rule, rk_lca_called *called_out /* n_query */,
                 uint32_t *clade_out /* optional */);
 
+/* ---- winner-take-all containment screen ---------------------------------------------------- */
+/* rk_screen_rows: which references are contained in a query sketch, and how much of each survives once every shared hash is credited to
+ * one reference only -- the question of `mash screen -w`, answered in one pass, in integers only.  Sketches are taken as SETS: an index
+ * whose references repeat a hash and queries that repeat a hash are RK_ERR_UNSUPPORTED, as in rk_gather_rows.
+ * Per selected query row q (row_first / row_step / row_block as in rk_gather_opts) with hash set S: matched[q] = the hashes of S that
+ * have a posting list; common(r) = |S n R_r|; size(r) = |R_r|; the candidates = the references with common(r) >= min_common
+ * (min_common >= 1); n_cand[q] = their number.  The candidates of a row are totally ordered: a is BETTER than b when, tested in this order,
+ *   1. common(a) * size(b) > common(b) * size(a): the larger containment of the reference in the query, which is monotone in Mash's
+ *      screen identity -- compared on 64-bit products, exact because every size is below 2^30;
+ *   2. the products are equal and size(a) > size(b): Mash's tie rule, the larger reference;
+ *   3. the sizes are equal too and the CALLER's index of a is smaller than that of b.
+ * A matched hash is CLAIMED by the best candidate among its holders, by nobody when no holder is a candidate.  won(r) = the hashes r
+ * claims; claimed[q] = the sum of won <= matched[q].  One record {query, ref, common, won, size_ref, size_query} per candidate with
+ * won(r) >= min_won (0: every candidate), in (query, ascending CALLER's reference index) order: the records of query q are
+ * (*recs_out)[off_out[q] .. off_out[q + 1]).  off_out (host, Q + 1 entries, every one written; an unselected row is empty);
+ * *recs_out is the library's (rk_free_host; NULL when there is no record); matched_out / n_cand_out / claimed_out (host, Q entries
+ * each): only the entries of the selected rows are written.
+ * The result is unique: it does not depend on the internal genome order, on how the index came to be (built or imported), on batches,
+ * on row shards or on the leg that ran.  A row depends on its own hashes alone: row shards concatenate, no merge call is needed.
+ * With min_common = 1, claimed == matched.  The best candidate of a row has won == common.  A candidate whose hashes within S are a
+ * subset of a better candidate's has won == 0.  common equals the count of rk_dist_rows for the pair.  When all references have one size,
+ * the best candidate is the rank-0 pick of rk_gather_rows and its won that pick's fresh.
+ * On the device (rk_screen.hip), one stream, per batch of query rows whose state fits RK_SCREEN_BATCH_BYTES (default 1 GiB; at least one
+ * row; a row costs 8 N bytes: its counter row and its won row): the counter rows of the query join (stage A of rk_dist_topn), columns in
+ * the caller's order; the winner pass, flat over all query hashes of the batch in tiles of tile_hashes, never one workgroup per sketch:
+ * the look-up (the bucket of the prefix directory, a binary search), then the walk of the hash's posting list -- by the lane that found
+ * it up to lane_max postings, by its wave up to wave_max (64 postings per trip, a wave reduction of the best key), by the workgroup
+ * beyond (an LDS queue) -- comparing (common, size, caller's index) of every posting that is a candidate; the winner takes +1 on
+ * won[row][ref] (a relaxed agent-scope integer add; equal (row, winner) of a wave are combined first, RK_SCREEN_COMBINE=0: lane by
+ * lane).  Then a count kernel (candidates, records and the sum of won per row), a scan over the rows, ONE read-back for the room, and a
+ * write kernel, one workgroup per row taking the row in chunks with a block scan: the records come out in ascending caller's index
+ * without atomics and without a sort.  No kernel waits for another workgroup.  One copy carries 24 records + 12 Q + 8 (Q + 1) bytes;
+ * counter rows and postings never leave the device.
+ * RK_SCREEN_DEVICE=0 answers inside the call as export + rk_screen_lists, with the same result; stats->path says which leg ran.
+ * RK_ERR_ARG: null pointers, min_common == 0, an index without posting lists (the join-only index of rk_index_join_shard, one hash range
+ * of a sharded build), queries and index of different hash widths.  RK_ERR_UNSUPPORTED: sketches that repeat a hash, an index of
+ * 2^31 - 1 postings or more, a sketch of 2^30 hashes or more (the products).  Nothing is written on a refusal.  No query: RK_OK, nothing
+ * runs.  An index without genomes: RK_OK, every row empty. */
+#define RK_MS_SCREEN 17         /* rk_screen_rows: the counts of the first batch through the last write kernel; 0 on the host leg */
+typedef struct rk_screen_opts {
+    uint32_t min_common;     /* >= 1: a candidate shares at least this many hashes with the query */
+    uint32_t min_won;        /* a record is written for a candidate that claims at least this many hashes; 0: every candidate */
+    uint32_t row_first, row_step, row_block;   /* the row shard, as in rk_gather_opts (0 0 0: every query) */
+} rk_screen_opts;            /* 20 bytes */
+typedef struct rk_screen_rec {
+    uint32_t query, ref;     /* the query row and the CALLER's reference index */
+    uint32_t common;         /* |S n R_ref| */
+    uint32_t won;            /* the hashes of the query that ref claims */
+    uint32_t size_ref, size_query;
+} rk_screen_rec;             /* 24 bytes */
+typedef struct rk_screen_stats {
+    uint64_t records, candidates, matched, claimed;   /* sums over the selected rows */
+    uint64_t postings_walked;   /* postings of the matched lists of the selected rows */
+    uint64_t adds;              /* atomic adds on the won rows, after any combine (device leg) */
+    uint64_t lane_lists, wave_lists, block_lists;   /* matched lists by who walks them (the host leg: by the class of their length) */
+    uint64_t rows_per_batch;
+    uint32_t path;           /* 0 nothing ran, 1 the device, 2 the host (RK_SCREEN_DEVICE=0) */
+    uint32_t rows;           /* selected rows */
+    uint32_t batches;
+    uint32_t launches;       /* kernels of this unit the host launched */
+    uint32_t read_backs;     /* synchronising reads of the counters: one per batch */
+    uint32_t lane_max, wave_max, tile_hashes, threads;   /* the constants of the winner pass (every path fills them) */
+    uint32_t pad_;
+} rk_screen_stats;           /* 120 bytes */
+int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out /* host, Q + 1 */,
+                   rk_screen_rec **recs_out, uint64_t *n_recs, uint32_t *matched_out /* host, Q */, uint32_t *n_cand_out /* host, Q */,
+                   uint32_t *claimed_out /* host, Q */, rk_screen_stats *stats /* optional */);
+/* Host only, no context: the same rule over posting lists as rk_index_export_lists / rk_index_export64 return them (reference ids below
+ * n_ref in any order within a list, repeats counted once) -- blind to the hash width: per query i the indices of the lists its hashes
+ * hit, strictly ascending, are q_lists[q_off[i] .. q_off[i + 1]).  ref_sizes (n_ref) is part of the rule; query_sizes (n_query) only
+ * fills the records.  The outputs are those of rk_screen_rows.  RK_ERR_ARG: null pointers (postings / counts may be NULL without lists,
+ * q_lists when no query hits a list, the size arrays and the per-query outputs when their number is 0), min_common == 0, offsets that do
+ * not ascend from 0, a list index >= n_lists or out of order, a posting >= n_ref, a size of 2^30 or more, a reference of a selected row
+ * whose common exceeds its ref_sizes entry.  Nothing is written on a refusal. */
+int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off /* n_query + 1 */,
+                    const uint64_t *q_lists, uint32_t n_query, uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes,
+                    const rk_screen_opts *opts, uint64_t *off_out /* n_query + 1 */, rk_screen_rec **recs_out, uint64_t *n_recs,
+                    uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out);
+
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,
                   const rk_hit *hit);

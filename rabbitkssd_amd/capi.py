@@ -33,7 +33,7 @@ EXPORTS = [
     "rk_knn_rows", "rk_knn_hits", "rk_knn_merge", "rk_dbscan_rows", "rk_dbscan_hits", "rk_mreach_rows", "rk_mreach_hits", "rk_mreach_cut",
     "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
     "rk_group_sketches", "rk_group_lists", "rk_gather_rows", "rk_gather_lists", "rk_sketches_mask", "rk_mask_lists",
-    "rk_lca_rows", "rk_lca_lists", "rk_lca_call",
+    "rk_lca_rows", "rk_lca_lists", "rk_lca_call", "rk_screen_rows", "rk_screen_lists",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -59,6 +59,9 @@ LCA_NONE = 0xFFFFFFFF       # RK_LCA_NONE: the taxon of an unlabelled reference;
 # rk_lca_count: one record of a query's tally; rk_lca_called: the call on it
 LCA_COUNT_DTYPE = np.dtype([("taxon", "<u4"), ("direct", "<u4")])
 LCA_CALLED_DTYPE = np.dtype([("taxon", "<u4"), ("candidate", "<u4"), ("clade", "<u4"), ("score", "<u4"), ("retained", "<u4"), ("n_taxa", "<u4")])
+MS_SCREEN = 17              # RK_MS_SCREEN: the timed span of rk_screen_rows (Context.last_ms)
+# rk_screen_rec: one record per candidate of rk_screen_rows / rk_screen_lists that claims at least min_won hashes
+SCREEN_REC_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("common", "<u4"), ("won", "<u4"), ("size_ref", "<u4"), ("size_query", "<u4")])
 # rk_gather_pick: one record per pick of rk_gather_rows / rk_gather_lists
 GATHER_PICK_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("rank", "<u4"), ("common", "<u4"), ("fresh", "<u4"), ("left", "<u4"),
                               ("size_ref", "<u4"), ("size_query", "<u4")])
@@ -180,6 +183,19 @@ class GatherStats(C.Structure):
                 ("wave_lists", C.c_uint64), ("block_lists", C.c_uint64), ("rows_per_batch", C.c_uint64), ("path", C.c_uint32), ("rows", C.c_uint32),
                 ("batches", C.c_uint32), ("rounds", C.c_uint32), ("launched_rounds", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32),
                 ("compactions", C.c_uint32), ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("sync_every", C.c_uint32), ("threads", C.c_uint32)]
+
+
+class ScreenOpts(C.Structure):
+    """rk_screen_opts: a candidate shares at least min_common hashes, a record claims at least min_won (0: every candidate), the row shard"""
+    _fields_ = [("min_common", C.c_uint32), ("min_won", C.c_uint32), ("row_first", C.c_uint32), ("row_step", C.c_uint32), ("row_block", C.c_uint32)]
+
+
+class ScreenStats(C.Structure):
+    """rk_screen_stats: what one rk_screen_rows call did"""
+    _fields_ = [("records", C.c_uint64), ("candidates", C.c_uint64), ("matched", C.c_uint64), ("claimed", C.c_uint64), ("postings_walked", C.c_uint64),
+                ("adds", C.c_uint64), ("lane_lists", C.c_uint64), ("wave_lists", C.c_uint64), ("block_lists", C.c_uint64), ("rows_per_batch", C.c_uint64),
+                ("path", C.c_uint32), ("rows", C.c_uint32), ("batches", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32),
+                ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("tile_hashes", C.c_uint32), ("threads", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class MaskRule(C.Structure):
@@ -786,6 +802,31 @@ class Context:
                                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(st)))
         return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + tuple(out) + (_stats_dict(st),)
 
+    def screen_rows(self, index, queries, min_common=1, min_won=0, row_first=0, row_step=1, row_block=0, out=None):
+        """the references contained in each query sketch, every shared hash credited to one of them (rk_screen_rows): (off, recs,
+        matched, n_cand, claimed, stats) -- a hash goes to the best candidate among its holders: the larger common / size (exactly), then
+        the larger size, then the smaller index.  recs (SCREEN_REC_DTYPE) in (query, ref) order, those of query q at
+        recs[off[q]:off[q + 1]] (off: uint64, Q + 1), one per reference with common >= min_common and won >= min_won; matched / n_cand /
+        claimed (uint32, Q): the query's hashes that have a posting list, the candidates, the sum of won.  Only the entries of the
+        selected query rows are written: `out` (matched, n_cand, claimed as returned) lets row shards write into one set; their
+        records concatenate"""
+        q = queries.count if queries is not None else 0
+        if out is None:
+            out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(3))
+        elif len(out) != 3 or any(not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.shape == (q,) and a.flags.c_contiguous and a.flags.writeable)
+                                  for a in out):
+            raise ValueError("out needs (matched, n_cand, claimed): writable contiguous uint32 arrays of one entry per query")
+        o = ScreenOpts(int(min_common), int(min_won), int(row_first), int(row_step), int(row_block))
+        off = np.zeros(q + 1, dtype=np.uint64)
+        recs, n = C.c_void_p(), C.c_uint64()
+        st = ScreenStats()
+        L = lib()
+        L.rk_screen_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScreenOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScreenStats)]
+        self.check(L.rk_screen_rows(self._h, index._h, queries._h if queries is not None else None, C.byref(o), _ptr(off), C.byref(recs), C.byref(n),
+                                    _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(st)))
+        return (off, _take_array(recs, n.value, SCREEN_REC_DTYPE)) + tuple(out) + (_stats_dict(st),)
+
     def lca_rows(self, index, queries, taxa, parent, row_first=0, row_step=1, row_block=0, out=None):
         """the tally of per-hash lowest common ancestors of each query sketch (rk_lca_rows): (off, counts, matched, unlabelled, stats) --
         parent (uint32, one entry per node of the taxonomy, the root names itself), taxa (uint32, one node or LCA_NONE per reference in
@@ -1256,6 +1297,39 @@ def gather_lists(postings, counts, q_off, q_lists, n_ref, ref_sizes, query_sizes
         raise RkError(rc, "rk_gather_lists: min_new == 0, offsets that do not ascend from 0, a list index beyond the lists or out of order, "
                           "or a posting beyond the number of references")
     return (off, _take_array(picks, n.value, GATHER_PICK_DTYPE)) + out
+
+
+def screen_lists(postings, counts, q_off, q_lists, n_ref, ref_sizes, query_sizes, min_common=1, min_won=0, row_first=0, row_step=1, row_block=0):
+    """the rule of Context.screen_rows over exported posting lists (rk_screen_lists, host only): (off, recs, matched, n_cand, claimed) --
+    the lists back to back in `postings` with their lengths in `counts` (Index.export_lists / export64), reference ids in any order
+    within a list, repeats counted once; q_lists[q_off[i]:q_off[i + 1]] = the indices of the lists query i's hashes hit, ascending.
+    ref_sizes is part of the rule: a hash goes to the holder with the larger common / size"""
+    postings = np.ascontiguousarray(postings, dtype=np.uint32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if int(counts.sum(dtype=np.uint64)) != len(postings):
+        raise ValueError("screen_lists: the counts do not add up to the postings")
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    q_lists = np.ascontiguousarray(q_lists, dtype=np.uint64)
+    ref_sizes = np.ascontiguousarray(ref_sizes, dtype=np.uint32)
+    query_sizes = np.ascontiguousarray(query_sizes, dtype=np.uint32)
+    q = len(query_sizes)
+    if len(q_off) != q + 1 or len(ref_sizes) != int(n_ref) or (q and int(q_off[-1]) != len(q_lists)):
+        raise ValueError("screen_lists needs one size per reference and query and q_off of one entry more than the queries, ending at len(q_lists)")
+    o = ScreenOpts(int(min_common), int(min_won), int(row_first), int(row_step), int(row_block))
+    off = np.zeros(q + 1, dtype=np.uint64)
+    out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(3))
+    recs, n = C.c_void_p(), C.c_uint64()
+    L = lib()
+    L.rk_screen_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                  C.POINTER(ScreenOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.rk_screen_lists(_ptr(postings) if len(postings) else None, _ptr(counts) if len(counts) else None, C.c_uint64(len(counts)), _ptr(q_off),
+                           _ptr(q_lists) if len(q_lists) else None, C.c_uint32(q), C.c_uint32(n_ref), _ptr(ref_sizes) if n_ref else None,
+                           _ptr(query_sizes) if q else None, C.byref(o), _ptr(off), C.byref(recs), C.byref(n), _ptr(out[0]) if q else None,
+                           _ptr(out[1]) if q else None, _ptr(out[2]) if q else None)
+    if rc:
+        raise RkError(rc, "rk_screen_lists: min_common == 0, offsets that do not ascend from 0, a list index beyond the lists or out of order, "
+                          "a posting beyond the number of references, a size of 2^30 or more, or a reference that shares more hashes than its size")
+    return (off, _take_array(recs, n.value, SCREEN_REC_DTYPE)) + out
 
 
 def lca_lists(postings, counts, q_off, q_lists, taxa, parent, row_first=0, row_step=1, row_block=0):

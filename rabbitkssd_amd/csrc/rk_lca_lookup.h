@@ -1,6 +1,6 @@
 // rk_lca_lookup.h -- the posting list of a query hash: the bucket of the prefix directory, then a binary search among the distinct hashes
 // of the index, the kTrips searches of a lane advancing together (one probe of each per step: the loads of a step are in flight at once).
-// The look-up of k_mask_flag (rk_mask.hip), which keeps its own copy: this header is used by rk_lca.hip only.
+// The look-up of k_mask_flag (rk_mask.hip), which keeps its own copy: this header is used by rk_lca.hip and rk_screen.hip.
 #pragma once
 #include <cstdint>
 

@@ -1,0 +1,867 @@
+// rk_screen.hip -- which references are contained in a query sketch, and how much of each survives once every shared hash is credited to
+// one reference only (rk_screen_rows): the winner-take-all containment screen of `mash screen -w`, in integers only, and the same rule on
+// the host over exported lists (rk_screen_lists).  Sketches are SETS.  Per query with hash set S: matched = the hashes of S with a posting
+// list, common(r) = |S n R_r|, the candidates = the references with common >= min_common.  Candidate a is better than b when
+// common(a) size(b) > common(b) size(a) (64-bit products, exact: every size is below 2^30), or the products are equal and size(a) > size(b),
+// or the sizes are equal too and the CALLER's index of a is smaller.  A matched hash is claimed by the best candidate among its holders;
+// won(r) = the hashes r claims.  One record per candidate with won >= min_won, in (query, caller's index) order.  include/rabbitkssd.h,
+// winner-take-all containment screen.
+//
+// Per batch of query rows (as many counter rows and won rows as RK_SCREEN_BATCH_BYTES holds), all on ctx->stream:
+//   counts   rk_distq_counts (stage A of rk_dist_topn): int32 cnt[slot][N], columns in the caller's order; won[slot][N] starts at 0;
+//   winners  k_screen_win: flat over ALL query hashes of the batch in tiles of kTileHashes, whatever sketch they belong to.  Per hash its
+//            slot (a binary search among the batch's hash offsets: runs of empty sketches fall out), the look-up (rk_lca_lookup.h), then
+//            the walk of its posting list by its length: the lane that found it up to lane_max postings, its wave up to wave_max (64
+//            postings per trip, a wave reduction of the best key), the workgroup beyond (an LDS queue, partial keys per wave).  Per posting
+//            p: r = orig[p], c = cnt[slot][r]; below min_common it is skipped, else (c, size, r) is compared with the best so far.  The
+//            winner takes +1 on won[slot][r], a relaxed agent-scope add; equal (slot, winner) of a wave are combined first (up to
+//            kCombineRounds leaders by ballots, the rest lane by lane; RK_SCREEN_COMBINE=0: every add lane by lane);
+//   count    k_screen_count, one workgroup per row: n_cand = the cells with cnt >= min_common, the records = those with won >= min_won,
+//            claimed = the sum of won;
+//   scan     k_screen_scan over the rows' record counts; ONE read-back of the counters gives the room;
+//   write    k_screen_write, one workgroup per row, the row in chunks of the block size with a block scan: the records come out by
+//            ascending caller's index without atomics and without a sort;
+//   result   off[Q + 1] by k_screen_scan over all rows; ONE copy to the host: 8 (Q + 1) + 12 Q + 24 records bytes.
+//
+// Memory scope: every array is written by one kernel and read by a later one on the same stream.  INSIDE a launch the only communication
+// between workgroups is relaxed agent-scope atomic adds -- the +1 on the won rows, matched[] and the statistics, none of which is read
+// before the launch is over -- and LDS between barriers.  No loop waits for another workgroup: any grid works.  DESIGN.md 4.18.
+#include <algorithm>
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "rk_internal.h"
+#include "rk_lca_lookup.h"
+
+namespace {
+
+constexpr int kScreenThreads = 256;                 // threads of every workgroup of this unit: 4 waves
+constexpr int kWaves = kScreenThreads / 64;
+constexpr uint32_t kLaneMax = 16;                   // the longest list the lane that found it walks itself
+constexpr uint32_t kWaveMax = 1024;                 // the longest list its wave walks (64 postings per trip); beyond: the workgroup
+constexpr int kTrips = 4;                           // runs of 64 hashes one wave takes of a tile
+constexpr int kTileHashes = kScreenThreads * kTrips;   // 1024
+constexpr int kCombineRounds = 4;                   // leaders of a wave whose equal (slot, winner) are added once
+constexpr uint32_t kSizeLimit = 1u << 30;           // sizes at or above it are refused: common * size stays below 2^60
+static_assert(sizeof(rk_screen_opts) == 20 && sizeof(rk_screen_rec) == 24 && sizeof(rk_screen_stats) == 120, "the layouts of include/rabbitkssd.h");
+static_assert(kLaneMax < kWaveMax && kWaveMax % 64 == 0, "the classes of list lengths");
+
+struct Counters {   // one device block, read back in one copy
+    unsigned long long walked, adds, lane_lists, wave_lists, block_lists, rec_total, all_total;
+};
+
+// (common, size, caller's index) of a candidate; c == 0: none
+struct Key {
+    uint32_t c, sz, r;
+};
+
+// the order of the candidates of a row: include/rabbitkssd.h.  Both products lie below 2^60.
+__host__ __device__ __forceinline__ bool better(const Key &a, const Key &b)
+{
+    if (!a.c) return false;
+    if (!b.c) return true;
+    const unsigned long long ab = (unsigned long long)a.c * b.sz, ba = (unsigned long long)b.c * a.sz;
+    if (ab != ba) return ab > ba;
+    if (a.sz != b.sz) return a.sz > b.sz;
+    return a.r < b.r;
+}
+
+__device__ __forceinline__ unsigned long long add_u64(unsigned long long *p, unsigned long long v)
+{
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void add_u32(uint32_t *p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long lanes_below(int lane) { return lane ? (~0ULL >> (64 - lane)) : 0ULL; }
+// the best key of a wave, in every lane (the order is total: every lane ends with the same key)
+__device__ __forceinline__ Key wave_best(Key k)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Key x;
+        x.c = (uint32_t)__shfl_xor((int)k.c, o);
+        x.sz = (uint32_t)__shfl_xor((int)k.sz, o);
+        x.r = (uint32_t)__shfl_xor((int)k.r, o);
+        if (better(x, k)) k = x;
+    }
+    return k;
+}
+
+// sizes[caller's index] = the sketch size (orig == null: the identity)
+__global__ void k_screen_prepare(const uint32_t *orig, const uint32_t *sizes_internal, uint32_t n, uint32_t *sizes)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    sizes[orig ? orig[i] : i] = sizes_internal[i];   // (orig[] < n: rk_index_build's permutation, checked on every import of a blob)
+}
+
+// One workgroup: off[i] = the sum of val[row_of[j]] over j < i (row_of null: j itself), off[n] = the total
+__global__ void __launch_bounds__(kScreenThreads) k_screen_scan(const uint32_t *val, const uint32_t *row_of, uint32_t n, unsigned long long *off,
+                                                               unsigned long long *total_out)
+{
+    __shared__ unsigned long long s_wave[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned long long run = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += kScreenThreads) {   // (uniform)
+        const uint32_t i = c0 + tid;
+        const uint32_t v = i < n ? val[row_of ? row_of[i] : i] : 0u;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long x = shfl_u64(incl, (lane - o) & 63);
+            if (lane >= o) incl += x;
+        }
+        if (lane == 63) s_wave[w] = incl;
+        __syncthreads();
+        unsigned long long before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; k++) {
+            if (k < w) before += s_wave[k];
+            all += s_wave[k];
+        }
+        if (i < n) off[i] = run + before + incl - v;
+        run += all;
+        __syncthreads();   // (s_wave is rewritten by the next chunk)
+    }
+    if (tid == 0) {
+        off[n] = run;
+        if (total_out) *total_out = run;
+    }
+}
+
+struct WinArgs {
+    const void *q_hashes;              // Hash[total]
+    const uint64_t *q_off;             // u64[Q + 1]
+    const uint32_t *row_of;            // the batch: slot s is query row row_of[s]
+    const unsigned long long *hoff;    // nb + 1: the hashes of the slots before s, from hoff[0] (any base)
+    uint32_t nb;
+    unsigned long long n_hashes;       // hoff[nb] - hoff[0]
+    LcaLookup ix;
+    const uint32_t *postings, *upos, *orig, *sizes_internal;   // the index (orig null: the identity)
+    const int32_t *cnt;                // [nb][n_ref], columns in the caller's order
+    uint32_t *won;                     // [nb][n_ref]
+    uint32_t n_ref, min_common, lane_max, wave_max;
+    uint32_t *matched_q;               // per QUERY row
+    Counters *c;
+};
+
+struct Walk {   // what one walk reads
+    const uint32_t *postings, *orig, *sizes_internal;
+    const int32_t *cnt;
+    uint32_t min_common;
+    __device__ __forceinline__ void see(uint32_t at, Key *best) const
+    {
+        const uint32_t p = postings[at];
+        Key k;
+        k.r = orig ? orig[p] : p;           // (p < n_ref and orig[] < n_ref: the index's own arrays)
+        k.c = (uint32_t)cnt[k.r];
+        if (k.c < min_common) return;       // (min_common >= 1)
+        k.sz = sizes_internal[p];
+        if (better(k, *best)) *best = k;
+    }
+};
+
+template <class Hash, bool COMBINE> __global__ void __launch_bounds__(kScreenThreads) k_screen_win(WinArgs a)
+{
+    __shared__ uint32_t s_qn[kTrips], s_qbeg[kScreenThreads], s_qlen[kScreenThreads], s_qslot[kScreenThreads];
+    __shared__ Key s_part[kScreenThreads][kWaves];
+    const uint32_t tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    if (tid < (uint32_t)kTrips) s_qn[tid] = 0;   // one counter per trip: none is reset while another wave may still read it
+    const unsigned long long base = (unsigned long long)blockIdx.x * kTileHashes + (unsigned long long)wave * (kTrips * 64);
+    const Hash *q = (const Hash *)a.q_hashes;
+    const unsigned long long h0 = a.hoff[0];
+    // the slot of hash j of the batch: the last s with hoff[s] - h0 <= j (j < n_hashes: s < nb); the searches of a lane advance together
+    uint32_t slo[kTrips], shi[kTrips];
+    bool in[kTrips];
+#pragma unroll
+    for (int t = 0; t < kTrips; t++) {
+        in[t] = base + 64 * t + lane < a.n_hashes;
+        slo[t] = 0;
+        shi[t] = in[t] ? a.nb - 1 : 0u;
+    }
+    for (bool more = true; more;) {
+        more = false;
+#pragma unroll
+        for (int t = 0; t < kTrips; t++)
+            if (slo[t] < shi[t]) {
+                const uint32_t mid = slo[t] + (shi[t] - slo[t] + 1) / 2;   // (1 <= mid <= nb - 1)
+                if (a.hoff[mid] - h0 <= base + 64 * t + lane) slo[t] = mid; else shi[t] = mid - 1;
+                more |= slo[t] < shi[t];
+            }
+    }
+    unsigned long long h[kTrips];
+    uint32_t list[kTrips];
+#pragma unroll
+    for (int t = 0; t < kTrips; t++) {
+        h[t] = 0;
+        if (in[t]) {
+            const uint32_t row = a.row_of[slo[t]];
+            h[t] = (unsigned long long)q[a.q_off[row] + (base + 64 * t + lane - (a.hoff[slo[t]] - h0))];
+        }
+    }
+    lca_lookup<Hash, kTrips>(a.ix, h, in, list);
+    unsigned long long walked = 0, adds = 0, n_lane = 0, n_wave = 0, n_block = 0;
+    __syncthreads();   // (s_qn)
+#pragma unroll
+    for (int t = 0; t < kTrips; t++) {
+        const uint32_t slot = slo[t];
+        uint32_t beg = 0, len = 0;
+        if (list[t] != kNoList) {
+            beg = a.upos[list[t]];
+            len = a.upos[list[t] + 1] - beg;
+        }
+        const bool found = len > 0;
+        // matched: the equal slots of a run of 64 hashes are counted by ballots (neighbours share their row), one add per slot and wave
+        {
+            unsigned long long pending = __ballot(found);
+            while (pending) {   // (uniform)
+                const int lead = __ffsll((long long)pending) - 1;
+                const uint32_t sl = (uint32_t)__shfl((int)slot, lead);
+                const unsigned long long m = __ballot(found && slot == sl);
+                if (lane == lead) add_u32(a.matched_q + a.row_of[sl], (uint32_t)__popcll(m));
+                pending &= ~m;
+            }
+        }
+        const bool by_lane = found && len <= a.lane_max, by_wave = found && !by_lane && len <= a.wave_max, by_block = found && !by_lane && !by_wave;
+        Walk wk{a.postings, a.orig, a.sizes_internal, a.cnt + (size_t)slot * a.n_ref, a.min_common};
+        Key win{0, 0, 0};
+        if (by_lane)
+            for (uint32_t j = 0; j < len; j++) wk.see(beg + j, &win);
+        unsigned long long pending = __ballot(by_wave);
+        while (pending) {   // (uniform in the wave)
+            const int src = __ffsll((long long)pending) - 1;
+            pending &= pending - 1;
+            const uint32_t b = (uint32_t)__shfl((int)beg, src), l = (uint32_t)__shfl((int)len, src), sl = (uint32_t)__shfl((int)slot, src);
+            Walk ww{a.postings, a.orig, a.sizes_internal, a.cnt + (size_t)sl * a.n_ref, a.min_common};
+            Key mine{0, 0, 0};
+            for (uint32_t j = lane; j < l; j += 64) ww.see(b + j, &mine);
+            mine = wave_best(mine);
+            if (lane == src) win = mine;
+        }
+        uint32_t at = 0;
+        if (by_block) {
+            at = atomicAdd(&s_qn[t], 1u);   // (at most one per thread and trip: at < kScreenThreads)
+            s_qbeg[at] = beg;
+            s_qlen[at] = len;
+            s_qslot[at] = slot;
+        }
+        __syncthreads();
+        const uint32_t qn = s_qn[t];
+        if (qn) {   // (uniform in the workgroup)
+            for (uint32_t k = 0; k < qn; k++) {
+                Walk wb{a.postings, a.orig, a.sizes_internal, a.cnt + (size_t)s_qslot[k] * a.n_ref, a.min_common};
+                const uint32_t b = s_qbeg[k], l = s_qlen[k];
+                Key mine{0, 0, 0};
+                for (uint32_t j = tid; j < l; j += kScreenThreads) wb.see(b + j, &mine);
+                mine = wave_best(mine);
+                if (lane == 0) s_part[k][wave] = mine;
+            }
+            __syncthreads();
+            if (by_block) {
+                win = s_part[at][0];
+#pragma unroll
+                for (int w = 1; w < kWaves; w++)
+                    if (better(s_part[at][w], win)) win = s_part[at][w];
+            }
+            __syncthreads();   // (the queue and the partial keys are free for the next trip)
+        }
+        // the winners' +1: won[slot][r]
+        bool has = win.c != 0;
+        const unsigned long long key = ((unsigned long long)slot << 32) | win.r;
+        if (COMBINE) {
+            unsigned long long todo = __ballot(has);
+            for (int round = 0; round < kCombineRounds && todo; round++) {   // (uniform)
+                const int lead = __ffsll((long long)todo) - 1;
+                const unsigned long long kl = shfl_u64(key, lead);
+                const bool same = has && key == kl;
+                const unsigned long long m = __ballot(same);
+                if (lane == lead) {
+                    add_u32(a.won + (size_t)slot * a.n_ref + win.r, (uint32_t)__popcll(m));
+                    adds++;
+                }
+                if (same) has = false;
+                todo &= ~m;
+            }
+        }
+        if (has) {
+            add_u32(a.won + (size_t)slot * a.n_ref + win.r, 1u);
+            adds++;
+        }
+        walked += len;
+        n_lane += by_lane;
+        n_wave += by_wave;
+        n_block += by_block;
+    }
+    // the statistics: one atomic per wave and counter that moved
+    walked = wave_sum(walked);
+    adds = wave_sum(adds);
+    n_lane = wave_sum(n_lane);
+    n_wave = wave_sum(n_wave);
+    n_block = wave_sum(n_block);
+    if (lane == 0) {
+        if (walked) add_u64(&a.c->walked, walked);
+        if (adds) add_u64(&a.c->adds, adds);
+        if (n_lane) add_u64(&a.c->lane_lists, n_lane);
+        if (n_wave) add_u64(&a.c->wave_lists, n_wave);
+        if (n_block) add_u64(&a.c->block_lists, n_block);
+    }
+}
+
+struct RowArgs {   // a batch of nb rows: slot s of the batch is query row row_of[s], its rows cnt + s * n_ref and won + s * n_ref
+    const int32_t *cnt;
+    const uint32_t *won;
+    const uint32_t *row_of;
+    uint32_t n_ref, min_common, min_won;
+    uint32_t *n_cand_q, *claimed_q, *nrec_q;   // per QUERY row
+    const unsigned long long *rec_off;         // per slot: nb + 1
+    rk_screen_rec *recs;
+    const uint32_t *sizes;                     // per caller's reference index
+    const uint64_t *q_off;
+};
+
+// One workgroup per row: the candidates, the records and the sum of won
+__global__ void __launch_bounds__(kScreenThreads) k_screen_count(RowArgs a)
+{
+    __shared__ uint32_t s_cand, s_rec, s_claimed;
+    const uint32_t s = blockIdx.x, tid = threadIdx.x;
+    const int32_t *cnt = a.cnt + (size_t)s * a.n_ref;
+    const uint32_t *won = a.won + (size_t)s * a.n_ref;
+    if (tid == 0) s_cand = s_rec = s_claimed = 0;
+    __syncthreads();
+    uint32_t n_cand = 0, n_rec = 0, claimed = 0;
+    for (uint32_t c = tid; c < a.n_ref; c += kScreenThreads) {
+        const bool cand = (uint32_t)cnt[c] >= a.min_common;
+        const uint32_t w = won[c];   // (only a candidate wins)
+        n_cand += cand;
+        n_rec += cand && w >= a.min_won;
+        claimed += w;
+    }
+    if (n_cand) atomicAdd(&s_cand, n_cand);
+    if (n_rec) atomicAdd(&s_rec, n_rec);
+    if (claimed) atomicAdd(&s_claimed, claimed);
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t row = a.row_of[s];
+        a.n_cand_q[row] = s_cand;
+        a.nrec_q[row] = s_rec;
+        a.claimed_q[row] = s_claimed;
+    }
+}
+
+// One workgroup per row, the row in chunks of the block size: the records at rec_off[s] + the records of the cells before, in the
+// order of the cells
+__global__ void __launch_bounds__(kScreenThreads) k_screen_write(RowArgs a)
+{
+    __shared__ uint32_t s_cnt[kWaves];
+    const uint32_t s = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6;
+    const int32_t *cnt = a.cnt + (size_t)s * a.n_ref;
+    const uint32_t *won = a.won + (size_t)s * a.n_ref;
+    const unsigned long long beg = a.rec_off[s], room = a.rec_off[s + 1] - beg;
+    if (!room) return;   // (uniform)
+    const uint32_t row = a.row_of[s], size_query = (uint32_t)(a.q_off[row + 1] - a.q_off[row]);
+    unsigned long long run = 0;
+    for (uint32_t c0 = 0; c0 < a.n_ref; c0 += kScreenThreads) {   // (uniform)
+        const uint32_t c = c0 + tid;
+        uint32_t common = 0, wn = 0;
+        bool keep = false;
+        if (c < a.n_ref) {
+            common = (uint32_t)cnt[c];
+            wn = won[c];
+            keep = common >= a.min_common && wn >= a.min_won;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) s_cnt[w] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; k++) {
+            if (k < w) before += s_cnt[k];
+            all += s_cnt[k];
+        }
+        const unsigned long long at = run + before + (uint32_t)__popcll(m & lanes_below(lane));
+        if (keep && at < room) a.recs[beg + at] = rk_screen_rec{row, c, common, wn, a.sizes[c], size_query};
+        run += all;
+        __syncthreads();   // (s_cnt is rewritten by the next chunk)
+    }
+}
+
+// ---- host: the rule, exactly ------------------------------------------------------------------------------------------------
+struct RowSel {   // the selected rows of Q, ascending (block-cyclic, as rk_gather_rows deals them)
+    std::vector<uint32_t> rows;
+    RowSel(const rk_screen_opts *o, uint32_t Q)
+    {
+        const uint64_t rb = o->row_block ? o->row_block : 1, rs = o->row_step ? o->row_step : 1;
+        for (uint64_t blk = o->row_first; blk * rb < Q; blk += rs)
+            for (uint64_t r = blk * rb; r < std::min<uint64_t>(Q, (blk + 1) * rb); r++) rows.push_back((uint32_t)r);
+    }
+};
+
+struct HostResult {
+    std::vector<rk_screen_rec> recs;
+    std::vector<uint64_t> off;                          // Q + 1
+    std::vector<uint32_t> matched, n_cand, claimed;     // per selected row, in the order of RowSel
+    uint64_t walked = 0, lane_lists = 0, wave_lists = 0, block_lists = 0;
+};
+
+// lists: list u is post[pos[u] .. pos[u + 1]), strictly ascending reference ids below n_ref.  The winner of a list is found by scanning
+// its candidates with the comparator -- no ranking of the row, unlike tests/_screen_ref.py's second statement.
+// RK_ERR_ARG (strict only): a reference of a selected row shares more hashes than its size.
+int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off, const uint64_t *q_lists, uint32_t Q, uint32_t n_ref, const uint32_t *ref_sizes,
+                const uint32_t *query_sizes, const rk_screen_opts *o, const RowSel &sel, bool strict, HostResult *out)
+{
+    std::vector<uint32_t> common(n_ref, 0), won(n_ref, 0), touched, n_rec(Q, 0);
+    for (const uint32_t q : sel.rows) {
+        const uint64_t *lists = q_lists + q_off[q];
+        const uint64_t nl = q_off[q + 1] - q_off[q];
+        touched.clear();
+        uint32_t matched = 0;
+        for (uint64_t k = 0; k < nl; k++) {
+            const uint64_t u = lists[k], len = pos[u + 1] - pos[u];
+            matched += len > 0;   // (an empty list matches nothing)
+            for (uint64_t i = pos[u]; i < pos[u + 1]; i++)
+                if (!common[post[i]]++) touched.push_back(post[i]);
+            out->walked += len;
+            if (len && len <= kLaneMax) out->lane_lists++;
+            else if (len && len <= kWaveMax) out->wave_lists++;
+            else if (len) out->block_lists++;
+        }
+        bool bad = false;
+        for (const uint32_t r : touched) bad = bad || (strict && common[r] > ref_sizes[r]);
+        if (bad) return RK_ERR_ARG;
+        uint32_t claimed = 0;
+        for (uint64_t k = 0; k < nl; k++) {
+            Key best{0, 0, 0};
+            for (uint64_t i = pos[lists[k]]; i < pos[lists[k] + 1]; i++) {
+                const uint32_t r = post[i];
+                const Key key{common[r], ref_sizes[r], r};
+                if (key.c >= o->min_common && better(key, best)) best = key;
+            }
+            if (best.c) {
+                won[best.r]++;
+                claimed++;
+            }
+        }
+        std::sort(touched.begin(), touched.end());
+        uint32_t n_cand = 0;
+        for (const uint32_t r : touched) {
+            if (common[r] >= o->min_common) {
+                n_cand++;
+                if (won[r] >= o->min_won) {
+                    out->recs.push_back(rk_screen_rec{q, r, common[r], won[r], ref_sizes[r], query_sizes[q]});
+                    n_rec[q]++;
+                }
+            }
+            common[r] = won[r] = 0;
+        }
+        out->matched.push_back(matched);
+        out->n_cand.push_back(n_cand);
+        out->claimed.push_back(claimed);
+    }
+    out->off.assign((size_t)Q + 1, 0);
+    for (uint32_t q = 0; q < Q; q++) out->off[q + 1] = out->off[q] + n_rec[q];
+    return RK_OK;
+}
+
+// lists as exported: their offsets, and a sorted copy without repeats where a list does not ascend strictly.  RK_ERR_ARG for a posting >= n_ref.
+int prepare_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, uint32_t n_ref, std::vector<uint64_t> *pos, std::vector<uint32_t> *fixed,
+                  const uint32_t **post)
+{
+    pos->assign((size_t)n_lists + 1, 0);
+    bool ascending = true;
+    for (uint64_t u = 0; u < n_lists; u++) (*pos)[u + 1] = (*pos)[u] + counts[u];
+    for (uint64_t u = 0; u < n_lists; u++)
+        for (uint64_t i = (*pos)[u]; i < (*pos)[u + 1]; i++) {
+            if (postings[i] >= n_ref) return RK_ERR_ARG;
+            if (i > (*pos)[u] && postings[i - 1] >= postings[i]) ascending = false;
+        }
+    *post = postings;
+    if (ascending) return RK_OK;
+    std::vector<uint64_t> npos((size_t)n_lists + 1, 0);
+    fixed->clear();
+    std::vector<uint32_t> list;
+    for (uint64_t u = 0; u < n_lists; u++) {
+        list.assign(postings + (*pos)[u], postings + (*pos)[u + 1]);
+        std::sort(list.begin(), list.end());
+        list.erase(std::unique(list.begin(), list.end()), list.end());
+        fixed->insert(fixed->end(), list.begin(), list.end());
+        npos[u + 1] = fixed->size();
+    }
+    pos->swap(npos);
+    *post = fixed->data();
+    return RK_OK;
+}
+
+// the outputs of both entry points from a host result; RK_ERR_NOMEM leaves them untouched
+int hand_out(const HostResult &r, const RowSel &sel, uint32_t Q, uint64_t *off_out, rk_screen_rec **recs_out, uint64_t *n_recs, uint32_t *matched_out,
+             uint32_t *n_cand_out, uint32_t *claimed_out)
+{
+    rk_screen_rec *p = nullptr;
+    if (!r.recs.empty()) {
+        p = (rk_screen_rec *)malloc(r.recs.size() * sizeof(rk_screen_rec));
+        if (!p) return RK_ERR_NOMEM;
+        memcpy(p, r.recs.data(), r.recs.size() * sizeof(rk_screen_rec));
+    }
+    memcpy(off_out, r.off.data(), ((size_t)Q + 1) * 8);
+    for (size_t k = 0; k < sel.rows.size(); k++) {
+        matched_out[sel.rows[k]] = r.matched[k];
+        n_cand_out[sel.rows[k]] = r.n_cand[k];
+        claimed_out[sel.rows[k]] = r.claimed[k];
+    }
+    *recs_out = p;
+    *n_recs = r.recs.size();
+    return RK_OK;
+}
+
+void fill_constants(rk_screen_stats *st)
+{
+    st->lane_max = kLaneMax;
+    st->wave_max = kWaveMax;
+    st->tile_hashes = kTileHashes;
+    st->threads = kScreenThreads;
+}
+
+unsigned long long env_number(const char *name, unsigned long long otherwise)
+{
+    const char *sw = getenv(name);
+    const unsigned long long v = sw ? strtoull(sw, nullptr, 10) : 0;
+    return v ? v : otherwise;
+}
+
+// RK_SCREEN_DEVICE=0: export + the lists of the selected queries' hashes (a binary search each) + the rule on the host
+template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_screen_opts *o, const RowSel &sel, HostResult *out)
+{
+    const uint32_t N = idx->n_ref, Q = qs->n;
+    std::vector<uint32_t> postings(idx->H), counts(idx->U), ref_sizes(N), query_sizes(Q);
+    std::vector<Hash> hashes(idx->U), qh(qs->total);
+    std::vector<uint64_t> qoff((size_t)Q + 1);
+    if constexpr (sizeof(Hash) == 8) {
+        RK_TRY(rk_index_export64(idx, postings.data(), hashes.data(), counts.data()));
+        RK_TRY(rk_sketches_download64(qs, qh.data(), qoff.data()));
+    } else {
+        RK_TRY(rk_index_export_lists(idx, postings.data(), hashes.data(), counts.data()));
+        RK_TRY(rk_sketches_download(qs, qh.data(), qoff.data()));
+    }
+    {   // the sizes the index carries (an import: the caller's), in the caller's order
+        std::vector<uint32_t> sizes(N), orig(N);
+        RK_TRY(rk_index_order(idx, orig.data()));
+        RK_HIP(ctx, hipMemcpyAsync(sizes.data(), idx->d_sizes, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t i = 0; i < N; i++) ref_sizes[orig[i] < N ? orig[i] : i] = sizes[i];
+    }
+    std::vector<uint64_t> l_off((size_t)Q + 1, 0), l;
+    size_t next = 0;
+    for (uint32_t q = 0; q < Q; q++) {
+        query_sizes[q] = (uint32_t)(qoff[q + 1] - qoff[q]);
+        if (next < sel.rows.size() && sel.rows[next] == q) {
+            next++;
+            for (uint64_t j = qoff[q]; j < qoff[q + 1]; j++) {
+                const auto it = std::lower_bound(hashes.begin(), hashes.end(), qh[j]);
+                if (it != hashes.end() && *it == qh[j]) l.push_back((uint64_t)(it - hashes.begin()));
+            }
+        }
+        l_off[q + 1] = l.size();
+    }
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> fixed;
+    const uint32_t *post = nullptr;
+    if (prepare_lists(postings.data(), counts.data(), idx->U, N, &pos, &fixed, &post))
+        return rk_fail(ctx, RK_ERR_HIP, "rk_screen_rows: an exported posting names a genome beyond their number (internal error)");
+    return screen_core(post, pos.data(), l_off.data(), l.data(), Q, N, ref_sizes.data(), query_sizes.data(), o, sel, false, out);
+}
+
+struct DeviceResult {
+    std::vector<unsigned char> block;   // off u64[Q + 1] | matched, n_cand, claimed u32[Q] each (+ 4 bytes when Q is odd) | the records
+    uint64_t n_recs = 0;
+};
+
+int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_screen_opts *o, const RowSel &sel, rk_screen_stats *st, DeviceResult *res)
+{
+    const uint32_t N = idx->n_ref, Q = qs->n;
+    const uint64_t n_sel = sel.rows.size();
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const TimedSpan span{ctx, RK_MS_SCREEN};
+    const bool combine = !rk_switched_off("RK_SCREEN_COMBINE");
+    RK_TRY(rk_index_ensure_dir(ctx, const_cast<rk_index *>(idx), stream));
+    rk_dist_opts dopts;   // the row shard for rk_distq_counts; nothing of a distance is evaluated
+    memset(&dopts, 0, sizeof dopts);
+    dopts.kmer_size = 1;
+    dopts.max_dist = 1.0;
+    dopts.row_block = (int32_t)std::min<uint32_t>(o->row_block, (uint32_t)INT_MAX);
+    dopts.row_first = o->row_first;
+    dopts.row_step = o->row_step;
+
+    // the selected rows and the hashes before each of them, uploaded once (pageable memory of this function: the stream is synchronised
+    // by the first read-back, before the vectors go)
+    std::vector<unsigned long long> hoff(n_sel + 1, 0);
+    for (uint64_t s = 0; s < n_sel; s++) hoff[s + 1] = hoff[s] + (qs->h_off[sel.rows[s] + 1] - qs->h_off[sel.rows[s]]);
+
+    DevBuf<uint32_t> per_q(ctx), sizes(ctx), row_of(ctx), won(ctx);
+    DevBuf<Counters> cnt_dev(ctx);
+    DevBuf<unsigned long long> hoff_dev(ctx), rec_off(ctx);
+    DevBuf<int32_t> counts(ctx);
+    RK_HIP(ctx, per_q.alloc((size_t)4 * Q));   // n_cand, matched, claimed, nrec
+    RK_HIP(ctx, sizes.alloc(N));
+    RK_HIP(ctx, cnt_dev.alloc(1));
+    RK_HIP(ctx, row_of.alloc(n_sel));
+    RK_HIP(ctx, hoff_dev.alloc(n_sel + 1));
+    RK_HIP(ctx, hipMemsetAsync(per_q.p, 0, (size_t)16 * Q, stream));
+    RK_HIP(ctx, hipMemcpyAsync(row_of.p, sel.rows.data(), (size_t)n_sel * 4, hipMemcpyHostToDevice, stream));
+    RK_HIP(ctx, hipMemcpyAsync(hoff_dev.p, hoff.data(), (size_t)(n_sel + 1) * 8, hipMemcpyHostToDevice, stream));
+    RK_HIP(ctx, span.begin());
+    hipLaunchKernelGGL(k_screen_prepare, dim3(blocks_for(N)), dim3(kThreads), 0, stream, idx->relabeled ? idx->d_orig : nullptr, idx->d_sizes, N, sizes.p);
+    RK_HIP(ctx, hipGetLastError());
+    st->launches++;
+
+    // device bytes of one row of a batch: its counter row and its won row
+    const uint64_t row_bytes = (uint64_t)N * 8 + 16;
+    const uint64_t rows_per_batch = std::max<uint64_t>(1, std::min<uint64_t>(n_sel, env_number("RK_SCREEN_BATCH_BYTES", 1ULL << 30) / row_bytes));
+    st->rows_per_batch = rows_per_batch;
+    RK_HIP(ctx, counts.alloc(rows_per_batch * N));
+    RK_HIP(ctx, won.alloc(rows_per_batch * N));
+    RK_HIP(ctx, rec_off.alloc(rows_per_batch + 1));
+
+    struct Taken {   // the records of one batch, in order, until the result is put together
+        rk_ctx *ctx;
+        std::vector<std::pair<rk_screen_rec *, uint64_t>> parts;
+        ~Taken() { for (auto &p : parts) rk_pool_free(ctx, p.first); }
+    } taken{ctx, {}};
+    uint64_t total_recs = 0;
+
+    for (uint64_t s0 = 0; s0 < n_sel; s0 += rows_per_batch) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(rows_per_batch, n_sel - s0);
+        st->batches++;
+        const uint64_t hashes = hoff[s0 + nb] - hoff[s0], tiles = (hashes + kTileHashes - 1) / kTileHashes;
+        if (tiles > 0x7FFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_screen_rows: more than 2^31 tiles of query hashes in one batch");
+        RK_TRY(rk_distq_counts(ctx, idx, qs, &dopts, (uint32_t)s0, nb, counts.p, stream));
+        RK_HIP(ctx, hipMemsetAsync(won.p, 0, (size_t)nb * N * 4, stream));
+        RK_HIP(ctx, hipMemsetAsync(cnt_dev.p, 0, sizeof(Counters), stream));
+        if (tiles && idx->U) {
+            WinArgs w;
+            memset(&w, 0, sizeof w);
+            w.q_hashes = qs->wide ? (const void *)qs->d_hashes64 : (const void *)qs->d_hashes;
+            w.q_off = qs->d_off;
+            w.row_of = row_of.p + s0;
+            w.hoff = hoff_dev.p + s0;
+            w.nb = nb;
+            w.n_hashes = hashes;
+            w.ix.uhash = idx->wide ? (const void *)idx->d_uhash64 : (const void *)idx->d_uhash;
+            w.ix.dir = idx->d_dir;
+            w.ix.U = idx->U;
+            w.ix.hash_bits = idx->hash_bits;
+            w.ix.dir_shift = idx->dir_shift;
+            w.postings = idx->d_postings;
+            w.upos = idx->d_upos;
+            w.orig = idx->relabeled ? idx->d_orig : nullptr;
+            w.sizes_internal = idx->d_sizes;
+            w.cnt = counts.p;
+            w.won = won.p;
+            w.n_ref = N;
+            w.min_common = o->min_common;
+            w.lane_max = st->lane_max;
+            w.wave_max = st->wave_max;
+            w.matched_q = per_q.p + Q;
+            w.c = cnt_dev.p;
+            const auto win = qs->wide ? (combine ? k_screen_win<uint64_t, true> : k_screen_win<uint64_t, false>)
+                                      : (combine ? k_screen_win<uint32_t, true> : k_screen_win<uint32_t, false>);
+            hipLaunchKernelGGL(win, dim3((unsigned)tiles), dim3(kScreenThreads), 0, stream, w);
+            RK_HIP(ctx, hipGetLastError());
+            st->launches++;
+        }
+        RowArgs a;
+        memset(&a, 0, sizeof a);
+        a.cnt = counts.p;
+        a.won = won.p;
+        a.row_of = row_of.p + s0;
+        a.n_ref = N;
+        a.min_common = o->min_common;
+        a.min_won = o->min_won;
+        a.n_cand_q = per_q.p;
+        a.claimed_q = per_q.p + 2 * (size_t)Q;
+        a.nrec_q = per_q.p + 3 * (size_t)Q;
+        a.rec_off = rec_off.p;
+        a.sizes = sizes.p;
+        a.q_off = qs->d_off;
+        hipLaunchKernelGGL(k_screen_count, dim3(nb), dim3(kScreenThreads), 0, stream, a);
+        hipLaunchKernelGGL(k_screen_scan, dim3(1), dim3(kScreenThreads), 0, stream, a.nrec_q, a.row_of, nb, rec_off.p, &cnt_dev.p->rec_total);
+        RK_HIP(ctx, hipGetLastError());
+        st->launches += 2;
+        Counters home;
+        RK_TRY(rk_read_back(ctx, &home, cnt_dev.p, sizeof home, stream));   // the room of the records
+        st->read_backs++;
+        if (home.rec_total > (unsigned long long)nb * N) return rk_fail(ctx, RK_ERR_HIP, "rk_screen_rows: more records than cells (internal error)");
+        st->postings_walked += home.walked;
+        st->adds += home.adds;
+        st->lane_lists += home.lane_lists;
+        st->wave_lists += home.wave_lists;
+        st->block_lists += home.block_lists;
+        if (home.rec_total) {
+            rk_screen_rec *part = static_cast<rk_screen_rec *>(rk_pool_alloc(ctx, home.rec_total * sizeof(rk_screen_rec)));
+            if (!part) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu records on the device", home.rec_total);
+            taken.parts.emplace_back(part, home.rec_total);
+            a.recs = part;
+            hipLaunchKernelGGL(k_screen_write, dim3(nb), dim3(kScreenThreads), 0, stream, a);
+            RK_HIP(ctx, hipGetLastError());
+            st->launches++;
+            total_recs += home.rec_total;
+        }
+    }
+    // the result in one block, one copy
+    const size_t head = ((size_t)Q + 1) * 8 + (((size_t)Q * 12 + 7) & ~(size_t)7), bytes = head + total_recs * sizeof(rk_screen_rec);
+    DevBuf<unsigned char> block(ctx);
+    RK_HIP(ctx, block.alloc(bytes));
+    hipLaunchKernelGGL(k_screen_scan, dim3(1), dim3(kScreenThreads), 0, stream, per_q.p + 3 * (size_t)Q, (const uint32_t *)nullptr, Q, (unsigned long long *)block.p,
+                       &cnt_dev.p->all_total);
+    RK_HIP(ctx, hipGetLastError());
+    st->launches++;
+    if (Q) RK_HIP(ctx, hipMemcpyAsync(block.p + ((size_t)Q + 1) * 8, per_q.p + Q, (size_t)4 * Q, hipMemcpyDeviceToDevice, stream));              // matched
+    if (Q) RK_HIP(ctx, hipMemcpyAsync(block.p + ((size_t)Q + 1) * 8 + (size_t)4 * Q, per_q.p, (size_t)4 * Q, hipMemcpyDeviceToDevice, stream));   // n_cand
+    if (Q) RK_HIP(ctx, hipMemcpyAsync(block.p + ((size_t)Q + 1) * 8 + (size_t)8 * Q, per_q.p + 2 * (size_t)Q, (size_t)4 * Q, hipMemcpyDeviceToDevice, stream));
+    size_t at = head;
+    for (const auto &p : taken.parts) {
+        RK_HIP(ctx, hipMemcpyAsync(block.p + at, p.first, p.second * sizeof(rk_screen_rec), hipMemcpyDeviceToDevice, stream));
+        at += p.second * sizeof(rk_screen_rec);
+    }
+    RK_HIP(ctx, span.end());
+    res->block.resize(bytes);
+    RK_HIP(ctx, hipMemcpyAsync(res->block.data(), block.p, bytes, hipMemcpyDeviceToHost, stream));
+    RK_HIP(ctx, hipStreamSynchronize(stream));
+    span.read();
+    res->n_recs = total_recs;
+    const uint64_t *off = (const uint64_t *)res->block.data();
+    if (off[0] != 0 || off[Q] != total_recs) return rk_fail(ctx, RK_ERR_HIP, "rk_screen_rows: the offsets of the rows do not span the records (internal error)");
+    return RK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off, const uint64_t *q_lists, uint32_t n_query,
+                    uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes, const rk_screen_opts *opts, uint64_t *off_out,
+                    rk_screen_rec **recs_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out)
+{
+    if (!q_off || !opts || !off_out || !recs_out || !n_recs) return RK_ERR_ARG;
+    if (n_query && (!query_sizes || !matched_out || !n_cand_out || !claimed_out)) return RK_ERR_ARG;
+    if ((n_lists && !counts) || (n_ref && !ref_sizes) || !opts->min_common) return RK_ERR_ARG;
+    if (q_off[0] != 0) return RK_ERR_ARG;
+    for (uint32_t q = 0; q < n_query; q++)
+        if (q_off[q + 1] < q_off[q]) return RK_ERR_ARG;
+    if (q_off[n_query] && !q_lists) return RK_ERR_ARG;
+    for (uint32_t q = 0; q < n_query; q++)
+        for (uint64_t j = q_off[q]; j < q_off[q + 1]; j++)
+            if (q_lists[j] >= n_lists || (j > q_off[q] && q_lists[j - 1] >= q_lists[j])) return RK_ERR_ARG;
+    for (uint32_t r = 0; r < n_ref; r++)
+        if (ref_sizes[r] >= kSizeLimit) return RK_ERR_ARG;
+    for (uint32_t q = 0; q < n_query; q++)
+        if (query_sizes[q] >= kSizeLimit) return RK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint64_t u = 0; u < n_lists; u++) total += counts[u];
+    if (total && !postings) return RK_ERR_ARG;
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> fixed;
+    const uint32_t *post = nullptr;
+    if (int rc = prepare_lists(postings, counts, n_lists, n_ref, &pos, &fixed, &post)) return rc;
+    const RowSel sel(opts, n_query);
+    HostResult r;
+    if (int rc = screen_core(post, pos.data(), q_off, q_lists, n_query, n_ref, ref_sizes, query_sizes, opts, sel, true, &r)) return rc;
+    return hand_out(r, sel, n_query, off_out, recs_out, n_recs, matched_out, n_cand_out, claimed_out);
+}
+
+int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out, rk_screen_rec **recs_out,
+                   uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out, rk_screen_stats *stats)
+{
+    if (!ctx || !idx || !queries || !opts || !off_out || !recs_out || !n_recs) return RK_ERR_ARG;
+    const char *const who = "rk_screen_rows";
+    const uint32_t N = idx->n_ref, Q = queries->n;
+    if (Q && (!matched_out || !n_cand_out || !claimed_out)) return rk_fail(ctx, RK_ERR_ARG, "%s: matched_out, n_cand_out or claimed_out is null", who);
+    if (!opts->min_common) return rk_fail(ctx, RK_ERR_ARG, "%s: min_common must be at least 1", who);
+    if (queries->wide != idx->wide) return rk_fail(ctx, RK_ERR_ARG, "query sketches and index use different hash widths");
+    if (N && (!idx->d_postings || !idx->d_upos || idx->n_shards > 1))
+        return rk_fail(ctx, RK_ERR_ARG, "%s: an index without all posting lists (rk_index_join_shard, one hash range of a sharded build)", who);
+    if (N && Q && (!idx->ref_sets || !queries->is_set)) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s takes sketches as sets: a sketch repeats a hash", who);
+    if (idx->H >= 0x7FFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "explicit queries against an index of 2^31-1 postings or more");
+    if (N && Q && (idx->max_ref_size >= kSizeLimit || queries->max_size >= kSizeLimit))
+        return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: a sketch of 2^30 hashes or more (the products of the comparison stay below 2^60)", who);
+    rk_screen_stats st;
+    memset(&st, 0, sizeof st);
+    fill_constants(&st);
+    const TimedSpan span{ctx, RK_MS_SCREEN};
+    span.clear();
+    const RowSel sel(opts, Q);
+    st.rows = (uint32_t)sel.rows.size();
+    if (!N || sel.rows.empty()) {   // nothing runs: every row is empty
+        memset(off_out, 0, ((size_t)Q + 1) * 8);
+        for (const uint32_t q : sel.rows) matched_out[q] = n_cand_out[q] = claimed_out[q] = 0;
+        *recs_out = nullptr;
+        *n_recs = 0;
+        if (stats) *stats = st;
+        return RK_OK;
+    }
+    if (rk_switched_off("RK_SCREEN_DEVICE")) {
+        st.path = 2;
+        HostResult r;
+        RK_TRY(idx->wide ? screen_on_host<uint64_t>(ctx, idx, queries, opts, sel, &r) : screen_on_host<uint32_t>(ctx, idx, queries, opts, sel, &r));
+        st.records = r.recs.size();
+        for (size_t k = 0; k < r.matched.size(); k++) {
+            st.matched += r.matched[k];
+            st.candidates += r.n_cand[k];
+            st.claimed += r.claimed[k];
+        }
+        st.postings_walked = r.walked;
+        st.lane_lists = r.lane_lists;
+        st.wave_lists = r.wave_lists;
+        st.block_lists = r.block_lists;
+        st.batches = 1;
+        st.rows_per_batch = sel.rows.size();
+        if (hand_out(r, sel, Q, off_out, recs_out, n_recs, matched_out, n_cand_out, claimed_out)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+        if (stats) *stats = st;
+        return RK_OK;
+    }
+    st.path = 1;
+    DeviceResult res;
+    RK_TRY(screen_on_device(ctx, idx, queries, opts, sel, &st, &res));
+    const unsigned char *b = res.block.data();
+    const uint64_t *off = (const uint64_t *)b;
+    const uint32_t *matched = (const uint32_t *)(b + ((size_t)Q + 1) * 8), *n_cand = matched + Q, *claimed = n_cand + Q;
+    const size_t head = ((size_t)Q + 1) * 8 + (((size_t)Q * 12 + 7) & ~(size_t)7);
+    rk_screen_rec *p = nullptr;
+    if (res.n_recs) {
+        p = (rk_screen_rec *)malloc(res.n_recs * sizeof(rk_screen_rec));
+        if (!p) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+        memcpy(p, b + head, res.n_recs * sizeof(rk_screen_rec));
+    }
+    memcpy(off_out, off, ((size_t)Q + 1) * 8);
+    for (const uint32_t q : sel.rows) {
+        matched_out[q] = matched[q];
+        n_cand_out[q] = n_cand[q];
+        claimed_out[q] = claimed[q];
+        st.matched += matched[q];
+        st.candidates += n_cand[q];
+        st.claimed += claimed[q];
+    }
+    st.records = res.n_recs;
+    *recs_out = p;
+    *n_recs = res.n_recs;
+    if (stats) *stats = st;
+    return RK_OK;
+}
+
+}  // extern "C"

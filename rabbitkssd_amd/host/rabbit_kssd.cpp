@@ -1904,6 +1904,95 @@ static int cmd_gather(const Args &a)
     SelfJoin::leave();
 }
 
+// screen: which references are contained in each query sketch, every shared hash credited to one reference only (rk_screen_rows): the
+// winner-take-all containment screen of `mash screen -w`.  One line per record: query, reference, common, size_ref, won,
+// identity = (common / size_ref)^(1/K), identity_won = (won / size_ref)^(1/K), K the k-mer length of the sketches.
+// --sub host.sketch: the queries lose the hashes of host.sketch on the device first (rk_sketches_mask {0, 0}), as gather --sub does.
+static int cmd_screen(const Args &a)
+{
+    if (!a.has("r") || !a.has("q")) die("screen needs -r and -q");
+    if (a.num("gpus", 1) != 1) die("command_screen(), screen runs on one GPU (--gpus 1)");
+    if (a.has("min-common") && a.num("min-common", 1) < 1) die("command_screen(), --min-common must be >= 1");
+    if (a.has("min-won") && a.num("min-won", 0) < 0) die("command_screen(), --min-won must be >= 0 (0: every candidate)");
+    const string out = a.str("o", "result.out");
+    const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    GpuSet set(a.num("device", 0), 1, false);
+    SketchSet ref, qry;
+    string ref_path, qry_path;
+    {   // .sketch inputs are read while the runtime starts
+        string err;
+        if (is_sketch_file(a.str("r", ""))) {
+            ref_path = a.str("r", "");
+            if (!read_sketches(ref_path, ref, err)) die("readSketches(), %s", err.c_str());
+        }
+        if (is_sketch_file(a.str("q", ""))) {
+            qry_path = a.str("q", "");
+            if (!read_sketches(qry_path, qry, err)) die("readSketches(), %s", err.c_str());
+        }
+    }
+    if (ref_path.empty()) load_or_sketch(set[0], a.str("r", ""), a, threads, ref, ref_path);
+    cerr << "the ref_sketch size is: " << ref.size() << endl;
+    if (qry_path.empty()) load_or_sketch(set[0], a.str("q", ""), a, threads, qry, qry_path);
+    if (qry.info.id != ref.info.id)
+        die("command_screen(), the sketch infos between reference and query files are not match\n"
+            "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    const size_t N = ref.size(), Q = qry.size();
+    const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
+    vector<rk_index *> idx(1, nullptr);
+    build_everywhere(set, ref, ref_path, missing, idx);
+    stamp("index built");
+    cerr << "=====total: " << Q << endl;
+    const rk_screen_opts o{(uint32_t)a.num("min-common", 1), (uint32_t)a.num("min-won", 0), 0, 0, 0};
+    vector<uint64_t> off(Q + 1, 0);
+    vector<uint32_t> matched(Q ? Q : 1, 0), n_cand(Q ? Q : 1, 0), claimed(Q ? Q : 1, 0);
+    rk_screen_rec *recs = nullptr;
+    uint64_t n_recs = 0;
+    rk_screen_stats stats;
+    rk_sketches *qs = nullptr;
+    vector<uint64_t> q_off = qry.off;   // the sizes of the queries as they are screened
+    if (a.has("sub")) {
+        const string host_path = a.str("sub", "");
+        if (!is_sketch_file(host_path)) die("command_screen(), %s is not sketch file, --sub needs a sketch file", host_path.c_str());
+        SketchSet host;
+        string err;
+        if (!read_sketches(host_path, host, err)) die("readSketches(), %s", err.c_str());
+        if (host.info.id != qry.info.id) die("command_screen(), the sketch infos between the --sub sketches and the query sketches are not same");
+        qs = masked_queries(set, host, host_path, false, qry, rk_mask_rule{0, 0}, nullptr);
+        if (qs) set[0].check(rk_sketches_download(qs, nullptr, q_off.data()), "rk_sketches_download");
+        stamp("queries masked");
+    }
+    if (!qs) qs = upload(set[0], qry);
+    set[0].check(rk_screen_rows(set[0].ctx, idx[0], qs, &o, off.data(), &recs, &n_recs, matched.data(), n_cand.data(), claimed.data(), &stats), "rk_screen_rows");
+    rk_sketches_free(qs);
+    stamp("queries screened");
+    const double inv_k = 1.0 / (double)(2 * ref.info.half_k);   // the k-mer length, as dist reads it
+    FILE *fp = fopen(out.c_str(), "w");
+    if (!fp) die("cannot write %s", out.c_str());
+    for (uint64_t k = 0; k < n_recs; k++) {
+        const rk_screen_rec &p = recs[k];
+        fprintf(fp, "%s\t%s\t%u\t%u\t%u\t%.6f\t%.6f\n", qry.names[p.query].c_str(), ref.names[p.ref].c_str(), p.common, p.size_ref, p.won,
+                pow((double)p.common / (double)p.size_ref, inv_k), p.won ? pow((double)p.won / (double)p.size_ref, inv_k) : 0.0);
+    }
+    fclose(fp);
+    if (a.has("summary")) {
+        FILE *sp = fopen(a.str("summary", "").c_str(), "w");
+        if (!sp) die("cannot write %s", a.str("summary", "").c_str());
+        for (size_t q = 0; q < Q; q++)
+            fprintf(sp, "%s\t%llu\t%u\t%u\t%u\t%llu\n", qry.names[q].c_str(), (unsigned long long)(q_off[q + 1] - q_off[q]), matched[q], n_cand[q], claimed[q],
+                    (unsigned long long)(off[q + 1] - off[q]));
+        fclose(sp);
+    }
+    if (getenv("RK_TIMING"))
+        fprintf(stderr, "[timing] %zu queries against %zu references: %llu records of %llu candidates, %llu of %llu matched hashes claimed, %llu postings walked "
+                        "(%llu lists by lane, %llu by wave, %llu by workgroup), %llu adds, %u batches, %u launches, %u read-backs, path %u, %.3f ms on the device\n",
+                Q, N, (unsigned long long)stats.records, (unsigned long long)stats.candidates, (unsigned long long)stats.claimed, (unsigned long long)stats.matched,
+                (unsigned long long)stats.postings_walked, (unsigned long long)stats.lane_lists, (unsigned long long)stats.wave_lists,
+                (unsigned long long)stats.block_lists, (unsigned long long)stats.adds, stats.batches, stats.launches, stats.read_backs, stats.path,
+                rk_ctx_last_ms(set[0].ctx, RK_MS_SCREEN));
+    rk_free_host(recs);
+    SelfJoin::leave();
+}
+
 // --taxonomy FILE of lca: one line per node, id<TAB>parent id[<TAB>name]; ids are arbitrary non-negative integers (NCBI taxids work),
 // the root names itself.  The nodes become dense numbers by ascending id: id[] ascending, parent[] in node numbers, name[] ("" without).
 struct Taxonomy {
@@ -2386,7 +2475,7 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert merge lca info mask\n"
+            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert screen merge lca info mask\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
             "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
@@ -2400,6 +2489,7 @@ static int usage()
             "  assign -r ref.sketch|list -q qry.sketch|list -D maxDist [-M 0|1] (--labels FILE | --by cluster|greedy|dbscan -m minPts) -o out [--novel FILE] [--gpus G] [--device N]   (placement of the queries into the clustered references: per query the cluster of its nearest labelled reference within -D, that reference's dist line, the query's references of that cluster, labelled and all within -D, and the runner-up cluster with its distance; - when novel; -D below 1.0; the labels from --labels -- one line per reference, an integer below their number or - -- or from --by on the same index (default cluster; dbscan needs -m and leaves non-core references unlabelled; greedy and dbscan on the first GPU); --novel: the names of the unplaced queries)\n"
             "  group -i in.sketch|genomes.list (--labels FILE | --by cluster|greedy|dbscan [-D 0.05] [-M 0|1] [-m 5]) [--pan | --core | --share P/Q] [--min-count C] [--only] -o out.sketch [--map FILE] [--device N]   (one sketch per cluster: --pan, the default, the union of its members' sketches; --core the hashes every member holds; --share P/Q those at least P of Q of its members hold; --min-count C: at least C members hold it; --only: no genome outside the cluster holds it -- its markers; the labels as medoid takes them; out.sketch: one sketch per cluster by ascending label, named after its first member; --map: per cluster its number, label, genomes, hashes kept and name; one GPU)\n"
             "  gather -r ref.sketch|list -q qry.sketch|list [--min-new 1] [--max-picks 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references explain each query, greedily: per round the reference that holds most of the query's hashes no earlier pick held, ties to the earlier reference, until a pick would add fewer than --min-new hashes or --max-picks are made; one line per pick: query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref; --summary: per query its name, size, hashes some reference holds, hashes the picks explain, references sharing at least --min-new hashes, picks; --sub: the queries first lose every hash a sketch of host.sketch holds, on the device -- the cover of what sub would write; one GPU)\n"
+            "  screen  -r ref.sketch|list -q qry.sketch|list [--min-common 1] [--min-won 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references are contained in each query, every shared hash credited to one of them -- mash screen -w in one pass: among the references that share at least --min-common hashes with the query a hash goes to the one with the larger common / size, compared exactly, then to the larger, then to the earlier one; one line per reference that keeps at least --min-won hashes: query, reference, common, size_ref, won, identity = (common / size_ref)^(1/K) and identity_won = (won / size_ref)^(1/K) for the sketches' k-mer length K; --summary: per query its name, size, hashes some reference holds, candidates, hashes claimed, records; --sub as in gather; Mash's p-value and median multiplicity are not offered: Kssd sketches carry no multiplicities; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
@@ -2424,7 +2514,7 @@ int main(int argc, char **argv)
         {"-F", "F"}, {"--Fined", "F"}, {"--device", "device"}, {"--query", "q"}, {"-q", "q"},
         {"--reverse", "reverse"}, {"--rs", "rs"}, {"--qs", "qs"}, {"--gpus", "gpus"}, {"--same-device", "same-device"}, {"--reps", "reps"}, {"-m", "m"}, {"--minPts", "m"}, {"--core", "core"}, {"--cut", "cut"}, {"--labels", "labels"}, {"--by", "by"}, {"--census", "census"}, {"--novel", "novel"},
         {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"},
-        {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--summary", "summary"}, {"--sub", "sub"},
+        {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--min-common", "min-common"}, {"--min-won", "min-won"}, {"--summary", "summary"}, {"--sub", "sub"},
         {"--keep", "keep"}, {"--min-refs", "min-refs"}, {"--max-refs", "max-refs"},
         {"--taxonomy", "taxonomy"}, {"--taxa", "taxa"}, {"--confidence", "confidence"}, {"--of", "of"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
@@ -2444,7 +2534,7 @@ int main(int argc, char **argv)
     // set up (their queues: ~10 ms before the first upload, ~10 ms before the first read-back -- `index built` 34 -> 16 ms,
     // `distances` 14.6 -> 3.7 ms of the stamps of RK_TIMING) than blit kernels need to copy it.  Sketching from FASTA lists keeps
     // them: there gigabytes of uploads run beside the scan kernel.  (Set HSA_ENABLE_SDMA yourself to overrule.)
-    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather" || sub == "mask" || sub == "lca") {
+    if (sub == "alldist" || sub == "dist" || sub == "cluster" || sub == "forest" || sub == "greedy" || sub == "knn" || sub == "dbscan" || sub == "mreach" || sub == "medoid" || sub == "assign" || sub == "group" || sub == "gather" || sub == "mask" || sub == "lca" || sub == "screen") {
         bool from_sketches = true;
         for (int i = 2; i + 1 < argc; i++) {
             const string f = argv[i];
@@ -2472,6 +2562,7 @@ int main(int argc, char **argv)
     if (sub == "assign") { cerr << "-----run the subcommand: assign" << endl; return leave(cmd_assign(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "group") { cerr << "-----run the subcommand: group" << endl; return leave(cmd_group(parse_args(argc, argv, 2, alias, {"pan", "core", "only"}))); }   // (--core is a flag here, a file of mreach)
     if (sub == "gather") { cerr << "-----run the subcommand: gather" << endl; return leave(cmd_gather(parse_args(argc, argv, 2, alias, {}))); }
+    if (sub == "screen") { cerr << "-----run the subcommand: screen" << endl; return leave(cmd_screen(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "mask") { cerr << "-----run the subcommand: mask" << endl; return leave(cmd_mask(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "lca") { cerr << "-----run the subcommand: lca" << endl; return leave(cmd_lca(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
