@@ -32,6 +32,7 @@
 #include "rk_internal.h"
 #include "rk_dist_common.h"
 #include "rk_dist_plan.h"
+#include "rk_tile_cells.h"
 
 namespace {
 

@@ -78,6 +78,13 @@ template <uint32_t kTileThreads, bool SROW>
 __global__ __launch_bounds__(kTileThreads, kTileThreads == 256 ? 6 : 4) void rk_tile_kernel(TileArgs a, const uint2 *__restrict__ contrib, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ cols)
 {
     constexpr uint32_t kTileWaves = kTileThreads / 64;
+    // a wave's share of a tile's records is rounded up to this many.  Eight and sixteen waves (launches of one round of
+    // workgroups: a tile's chain is the launch) take EVEN shares in whole groups of 16 records: whole 128-record steps left
+    // seven waves five steps and the eighth two on a tile of 4,728 records, and three of eight waves idle on one of 1,194.
+    // Four waves (launches of several rounds, bound by vector issue) keep whole steps: there a chain's length buys nothing and
+    // a partial step costs more instructions per record (measured with groups of 16: 50,000 genomes 0.0629 -> 0.0642 ms,
+    // species of 1,000 strains 0.0479 -> 0.0482; DESIGN 4.3c)
+    constexpr uint32_t kTileShare = kTileWaves >= 8 ? 16u : 128u;
     // hits are staged in the LDS that held the tile's records while it was counted (flushed when a round of cells may not
     // fit, and at the end of every tile)
     constexpr uint32_t kTileStage = (uint32_t)(8 * kTileThreads * sizeof(uint2) / sizeof(rk_hit));
@@ -232,7 +239,10 @@ __global__ __launch_bounds__(kTileThreads, kTileThreads == 256 ? 6 : 4) void rk_
                 const unsigned long long *__restrict__ tile_rows = reinterpret_cast<const unsigned long long *>(rows + slot0);
                 const uint32_t n_rec = d1.x;
                 const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);
-                const uint32_t per = ((n_rec + kTileWaves - 1) / kTileWaves + 127u) & ~127u;
+                // a wave's share (kTileShare above): it starts on an even record, so the pairs of row masks stay aligned, and its
+                // tail takes the partial-step paths below.  Furthest slot read: below w0 + n_sub * 128 <= w1 + 127 <= n_rec + 127,
+                // inside the 256 slots that pad the arrays.  (to_lds() counts per lane, whatever the share.)
+                const uint32_t per = ((n_rec + kTileWaves - 1) / kTileWaves + kTileShare - 1u) & ~(kTileShare - 1u);
                 const uint32_t w0 = min(n_rec, wave_u * per), w1 = min(n_rec, w0 + per);
                 const uint32_t n_sub = (w1 - w0 + 127u) / 128u;
                 const uint32_t *__restrict__ tile_cols = cols + slot0;   // (the column masks in the same padded slots)
@@ -342,7 +352,8 @@ __global__ __launch_bounds__(kTileThreads, kTileThreads == 256 ? 6 : 4) void rk_
                 // (positions inside the tile in 32 bits: a tile has fewer than 2^32 records -- the directory entry says so)
                 const uint2 *__restrict__ tile = contrib + s0;
                 const uint32_t n_rec = d1.x;
-                const uint32_t per = ((n_rec + kTileWaves - 1) / kTileWaves + 127u) & ~127u;
+                // (a wave's share: kTileShare above; loads are clamped to the tile: nothing is read behind it)
+                const uint32_t per = ((n_rec + kTileWaves - 1) / kTileWaves + kTileShare - 1u) & ~(kTileShare - 1u);
                 const uint32_t w0 = min(n_rec, wave * per), w1 = min(n_rec, w0 + per);
                 const uint32_t n_sub = (w1 - w0 + 127u) / 128u;
                 uint2 *mine = recs + wave * 512;   // 4 slots x 128 records
@@ -491,13 +502,27 @@ __global__ __launch_bounds__(kTileThreads, kTileThreads == 256 ? 6 : 4) void rk_
             }
         }
         __syncthreads();
-        // ---- evaluation: 1,024 cells, one per lane and round
-        for (uint32_t round = 0; round < 1024 / kTileThreads; round++) {
+        // ---- evaluation: one cell per lane and round.  A tile off the diagonal has 1,024 cells.  In a DIAGONAL tile (b == w) only
+        // the 496 cells with col > row pass `gcol > grow` below: they are numbered by rk_tile_tri_cell (rk_tile_cells.h; a wave's
+        // reads of cnt meet 2-way at most) and take ceil(496 / threads) rounds -- one instead of two at 512 threads --, the
+        // lanes from 496 on hold no cell.  The diagonal and the lower triangle of cnt are never read and need no clearing here:
+        // a workgroup counts ONE tile, and the whole matrix is zeroed where it always was, at the tile's start.
+        const bool diag = b == w;   // (uniform)
+        const uint32_t n_rounds = diag ? (kTileTriCells + kTileThreads - 1) / kTileThreads : 1024 / kTileThreads;
+        for (uint32_t round = 0; round < n_rounds; round++) {
             if (s_cursor + kTileThreads > kTileStage) flush_stage();   // (uniform: s_cursor only changes between barriers)
-            const uint32_t ci = round * kTileThreads + tid;
-            const uint32_t col = ci >> 5, r = ci & 31;
-            const uint32_t common = cnt[ci];
-            cnt[ci] = 0;
+            uint32_t ci = round * kTileThreads + tid;
+            uint32_t col = ci >> 5, r = ci & 31;
+            bool cell = true;
+            if (diag) {
+                cell = rk_tile_tri_cell(ci, r, col);
+                ci = cell ? col * 32 + r : 0u;
+            }
+            uint32_t common = 0;
+            if (cell) {
+                common = cnt[ci];
+                cnt[ci] = 0;
+            }
             const uint32_t grow = b * 32 + r, gcol = w * 32 + col;
             bool ok = common != 0 && gcol > grow && gcol < a.n_ref && !(a.debug & 2);
             if (ok && a.row_step > 1) ok = (grow / a.row_block) % a.row_step == a.row_first;
