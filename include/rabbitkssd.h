@@ -202,6 +202,17 @@ int rk_sketch_batch_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, cons
 int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
                             uint64_t packed_bytes, const uint64_t *gbeg, const uint64_t *gend,
                             uint32_t n_genomes, uint32_t min_count, void *stream, rk_sketches **out);
+/* Counted variants of the two calls above: the same arguments, the same hashes and offsets byte for byte, and per kept hash
+ * the number of candidates (selected k-mer windows) of its genome that carried it -- what the dedup of the uncounted calls
+ * computes and drops.  A hash is kept iff its count >= min_count, as above; the count is the full count (>= 1, <= the genome's
+ * candidate count), never clipped.  FASTA and FASTQ alike: the quality gate removes windows before they are counted.  The
+ * result is an rk_sketches with counts (rk_sketches_has_counts); rk_sketch_last_plan is left as the uncounted calls leave it. */
+int rk_sketch_batch_counts(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const uint8_t *qual,
+                           int least_qual, uint32_t min_count, const uint64_t *rec_off, uint64_t n_rec,
+                           const uint64_t *genome_rec, uint32_t n_genomes, rk_sketches **out);
+int rk_sketch_packed_dev_counts(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
+                                uint64_t packed_bytes, const uint64_t *gbeg, const uint64_t *gend,
+                                uint32_t n_genomes, uint32_t min_count, void *stream, rk_sketches **out);
 /* What the last rk_sketch_packed_dev(_ex) call on this context did (rk_sketch_batch(_ex) end in one): the scan kernel as a
  * profiler prints it (e.g. "rk_scan2_kernel<20, 8>", "rk_sketch_kernel<0, 0, false, 1>"), the LDS image (2 two-stage scan,
  * 1 / 0 rk_sketch_kernel with the 64 / 144 KiB image) and whether the exact table confirms the survivors, the chunk length in
@@ -249,6 +260,22 @@ uint64_t rk_sketches_windows(const rk_sketches *s);
 int rk_sketches_download(const rk_sketches *s, uint32_t *hashes, uint64_t *off);
 const uint32_t *rk_sketches_hashes_dev(const rk_sketches *s);
 const uint64_t *rk_sketches_off_dev(const rk_sketches *s);
+/* Counted sketches.  An rk_sketches may carry an optional device array counts[total], aligned with its hashes: counts[i] is the
+ * multiplicity of hash i in its genome.  The counted sketch calls produce it, rk_sketches_from_host_counts imports it.
+ * EVERY consumer of sketches ignores the counts -- rk_index_build, the joins (rk_dist_rows, rk_dist_topn, ...), rk_sketches_mask,
+ * rk_group_sketches, rk_gather_rows, rk_screen_rows, rk_lca_rows, the shard calls -- and the objects they derive carry none.
+ *   rk_sketches_has_counts       1 with counts, 0 without (or s == NULL)
+ *   rk_sketches_counts_dev       the device array, NULL without counts
+ *   rk_sketches_download_counts  copies counts[total] to a caller buffer; RK_ERR_UNSUPPORTED without counts
+ *   rk_sketches_from_host_counts imports hashes (uint32_t[total], or uint64_t[total] when wide != 0), counts and offsets.  Every
+ *                                genome's hashes must be strictly ascending -- the library sorts uncounted imports, which would tear
+ *                                the counts from their hashes -- and every count at least 1: RK_ERR_ARG otherwise (checked on the
+ *                                device; nothing is created). */
+int rk_sketches_has_counts(const rk_sketches *s);
+const uint32_t *rk_sketches_counts_dev(const rk_sketches *s);
+int rk_sketches_download_counts(const rk_sketches *s, uint32_t *counts);
+int rk_sketches_from_host_counts(rk_ctx *ctx, const void *hashes, int wide, const uint32_t *counts, const uint64_t *off,
+                                 uint32_t n_genomes, rk_sketches **out);
 void rk_sketches_free(rk_sketches *s);
 
 /* ---- inverted index ------------------------------------------------------------- */

@@ -25,6 +25,7 @@ EXPORTS = [
     "rk_sketch_batch", "rk_sketch_batch_ex", "rk_sketch_packed_dev", "rk_sketch_packed_dev_ex", "rk_sketch_last_plan", "rk_pack_layout", "rk_pack_genomes",
     "rk_sketches_from_host", "rk_sketches_from_host64", "rk_sketches_download64", "rk_sketches_is64", "rk_sketches_from_dev", "rk_sketches_count", "rk_sketches_total", "rk_sketches_windows",
     "rk_sketches_download", "rk_sketches_hashes_dev", "rk_sketches_off_dev", "rk_sketches_free",
+    "rk_sketch_batch_counts", "rk_sketch_packed_dev_counts", "rk_sketches_has_counts", "rk_sketches_counts_dev", "rk_sketches_download_counts", "rk_sketches_from_host_counts",
     "rk_index_build", "rk_index_import", "rk_index_export", "rk_index_export_lists", "rk_index_import64", "rk_index_export64", "rk_index_total",
     "rk_index_distinct", "rk_index_genomes", "rk_index_order", "rk_index_hash_bits", "rk_index_built_fast", "rk_index_build_plan", "rk_index_build_report", "rk_index_products", "rk_index_sum_sq", "rk_index_self_stats", "rk_index_tile_stats", "rk_index_build_shard", "rk_index_shard_records", "rk_index_shard_pack", "rk_index_join_shard", "rk_index_shard_exchange",
     "rk_sketches_signature", "rk_sketches_shard_keys", "rk_sketches_shard_pack", "rk_index_build_shard_keys",
@@ -287,7 +288,14 @@ def lib():
         L.rk_index_hash_bits.argtypes = [C.c_void_p]
         L.rk_index_built_fast.argtypes = [C.c_void_p]
         L.rk_index_products.argtypes = [C.c_void_p]
-        for f in ("rk_sketches_hashes_dev", "rk_sketches_off_dev"):
+        L.rk_sketches_has_counts.argtypes = [C.c_void_p]
+        L.rk_sketches_download_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.rk_sketches_from_host_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.rk_sketch_batch_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.rk_sketch_packed_dev_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.POINTER(C.c_void_p)]
+        for f in ("rk_sketches_hashes_dev", "rk_sketches_off_dev", "rk_sketches_counts_dev"):
             getattr(L, f).restype = C.c_void_p
             getattr(L, f).argtypes = [C.c_void_p]
         _LIB = L
@@ -480,6 +488,40 @@ class Context:
         self.check(lib().rk_sketch_batch_ex(self._h, flt._h, _ptr(seq), _ptr(qual), int(least_qual),
                                             C.c_uint32(min_count), _ptr(rec_off), C.c_uint64(len(rec_off) - 1),
                                             _ptr(genome_rec), C.c_uint32(len(genome_rec) - 1), C.byref(h)))
+        return Sketches(self, h)
+
+    def sketch_batch_counts(self, flt, seq, rec_off, genome_rec, qual=None, least_qual=0, min_count=1):
+        """rk_sketch_batch_counts: sketch_batch (qual=None) or sketch_batch_fastq with per-hash occurrence counts (Sketches.download_counts)"""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8) if qual is not None else None
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        genome_rec = np.ascontiguousarray(genome_rec, dtype=np.uint64)
+        h = C.c_void_p()
+        self.check(lib().rk_sketch_batch_counts(self._h, flt._h, _ptr(seq), _ptr(qual), int(least_qual),
+                                                C.c_uint32(min_count), _ptr(rec_off), C.c_uint64(len(rec_off) - 1),
+                                                _ptr(genome_rec), C.c_uint32(len(genome_rec) - 1), C.byref(h)))
+        return Sketches(self, h)
+
+    def sketch_packed_dev_counts(self, flt, packed_dev_ptr, packed_bytes, gbeg, gend, min_count=1, stream=0):
+        gbeg = np.ascontiguousarray(gbeg, dtype=np.uint64)
+        gend = np.ascontiguousarray(gend, dtype=np.uint64)
+        h = C.c_void_p()
+        self.check(lib().rk_sketch_packed_dev_counts(self._h, flt._h, C.c_void_p(packed_dev_ptr), C.c_uint64(packed_bytes), _ptr(gbeg), _ptr(gend),
+                                                     C.c_uint32(len(gbeg)), C.c_uint32(min_count), C.c_void_p(stream), C.byref(h)))
+        return Sketches(self, h)
+
+    def sketches_from_host_counts(self, hashes, counts, off, wide=None):
+        """rk_sketches_from_host_counts: a counted sketch; wide (default: by the dtype of hashes) picks the 64-bit hash layout.  Every
+        genome's hashes strictly ascending, every count >= 1, or RkError (RK_ERR_ARG)"""
+        if wide is None:
+            wide = np.asarray(hashes).dtype.itemsize == 8
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64 if wide else np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        assert len(counts) == len(hashes)
+        h = C.c_void_p()
+        self.check(lib().rk_sketches_from_host_counts(self._h, _ptr(hashes), 1 if wide else 0, _ptr(counts), _ptr(off),
+                                                      C.c_uint32(len(off) - 1), C.byref(h)))
         return Sketches(self, h)
 
     def sketch_packed_dev(self, flt, packed_dev_ptr, packed_bytes, gbeg, gend, stream=0):
@@ -936,6 +978,16 @@ class Sketches(_Obj):
             hashes = np.zeros(self.total, dtype=np.uint32)
             self.ctx.check(lib().rk_sketches_download(self._h, _ptr(hashes), _ptr(off)))
         return hashes, off
+
+    @property
+    def has_counts(self):
+        return bool(lib().rk_sketches_has_counts(self._h))
+
+    def download_counts(self):
+        """the per-hash occurrence counts (uint32, aligned with download()'s hashes); RkError (RK_ERR_UNSUPPORTED) without counts"""
+        counts = np.zeros(max(1, self.total), dtype=np.uint32)
+        self.ctx.check(lib().rk_sketches_download_counts(self._h, _ptr(counts)))
+        return counts[:self.total]
 
 
 class Index(_Obj):

@@ -192,6 +192,8 @@ struct rk_sketches {
     uint32_t *d_hashes = nullptr; // u32[total] when !wide
     uint64_t *d_hashes64 = nullptr; // u64[total] when wide
     uint64_t *d_off = nullptr;
+    uint32_t *d_counts = nullptr; // u32[total], optional: per hash the candidates of its genome that carried it (counted sketches:
+                                  // rk_sketch_*_counts, rk_sketches_from_host_counts); every consumer of sketches ignores it
     std::vector<uint64_t> h_off;  // host mirror of d_off (n+1)
     bool is_set = false;          // every genome's hashes are strictly ascending (sorted, no repeats)
     uint64_t max_size = 0;        // largest sketch

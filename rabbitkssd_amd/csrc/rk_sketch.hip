@@ -474,10 +474,12 @@ struct SketchTail {  // device-side results of one sketch pass, read back in one
 };
 static_assert(sizeof(SketchTail) == kTailBytes, "the head of the work buffer (PassLayout)");
 
-template <class K>
+// COUNTS: every kept hash also gets the length of its run -- the number of candidates of the genome that carried it -- in
+// counts_out, at the position of the hash (rk_sketch_*_counts); the uncounted instantiation never touches counts_out
+template <class K, bool COUNTS>
 __global__ __launch_bounds__(kDedupThreads) void k_dedup(const unsigned long long *cand, const GenomeRow *rows,
                                                         const uint32_t *gcount, uint32_t min_count, K *sorted_out,
-                                                        uint32_t *usize, SketchTail *tail)
+                                                        uint32_t *usize, SketchTail *tail, uint32_t *counts_out)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dedup_lds[];
     K *a = reinterpret_cast<K *>(dedup_lds);
@@ -529,8 +531,23 @@ __global__ __launch_bounds__(kDedupThreads) void k_dedup(const unsigned long lon
         while (len < min_count && i + len < n && a[i + len] == a[i]) len++;
         return len >= min_count;
     };
+    // COUNTS: the length of the run that starts at head i, 0 where i is no head or the run is shorter than min_count.  The end of
+    // the run is the upper bound of its key in a[i + 1, n), by binary search: a walk would leave one hash that fills the region to one
+    // thread.  The search never looks beyond n: a padding key may equal a real one (all ones at 32 hash bits).
+    auto run_kept = [&](uint32_t i) -> uint32_t {
+        const K key = a[i];
+        if (i && key == a[i - 1]) return 0;
+        uint32_t lo = i + 1, hi = n;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a[mid] <= key) lo = mid + 1;
+            else hi = mid;
+        }
+        const uint32_t len = lo - i;
+        return len >= min_count ? len : 0;
+    };
     uint32_t mine = 0;
-    for (uint32_t i = i0; i < i1; i++) mine += kept(i);
+    for (uint32_t i = i0; i < i1; i++) mine += COUNTS ? (run_kept(i) != 0) : kept(i);
     uint32_t incl = mine;
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t t = __shfl_up(incl, o);
@@ -541,8 +558,17 @@ __global__ __launch_bounds__(kDedupThreads) void k_dedup(const unsigned long lon
     uint32_t at = incl - mine;
     for (uint32_t w = 0; w < wave; w++) at += wave_tot[w];
     K *dst = sorted_out + row.reg_off;
-    for (uint32_t i = i0; i < i1; i++)
-        if (kept(i)) dst[at++] = a[i];
+    if constexpr (COUNTS) {
+        uint32_t *cdst = counts_out + row.reg_off;
+        for (uint32_t i = i0; i < i1; i++)
+            if (const uint32_t len = run_kept(i)) {
+                dst[at] = a[i];
+                cdst[at++] = len;
+            }
+    } else {
+        for (uint32_t i = i0; i < i1; i++)
+            if (kept(i)) dst[at++] = a[i];
+    }
     if (tid == kDedupThreads - 1) usize[g] = at;
 }
 
@@ -593,6 +619,20 @@ __global__ void k_count_flags(const unsigned int *counts, uint64_t n, uint32_t m
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) flags[i] = counts[i] >= min_count ? 1 : 0;
+}
+
+// run lengths as 64-bit words: the counts of a big genome are selected by rk_prim_select_u64 with the flags of its keys
+__global__ void k_widen_counts(const unsigned int *counts, uint64_t n, unsigned long long *out)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = counts[i];
+}
+
+// rk_sketches_from_host_counts: no count may be 0
+__global__ void k_check_counts(const uint32_t *counts, uint64_t total, uint32_t *bad)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total && counts[i] == 0) *bad = 1;
 }
 
 template <class K> __global__ void k_narrow_keys(const unsigned long long *ukeys, uint64_t n, K *out)
@@ -803,6 +843,7 @@ void rk_sketches_free(rk_sketches *s)
     rk_pool_free(s->ctx, s->d_hashes);
     rk_pool_free(s->ctx, s->d_hashes64);
     rk_pool_free(s->ctx, s->d_off);
+    rk_pool_free(s->ctx, s->d_counts);
     rk_pool_free(s->ctx, s->d_member_rec);
     rk_pool_free(s->ctx, s->d_member_seg);
     delete s;
@@ -882,9 +923,10 @@ int rk_sketch_packed_dev(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_
 }  // extern "C"
 
 // one big genome's candidate region: device-wide radix sort + unique (or run-length select), narrowed into its
-// slot of sorted_out; returns the number of distinct hashes kept
+// slot of sorted_out; returns the number of distinct hashes kept.  cdst (optional): the run length of every kept hash, next to
+// it -- the run-length route then serves min_count 1 too
 template <class K>
-static int dedup_big(rk_ctx *ctx, unsigned long long *region, uint32_t n, int hash_bits, uint32_t min_count, K *dst,
+static int dedup_big(rk_ctx *ctx, unsigned long long *region, uint32_t n, int hash_bits, uint32_t min_count, K *dst, uint32_t *cdst,
                      uint32_t *n_out, hipStream_t stream)
 {
     *n_out = 0;
@@ -895,11 +937,11 @@ static int dedup_big(rk_ctx *ctx, unsigned long long *region, uint32_t n, int ha
     RK_HIP(ctx, d_n.alloc(1));
     RK_TRY(rk_prim_sort_keys_u64(ctx, region, sorted.p, n, 0, (unsigned)hash_bits, stream));
     unsigned long long nu = 0;
-    if (min_count <= 1) {  // set semantics (FASTA, src/sketch.cpp:526-529)
+    if (min_count <= 1 && !cdst) {  // set semantics (FASTA, src/sketch.cpp:526-529)
         RK_TRY(rk_prim_unique_u64(ctx, sorted.p, uniq.p, d_n.p, n, stream));
         RK_TRY(rk_read_back(ctx, &nu, d_n.p, 8, stream));
     } else {  // FASTQ: keep a hash only if it occurred >= min_count times (src/sketch.cpp:828-845)
-        DevBuf<unsigned long long> runs(ctx);
+        DevBuf<unsigned long long> runs(ctx), wide_counts(ctx), kept_counts(ctx);
         DevBuf<unsigned int> counts(ctx);
         DevBuf<unsigned char> flags(ctx);
         RK_HIP(ctx, runs.alloc(n));
@@ -912,6 +954,15 @@ static int dedup_big(rk_ctx *ctx, unsigned long long *region, uint32_t n, int ha
             hipLaunchKernelGGL(k_count_flags, dim3(blocks_for(n_runs)), dim3(256), 0, stream, counts.p, n_runs, min_count, flags.p);
             RK_TRY(rk_prim_select_u64(ctx, runs.p, flags.p, uniq.p, d_n.p, n_runs, stream));
             RK_TRY(rk_read_back(ctx, &nu, d_n.p, 8, stream));
+            if (cdst && nu) {  // the counts, selected by the flags that selected the keys
+                RK_HIP(ctx, wide_counts.alloc(n_runs));
+                RK_HIP(ctx, kept_counts.alloc(n_runs));
+                hipLaunchKernelGGL(k_widen_counts, dim3(blocks_for(n_runs)), dim3(256), 0, stream, counts.p, n_runs, wide_counts.p);
+                RK_TRY(rk_prim_select_u64(ctx, wide_counts.p, flags.p, kept_counts.p, d_n.p, n_runs, stream));
+                hipLaunchKernelGGL(k_narrow_keys<uint32_t>, dim3(blocks_for(nu)), dim3(256), 0, stream, kept_counts.p, nu, cdst);
+                RK_HIP(ctx, hipGetLastError());
+                RK_HIP(ctx, hipStreamSynchronize(stream));  // wide_counts and kept_counts return to the pool with this scope
+            }
         }
     }
     if (nu) hipLaunchKernelGGL(k_narrow_keys<K>, dim3(blocks_for(nu)), dim3(256), 0, stream, uniq.p, nu, dst);
@@ -947,6 +998,7 @@ struct SketchPass {
     const rk_filter *f = nullptr;
     const uint8_t *packed = nullptr;
     uint32_t min_count = 1;
+    bool counts = false;  // a counted pass (rk_sketch_*_counts): the sketches carry per-hash occurrence counts
     hipStream_t stream = nullptr;
     int hash_bits = 0;
     bool wide = false;  // use64 layout
@@ -961,13 +1013,14 @@ struct SketchPass {
     DevBuf<char> d_work;
     DevBuf<unsigned long long> cand;
     DevBuf<char> sorted_out;  // per genome its sorted distinct hashes, at its region's offset
+    DevBuf<uint32_t> counts_out;  // counted pass: parallel to sorted_out, the count of every kept hash
     SketchTail *d_tail = nullptr;
     uint64_t *d_off_copy = nullptr;
     uint32_t *d_gcount = nullptr, *d_usize = nullptr, *d_tickets = nullptr;
     std::vector<uint32_t> gcount;
     SketchTail tail{0, 0};
     bool big_overflow = false;
-    explicit SketchPass(rk_ctx *c) : ctx(c), d_rows(c), d_chunks(c), d_work(c), cand(c), sorted_out(c) {}
+    explicit SketchPass(rk_ctx *c) : ctx(c), d_rows(c), d_chunks(c), d_work(c), cand(c), sorted_out(c), counts_out(c) {}
 };
 
 int pass_plan(SketchPass &p, const uint64_t *gbeg, const uint64_t *gend, uint32_t n_genomes, uint64_t packed_bytes)
@@ -1025,7 +1078,14 @@ template <class H> int pass_layout_regions(SketchPass &p)
     H *&hashes = hashes_of(p.s.p, H());
     rk_pool_free(p.ctx, hashes);
     hashes = nullptr;
-    return pool_array(p.ctx, &hashes, p.lay.total_cap + 1);
+    RK_TRY(pool_array(p.ctx, &hashes, p.lay.total_cap + 1));
+    if (!p.counts) return RK_OK;
+    // a counted pass: the counts of the regions and of the CSR, apart from the work buffer (PassLayout is that of an uncounted pass)
+    if (p.counts_out.alloc(counts_slots(p.lay, true)) != hipSuccess)
+        return rk_fail(p.ctx, RK_ERR_NOMEM, "cannot allocate %llu count slots", (unsigned long long)p.lay.total_cap);
+    rk_pool_free(p.ctx, p.s.p->d_counts);
+    p.s.p->d_counts = nullptr;
+    return pool_array(p.ctx, &p.s.p->d_counts, p.lay.total_cap + 1);
 }
 
 // rk_sketch_last_plan: the record of this attempt (max_candidates follows with the read-back)
@@ -1122,10 +1182,11 @@ int pass_scan(SketchPass &p)
 template <class H> int pass_dedup(SketchPass &p)
 {
     if (!p.plan.n_genomes) return RK_OK;
+    const auto kern = p.counts ? k_dedup<H, true> : k_dedup<H, false>;
     if (p.lay.small_lds > 48 * 1024)
-        RK_HIP(p.ctx, hipFuncSetAttribute((const void *)k_dedup<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.small_lds));
-    hipLaunchKernelGGL(k_dedup<H>, dim3(p.plan.n_genomes), dim3(kDedupThreads), p.lay.small_lds, p.stream, p.cand.p, p.d_rows.p, p.d_gcount,
-                       p.min_count, (H *)p.sorted_out.p, p.d_usize, p.d_tail);
+        RK_HIP(p.ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.small_lds));
+    hipLaunchKernelGGL(kern, dim3(p.plan.n_genomes), dim3(kDedupThreads), p.lay.small_lds, p.stream, p.cand.p, p.d_rows.p, p.d_gcount,
+                       p.min_count, (H *)p.sorted_out.p, p.d_usize, p.d_tail, p.counts ? p.counts_out.p : nullptr);
     RK_HIP(p.ctx, hipGetLastError());
     return RK_OK;
 }
@@ -1144,7 +1205,8 @@ template <class H> int pass_big_genomes(SketchPass &p)
     for (uint32_t g = 0; g < n_genomes && !p.big_overflow; g++) {
         if (!rows[g].is_big) continue;
         uint32_t nu = 0;
-        RK_TRY(dedup_big<H>(ctx, p.cand.p + rows[g].reg_off, p.gcount[g], p.hash_bits, p.min_count, (H *)p.sorted_out.p + rows[g].reg_off, &nu, p.stream));
+        RK_TRY(dedup_big<H>(ctx, p.cand.p + rows[g].reg_off, p.gcount[g], p.hash_bits, p.min_count, (H *)p.sorted_out.p + rows[g].reg_off,
+                             p.counts ? p.counts_out.p + rows[g].reg_off : nullptr, &nu, p.stream));
         memcpy(p.pinned, &nu, 4);
         RK_HIP(ctx, hipMemcpyAsync(p.d_usize + g, p.pinned, 4, hipMemcpyHostToDevice, p.stream));
         RK_HIP(ctx, hipStreamSynchronize(p.stream));  // the pinned word is reused
@@ -1160,6 +1222,9 @@ template <class H> int pass_place(SketchPass &p)
     if (p.plan.n_genomes)
         hipLaunchKernelGGL(k_csr_place<H>, dim3(p.plan.n_genomes), dim3(256), 0, p.stream, (const H *)p.sorted_out.p, p.d_rows.p, p.d_usize, s->d_off,
                            hashes_of(s, H()));
+    if (p.plan.n_genomes && p.counts)  // the counts follow their hashes: the same placement over the parallel region
+        hipLaunchKernelGGL(k_csr_place<uint32_t>, dim3(p.plan.n_genomes), dim3(256), 0, p.stream, (const uint32_t *)p.counts_out.p, p.d_rows.p, p.d_usize,
+                           s->d_off, s->d_counts);
     RK_HIP(p.ctx, hipGetLastError());
     return RK_OK;
 }
@@ -1205,11 +1270,9 @@ rk_sketches *pass_finish(SketchPass &p)
 }
 }  // namespace
 
-extern "C" {
-
-int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
-                            uint64_t packed_bytes, const uint64_t *gbeg, const uint64_t *gend,
-                            uint32_t n_genomes, uint32_t min_count, void *stream_v, rk_sketches **out)
+// rk_sketch_packed_dev_ex and rk_sketch_packed_dev_counts
+static int sketch_packed_dev(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev, uint64_t packed_bytes, const uint64_t *gbeg,
+                             const uint64_t *gend, uint32_t n_genomes, uint32_t min_count, bool counts, void *stream_v, rk_sketches **out)
 {
     if (!ctx || !f || !out || (!packed_dev && packed_bytes) || ((!gbeg || !gend) && n_genomes))
         return RK_ERR_ARG;
@@ -1219,6 +1282,7 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
     p.f = f;
     p.packed = packed_dev;
     p.min_count = min_count;
+    p.counts = counts;
     p.stream = (hipStream_t)stream_v;
     p.hash_bits = rk_hash_bits(&f->params);
     p.wide = p.hash_bits > 32;
@@ -1237,6 +1301,26 @@ int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *pack
     return RK_OK;
 }
 
+// rk_sketch_batch_ex and rk_sketch_batch_counts
+static int sketch_batch(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const uint8_t *qual, int least_qual, uint32_t min_count, bool counts,
+                        const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_rec, uint32_t n_genomes, rk_sketches **out);
+
+extern "C" {
+
+int rk_sketch_packed_dev_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
+                            uint64_t packed_bytes, const uint64_t *gbeg, const uint64_t *gend,
+                            uint32_t n_genomes, uint32_t min_count, void *stream_v, rk_sketches **out)
+{
+    return sketch_packed_dev(ctx, f, packed_dev, packed_bytes, gbeg, gend, n_genomes, min_count, false, stream_v, out);
+}
+
+int rk_sketch_packed_dev_counts(rk_ctx *ctx, const rk_filter *f, const uint8_t *packed_dev,
+                                uint64_t packed_bytes, const uint64_t *gbeg, const uint64_t *gend,
+                                uint32_t n_genomes, uint32_t min_count, void *stream_v, rk_sketches **out)
+{
+    return sketch_packed_dev(ctx, f, packed_dev, packed_bytes, gbeg, gend, n_genomes, min_count, true, stream_v, out);
+}
+
 int rk_sketch_batch(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const uint64_t *rec_off,
                     uint64_t n_rec, const uint64_t *genome_rec, uint32_t n_genomes, rk_sketches **out)
 {
@@ -1246,6 +1330,21 @@ int rk_sketch_batch(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const u
 int rk_sketch_batch_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const uint8_t *qual, int least_qual,
                        uint32_t min_count, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_rec,
                        uint32_t n_genomes, rk_sketches **out)
+{
+    return sketch_batch(ctx, f, seq, qual, least_qual, min_count, false, rec_off, n_rec, genome_rec, n_genomes, out);
+}
+
+int rk_sketch_batch_counts(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const uint8_t *qual, int least_qual,
+                           uint32_t min_count, const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_rec,
+                           uint32_t n_genomes, rk_sketches **out)
+{
+    return sketch_batch(ctx, f, seq, qual, least_qual, min_count, true, rec_off, n_rec, genome_rec, n_genomes, out);
+}
+
+}  // extern "C"
+
+static int sketch_batch(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, const uint8_t *qual, int least_qual, uint32_t min_count, bool counts,
+                        const uint64_t *rec_off, uint64_t n_rec, const uint64_t *genome_rec, uint32_t n_genomes, rk_sketches **out)
 {
     if (!ctx || !f || !rec_off || !genome_rec || !out || (!seq && rec_off[n_rec])) return RK_ERR_ARG;
     *out = nullptr;
@@ -1279,11 +1378,8 @@ int rk_sketch_batch_ex(rk_ctx *ctx, const rk_filter *f, const uint8_t *seq, cons
         rc = rk_fail(ctx, RK_ERR_HIP, "sequence upload failed");
     (void)hipHostFree(h_packed);
     if (rc) return rc;
-    return rk_sketch_packed_dev_ex(ctx, f, d_packed.p, bytes, gbeg.data(), gend.data(), n_genomes,
-                                   min_count ? min_count : 1, ctx->stream, out);
+    return sketch_packed_dev(ctx, f, d_packed.p, bytes, gbeg.data(), gend.data(), n_genomes, min_count ? min_count : 1, counts, ctx->stream, out);
 }
-
-}  // extern "C"
 
 static int check_sets(rk_ctx *ctx, rk_sketches *s, bool *ascending)
 {
@@ -1303,6 +1399,73 @@ static int check_sets(rk_ctx *ctx, rk_sketches *s, bool *ascending)
     *ascending = b == 0;
     return RK_OK;
 }
+
+// ---- counted sketches: the optional device array of per-hash occurrence counts ---------------------------------------------
+extern "C" {
+
+int rk_sketches_has_counts(const rk_sketches *s) { return s && s->d_counts ? 1 : 0; }
+const uint32_t *rk_sketches_counts_dev(const rk_sketches *s) { return s ? s->d_counts : nullptr; }
+
+int rk_sketches_download_counts(const rk_sketches *s, uint32_t *counts)
+{
+    if (!s || !counts) return RK_ERR_ARG;
+    rk_ctx *ctx = s->ctx;
+    if (!s->d_counts) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "these sketches carry no counts");
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    if (s->total) {
+        RK_HIP(ctx, hipMemcpyAsync(counts, s->d_counts, s->total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return RK_OK;
+}
+
+// A counted import is taken as it is or not at all: sorting it (rk_sketches_classify) would tear the counts from their hashes
+int rk_sketches_from_host_counts(rk_ctx *ctx, const void *hashes, int wide, const uint32_t *counts, const uint64_t *off, uint32_t n,
+                                 rk_sketches **out)
+{
+    if (!ctx || !off || !out || ((!hashes || !counts) && off[n])) return RK_ERR_ARG;
+    *out = nullptr;
+    if (off[0] != 0) return rk_fail(ctx, RK_ERR_ARG, "off[0] must be 0");
+    for (uint32_t g = 0; g < n; g++)
+        if (off[g + 1] < off[g]) return rk_fail(ctx, RK_ERR_ARG, "offsets must be non-decreasing");
+    RK_HIP(ctx, hipSetDevice(ctx->device));
+    rk_sketches *s = new (std::nothrow) rk_sketches;
+    if (!s) return RK_ERR_NOMEM;
+    s->ctx = ctx;
+    s->n = n;
+    s->wide = wide != 0;
+    s->total = off[n];
+    s->h_off.assign(off, off + n + 1);
+    SketchesGuard guard{s};
+    RK_TRY(with_hash_type(s->wide, [&](auto ht) -> int {
+        using H = decltype(ht);
+        RK_TRY(pool_array(ctx, &hashes_of(s, ht), s->total + 1));
+        if (s->total) RK_HIP(ctx, hipMemcpyAsync(hashes_of(s, ht), hashes, s->total * sizeof(H), hipMemcpyHostToDevice, ctx->stream));
+        return RK_OK;
+    }));
+    RK_TRY(pool_array(ctx, &s->d_counts, s->total + 1));
+    RK_TRY(pool_array(ctx, &s->d_off, (size_t)n + 1));
+    if (s->total) RK_HIP(ctx, hipMemcpyAsync(s->d_counts, counts, s->total * 4, hipMemcpyHostToDevice, ctx->stream));
+    RK_HIP(ctx, hipMemcpyAsync(s->d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (uint32_t g = 0; g < n; g++) s->max_size = std::max<uint64_t>(s->max_size, off[g + 1] - off[g]);
+    bool ascending = true;
+    RK_TRY(check_sets(ctx, s, &ascending));  // synchronises the stream
+    if (!ascending) return rk_fail(ctx, RK_ERR_ARG, "rk_sketches_from_host_counts: every genome's hashes must be strictly ascending");
+    DevBuf<uint32_t> bad(ctx);
+    RK_HIP(ctx, bad.alloc(1));
+    RK_HIP(ctx, hipMemsetAsync(bad.p, 0, 4, ctx->stream));
+    if (s->total) hipLaunchKernelGGL(k_check_counts, dim3(blocks_for(s->total)), dim3(256), 0, ctx->stream, s->d_counts, s->total, bad.p);
+    RK_HIP(ctx, hipGetLastError());
+    uint32_t b = 0;
+    RK_TRY(rk_read_back(ctx, &b, bad.p, 4, ctx->stream));
+    if (b) return rk_fail(ctx, RK_ERR_ARG, "rk_sketches_from_host_counts: a count of 0");
+    s->is_set = true;
+    guard.p = nullptr;
+    *out = s;
+    return RK_OK;
+}
+
+}  // extern "C"
 
 // Sketches that crossed the boundary from the host (or from caller-owned device arrays).  A `.sketch` written by the
 // reference lists every genome's hashes in `unordered_set` iteration order (src/sketch.cpp:537-553: the sort is commented

@@ -148,6 +148,10 @@ inline AttemptLayout layout_attempt(std::vector<GenomeRow> &rows, uint32_t n_gen
     return a;
 }
 
+// a counted pass (rk_sketch_*_counts) keeps one 32-bit count per slot of sorted_out, in a region of its own with the regions'
+// offsets: the work buffer (PassLayout) and the candidate regions are those of the uncounted pass, which allocates no count
+inline uint64_t counts_slots(const AttemptLayout &a, bool counted) { return counted ? a.total_cap : 0; }
+
 // after the read-back: a genome that emitted more candidates than its region holds gets exactly that many on the second pass;
 // `overflowed`: the device (k_dedup's flag) or the big-genome loop saw one
 struct RetryOutcome {

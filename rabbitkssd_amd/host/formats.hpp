@@ -31,6 +31,8 @@ struct SketchSet {  // in-memory form of a .sketch file
     std::vector<uint32_t> hashes;    // CSR values, 32-bit layout (half_k - drlevel <= 8)
     std::vector<uint64_t> hashes64;  // CSR values, 64-bit layout (use64, src/sketch.cpp:336)
     std::vector<uint64_t> off{0};    // CSR offsets, names.size()+1
+    std::vector<uint32_t> counts;    // optional, aligned with the hashes: occurrences of every hash in its genome (the side-car
+                                     // <path>.sketch.abund, not the .sketch file); empty without
     size_t size() const { return names.size(); }
     bool wide() const { return info.half_k - info.drlevel > 8; }
     uint64_t total() const { return off.empty() ? 0 : off.back(); }
@@ -128,6 +130,7 @@ inline bool save_sketches(const std::string &path, SketchSet &s, std::string &er
     fwrite(cnt.data(), 4, s.size(), fp);
     for (size_t i = 0; i < s.size(); i++) {
         fwrite(s.names[i].data(), 1, s.names[i].size(), fp);
+        if (!cnt[i]) continue;   // (sketches without any hash have no array to point into)
         if (s.wide()) fwrite(s.hashes64.data() + s.off[i], 8, (size_t)cnt[i], fp);  // :1055-1058
         else fwrite(s.hashes.data() + s.off[i], 4, (size_t)cnt[i], fp);
     }
@@ -172,6 +175,122 @@ inline bool read_sketches(const std::string &path, SketchSet &s, std::string &er
     }
     fclose(fp);
     return true;
+}
+
+// ---- .sketch.abund: the occurrence counts of a counted sketch ------------------------------
+// The .sketch format is the reference's and knows no counts: they go to a side-car next to it, little-endian:
+//   char magic[8] = "RKABUND1"; u32 n_genomes; u32 reserved = 0; u64 total; u32 sizes[n_genomes]; u32 counts[total]
+// counts[i] belongs to the i-th hash as the .sketch file stores it; sizes repeat the sketch sizes, so that a side-car that
+// belongs to another .sketch is noticed.
+struct AbundHeader {
+    char magic[8];
+    uint32_t n_genomes, reserved;
+    uint64_t total;
+};
+static_assert(sizeof(AbundHeader) == 24, "written as raw bytes");
+inline const char *abund_magic() { return "RKABUND1"; }
+inline std::string abund_path(const std::string &sketch_path) { return sketch_path + ".abund"; }
+
+// s.counts next to s, to `path` (abund_path of where s is saved)
+inline bool save_abund(const std::string &path, const SketchSet &s, std::string &err)
+{
+    if (s.counts.size() != s.total()) { err = "counts do not match the sketches: " + path; return false; }
+    FILE *fp = fopen(path.c_str(), "wb");
+    if (!fp) { err = "cannot write " + path; return false; }
+    AbundHeader h;
+    memcpy(h.magic, abund_magic(), 8);
+    h.n_genomes = (uint32_t)s.size();
+    h.reserved = 0;
+    h.total = s.total();
+    std::vector<uint32_t> sizes(s.size());
+    for (size_t i = 0; i < s.size(); i++) sizes[i] = (uint32_t)(s.off[i + 1] - s.off[i]);
+    bool good = fwrite(&h, sizeof(h), 1, fp) == 1 && (sizes.empty() || fwrite(sizes.data(), 4, sizes.size(), fp) == sizes.size()) &&
+                (s.counts.empty() || fwrite(s.counts.data(), 4, s.counts.size(), fp) == s.counts.size());
+    if (fclose(fp)) good = false;
+    if (!good) { err = "write error on " + path; return false; }
+    return true;
+}
+
+// the side-car of the sketches s (already read) into s.counts; every refusal names the file
+inline bool read_abund(const std::string &path, SketchSet &s, std::string &err)
+{
+    s.counts.clear();
+    FILE *fp = fopen(path.c_str(), "rb");
+    if (!fp) { err = "cannot open the abundance file: " + path; return false; }
+    auto fail = [&](const std::string &what) { fclose(fp); s.counts.clear(); err = what + ": " + path; return false; };
+    struct stat st;
+    if (fstat(fileno(fp), &st)) return fail("cannot stat the abundance file");
+    AbundHeader h;
+    if (fread(&h, sizeof(h), 1, fp) != 1 || memcmp(h.magic, abund_magic(), 8) != 0) return fail("not an abundance file (wrong magic)");
+    const unsigned __int128 want = (unsigned __int128)sizeof(h) + (unsigned __int128)h.n_genomes * 4 + (unsigned __int128)h.total * 4;
+    if ((unsigned __int128)st.st_size != want) return fail("the file length is not what the abundance header implies");
+    if (h.n_genomes != s.size()) return fail("the number of genomes differs from the sketch file's");
+    std::vector<uint32_t> sizes(h.n_genomes);
+    if (!sizes.empty() && fread(sizes.data(), 4, sizes.size(), fp) != sizes.size()) return fail("mismatched read of the sizes");
+    for (size_t i = 0; i < s.size(); i++)
+        if (sizes[i] != s.off[i + 1] - s.off[i]) return fail("a sketch size differs from the sketch file's (genome " + std::to_string(i) + ")");
+    if (h.total != s.total()) return fail("the total differs from the sketch file's");
+    s.counts.resize(h.total);
+    if (h.total && fread(s.counts.data(), 4, s.counts.size(), fp) != s.counts.size()) return fail("mismatched read of the counts");
+    for (uint32_t c : s.counts)
+        if (c == 0) return fail("a count of 0");
+    fclose(fp);
+    return true;
+}
+
+// what `abund` reports of one genome: spectrum[c] hashes occur c times for 1 <= c < bins, spectrum[bins] the rest
+struct AbundStats {
+    uint64_t distinct = 0, occurrences = 0;
+    uint32_t largest = 0, median = 0;   // lower median; 0 for an empty genome
+    std::vector<uint64_t> spectrum;
+};
+inline AbundStats abund_stats(const uint32_t *c, uint64_t n, uint32_t bins)
+{
+    AbundStats r;
+    r.distinct = n;
+    r.spectrum.assign((size_t)bins + 1, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        r.occurrences += c[i];
+        r.largest = std::max(r.largest, c[i]);
+        r.spectrum[std::min(c[i], bins)]++;
+    }
+    if (n) {
+        std::vector<uint32_t> v(c, c + n);
+        std::nth_element(v.begin(), v.begin() + (n - 1) / 2, v.end());
+        r.median = v[(n - 1) / 2];
+    }
+    return r;
+}
+
+// per genome: name, distinct hashes, occurrences, largest count, lower median; then `count<TAB>n_hashes` per non-empty bin,
+// the hashes with bins occurrences and more as `>=bins`
+inline void write_abund_report(FILE *fp, const SketchSet &s, uint32_t bins)
+{
+    for (size_t g = 0; g < s.size(); g++) {
+        const AbundStats a = abund_stats(s.counts.data() + s.off[g], s.off[g + 1] - s.off[g], bins);
+        fprintf(fp, "%s\t%llu\t%llu\t%u\t%u\n", s.names[g].c_str(), (unsigned long long)a.distinct, (unsigned long long)a.occurrences, a.largest, a.median);
+        for (uint32_t c = 1; c < bins; c++)
+            if (a.spectrum[c]) fprintf(fp, "%u\t%llu\n", c, (unsigned long long)a.spectrum[c]);
+        if (a.spectrum[bins]) fprintf(fp, ">=%u\t%llu\n", bins, (unsigned long long)a.spectrum[bins]);
+    }
+}
+
+// the sketches reduced to the hashes whose count lies in [lo, hi]: the same header and names, emptied genomes kept
+inline void abund_threshold(const SketchSet &in, uint32_t lo, uint32_t hi, SketchSet &out)
+{
+    out = SketchSet();
+    out.info = in.info;
+    out.names = in.names;
+    out.off.assign(1, 0);
+    for (size_t g = 0; g < in.size(); g++) {
+        for (uint64_t i = in.off[g]; i < in.off[g + 1]; i++) {
+            if (in.counts[i] < lo || in.counts[i] > hi) continue;
+            if (in.wide()) out.hashes64.push_back(in.hashes64[i]);
+            else out.hashes.push_back(in.hashes[i]);
+            out.counts.push_back(in.counts[i]);
+        }
+        out.off.push_back(out.counts.size());
+    }
 }
 
 // ---- .dict / .index, 32-bit layout (src/sketch.cpp:991-1011, src/dist.cpp:86-129) -------

@@ -6,6 +6,8 @@
 //                                             FASTA or FASTQ lists, plain or .gz)
 //   alldist  -i sketch|list -o out [-D -M -L]            (GPU: rk_index_build, rk_dist_rows)
 //   dist     -r ref -q qry -o out [-D -M -N -L]          (GPU: rk_dist_rows; -N: rk_dist_topn)
+//   sketch   ... --abund                     (the counted calls: also <out>.sketch.abund, the occurrence count of every kept hash)
+//   abund    -i sketch [-o out] [--bins B] | --min-count N [--max-count M] -o out.sketch   (host only: report / band of counts)
 //   info     -i sketch -o out [-F]           (host only, src/subCommand.cpp:70-147)
 //   merge    -i list -o out                  (host only, src/subCommand.cpp:796-892)
 //   union / sub                              (host only, src/subCommand.cpp:307-794)
@@ -172,6 +174,7 @@ struct ListSketcher {
     const int threads;
     const FastqOpts &fq;
     SketchSet &out;
+    const bool abund;   // --abund: every sketch call is the counted one, out.counts follows out.hashes
     const bool timing = getenv("RK_TIMING") != nullptr;
     uint64_t total_windows = 0;
 
@@ -189,6 +192,9 @@ struct ListSketcher {
     PieceRing<size_t> staging{2, 1};
 
     uint32_t min_count() const { return (uint32_t)std::max(1, fq.least_num); }
+    // the packed sketch call of this job: the counted one with --abund (the same arguments)
+    decltype(&rk_sketch_packed_dev_ex) packed_call() const { return abund ? rk_sketch_packed_dev_counts : rk_sketch_packed_dev_ex; }
+    const char *packed_name() const { return abund ? "rk_sketch_packed_dev_counts" : "rk_sketch_packed_dev_ex"; }
 
     void plan()
     {
@@ -246,6 +252,10 @@ struct ListSketcher {
             d.hashes.resize(rk_sketches_total(sk));
             gpu.check(rk_sketches_download(sk, d.hashes.data(), d.off.data()), "rk_sketches_download");
         }
+        if (abund) {
+            d.counts.resize(rk_sketches_total(sk));
+            if (!d.counts.empty()) gpu.check(rk_sketches_download_counts(sk, d.counts.data()), "rk_sketches_download_counts");
+        }
         total_windows += rk_sketches_windows(sk);
         return d;
     }
@@ -253,6 +263,7 @@ struct ListSketcher {
     {
         if (out.wide()) out.hashes64.insert(out.hashes64.end(), d.hashes64.begin() + d.off[first], d.hashes64.begin() + d.off[last]);
         else out.hashes.insert(out.hashes.end(), d.hashes.begin() + d.off[first], d.hashes.begin() + d.off[last]);
+        if (abund) out.counts.insert(out.counts.end(), d.counts.begin() + d.off[first], d.counts.begin() + d.off[last]);
         for (uint32_t i = first; i < last; i++) out.off.push_back(out.off.back() + (d.off[i + 1] - d.off[i]));
     }
     void slow_path(size_t file_idx, rk_sketches **sk)  // whole file through rk_sketch_batch_ex
@@ -263,8 +274,9 @@ struct ListSketcher {
             die("cannot open the genome file: %s", files[file_idx].c_str());
         if (rec_off.empty()) rec_off.push_back(0);
         genome_rec.push_back(rec_off.size() - 1);
-        gpu.check(rk_sketch_batch_ex(gpu.ctx, flt, seq.data(), fq.fastq ? qual.data() : nullptr, fq.least_qual, min_count(), rec_off.data(),
-                                     rec_off.size() - 1, genome_rec.data(), 1, sk), "rk_sketch_batch_ex");
+        gpu.check((abund ? rk_sketch_batch_counts : rk_sketch_batch_ex)(gpu.ctx, flt, seq.data(), fq.fastq ? qual.data() : nullptr, fq.least_qual, min_count(),
+                                                                        rec_off.data(), rec_off.size() - 1, genome_rec.data(), 1, sk),
+                  abund ? "rk_sketch_batch_counts" : "rk_sketch_batch_ex");
     }
     // rare: the genomes of a batch whose slots overflowed take the slow path, spliced in in list order
     void append_spliced(const Batch &bt, rk_sketches *sk)
@@ -316,8 +328,8 @@ struct ListSketcher {
         {
             const double t = get_sec();
             const uint64_t gbeg = 0, gend = used;
-            job.gpu.check(rk_sketch_packed_dev_ex(job.gpu.ctx, job.flt, (const uint8_t *)d_buf, used, &gbeg, &gend, 1, job.min_count(), job.stream,
-                                                  sk_out), "rk_sketch_packed_dev_ex");
+            job.gpu.check(job.packed_call()(job.gpu.ctx, job.flt, (const uint8_t *)d_buf, used, &gbeg, &gend, 1, job.min_count(), job.stream, sk_out),
+                          job.packed_name());
             kernel_sec = get_sec() - t;
         }
     };
@@ -414,8 +426,7 @@ struct ListSketcher {
             }
             const double t_gpu = get_sec();
             gpu.check(rk_upload_async(gpu.ctx, dev[bi], bt.pageable ? big_stage.data() : stage[bi], bt.bytes, stream), "rk_upload_async");
-            gpu.check(rk_sketch_packed_dev_ex(gpu.ctx, flt, (const uint8_t *)dev[bi], bt.bytes, gbeg.data(), gend.data(), nb, min_count(),
-                                              stream, &sk), "rk_sketch_packed_dev_ex");
+            gpu.check(packed_call()(gpu.ctx, flt, (const uint8_t *)dev[bi], bt.bytes, gbeg.data(), gend.data(), nb, min_count(), stream, &sk), packed_name());
             if (timing) fprintf(stderr, "[timing] batch %zu: upload + sketch of %.1f MB: %.3f s\n", k, bt.bytes / 1e6, get_sec() - t_gpu);
         }
         staging.release(bi);   // the call above synchronised the stream: the staging buffer can be refilled
@@ -442,7 +453,7 @@ struct ListSketcher {
 };
 
 static void sketch_list(Gpu &gpu, const string &list, const Shuf &shuf, int threads, SketchSet &out, const string &out_path_in,
-                        const FastqOpts &fq = FastqOpts())
+                        const FastqOpts &fq = FastqOpts(), bool abund = false)
 {
     const double t0 = get_sec();
     rk_params P;
@@ -462,7 +473,7 @@ static void sketch_list(Gpu &gpu, const string &list, const Shuf &shuf, int thre
     out.names = files;
     out.off.assign(1, 0);
 
-    ListSketcher job{gpu, flt, files, shuf, threads, fq, out};
+    ListSketcher job{gpu, flt, files, shuf, threads, fq, out, abund};
     job.run();
     rk_filter_free(flt);
 
@@ -471,6 +482,10 @@ static void sketch_list(Gpu &gpu, const string &list, const Shuf &shuf, int thre
     string err;
     if (!save_sketches(out_path, out, err)) die("%s", err.c_str());
     cerr << "save the sketches into: " << out_path << endl;
+    if (abund) {   // the occurrence counts, next to the .sketch (which stays the reference's format)
+        if (!save_abund(abund_path(out_path), out, err)) die("%s", err.c_str());
+        cerr << "save the occurrence counts into: " << abund_path(out_path) << endl;
+    }
     cerr << "===================time of sketching " << files.size() << " genomes (" << job.total_windows
          << " k-mers) is: " << get_sec() - t0 << endl;
 }
@@ -705,6 +720,7 @@ static int cmd_sketch(const Args &a)
     const string in = a.str("i", ""), out = a.str("o", "");
     const bool is_query = a.has("q");
     const int threads = a.num("t", (int)std::thread::hardware_concurrency());
+    if (a.has("abund") && is_sketch_file(in)) die("sketch --abund needs sequence files: a .sketch file holds no occurrence counts");
     Gpu gpu(a.num("device", 0));
     string err;
     if (is_sketch_file(in)) {  // src/main.cpp:189-214: copy, and (re)build the index unless -q
@@ -724,7 +740,7 @@ static int cmd_sketch(const Args &a)
     fq.least_num = a.num("n", 1);
     SketchSet s;
     string out_path = out;
-    sketch_list(gpu, in, shuf, threads, s, out_path, fq);
+    sketch_list(gpu, in, shuf, threads, s, out_path, fq, a.has("abund"));
     if (!is_sketch_file(out_path)) out_path += ".sketch";
     if (!is_query) rk_index_free(build_index(gpu, s, out_path, true));
     return 0;
@@ -2233,6 +2249,41 @@ static int cmd_info(const Args &a)
     return 0;
 }
 
+// abund: what the side-car of a counted sketch (sketch --abund) holds.  Host only: no GPU is opened.
+//   -i x.sketch [-o FILE] [--bins B]: per genome its name, distinct hashes, occurrences, largest count and lower median, then the
+//   count spectrum (write_abund_report)
+//   -i x.sketch --min-count N [--max-count M] -o y.sketch: the sketches reduced to the hashes with N <= count <= M, and y.sketch.abund
+static int cmd_abund(const Args &a)
+{
+    if (!a.has("i")) die("abund needs -i");
+    const string in = a.str("i", "");
+    SketchSet s;
+    string err;
+    if (!read_sketches(in, s, err)) die("command_abund(), %s", err.c_str());
+    if (!read_abund(abund_path(in), s, err)) die("command_abund(), %s", err.c_str());
+    if (a.has("min-count") || a.has("max-count")) {
+        const long long lo = atoll(a.str("min-count", "1").c_str()), hi = a.has("max-count") ? atoll(a.str("max-count", "").c_str()) : 0xFFFFFFFFLL;
+        if (lo < 1) die("command_abund(), --min-count must be at least 1");
+        if (hi < lo) die("command_abund(), --max-count must not be below --min-count");
+        if (!a.has("o")) die("abund --min-count / --max-count needs -o");
+        string out = a.str("o", "");
+        if (!is_sketch_file(out)) out += ".sketch";
+        SketchSet kept;
+        abund_threshold(s, (uint32_t)std::min(lo, 0xFFFFFFFFLL), (uint32_t)std::min(hi, 0xFFFFFFFFLL), kept);
+        if (!save_sketches(out, kept, err)) die("%s", err.c_str());
+        if (!save_abund(abund_path(out), kept, err)) die("%s", err.c_str());
+        cerr << "kept " << kept.total() << " of " << s.total() << " hashes of " << s.size() << " genomes" << endl;
+        return 0;
+    }
+    const int bins = a.num("bins", 64);
+    if (bins < 1) die("command_abund(), --bins must be at least 1");
+    FILE *fp = a.has("o") ? fopen(a.str("o", "").c_str(), "w") : stdout;
+    if (!fp) die("cannot write %s", a.str("o", "").c_str());
+    write_abund_report(fp, s, (uint32_t)bins);
+    if (fp != stdout) fclose(fp);
+    return 0;
+}
+
 static int cmd_merge(const Args &a)
 {
     if (!a.has("i") || !a.has("o")) die("merge needs -i and -o");
@@ -2475,9 +2526,9 @@ static int cmd_parse(int argc, char **argv)
 static int usage()
 {
     cerr << "rabbit_kssd (MI355X build, " << rk_version() << ")\n"
-            "subcommands: shuffle sketch alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert screen merge lca info mask\n"
+            "subcommands: shuffle sketch abund alldist cluster forest greedy knn dbscan mreach medoid assign dist group union sub gather convert screen merge lca info mask\n"
             "  shuffle -k K -s S -l L -o out.shuf\n"
-            "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--device N]\n"
+            "  sketch  -i genomes.list -o out[.sketch] [-L file.shuf] [-t T] [-q] [--abund] [--device N]   (--abund: also out.sketch.abund, how often every kept hash occurred in its genome or read set)\n"
             "  alldist -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]\n"
             "  cluster -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (single-linkage clusters of alldist's pairs)\n"
             "  forest -i in.sketch|genomes.list -o out [-D maxDist] [-M 0|1] [-L file.shuf] [--device N] [--gpus G]   (minimum spanning forest of alldist's pairs: the single-linkage dendrogram up to -D, one alldist line per edge)\n"
@@ -2491,6 +2542,7 @@ static int usage()
             "  gather -r ref.sketch|list -q qry.sketch|list [--min-new 1] [--max-picks 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references explain each query, greedily: per round the reference that holds most of the query's hashes no earlier pick held, ties to the earlier reference, until a pick would add fewer than --min-new hashes or --max-picks are made; one line per pick: query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref; --summary: per query its name, size, hashes some reference holds, hashes the picks explain, references sharing at least --min-new hashes, picks; --sub: the queries first lose every hash a sketch of host.sketch holds, on the device -- the cover of what sub would write; one GPU)\n"
             "  screen  -r ref.sketch|list -q qry.sketch|list [--min-common 1] [--min-won 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references are contained in each query, every shared hash credited to one of them -- mash screen -w in one pass: among the references that share at least --min-common hashes with the query a hash goes to the one with the larger common / size, compared exactly, then to the larger, then to the earlier one; one line per reference that keeps at least --min-won hashes: query, reference, common, size_ref, won, identity = (common / size_ref)^(1/K) and identity_won = (won / size_ref)^(1/K) for the sketches' k-mer length K; --summary: per query its name, size, hashes some reference holds, candidates, hashes claimed, records; --sub as in gather; Mash's p-value and median multiplicity are not offered: Kssd sketches carry no multiplicities; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
+            "  abund   -i in.sketch [-o out] [--bins 64]   |   abund -i in.sketch --min-count N [--max-count M] -o out.sketch   (the occurrence counts of a counted sketch, in.sketch.abund as sketch --abund writes it: per genome a line name, distinct hashes, occurrences, largest count, lower median, then count<TAB>hashes per non-empty bin below --bins and >=bins for the rest; with --min-count / --max-count the sketches reduced to the hashes whose count lies in [N, M], emptied genomes kept, and out.sketch.abund; host only)\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
             "  union   -i in.sketch -o out.sketch\n"
@@ -2516,6 +2568,7 @@ int main(int argc, char **argv)
         {"--pan", "pan"}, {"--share", "share"}, {"--min-count", "min-count"}, {"--only", "only"}, {"--map", "map"},
         {"--min-new", "min-new"}, {"--max-picks", "max-picks"}, {"--min-common", "min-common"}, {"--min-won", "min-won"}, {"--summary", "summary"}, {"--sub", "sub"},
         {"--keep", "keep"}, {"--min-refs", "min-refs"}, {"--max-refs", "max-refs"},
+        {"--abund", "abund"}, {"--max-count", "max-count"}, {"--bins", "bins"},
         {"--taxonomy", "taxonomy"}, {"--taxa", "taxa"}, {"--confidence", "confidence"}, {"--of", "of"}};
     if (sub == "_parse") return cmd_parse(argc, argv);
     if (sub == "_format") return cmd_format(argc, argv);
@@ -2550,7 +2603,7 @@ int main(int argc, char **argv)
         _exit(rc);
         return rc;
     };
-    if (sub == "sketch") { cerr << "-----run the subcommand: sketch" << endl; return leave(cmd_sketch(parse_args(argc, argv, 2, alias, {"q"}))); }
+    if (sub == "sketch") { cerr << "-----run the subcommand: sketch" << endl; return leave(cmd_sketch(parse_args(argc, argv, 2, alias, {"q", "abund"}))); }
     if (sub == "alldist") { cerr << "-----run the subcommand: alldist" << endl; return leave(cmd_alldist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "cluster") { cerr << "-----run the subcommand: cluster" << endl; return leave(cmd_cluster(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "forest") { cerr << "-----run the subcommand: forest" << endl; return leave(cmd_forest(parse_args(argc, argv, 2, alias, {"same-device"}))); }
@@ -2566,6 +2619,7 @@ int main(int argc, char **argv)
     if (sub == "mask") { cerr << "-----run the subcommand: mask" << endl; return leave(cmd_mask(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "lca") { cerr << "-----run the subcommand: lca" << endl; return leave(cmd_lca(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
+    if (sub == "abund") { cerr << "-----run the subcommand: abund" << endl; return cmd_abund(parse_args(argc, argv, 2, alias, {})); }
     if (sub == "info") { cerr << "-----run the subcommand: info" << endl; return cmd_info(parse_args(argc, argv, 2, alias, {"F"})); }
     if (sub == "merge") { cerr << "-----run the subcommand: merge" << endl; return cmd_merge(parse_args(argc, argv, 2, alias, {})); }
     if (sub == "convert") { cerr << "-----run the subcommand: convert" << endl; return cmd_convert(parse_args(argc, argv, 2, alias, {"q", "reverse"})); }
