@@ -42,6 +42,7 @@
 #include "rk_dist_plan.h"
 #include "rk_edge_order.h"
 #include "rk_edge_stage.h"
+#include "rk_query_dev.h"
 
 namespace {
 
@@ -61,8 +62,6 @@ __host__ __device__ inline rk_hit absent_record()
 {
     return rk_hit{kNone, kNone, 0, 0, 0, 0, 0.0, 0.0};
 }
-
-__device__ __forceinline__ void add_u32(uint32_t *p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // records: nearest / runner_up may be null (no record array asked for).  label[] is written by k_assign_label, the counts by a memset
 __global__ void k_assign_init(unsigned long long *best_w, unsigned long long *second_w, uint32_t *best_nb, uint32_t *second_nb, rk_hit *nearest, rk_hit *runner_up,

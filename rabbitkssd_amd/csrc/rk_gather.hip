@@ -7,9 +7,9 @@
 //
 // Per batch of query rows (as many counter rows as RK_GATHER_BATCH_BYTES holds), all on ctx->stream:
 //   counts      rk_distq_counts (stage A of rk_dist_topn): int32 cnt[slot][N], columns in the caller's order.  These rows are the MUTABLE rem;
-//   candidates  k_gather_candidates<false> counts the cells >= min_new of a row (n_cand), k_gather_scan turns the counts into the rows'
+//   candidates  k_gather_candidates<false> counts the cells >= min_new of a row (n_cand), k_query_scan turns the counts into the rows'
 //               regions, k_gather_candidates<true> compacts (common << 32 | ref) into them -- exact room, no retry; one reservation per wave;
-//   match       k_gather_match: per query hash the index of its posting list through the prefix directory (or none); the hits are appended
+//   match       k_gather_match: per query hash the index of its posting list (the look-up of rk_query_dev.h) or none; the hits are appended
 //               as items slot << 32 | list (one reservation per wave) and counted per row (matched);
 //   rounds      two kernels per round over the whole batch:
 //               k_gather_pick   one workgroup per live row: the maximum of (rem, -ref) over the row's candidates, rem read from the
@@ -23,8 +23,8 @@
 //                               by the workgroup (an LDS queue) beyond.  A list dies at most once: the decrements of a batch total at
 //                               most the postings under its matched lists;
 //               the items are compacted (k_gather_compact) when fewer than half are alive;
-//   picks       k_gather_scan over the rows' pick counts + k_gather_take: the batch's picks in (query, rank) order;
-//   result      off[Q + 1] by k_gather_scan over all rows; ONE copy to the host: 8 (Q + 1) + 12 Q + 32 picks bytes.
+//   picks       k_query_scan over the rows' pick counts + k_gather_take: the batch's picks in (query, rank) order;
+//   result      off[Q + 1] by k_query_scan over all rows; ONE copy to the host: 8 (Q + 1) + 12 Q + 32 picks bytes.
 //
 // Termination: a round either appends a pick with fresh >= min_new >= 1 or retires the row, and a pick takes fresh hashes out of M, so a
 // row makes at most min(max_picks, matched, N) picks and retires in the round after its last one at the latest: the host launches at
@@ -41,6 +41,8 @@
 #include <vector>
 
 #include "rk_internal.h"
+#include "rk_query_dev.h"
+#include "rk_query_host.h"
 
 namespace {
 
@@ -56,82 +58,6 @@ struct Counters {   // one device block, read back in one copy
     unsigned long long live_rows, n_items, dead_items, n_compacted, picks, decrements, lane_lists, wave_lists, block_lists;
     unsigned long long cand_total, region_total, take_total;
 };
-
-__device__ __forceinline__ unsigned long long add_u64(unsigned long long *p, unsigned long long v)
-{
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return lane ? (~0ULL >> (64 - lane)) : 0ULL; }
-
-// Every lane of a full wave calls it in converged code; at most one entry per lane, ONE atomic per wave (as rk_group.hip's wave_append)
-__device__ __forceinline__ void wave_append(bool mine, unsigned long long key, unsigned long long *counter, unsigned long long *buf, unsigned long long cap)
-{
-    const unsigned long long m = __ballot(mine);
-    if (!m) return;   // (uniform)
-    const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == lead) base = add_u64(counter, (unsigned long long)__popcll(m));
-    const unsigned long long at = shfl_u64(base, lead) + (unsigned long long)__popcll(m & lanes_below(lane));
-    if (mine && at < cap) buf[at] = key;
-}
-
-// inv[caller's index] = internal id, sizes[caller's index] = the sketch size (orig == null: the identity)
-__global__ void k_gather_prepare(const uint32_t *orig, const uint32_t *sizes_internal, uint32_t n, uint32_t *inv, uint32_t *sizes)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t c = orig ? orig[i] : i;   // (orig[] < n: rk_index_build's permutation, checked on every import of a blob)
-    inv[c] = i;
-    sizes[c] = sizes_internal[i];
-}
-
-// One workgroup: off[i] = the sum of min(val[row_of[j]], limit) over j < i (row_of null: j itself; limit 0: none), off[n] = the total
-__global__ void __launch_bounds__(kGatherThreads) k_gather_scan(const uint32_t *val, const uint32_t *row_of, uint32_t n, uint32_t limit,
-                                                                unsigned long long *off, unsigned long long *total_out)
-{
-    __shared__ unsigned long long s_wave[kGatherThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned long long run = 0;
-    for (uint32_t c0 = 0; c0 < n; c0 += kGatherThreads) {   // (uniform)
-        const uint32_t i = c0 + tid;
-        uint32_t v = 0;
-        if (i < n) {
-            v = val[row_of ? row_of[i] : i];
-            if (limit && v > limit) v = limit;
-        }
-        unsigned long long incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long x = shfl_u64(incl, (lane - o) & 63);
-            if (lane >= o) incl += x;
-        }
-        if (lane == 63) s_wave[w] = incl;
-        __syncthreads();
-        unsigned long long before = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < kGatherThreads / 64; k++) {
-            if (k < w) before += s_wave[k];
-            all += s_wave[k];
-        }
-        if (i < n) off[i] = run + before + incl - v;
-        run += all;
-        __syncthreads();   // (s_wave is rewritten by the next chunk)
-    }
-    if (tid == 0) {
-        off[n] = run;
-        if (total_out) *total_out = run;
-    }
-}
 
 struct RowArgs {   // a batch of nb rows: slot s of the batch is query row row_of[s], its counter row cnt + s * n_ref
     int32_t *cnt;
@@ -184,46 +110,33 @@ template <bool WRITE> __global__ void __launch_bounds__(kGatherThreads) k_gather
 }
 
 struct MatchArgs {
-    const void *q_hashes, *uhash;
+    const void *q_hashes;
     const uint64_t *q_off;
-    const uint32_t *dir, *row_of;
-    int32_t hash_bits, dir_shift;
-    unsigned long long U;
+    const uint32_t *row_of;
+    IndexLookup ix;
     unsigned long long *items, cap;
     uint32_t *matched_q;
     Counters *c;
 };
 
-// One workgroup per row, one query hash per lane and trip: the bucket of the prefix directory, then a binary search among the sorted
-// distinct hashes of the bucket.  A hash that has a posting list appends the item slot << 32 | list.
+// One workgroup per row, one query hash per lane and trip: a hash that has a posting list appends the item slot << 32 | list.
 template <class Hash> __global__ void __launch_bounds__(kGatherThreads) k_gather_match(MatchArgs a)
 {
     __shared__ uint32_t s_n;
     const uint32_t s = blockIdx.x, tid = threadIdx.x, row = a.row_of[s];
-    const Hash *q = (const Hash *)a.q_hashes, *uhash = (const Hash *)a.uhash;
+    const Hash *q = (const Hash *)a.q_hashes;
     const uint64_t qb = a.q_off[row], qe = a.q_off[row + 1];
     if (tid == 0) s_n = 0;
     __syncthreads();
     uint32_t mine = 0;
     for (uint64_t j0 = qb; j0 < qe; j0 += kGatherThreads) {   // (uniform)
         const uint64_t j = j0 + tid;
-        bool found = false;
-        uint32_t u = 0;
-        if (j < qe) {
-            const unsigned long long h = (unsigned long long)q[j];
-            if (a.hash_bits >= 64 || (h >> a.hash_bits) == 0) {   // (a hash beyond the index's bits has no bucket)
-                const uint32_t b = (uint32_t)(h >> a.dir_shift);
-                uint32_t lo = a.dir[b], hi = a.dir[b + 1];
-                const uint32_t end = hi;
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if ((unsigned long long)uhash[mid] < h) lo = mid + 1; else hi = mid;
-                }
-                found = lo < end && (unsigned long long)lo < a.U && (unsigned long long)uhash[lo] == h;
-                u = lo;
-            }
-        }
-        wave_append(found, ((unsigned long long)s << 32) | u, &a.c->n_items, a.items, a.cap);
+        const bool in[1] = {j < qe};
+        const unsigned long long h[1] = {in[0] ? (unsigned long long)q[j] : 0ULL};
+        uint32_t u[1];
+        index_lookup<Hash, 1>(a.ix, h, in, u);
+        const bool found = u[0] != kNoList;
+        wave_append(found, ((unsigned long long)s << 32) | u[0], &a.c->n_items, a.items, a.cap);
         mine += found;
     }
     if (mine) atomicAdd(&s_n, mine);
@@ -425,7 +338,7 @@ __global__ void __launch_bounds__(kGatherThreads) k_gather_compact(const unsigne
     wave_append(item != kDeadItem, item, counter, out, cap);
 }
 
-// the picks of the batch's rows, back to back in (row, rank) order: take_off = k_gather_scan over the rows' pick counts
+// the picks of the batch's rows, back to back in (row, rank) order: take_off = k_query_scan over the rows' pick counts
 __global__ void __launch_bounds__(kGatherThreads) k_gather_take(RowArgs a, const unsigned long long *take_off, rk_gather_pick *out)
 {
     const uint32_t s = blockIdx.x;
@@ -435,20 +348,10 @@ __global__ void __launch_bounds__(kGatherThreads) k_gather_take(RowArgs a, const
 }
 
 // ---- host: the rule, exactly ------------------------------------------------------------------------------------------------
-struct RowSel {   // the selected rows of Q, ascending (block-cyclic, as rk_distq_kernel deals its row slots)
-    std::vector<uint32_t> rows;
-    RowSel(const rk_gather_opts *o, uint32_t Q)
-    {
-        const uint64_t rb = o->row_block ? o->row_block : 1, rs = o->row_step ? o->row_step : 1;
-        for (uint64_t blk = o->row_first; blk * rb < Q; blk += rs)
-            for (uint64_t r = blk * rb; r < std::min<uint64_t>(Q, (blk + 1) * rb); r++) rows.push_back((uint32_t)r);
-    }
-};
-
 struct HostResult {
     std::vector<rk_gather_pick> picks;
     std::vector<uint64_t> off;                          // Q + 1
-    std::vector<uint32_t> matched, n_cand, covered;     // per selected row, in the order of RowSel
+    std::vector<uint32_t> matched, n_cand, covered;     // Q (unselected rows: 0)
 };
 
 // lists: list u is post[pos[u] .. pos[u + 1]), strictly ascending reference ids below n_ref
@@ -460,6 +363,9 @@ void gather_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_of
     std::vector<uint32_t> by_ref;     // per touched reference the local numbers of the lists that hold it
     std::vector<uint8_t> alive;
     std::vector<uint32_t> n_picks(Q, 0);
+    out->matched.assign(Q, 0);
+    out->n_cand.assign(Q, 0);
+    out->covered.assign(Q, 0);
     for (const uint32_t q : sel.rows) {
         const uint64_t *lists = q_lists + q_off[q];
         const uint64_t nl = q_off[q + 1] - q_off[q];
@@ -515,62 +421,19 @@ void gather_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_of
         }
         for (const uint32_t r : touched) rem[r] = 0;
         n_picks[q] = t;
-        out->matched.push_back(matched);
-        out->n_cand.push_back(n_cand);
-        out->covered.push_back(covered);
+        out->matched[q] = matched;
+        out->n_cand[q] = n_cand;
+        out->covered[q] = covered;
     }
     out->off.assign((size_t)Q + 1, 0);
     for (uint32_t q = 0; q < Q; q++) out->off[q + 1] = out->off[q] + n_picks[q];
 }
 
-// lists as exported: their offsets, and a sorted copy without repeats where a list does not ascend strictly.  RK_ERR_ARG for a posting >= n_ref.
-int prepare_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, uint32_t n_ref, std::vector<uint64_t> *pos, std::vector<uint32_t> *fixed,
-                  const uint32_t **post)
-{
-    pos->assign((size_t)n_lists + 1, 0);
-    bool ascending = true;
-    for (uint64_t u = 0; u < n_lists; u++) (*pos)[u + 1] = (*pos)[u] + counts[u];
-    for (uint64_t u = 0; u < n_lists; u++)
-        for (uint64_t i = (*pos)[u]; i < (*pos)[u + 1]; i++) {
-            if (postings[i] >= n_ref) return RK_ERR_ARG;
-            if (i > (*pos)[u] && postings[i - 1] >= postings[i]) ascending = false;
-        }
-    *post = postings;
-    if (ascending) return RK_OK;
-    std::vector<uint64_t> npos((size_t)n_lists + 1, 0);
-    fixed->clear();
-    std::vector<uint32_t> list;
-    for (uint64_t u = 0; u < n_lists; u++) {
-        list.assign(postings + (*pos)[u], postings + (*pos)[u + 1]);
-        std::sort(list.begin(), list.end());
-        list.erase(std::unique(list.begin(), list.end()), list.end());
-        fixed->insert(fixed->end(), list.begin(), list.end());
-        npos[u + 1] = fixed->size();
-    }
-    pos->swap(npos);
-    *post = fixed->data();
-    return RK_OK;
-}
+using Result = RowsResult<rk_gather_pick, 3>;   // per row: matched, n_cand, covered
 
-// the outputs of both entry points from a host result; RK_ERR_NOMEM leaves them untouched
-int hand_out(const HostResult &r, const RowSel &sel, uint32_t Q, uint64_t *off_out, rk_gather_pick **picks_out, uint64_t *n_picks, uint32_t *matched_out,
-             uint32_t *n_cand_out, uint32_t *covered_out)
+Result view(const HostResult &r)
 {
-    rk_gather_pick *p = nullptr;
-    if (!r.picks.empty()) {
-        p = (rk_gather_pick *)malloc(r.picks.size() * sizeof(rk_gather_pick));
-        if (!p) return RK_ERR_NOMEM;
-        memcpy(p, r.picks.data(), r.picks.size() * sizeof(rk_gather_pick));
-    }
-    memcpy(off_out, r.off.data(), ((size_t)Q + 1) * 8);
-    for (size_t k = 0; k < sel.rows.size(); k++) {
-        matched_out[sel.rows[k]] = r.matched[k];
-        n_cand_out[sel.rows[k]] = r.n_cand[k];
-        covered_out[sel.rows[k]] = r.covered[k];
-    }
-    *picks_out = p;
-    *n_picks = r.picks.size();
-    return RK_OK;
+    return Result{r.off.data(), {r.matched.data(), r.n_cand.data(), r.covered.data()}, r.picks.data(), r.picks.size()};
 }
 
 void fill_constants(rk_gather_stats *st, uint32_t lane_max, uint32_t wave_max, uint32_t sync_every)
@@ -586,16 +449,6 @@ unsigned long long env_number(const char *name, unsigned long long otherwise)
     const char *sw = getenv(name);
     const unsigned long long v = sw ? strtoull(sw, nullptr, 10) : 0;
     return v ? v : otherwise;
-}
-
-void census(const HostResult &r, rk_gather_stats *st)
-{
-    st->picks = r.picks.size();
-    for (size_t k = 0; k < r.matched.size(); k++) {
-        st->matched += r.matched[k];
-        st->candidates += r.n_cand[k];
-    }
-    for (size_t q = 0; q + 1 < r.off.size(); q++) st->rounds = std::max<uint32_t>(st->rounds, (uint32_t)(r.off[q + 1] - r.off[q]));
 }
 
 // RK_GATHER_DEVICE=0: export + the lists of the selected queries' hashes (a binary search each) + the rule on the host
@@ -642,7 +495,7 @@ template <class Hash> int gather_on_host(rk_ctx *ctx, const rk_index *idx, const
 }
 
 struct DeviceResult {
-    std::vector<unsigned char> block;   // off u64[Q + 1] | matched, n_cand, covered u32[Q] each (+ 4 bytes when Q is odd) | the picks
+    std::vector<unsigned char> block;   // Result::from_block
     uint64_t n_picks = 0;
 };
 
@@ -674,7 +527,7 @@ int gather_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
     RK_HIP(ctx, cnt_dev.alloc(1));
     RK_HIP(ctx, hipMemsetAsync(per_q.p, 0, (size_t)16 * Q, stream));
     RK_HIP(ctx, span.begin());
-    hipLaunchKernelGGL(k_gather_prepare, dim3(blocks_for(N)), dim3(kThreads), 0, stream, idx->relabeled ? idx->d_orig : nullptr, idx->d_sizes, N, inv.p, sizes.p);
+    hipLaunchKernelGGL(k_query_prepare, dim3(blocks_for(N)), dim3(kThreads), 0, stream, idx->relabeled ? idx->d_orig : nullptr, idx->d_sizes, N, inv.p, sizes.p);
     RK_HIP(ctx, hipGetLastError());
     st->launches++;
 
@@ -734,13 +587,9 @@ int gather_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         if (hashes && idx->U) {
             MatchArgs m;
             m.q_hashes = qs->wide ? (const void *)qs->d_hashes64 : (const void *)qs->d_hashes;
-            m.uhash = idx->wide ? (const void *)idx->d_uhash64 : (const void *)idx->d_uhash;
             m.q_off = qs->d_off;
-            m.dir = idx->d_dir;
             m.row_of = row_of.p;
-            m.hash_bits = idx->hash_bits;
-            m.dir_shift = idx->dir_shift;
-            m.U = idx->U;
+            m.ix = index_lookup_of(idx);
             m.items = items.p;
             m.cap = hashes;
             m.matched_q = a.matched_q;
@@ -749,8 +598,8 @@ int gather_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
             else hipLaunchKernelGGL(k_gather_match<uint32_t>, dim3(nb), dim3(kGatherThreads), 0, stream, m);
             st->launches++;
         }
-        hipLaunchKernelGGL(k_gather_scan, dim3(1), dim3(kGatherThreads), 0, stream, a.n_cand_q, row_of.p, nb, 0u, offs.p, &cnt_dev.p->cand_total);
-        hipLaunchKernelGGL(k_gather_scan, dim3(1), dim3(kGatherThreads), 0, stream, a.n_cand_q, row_of.p, nb, o->max_picks, offs.p + (rows_per_batch + 1),
+        hipLaunchKernelGGL(k_query_scan<kGatherThreads>, dim3(1), dim3(kGatherThreads), 0, stream, a.n_cand_q, row_of.p, nb, 0u, offs.p, &cnt_dev.p->cand_total);
+        hipLaunchKernelGGL(k_query_scan<kGatherThreads>, dim3(1), dim3(kGatherThreads), 0, stream, a.n_cand_q, row_of.p, nb, o->max_picks, offs.p + (rows_per_batch + 1),
                            &cnt_dev.p->region_total);
         hipLaunchKernelGGL(k_gather_init, dim3(blocks_for(nb)), dim3(kThreads), 0, stream, a, nb);
         RK_HIP(ctx, hipGetLastError());
@@ -825,7 +674,7 @@ int gather_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
             rk_gather_pick *part = static_cast<rk_gather_pick *>(rk_pool_alloc(ctx, home.picks * sizeof(rk_gather_pick)));
             if (!part) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu picks on the device", home.picks);
             taken.parts.emplace_back(part, home.picks);
-            hipLaunchKernelGGL(k_gather_scan, dim3(1), dim3(kGatherThreads), 0, stream, a.npicks_q, row_of.p, nb, 0u, take_off, &cnt_dev.p->take_total);
+            hipLaunchKernelGGL(k_query_scan<kGatherThreads>, dim3(1), dim3(kGatherThreads), 0, stream, a.npicks_q, row_of.p, nb, 0u, take_off, &cnt_dev.p->take_total);
             hipLaunchKernelGGL(k_gather_take, dim3(nb), dim3(kGatherThreads), 0, stream, a, take_off, part);
             RK_HIP(ctx, hipGetLastError());
             st->launches += 2;
@@ -833,10 +682,10 @@ int gather_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         }
     }
     // the result in one block, one copy
-    const size_t head = ((size_t)Q + 1) * 8 + (((size_t)Q * 12 + 7) & ~(size_t)7), bytes = head + total_picks * sizeof(rk_gather_pick);
+    const size_t head = Result::head_bytes(Q), bytes = head + total_picks * sizeof(rk_gather_pick);
     DevBuf<unsigned char> block(ctx);
     RK_HIP(ctx, block.alloc(bytes));
-    hipLaunchKernelGGL(k_gather_scan, dim3(1), dim3(kGatherThreads), 0, stream, per_q.p + 3 * (size_t)Q, (const uint32_t *)nullptr, Q, 0u, (unsigned long long *)block.p,
+    hipLaunchKernelGGL(k_query_scan<kGatherThreads>, dim3(1), dim3(kGatherThreads), 0, stream, per_q.p + 3 * (size_t)Q, (const uint32_t *)nullptr, Q, 0u, (unsigned long long *)block.p,
                        &cnt_dev.p->take_total);
     RK_HIP(ctx, hipGetLastError());
     st->launches++;
@@ -884,10 +733,10 @@ int rk_gather_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n
     std::vector<uint32_t> fixed;
     const uint32_t *post = nullptr;
     if (int rc = prepare_lists(postings, counts, n_lists, n_ref, &pos, &fixed, &post)) return rc;
-    const RowSel sel(opts, n_query);
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, n_query);
     HostResult r;
     gather_core(post, pos.data(), q_off, q_lists, n_query, n_ref, ref_sizes, query_sizes, opts, sel, &r);
-    return hand_out(r, sel, n_query, off_out, picks_out, n_picks, matched_out, n_cand_out, covered_out);
+    return hand_out(view(r), sel, n_query, off_out, picks_out, n_picks, {matched_out, n_cand_out, covered_out});
 }
 
 int rk_gather_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_gather_opts *opts, uint64_t *off_out, rk_gather_pick **picks_out,
@@ -910,51 +759,30 @@ int rk_gather_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
     fill_constants(&st, split ? split : lane_max, split ? split : std::max(lane_max, kWaveMax), (uint32_t)env_number("RK_GATHER_SYNC_EVERY", kSyncEvery));
     const TimedSpan span{ctx, RK_MS_GATHER};
     span.clear();
-    const RowSel sel(opts, Q);
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, Q);
     st.rows = (uint32_t)sel.rows.size();
-    if (!N || sel.rows.empty()) {   // nothing runs: every row is empty
-        memset(off_out, 0, ((size_t)Q + 1) * 8);
-        for (const uint32_t q : sel.rows) matched_out[q] = n_cand_out[q] = covered_out[q] = 0;
-        *picks_out = nullptr;
-        *n_picks = 0;
-        if (stats) *stats = st;
-        return RK_OK;
-    }
-    if (rk_switched_off("RK_GATHER_DEVICE")) {
+    uint32_t *const outs[3] = {matched_out, n_cand_out, covered_out};
+    HostResult host;
+    DeviceResult dev;
+    Result r;
+    const bool runs = N && !sel.rows.empty();   // (else every row is empty: r stays without offsets)
+    if (runs && rk_switched_off("RK_GATHER_DEVICE")) {
         st.path = 2;
-        HostResult r;
-        RK_TRY(idx->wide ? gather_on_host<uint64_t>(ctx, idx, queries, opts, sel, &r) : gather_on_host<uint32_t>(ctx, idx, queries, opts, sel, &r));
-        census(r, &st);
+        RK_TRY(idx->wide ? gather_on_host<uint64_t>(ctx, idx, queries, opts, sel, &host) : gather_on_host<uint32_t>(ctx, idx, queries, opts, sel, &host));
+        r = view(host);
         st.batches = 1;
-        if (hand_out(r, sel, Q, off_out, picks_out, n_picks, matched_out, n_cand_out, covered_out)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
-        if (stats) *stats = st;
-        return RK_OK;
+    } else if (runs) {
+        st.path = 1;
+        RK_TRY(gather_on_device(ctx, idx, queries, opts, sel, &st, &dev));
+        r = Result::from_block(dev.block.data(), Q, dev.n_picks);
     }
-    st.path = 1;
-    DeviceResult res;
-    RK_TRY(gather_on_device(ctx, idx, queries, opts, sel, &st, &res));
-    const unsigned char *b = res.block.data();
-    const uint64_t *off = (const uint64_t *)b;
-    const uint32_t *matched = (const uint32_t *)(b + ((size_t)Q + 1) * 8), *n_cand = matched + Q, *covered = n_cand + Q;
-    const size_t head = ((size_t)Q + 1) * 8 + (((size_t)Q * 12 + 7) & ~(size_t)7);
-    rk_gather_pick *p = nullptr;
-    if (res.n_picks) {
-        p = (rk_gather_pick *)malloc(res.n_picks * sizeof(rk_gather_pick));
-        if (!p) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
-        memcpy(p, b + head, res.n_picks * sizeof(rk_gather_pick));
-    }
-    memcpy(off_out, off, ((size_t)Q + 1) * 8);
+    if (hand_out(r, sel, Q, off_out, picks_out, n_picks, outs)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+    st.picks = r.n_recs;
     for (const uint32_t q : sel.rows) {
-        matched_out[q] = matched[q];
-        n_cand_out[q] = n_cand[q];
-        covered_out[q] = covered[q];
-        st.matched += matched[q];
-        st.candidates += n_cand[q];
-        st.rounds = std::max<uint32_t>(st.rounds, (uint32_t)(off[q + 1] - off[q]));
+        st.matched += matched_out[q];
+        st.candidates += n_cand_out[q];
+        st.rounds = std::max<uint32_t>(st.rounds, (uint32_t)(off_out[q + 1] - off_out[q]));
     }
-    st.picks = res.n_picks;
-    *picks_out = p;
-    *n_picks = res.n_picks;
     if (stats) *stats = st;
     return RK_OK;
 }

@@ -17,7 +17,7 @@
 //                            groups.  A list with more than kTableGroups groups is SPILLED: its raw keys list << 32 | group, and
 //                            list << 32 | ~0 per distinct genome, go to a global buffer;
 //             every (list u, group g) that passes appends the key g << 32 | u to the record buffer: ONE atomic reservation per wave
-//             (wave_reserve / wave_append), not one per lane;
+//             (wave_reserve here, wave_append of rk_query_dev.h), not one per lane;
 //   spill     rk_prim_sort_keys_u64 + rk_prim_rle_u64 over the raw keys: a run IS c_g(h), the run of ~0 is t(h); k_group_spill_emit
 //             applies the rule (t by binary search among the runs) and appends to the same record buffer;
 //   overflow  the counters keep counting past the capacities; the call then runs once more with the exact counts (attempts = 2);
@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "rk_internal.h"
+#include "rk_query_dev.h"
 
 namespace {
 
@@ -65,17 +66,7 @@ struct ListArgs {
     Counters *cnt;
 };
 
-__device__ __forceinline__ unsigned long long add_u64(unsigned long long *p, unsigned long long v)
-{
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// Every lane of a full wave calls these in converged code.  wave_reserve: room for n_mine entries per lane behind *counter, one atomic
+// Every lane of a full wave calls it in converged code.  wave_reserve: room for n_mine entries per lane behind *counter, one atomic
 // per wave; returns where this lane's entries begin (the counter counts past any capacity: the caller checks each slot).
 __device__ __forceinline__ unsigned long long wave_reserve(uint32_t n_mine, unsigned long long *counter)
 {
@@ -91,26 +82,6 @@ __device__ __forceinline__ unsigned long long wave_reserve(uint32_t n_mine, unsi
     unsigned long long base = 0;
     if (lane == 63) base = add_u64(counter, total);
     return shfl_u64(base, 63) + incl - n_mine;
-}
-// at most one entry per lane: the reservation by ballot
-__device__ __forceinline__ void wave_append(bool mine, unsigned long long key, unsigned long long *counter, unsigned long long *buf, unsigned long long cap)
-{
-    const unsigned long long m = __ballot(mine);
-    if (!m) return;   // (uniform)
-    const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == lead) base = add_u64(counter, (unsigned long long)__popcll(m));
-    const unsigned long long at = shfl_u64(base, lead) + (unsigned long long)__popcll(m & ((1ULL << lane) - 1ULL));
-    if (mine && at < cap) buf[at] = key;
-}
-__device__ __forceinline__ uint32_t queue_slot(bool mine, unsigned long long *counter)
-{
-    const unsigned long long m = __ballot(mine);
-    if (!m) return 0;   // (uniform)
-    const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == lead) base = add_u64(counter, (unsigned long long)__popcll(m));
-    return (uint32_t)(shfl_u64(base, lead) + (unsigned long long)__popcll(m & ((1ULL << lane) - 1ULL)));
 }
 
 __device__ __forceinline__ bool passes(uint32_t c, uint32_t t, uint32_t need, uint32_t only) { return c >= need && (!only || c == t); }

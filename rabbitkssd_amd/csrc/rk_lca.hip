@@ -19,7 +19,7 @@
 //                          reduced across the waves through LDS; thread 0 climbs;
 //             list_taxon[U] holds the CALLER's node id of lca(h), kUnlabelled for a list without a labelled holder;
 //   tally     k_lca_tally: flat over ALL query elements in tiles of kTileHashes, whatever sketch they belong to.  Per element the look-up
-//             (rk_lca_lookup.h), list_taxon, and its row: a binary search among the query offsets for the last row that starts at or
+//             (rk_query_dev.h), list_taxon, and its row: a binary search among the query offsets for the last row that starts at or
 //             before it (runs of empty sketches fall out).  Elements of unselected rows emit nothing.  The equal keys row << 32 | taxon
 //             of a run of 64 elements are counted by ballots, then added to an LDS table of kTableSlots slots (64-bit compare-and-swap on
 //             the key, an add on the count): more slots than a tile has elements, it cannot overflow.  Then ONE reservation per tile and
@@ -41,7 +41,8 @@
 #include <vector>
 
 #include "rk_internal.h"
-#include "rk_lca_lookup.h"
+#include "rk_query_dev.h"
+#include "rk_query_host.h"
 
 namespace {
 
@@ -83,7 +84,7 @@ struct TallyArgs {
     const uint64_t *q_off;             // u64[n + 1]
     unsigned long long total;
     uint32_t n;
-    LcaLookup ix;
+    IndexLookup ix;
     const uint32_t *list_taxon;
     uint32_t row_first, row_step, row_block;   // (step and block at least 1)
     unsigned long long *part_key, cap;         // row << 32 | taxon
@@ -91,15 +92,6 @@ struct TallyArgs {
     Counters *cnt;
 };
 
-__device__ __forceinline__ unsigned long long add_u64(unsigned long long *p, unsigned long long v)
-{
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
 __device__ __forceinline__ uint32_t wave_min(uint32_t v)
 {
 #pragma unroll
@@ -112,17 +104,6 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v)
     for (int o = 32; o; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
     return v;
 }
-// every lane of a full wave, converged: a slot of a queue for the lanes with `mine`, one atomic per wave
-__device__ __forceinline__ uint32_t queue_slot(bool mine, unsigned long long *counter)
-{
-    const unsigned long long m = __ballot(mine);
-    if (!m) return 0;   // (uniform)
-    const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == lead) base = add_u64(counter, (unsigned long long)__popcll(m));
-    return (uint32_t)(shfl_u64(base, lead) + (unsigned long long)__popcll(m & ((1ULL << lane) - 1ULL)));
-}
-
 // the preorder ids of the genomes' taxa in the index's internal genome order
 __global__ void k_lca_taxa(const uint32_t *taxa, const uint32_t *pre, const uint32_t *orig, uint32_t n, uint32_t *gtax)
 {
@@ -326,7 +307,7 @@ template <class Hash> __global__ void __launch_bounds__(kLcaThreads) k_lca_tally
         in[t] = j < a.total;
         h[t] = in[t] ? (unsigned long long)q[j] : 0ULL;
     }
-    lca_lookup<Hash, kTrips>(a.ix, h, in, list);
+    index_lookup<Hash, kTrips>(a.ix, h, in, list);
     uint32_t tx[kTrips];
 #pragma unroll
     for (int t = 0; t < kTrips; t++) tx[t] = list[t] != kNoList ? a.list_taxon[list[t]] : 0u;
@@ -457,16 +438,6 @@ unsigned long long env_number(const char *name, unsigned long long dflt)
     const char *s = getenv(name);
     return s && *s ? strtoull(s, nullptr, 10) : dflt;
 }
-
-struct RowSel {   // the selected rows of Q, ascending (block-cyclic, as rk_gather_rows deals them)
-    std::vector<uint32_t> rows;
-    RowSel(const rk_lca_opts *o, uint32_t Q)
-    {
-        const uint64_t rb = o->row_block ? o->row_block : 1, rs = o->row_step ? o->row_step : 1;
-        for (uint64_t blk = o->row_first; blk * rb < Q; blk += rs)
-            for (uint64_t r = blk * rb; r < std::min<uint64_t>(Q, (blk + 1) * rb); r++) rows.push_back((uint32_t)r);
-    }
-};
 
 // The taxonomy, checked: RK_OK and depth[] (the root's is 0), or RK_ERR_ARG.  A colouring walk towards the root: a node is open while
 // the walk that found it is under way; meeting an open node is a cycle.  No recursion.
@@ -638,24 +609,11 @@ void lca_core(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists
     st->records = out->recs.size();
 }
 
-// the outputs of both entry points from a HostResult; RK_ERR_NOMEM leaves everything untouched
-int hand_out(const HostResult &r, const RowSel &sel, uint32_t Q, uint64_t *off_out, rk_lca_count **counts_out, uint64_t *n_counts, uint32_t *matched_out,
-             uint32_t *unlabelled_out)
+using Result = RowsResult<rk_lca_count, 2>;   // per row: matched, unlabelled
+
+Result view(const HostResult &r)
 {
-    rk_lca_count *p = nullptr;
-    if (!r.recs.empty()) {
-        p = (rk_lca_count *)malloc(r.recs.size() * sizeof(rk_lca_count));
-        if (!p) return RK_ERR_NOMEM;
-        memcpy(p, r.recs.data(), r.recs.size() * sizeof(rk_lca_count));
-    }
-    memcpy(off_out, r.off.data(), ((size_t)Q + 1) * 8);
-    for (const uint32_t q : sel.rows) {
-        matched_out[q] = r.matched[q];
-        unlabelled_out[q] = r.unlabelled[q];
-    }
-    *counts_out = p;
-    *n_counts = r.recs.size();
-    return RK_OK;
+    return Result{r.off.data(), {r.matched.data(), r.unlabelled.data()}, r.recs.data(), r.recs.size()};
 }
 
 // RK_LCA_DEVICE=0: export + the lists of the selected rows' elements (a binary search each) + the rule over lists
@@ -694,7 +652,7 @@ int lca_on_host(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const u
 }
 
 struct DeviceResult {
-    std::vector<unsigned char> head;   // off u64[Q + 1] | matched u32[Q] | unlabelled u32[Q]
+    std::vector<unsigned char> head;   // Result::from_block without the records
     std::vector<rk_lca_count> recs;
 };
 
@@ -711,7 +669,7 @@ int lca_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const
     const TimedSpan span{ctx, RK_MS_LCA};
     RK_TRY(rk_index_ensure_dir(ctx, const_cast<rk_index *>(idx), stream));
     const uint64_t wave_cap = std::min<uint64_t>(U, H / (kLaneMax + 1) + 1), block_cap = std::min<uint64_t>(U, H / (kWaveMax + 1) + 1);
-    const size_t head_bytes = ((size_t)Q + 1) * 8 + (size_t)Q * 8;
+    const size_t head_bytes = Result::head_bytes(Q);
     DevBuf<uint32_t> d_tax(ctx), d_taxa(ctx), gtax(ctx), list_taxon(ctx), wave_q(ctx), block_q(ctx);
     DevBuf<Counters> cnt(ctx);
     DevBuf<unsigned char> head(ctx);
@@ -759,11 +717,7 @@ int lca_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const
     ta.q_off = qs->d_off;
     ta.total = total;
     ta.n = Q;
-    ta.ix.uhash = idx->wide ? (const void *)idx->d_uhash64 : (const void *)idx->d_uhash;
-    ta.ix.dir = idx->d_dir;
-    ta.ix.U = U;
-    ta.ix.hash_bits = idx->hash_bits;
-    ta.ix.dir_shift = idx->dir_shift;
+    ta.ix = index_lookup_of(idx);
     ta.list_taxon = list_taxon.p;
     ta.row_first = o->row_first;
     ta.row_step = o->row_step ? o->row_step : 1;
@@ -876,12 +830,12 @@ int rk_lca_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_li
     fill_constants(&st, 0);
     st.path = 2;
     st.attempts = 1;
-    const RowSel sel(opts, n_query);
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, n_query);
     st.rows = (uint32_t)sel.rows.size();
     for (const uint32_t q : sel.rows) st.elements += q_off[q + 1] - q_off[q];
     HostResult r;
     lca_core(postings, counts, n_lists, q_off, q_lists, n_query, taxa, parent, depth.data(), sel, &r, &st);
-    if (int rc = hand_out(r, sel, n_query, off_out, counts_out, n_counts, matched_out, unlabelled_out)) return rc;
+    if (int rc = hand_out(view(r), sel, n_query, off_out, counts_out, n_counts, {matched_out, unlabelled_out})) return rc;
     if (stats) *stats = st;
     return RK_OK;
 }
@@ -1001,49 +955,32 @@ int rk_lca_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, co
     memset(&st, 0, sizeof st);
     const TimedSpan span{ctx, RK_MS_LCA};
     span.clear();
-    const RowSel sel(opts, Q);
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, Q);
     st.rows = (uint32_t)sel.rows.size();
     for (const uint32_t q : sel.rows) st.elements += queries->h_off[q + 1] - queries->h_off[q];
-    if (!N || !idx->U || sel.rows.empty()) {   // nothing runs: no element has a posting list
-        if (Q) memset(off_out, 0, ((size_t)Q + 1) * 8);
-        else off_out[0] = 0;
-        for (const uint32_t q : sel.rows) matched_out[q] = unlabelled_out[q] = 0;
-        *counts_out = nullptr;
-        *n_counts = 0;
-        if (stats) *stats = st;
-        return RK_OK;
-    }
-    fill_constants(&st, queries->total);
-    if (rk_switched_off("RK_LCA_DEVICE")) {
+    uint32_t *const outs[2] = {matched_out, unlabelled_out};
+    HostResult host;
+    DeviceResult dev;
+    Result r;
+    const bool runs = N && idx->U && !sel.rows.empty();   // (else no element has a posting list: r stays without offsets)
+    if (runs) fill_constants(&st, queries->total);
+    if (runs && rk_switched_off("RK_LCA_DEVICE")) {
         st.path = 2;
         st.attempts = 1;
-        HostResult r;
-        RK_TRY(idx->wide ? lca_on_host<uint64_t>(ctx, idx, queries, taxa, parent, depth.data(), sel, &r, &st)
-                         : lca_on_host<uint32_t>(ctx, idx, queries, taxa, parent, depth.data(), sel, &r, &st));
-        if (hand_out(r, sel, Q, off_out, counts_out, n_counts, matched_out, unlabelled_out)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
-        if (stats) *stats = st;
-        return RK_OK;
+        RK_TRY(idx->wide ? lca_on_host<uint64_t>(ctx, idx, queries, taxa, parent, depth.data(), sel, &host, &st)
+                         : lca_on_host<uint32_t>(ctx, idx, queries, taxa, parent, depth.data(), sel, &host, &st));
+        r = view(host);
+    } else if (runs) {
+        st.path = 1;
+        RK_TRY(lca_on_device(ctx, idx, queries, taxa, parent, n_taxa, root, opts, &st, &dev));
+        r = Result::from_block(dev.head.data(), Q, dev.recs.size());
+        r.recs = dev.recs.data();   // (the records come home in a copy of their own)
+        for (const uint32_t q : sel.rows) {
+            st.matched += r.per_row[0][q];
+            st.unlabelled += r.per_row[1][q];
+        }
     }
-    st.path = 1;
-    DeviceResult res;
-    RK_TRY(lca_on_device(ctx, idx, queries, taxa, parent, n_taxa, root, opts, &st, &res));
-    rk_lca_count *p = nullptr;
-    if (!res.recs.empty()) {
-        p = (rk_lca_count *)malloc(res.recs.size() * sizeof(rk_lca_count));
-        if (!p) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
-        memcpy(p, res.recs.data(), res.recs.size() * sizeof(rk_lca_count));
-    }
-    const unsigned char *b = res.head.data();
-    const uint32_t *matched = (const uint32_t *)(b + ((size_t)Q + 1) * 8), *unl = matched + Q;
-    memcpy(off_out, b, ((size_t)Q + 1) * 8);
-    for (const uint32_t q : sel.rows) {
-        matched_out[q] = matched[q];
-        unlabelled_out[q] = unl[q];
-        st.matched += matched[q];
-        st.unlabelled += unl[q];
-    }
-    *counts_out = p;
-    *n_counts = res.recs.size();
+    if (hand_out(r, sel, Q, off_out, counts_out, n_counts, outs)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
     if (stats) *stats = st;
     return RK_OK;
 }

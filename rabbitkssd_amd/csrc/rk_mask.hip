@@ -7,9 +7,9 @@
 //   flag      k_mask_flag: flat over ALL query hashes in tiles of kTileHashes, whatever sketch they belong to (sketch sizes range from
 //             nothing to millions: a split by sketch would not balance).  A workgroup of kMaskThreads takes a tile, a wave kTrips
 //             consecutive runs of 64 hashes: lane l of run t reads element base + 64 t + l (coalesced; the ballot is in element order).
-//             The hashes of a lane's kTrips runs are loaded first, then their directory buckets, then the binary searches advance
-//             together, one probe of each per step: the loads of a step are in flight at once.  Per run one 64-bit keep word, per tile
-//             the number of survivors;
+//             The hashes of a lane's kTrips runs are loaded first, then looked up together (index_lookup of rk_query_dev.h: the
+//             directory buckets, then the binary searches, one probe of each per step).  Per run one 64-bit keep word, per tile the
+//             number of survivors;
 //   scan      an exclusive scan of the tile counts in 64 bits (the survivors may pass 2^32, which the 32-bit scan of rk_prims_scan.hip
 //             cannot hold): k_mask_scan_tiles, one workgroup per kScanTiles tiles, then k_mask_scan_blocks, one wave over the sums of
 //             those workgroups.  tile_prefix() adds the two;
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "rk_internal.h"
+#include "rk_query_dev.h"
 
 namespace {
 
@@ -50,10 +51,8 @@ struct MaskArgs {
     const uint64_t *q_off;             // u64[n + 1]
     unsigned long long total, tiles;
     uint32_t n;
-    const void *uhash;                 // Hash[U]: the index's distinct hashes, ascending
-    const uint32_t *upos, *dir;        // u32[U + 1], u32[2^dir_bits + 1]
-    unsigned long long U;              // 0: nothing is looked up, every c(h) is 0
-    int32_t hash_bits, dir_shift;
+    IndexLookup ix;                    // (U == 0: nothing is looked up, every c(h) is 0)
+    const uint32_t *upos;              // u32[U + 1]
     uint32_t min_refs, max_refs;
     uint32_t count_repeats;            // the queries are no sets: the result may or may not be
     unsigned long long *keep;          // u64[tiles * kTileWords]
@@ -64,21 +63,11 @@ struct MaskArgs {
     Counters *cnt;
 };
 
-__device__ __forceinline__ void add_u64(unsigned long long *p, unsigned long long v)
-{
-    if (v) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
 __device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int delta)
 {
     const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, delta), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), delta);
     return ((unsigned long long)hi << 32) | lo;
 }
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ULL << lane) - 1ULL; }
 
 // survivors before tile t
 __device__ __forceinline__ unsigned long long tile_prefix(const MaskArgs &a, unsigned long long t)
@@ -86,15 +75,17 @@ __device__ __forceinline__ unsigned long long tile_prefix(const MaskArgs &a, uns
     return a.block_base[t / kScanTiles] + a.tile_local[t];
 }
 
-template <class Hash> __global__ void __launch_bounds__(kMaskThreads) k_mask_flag(MaskArgs a)
+// (8 waves per SIMD: with the look-up in a function of its own the compiler would keep all of a lane's last probes in flight, at twice
+// the registers and half the waves -- k_lca_tally, which its LDS table holds to 3 waves anyway, takes that)
+template <class Hash> __global__ void __launch_bounds__(kMaskThreads, 8) k_mask_flag(MaskArgs a)
 {
     __shared__ uint32_t s_kept[kMaskThreads / 64], s_matched[kMaskThreads / 64], s_repeats[kMaskThreads / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long tile = blockIdx.x;
     const unsigned long long base = tile * kTileHashes + (unsigned long long)wave * (kTrips * 64);
-    const Hash *q = (const Hash *)a.q_hashes, *uhash = (const Hash *)a.uhash;
+    const Hash *q = (const Hash *)a.q_hashes;
     unsigned long long h[kTrips];
-    uint32_t lo[kTrips], hi[kTrips], end[kTrips];
+    uint32_t list[kTrips];
     bool in[kTrips], repeat[kTrips];
 #pragma unroll
     for (int t = 0; t < kTrips; t++) {
@@ -103,33 +94,11 @@ template <class Hash> __global__ void __launch_bounds__(kMaskThreads) k_mask_fla
         h[t] = in[t] ? (unsigned long long)q[j] : 0ULL;
         repeat[t] = a.count_repeats && in[t] && j > 0 && (unsigned long long)q[j - 1] == h[t];
     }
-#pragma unroll
-    for (int t = 0; t < kTrips; t++) {
-        // (a hash beyond the index's bits has no bucket; without distinct hashes there is no directory)
-        const bool look = in[t] && a.U && (a.hash_bits >= 64 || (h[t] >> a.hash_bits) == 0);
-        lo[t] = hi[t] = 0;
-        if (look) {
-            const uint32_t b = (uint32_t)(h[t] >> a.dir_shift);
-            lo[t] = a.dir[b];
-            hi[t] = a.dir[b + 1];
-        }
-        end[t] = hi[t];
-    }
-    for (bool more = true; more;) {   // the kTrips searches of a lane, one probe of each per step
-        more = false;
-#pragma unroll
-        for (int t = 0; t < kTrips; t++)
-            if (lo[t] < hi[t]) {
-                const uint32_t mid = (lo[t] + hi[t]) >> 1;   // (mid < hi <= dir[b + 1] <= U)
-                if ((unsigned long long)uhash[mid] < h[t]) lo[t] = mid + 1; else hi[t] = mid;
-                more |= lo[t] < hi[t];
-            }
-    }
+    index_lookup<Hash, kTrips>(a.ix, h, in, list);
     uint32_t kept = 0, matched = 0, repeats = 0;   // (uniform per wave)
 #pragma unroll
     for (int t = 0; t < kTrips; t++) {
-        uint32_t c = 0;
-        if (lo[t] < end[t] && (unsigned long long)lo[t] < a.U && (unsigned long long)uhash[lo[t]] == h[t]) c = a.upos[lo[t] + 1] - a.upos[lo[t]];
+        const uint32_t c = list[t] != kNoList ? a.upos[list[t] + 1] - a.upos[list[t]] : 0u;
         const bool keep = in[t] && c >= a.min_refs && c <= a.max_refs;
         const unsigned long long m = __ballot(keep);
         if (lane == 0) a.keep[tile * kTileWords + wave * kTrips + t] = m;
@@ -152,8 +121,8 @@ template <class Hash> __global__ void __launch_bounds__(kMaskThreads) k_mask_fla
             r += s_repeats[w];
         }
         a.tile_kept[tile] = k;
-        add_u64(&a.cnt->matched, m);
-        add_u64(&a.cnt->repeats, r);
+        if (m) add_u64(&a.cnt->matched, m);
+        if (r) add_u64(&a.cnt->repeats, r);
     }
 }
 
@@ -342,12 +311,8 @@ int mask_on_device(rk_ctx *ctx, const rk_sketches *qs, const rk_index *idx, cons
     a.total = total;
     a.tiles = tiles;
     a.n = n;
-    a.uhash = idx->wide ? (const void *)idx->d_uhash64 : (const void *)idx->d_uhash;
+    a.ix = index_lookup_of(idx);
     a.upos = idx->d_upos;
-    a.dir = idx->d_dir;
-    a.U = idx->U;
-    a.hash_bits = idx->hash_bits;
-    a.dir_shift = idx->dir_shift;
     a.min_refs = rule->min_refs;
     a.max_refs = rule->max_refs;
     a.count_repeats = qs->is_set ? 0u : 1u;

@@ -35,6 +35,7 @@
 #include "rk_dist_plan.h"
 #include "rk_edge_order.h"
 #include "rk_edge_stage.h"
+#include "rk_query_dev.h"
 
 namespace {
 
@@ -61,8 +62,6 @@ __device__ __forceinline__ void max_u64(unsigned long long *p, unsigned long lon
     // (as min_u64: the values only rise, a stale load costs an atomic, nothing else)
     if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void add_u32(uint32_t *p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void add_u64(unsigned long long *p, unsigned long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // records: far_in / near_out may be null (no record array asked for)
 __global__ void k_medoid_init(unsigned long long *far_w, unsigned long long *near_w, uint32_t *far_nb, uint32_t *near_nb, rk_hit *far_in, rk_hit *near_out, uint32_t n)

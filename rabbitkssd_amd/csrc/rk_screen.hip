@@ -10,7 +10,7 @@
 // Per batch of query rows (as many counter rows and won rows as RK_SCREEN_BATCH_BYTES holds), all on ctx->stream:
 //   counts   rk_distq_counts (stage A of rk_dist_topn): int32 cnt[slot][N], columns in the caller's order; won[slot][N] starts at 0;
 //   winners  k_screen_win: flat over ALL query hashes of the batch in tiles of kTileHashes, whatever sketch they belong to.  Per hash its
-//            slot (a binary search among the batch's hash offsets: runs of empty sketches fall out), the look-up (rk_lca_lookup.h), then
+//            slot (a binary search among the batch's hash offsets: runs of empty sketches fall out), the look-up (rk_query_dev.h), then
 //            the walk of its posting list by its length: the lane that found it up to lane_max postings, its wave up to wave_max (64
 //            postings per trip, a wave reduction of the best key), the workgroup beyond (an LDS queue, partial keys per wave).  Per posting
 //            p: r = orig[p], c = cnt[slot][r]; below min_common it is skipped, else (c, size, r) is compared with the best so far.  The
@@ -18,10 +18,10 @@
 //            kCombineRounds leaders by ballots, the rest lane by lane; RK_SCREEN_COMBINE=0: every add lane by lane);
 //   count    k_screen_count, one workgroup per row: n_cand = the cells with cnt >= min_common, the records = those with won >= min_won,
 //            claimed = the sum of won;
-//   scan     k_screen_scan over the rows' record counts; ONE read-back of the counters gives the room;
+//   scan     k_query_scan (rk_query_dev.h) over the rows' record counts; ONE read-back of the counters gives the room;
 //   write    k_screen_write, one workgroup per row, the row in chunks of the block size with a block scan: the records come out by
 //            ascending caller's index without atomics and without a sort;
-//   result   off[Q + 1] by k_screen_scan over all rows; ONE copy to the host: 8 (Q + 1) + 12 Q + 24 records bytes.
+//   result   off[Q + 1] by k_query_scan over all rows; ONE copy to the host: 8 (Q + 1) + 12 Q + 24 records bytes.
 //
 // Memory scope: every array is written by one kernel and read by a later one on the same stream.  INSIDE a launch the only communication
 // between workgroups is relaxed agent-scope atomic adds -- the +1 on the won rows, matched[] and the statistics, none of which is read
@@ -33,7 +33,8 @@
 #include <vector>
 
 #include "rk_internal.h"
-#include "rk_lca_lookup.h"
+#include "rk_query_dev.h"
+#include "rk_query_host.h"
 
 namespace {
 
@@ -68,26 +69,6 @@ __host__ __device__ __forceinline__ bool better(const Key &a, const Key &b)
     return a.r < b.r;
 }
 
-__device__ __forceinline__ unsigned long long add_u64(unsigned long long *p, unsigned long long v)
-{
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void add_u32(uint32_t *p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return lane ? (~0ULL >> (64 - lane)) : 0ULL; }
 // the best key of a wave, in every lane (the order is total: every lane ends with the same key)
 __device__ __forceinline__ Key wave_best(Key k)
 {
@@ -102,48 +83,6 @@ __device__ __forceinline__ Key wave_best(Key k)
     return k;
 }
 
-// sizes[caller's index] = the sketch size (orig == null: the identity)
-__global__ void k_screen_prepare(const uint32_t *orig, const uint32_t *sizes_internal, uint32_t n, uint32_t *sizes)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    sizes[orig ? orig[i] : i] = sizes_internal[i];   // (orig[] < n: rk_index_build's permutation, checked on every import of a blob)
-}
-
-// One workgroup: off[i] = the sum of val[row_of[j]] over j < i (row_of null: j itself), off[n] = the total
-__global__ void __launch_bounds__(kScreenThreads) k_screen_scan(const uint32_t *val, const uint32_t *row_of, uint32_t n, unsigned long long *off,
-                                                               unsigned long long *total_out)
-{
-    __shared__ unsigned long long s_wave[kWaves];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned long long run = 0;
-    for (uint32_t c0 = 0; c0 < n; c0 += kScreenThreads) {   // (uniform)
-        const uint32_t i = c0 + tid;
-        const uint32_t v = i < n ? val[row_of ? row_of[i] : i] : 0u;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long x = shfl_u64(incl, (lane - o) & 63);
-            if (lane >= o) incl += x;
-        }
-        if (lane == 63) s_wave[w] = incl;
-        __syncthreads();
-        unsigned long long before = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; k++) {
-            if (k < w) before += s_wave[k];
-            all += s_wave[k];
-        }
-        if (i < n) off[i] = run + before + incl - v;
-        run += all;
-        __syncthreads();   // (s_wave is rewritten by the next chunk)
-    }
-    if (tid == 0) {
-        off[n] = run;
-        if (total_out) *total_out = run;
-    }
-}
-
 struct WinArgs {
     const void *q_hashes;              // Hash[total]
     const uint64_t *q_off;             // u64[Q + 1]
@@ -151,7 +90,7 @@ struct WinArgs {
     const unsigned long long *hoff;    // nb + 1: the hashes of the slots before s, from hoff[0] (any base)
     uint32_t nb;
     unsigned long long n_hashes;       // hoff[nb] - hoff[0]
-    LcaLookup ix;
+    IndexLookup ix;
     const uint32_t *postings, *upos, *orig, *sizes_internal;   // the index (orig null: the identity)
     const int32_t *cnt;                // [nb][n_ref], columns in the caller's order
     uint32_t *won;                     // [nb][n_ref]
@@ -215,7 +154,7 @@ template <class Hash, bool COMBINE> __global__ void __launch_bounds__(kScreenThr
             h[t] = (unsigned long long)q[a.q_off[row] + (base + 64 * t + lane - (a.hoff[slo[t]] - h0))];
         }
     }
-    lca_lookup<Hash, kTrips>(a.ix, h, in, list);
+    index_lookup<Hash, kTrips>(a.ix, h, in, list);
     unsigned long long walked = 0, adds = 0, n_lane = 0, n_wave = 0, n_block = 0;
     __syncthreads();   // (s_qn)
 #pragma unroll
@@ -403,20 +342,10 @@ __global__ void __launch_bounds__(kScreenThreads) k_screen_write(RowArgs a)
 }
 
 // ---- host: the rule, exactly ------------------------------------------------------------------------------------------------
-struct RowSel {   // the selected rows of Q, ascending (block-cyclic, as rk_gather_rows deals them)
-    std::vector<uint32_t> rows;
-    RowSel(const rk_screen_opts *o, uint32_t Q)
-    {
-        const uint64_t rb = o->row_block ? o->row_block : 1, rs = o->row_step ? o->row_step : 1;
-        for (uint64_t blk = o->row_first; blk * rb < Q; blk += rs)
-            for (uint64_t r = blk * rb; r < std::min<uint64_t>(Q, (blk + 1) * rb); r++) rows.push_back((uint32_t)r);
-    }
-};
-
 struct HostResult {
     std::vector<rk_screen_rec> recs;
     std::vector<uint64_t> off;                          // Q + 1
-    std::vector<uint32_t> matched, n_cand, claimed;     // per selected row, in the order of RowSel
+    std::vector<uint32_t> matched, n_cand, claimed;     // Q (unselected rows: 0)
     uint64_t walked = 0, lane_lists = 0, wave_lists = 0, block_lists = 0;
 };
 
@@ -427,6 +356,9 @@ int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off
                 const uint32_t *query_sizes, const rk_screen_opts *o, const RowSel &sel, bool strict, HostResult *out)
 {
     std::vector<uint32_t> common(n_ref, 0), won(n_ref, 0), touched, n_rec(Q, 0);
+    out->matched.assign(Q, 0);
+    out->n_cand.assign(Q, 0);
+    out->claimed.assign(Q, 0);
     for (const uint32_t q : sel.rows) {
         const uint64_t *lists = q_lists + q_off[q];
         const uint64_t nl = q_off[q + 1] - q_off[q];
@@ -470,63 +402,20 @@ int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off
             }
             common[r] = won[r] = 0;
         }
-        out->matched.push_back(matched);
-        out->n_cand.push_back(n_cand);
-        out->claimed.push_back(claimed);
+        out->matched[q] = matched;
+        out->n_cand[q] = n_cand;
+        out->claimed[q] = claimed;
     }
     out->off.assign((size_t)Q + 1, 0);
     for (uint32_t q = 0; q < Q; q++) out->off[q + 1] = out->off[q] + n_rec[q];
     return RK_OK;
 }
 
-// lists as exported: their offsets, and a sorted copy without repeats where a list does not ascend strictly.  RK_ERR_ARG for a posting >= n_ref.
-int prepare_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, uint32_t n_ref, std::vector<uint64_t> *pos, std::vector<uint32_t> *fixed,
-                  const uint32_t **post)
-{
-    pos->assign((size_t)n_lists + 1, 0);
-    bool ascending = true;
-    for (uint64_t u = 0; u < n_lists; u++) (*pos)[u + 1] = (*pos)[u] + counts[u];
-    for (uint64_t u = 0; u < n_lists; u++)
-        for (uint64_t i = (*pos)[u]; i < (*pos)[u + 1]; i++) {
-            if (postings[i] >= n_ref) return RK_ERR_ARG;
-            if (i > (*pos)[u] && postings[i - 1] >= postings[i]) ascending = false;
-        }
-    *post = postings;
-    if (ascending) return RK_OK;
-    std::vector<uint64_t> npos((size_t)n_lists + 1, 0);
-    fixed->clear();
-    std::vector<uint32_t> list;
-    for (uint64_t u = 0; u < n_lists; u++) {
-        list.assign(postings + (*pos)[u], postings + (*pos)[u + 1]);
-        std::sort(list.begin(), list.end());
-        list.erase(std::unique(list.begin(), list.end()), list.end());
-        fixed->insert(fixed->end(), list.begin(), list.end());
-        npos[u + 1] = fixed->size();
-    }
-    pos->swap(npos);
-    *post = fixed->data();
-    return RK_OK;
-}
+using Result = RowsResult<rk_screen_rec, 3>;   // per row: matched, n_cand, claimed
 
-// the outputs of both entry points from a host result; RK_ERR_NOMEM leaves them untouched
-int hand_out(const HostResult &r, const RowSel &sel, uint32_t Q, uint64_t *off_out, rk_screen_rec **recs_out, uint64_t *n_recs, uint32_t *matched_out,
-             uint32_t *n_cand_out, uint32_t *claimed_out)
+Result view(const HostResult &r)
 {
-    rk_screen_rec *p = nullptr;
-    if (!r.recs.empty()) {
-        p = (rk_screen_rec *)malloc(r.recs.size() * sizeof(rk_screen_rec));
-        if (!p) return RK_ERR_NOMEM;
-        memcpy(p, r.recs.data(), r.recs.size() * sizeof(rk_screen_rec));
-    }
-    memcpy(off_out, r.off.data(), ((size_t)Q + 1) * 8);
-    for (size_t k = 0; k < sel.rows.size(); k++) {
-        matched_out[sel.rows[k]] = r.matched[k];
-        n_cand_out[sel.rows[k]] = r.n_cand[k];
-        claimed_out[sel.rows[k]] = r.claimed[k];
-    }
-    *recs_out = p;
-    *n_recs = r.recs.size();
-    return RK_OK;
+    return Result{r.off.data(), {r.matched.data(), r.n_cand.data(), r.claimed.data()}, r.recs.data(), r.recs.size()};
 }
 
 void fill_constants(rk_screen_stats *st)
@@ -587,7 +476,7 @@ template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const
 }
 
 struct DeviceResult {
-    std::vector<unsigned char> block;   // off u64[Q + 1] | matched, n_cand, claimed u32[Q] each (+ 4 bytes when Q is odd) | the records
+    std::vector<unsigned char> block;   // Result::from_block
     uint64_t n_recs = 0;
 };
 
@@ -626,7 +515,8 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
     RK_HIP(ctx, hipMemcpyAsync(row_of.p, sel.rows.data(), (size_t)n_sel * 4, hipMemcpyHostToDevice, stream));
     RK_HIP(ctx, hipMemcpyAsync(hoff_dev.p, hoff.data(), (size_t)(n_sel + 1) * 8, hipMemcpyHostToDevice, stream));
     RK_HIP(ctx, span.begin());
-    hipLaunchKernelGGL(k_screen_prepare, dim3(blocks_for(N)), dim3(kThreads), 0, stream, idx->relabeled ? idx->d_orig : nullptr, idx->d_sizes, N, sizes.p);
+    hipLaunchKernelGGL(k_query_prepare, dim3(blocks_for(N)), dim3(kThreads), 0, stream, idx->relabeled ? idx->d_orig : nullptr, idx->d_sizes, N, (uint32_t *)nullptr,
+                       sizes.p);
     RK_HIP(ctx, hipGetLastError());
     st->launches++;
 
@@ -662,11 +552,7 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
             w.hoff = hoff_dev.p + s0;
             w.nb = nb;
             w.n_hashes = hashes;
-            w.ix.uhash = idx->wide ? (const void *)idx->d_uhash64 : (const void *)idx->d_uhash;
-            w.ix.dir = idx->d_dir;
-            w.ix.U = idx->U;
-            w.ix.hash_bits = idx->hash_bits;
-            w.ix.dir_shift = idx->dir_shift;
+            w.ix = index_lookup_of(idx);
             w.postings = idx->d_postings;
             w.upos = idx->d_upos;
             w.orig = idx->relabeled ? idx->d_orig : nullptr;
@@ -700,7 +586,7 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         a.sizes = sizes.p;
         a.q_off = qs->d_off;
         hipLaunchKernelGGL(k_screen_count, dim3(nb), dim3(kScreenThreads), 0, stream, a);
-        hipLaunchKernelGGL(k_screen_scan, dim3(1), dim3(kScreenThreads), 0, stream, a.nrec_q, a.row_of, nb, rec_off.p, &cnt_dev.p->rec_total);
+        hipLaunchKernelGGL(k_query_scan<kScreenThreads>, dim3(1), dim3(kScreenThreads), 0, stream, a.nrec_q, a.row_of, nb, 0u, rec_off.p, &cnt_dev.p->rec_total);
         RK_HIP(ctx, hipGetLastError());
         st->launches += 2;
         Counters home;
@@ -724,11 +610,11 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         }
     }
     // the result in one block, one copy
-    const size_t head = ((size_t)Q + 1) * 8 + (((size_t)Q * 12 + 7) & ~(size_t)7), bytes = head + total_recs * sizeof(rk_screen_rec);
+    const size_t head = Result::head_bytes(Q), bytes = head + total_recs * sizeof(rk_screen_rec);
     DevBuf<unsigned char> block(ctx);
     RK_HIP(ctx, block.alloc(bytes));
-    hipLaunchKernelGGL(k_screen_scan, dim3(1), dim3(kScreenThreads), 0, stream, per_q.p + 3 * (size_t)Q, (const uint32_t *)nullptr, Q, (unsigned long long *)block.p,
-                       &cnt_dev.p->all_total);
+    hipLaunchKernelGGL(k_query_scan<kScreenThreads>, dim3(1), dim3(kScreenThreads), 0, stream, per_q.p + 3 * (size_t)Q, (const uint32_t *)nullptr, Q, 0u,
+                       (unsigned long long *)block.p, &cnt_dev.p->all_total);
     RK_HIP(ctx, hipGetLastError());
     st->launches++;
     if (Q) RK_HIP(ctx, hipMemcpyAsync(block.p + ((size_t)Q + 1) * 8, per_q.p + Q, (size_t)4 * Q, hipMemcpyDeviceToDevice, stream));              // matched
@@ -779,10 +665,10 @@ int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n
     std::vector<uint32_t> fixed;
     const uint32_t *post = nullptr;
     if (int rc = prepare_lists(postings, counts, n_lists, n_ref, &pos, &fixed, &post)) return rc;
-    const RowSel sel(opts, n_query);
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, n_query);
     HostResult r;
     if (int rc = screen_core(post, pos.data(), q_off, q_lists, n_query, n_ref, ref_sizes, query_sizes, opts, sel, true, &r)) return rc;
-    return hand_out(r, sel, n_query, off_out, recs_out, n_recs, matched_out, n_cand_out, claimed_out);
+    return hand_out(view(r), sel, n_query, off_out, recs_out, n_recs, {matched_out, n_cand_out, claimed_out});
 }
 
 int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out, rk_screen_rec **recs_out,
@@ -805,61 +691,35 @@ int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
     fill_constants(&st);
     const TimedSpan span{ctx, RK_MS_SCREEN};
     span.clear();
-    const RowSel sel(opts, Q);
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, Q);
     st.rows = (uint32_t)sel.rows.size();
-    if (!N || sel.rows.empty()) {   // nothing runs: every row is empty
-        memset(off_out, 0, ((size_t)Q + 1) * 8);
-        for (const uint32_t q : sel.rows) matched_out[q] = n_cand_out[q] = claimed_out[q] = 0;
-        *recs_out = nullptr;
-        *n_recs = 0;
-        if (stats) *stats = st;
-        return RK_OK;
-    }
-    if (rk_switched_off("RK_SCREEN_DEVICE")) {
+    uint32_t *const outs[3] = {matched_out, n_cand_out, claimed_out};
+    HostResult host;
+    DeviceResult dev;
+    Result r;
+    const bool runs = N && !sel.rows.empty();   // (else every row is empty: r stays without offsets)
+    if (runs && rk_switched_off("RK_SCREEN_DEVICE")) {
         st.path = 2;
-        HostResult r;
-        RK_TRY(idx->wide ? screen_on_host<uint64_t>(ctx, idx, queries, opts, sel, &r) : screen_on_host<uint32_t>(ctx, idx, queries, opts, sel, &r));
-        st.records = r.recs.size();
-        for (size_t k = 0; k < r.matched.size(); k++) {
-            st.matched += r.matched[k];
-            st.candidates += r.n_cand[k];
-            st.claimed += r.claimed[k];
-        }
-        st.postings_walked = r.walked;
-        st.lane_lists = r.lane_lists;
-        st.wave_lists = r.wave_lists;
-        st.block_lists = r.block_lists;
+        RK_TRY(idx->wide ? screen_on_host<uint64_t>(ctx, idx, queries, opts, sel, &host) : screen_on_host<uint32_t>(ctx, idx, queries, opts, sel, &host));
+        r = view(host);
+        st.postings_walked = host.walked;
+        st.lane_lists = host.lane_lists;
+        st.wave_lists = host.wave_lists;
+        st.block_lists = host.block_lists;
         st.batches = 1;
         st.rows_per_batch = sel.rows.size();
-        if (hand_out(r, sel, Q, off_out, recs_out, n_recs, matched_out, n_cand_out, claimed_out)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
-        if (stats) *stats = st;
-        return RK_OK;
+    } else if (runs) {
+        st.path = 1;
+        RK_TRY(screen_on_device(ctx, idx, queries, opts, sel, &st, &dev));
+        r = Result::from_block(dev.block.data(), Q, dev.n_recs);
     }
-    st.path = 1;
-    DeviceResult res;
-    RK_TRY(screen_on_device(ctx, idx, queries, opts, sel, &st, &res));
-    const unsigned char *b = res.block.data();
-    const uint64_t *off = (const uint64_t *)b;
-    const uint32_t *matched = (const uint32_t *)(b + ((size_t)Q + 1) * 8), *n_cand = matched + Q, *claimed = n_cand + Q;
-    const size_t head = ((size_t)Q + 1) * 8 + (((size_t)Q * 12 + 7) & ~(size_t)7);
-    rk_screen_rec *p = nullptr;
-    if (res.n_recs) {
-        p = (rk_screen_rec *)malloc(res.n_recs * sizeof(rk_screen_rec));
-        if (!p) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
-        memcpy(p, b + head, res.n_recs * sizeof(rk_screen_rec));
-    }
-    memcpy(off_out, off, ((size_t)Q + 1) * 8);
+    if (hand_out(r, sel, Q, off_out, recs_out, n_recs, outs)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+    st.records = r.n_recs;
     for (const uint32_t q : sel.rows) {
-        matched_out[q] = matched[q];
-        n_cand_out[q] = n_cand[q];
-        claimed_out[q] = claimed[q];
-        st.matched += matched[q];
-        st.candidates += n_cand[q];
-        st.claimed += claimed[q];
+        st.matched += matched_out[q];
+        st.candidates += n_cand_out[q];
+        st.claimed += claimed_out[q];
     }
-    st.records = res.n_recs;
-    *recs_out = p;
-    *n_recs = res.n_recs;
     if (stats) *stats = st;
     return RK_OK;
 }

@@ -317,6 +317,21 @@ def test_more_candidates_than_one_workgroup_has_threads(ctx):
     assert picks["ref"].tolist() == [2500] and n_cand.tolist() == [1] and covered.tolist() == [3] and matched.tolist() == [3000]
 
 
+@pytest.mark.parametrize("delta", [-1, 0, 1])
+def test_rows_around_one_chunk_of_the_scan(ctx, delta):
+    """k_query_scan (rk_query_dev.h, shared with rk_screen_rows) takes the rows in chunks of the workgroup's threads with a carry:
+    threads - 1, threads and threads + 1 rows in one batch, so that its scans -- the candidates, their room capped at max_picks, the
+    picks, and off[] over all rows -- end inside, at and one behind a chunk.  Row q holds a private hash of reference q % 8 and, when q
+    is odd, one of the next reference: one or two candidates, of which max_picks = 1 keeps one"""
+    threads = constants(ctx)[2]
+    pool = np.random.default_rng(23).permutation(1 << 22)[:800].astype(np.uint32)
+    refs = [np.sort(pool[100 * v: 100 * v + 100]) for v in range(8)]
+    queries = [np.sort(pool[[100 * (q % 8) + q // 8] + ([100 * ((q + 1) % 8) + q // 8] if q % 2 else [])]) for q in range(threads + delta)]
+    assert threads // 8 < 100
+    (off, picks, matched, n_cand, covered), st = gathered(ctx, index_of(ctx, refs), queries_of(ctx, queries), refs, queries, max_picks=1)
+    assert st["batches"] == 1 and off.tolist() == list(range(threads + delta + 1)) and n_cand.tolist() == [1 + q % 2 for q in range(threads + delta)]
+
+
 # ---- 7. batches, shards, the host leg ---------------------------------------------------------------------------------------------------------
 def test_batches_give_the_bytes_of_one_batch(ctx, monkeypatch):
     refs, queries, bits = clades(False)
