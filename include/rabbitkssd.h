@@ -262,8 +262,10 @@ const uint32_t *rk_sketches_hashes_dev(const rk_sketches *s);
 const uint64_t *rk_sketches_off_dev(const rk_sketches *s);
 /* Counted sketches.  An rk_sketches may carry an optional device array counts[total], aligned with its hashes: counts[i] is the
  * multiplicity of hash i in its genome.  The counted sketch calls produce it, rk_sketches_from_host_counts imports it.
- * EVERY consumer of sketches ignores the counts -- rk_index_build, the joins (rk_dist_rows, rk_dist_topn, ...), rk_sketches_mask,
- * rk_group_sketches, rk_gather_rows, rk_screen_rows, rk_lca_rows, the shard calls -- and the objects they derive carry none.
+ * Every consumer of sketches but two ignores the counts -- rk_index_build, the joins (rk_dist_rows, rk_dist_topn, ...), rk_sketches_mask,
+ * rk_group_sketches, rk_gather_rows, rk_screen_rows, rk_lca_rows, the shard calls -- and the objects they derive carry none.  The two
+ * that read them: rk_screen_abund_rows, the screen with the median and the summed multiplicity of every record, and
+ * rk_sketches_mask_counts, whose survivors keep their counts.
  *   rk_sketches_has_counts       1 with counts, 0 without (or s == NULL)
  *   rk_sketches_counts_dev       the device array, NULL without counts
  *   rk_sketches_download_counts  copies counts[total] to a caller buffer; RK_ERR_UNSUPPORTED without counts
@@ -1173,6 +1175,18 @@ int rk_mask_lists(const void *q_hashes, int wide, const uint64_t *q_off /* n_que
                   const uint32_t *counts, uint64_t n_lists, const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out /* n_query + 1 */,
                   rk_mask_stats *stats /* optional */);
 
+/* rk_sketches_mask_counts: rk_sketches_mask for COUNTED queries (rk_sketches_has_counts; RK_ERR_UNSUPPORTED without counts, nothing
+ * written).  The rule, the statistics, the hashes and the offsets are those of rk_sketches_mask, byte for byte; *out carries counts:
+ * every surviving hash keeps its count (the scatter kernel in a second instantiation writes it beside the hash).  RK_MASK_DEVICE=0
+ * answers inside the call as export + rk_mask_lists_counts + rk_sketches_from_host_counts.  rk_mask_lists_counts: rk_mask_lists with
+ * q_counts parallel to q_hashes (RK_ERR_ARG when NULL with hashes) and *counts_out (rk_free_host; NULL when nothing survives)
+ * parallel to *hashes_out. */
+int rk_sketches_mask_counts(rk_ctx *ctx, const rk_sketches *queries, const rk_index *idx, const rk_mask_rule *rule, rk_sketches **out,
+                            rk_mask_stats *stats /* optional */);
+int rk_mask_lists_counts(const void *q_hashes, const uint32_t *q_counts, int wide, const uint64_t *q_off /* n_query + 1 */, uint32_t n_query,
+                         const void *list_hashes, const uint32_t *counts, uint64_t n_lists, const rk_mask_rule *rule, void **hashes_out,
+                         uint32_t **counts_out, uint64_t *off_out /* n_query + 1 */, rk_mask_stats *stats /* optional */);
+
 /* ---- taxonomic classification by per-hash LCA -------------------------------------------- */
 /* rk_lca_rows: per query sketch the tally of the lowest common ancestors of its hashes in a taxonomy over the references -- the rule of
  * Kraken and of sourmash `lca classify` / `summarize`, on the device, in integers only.
@@ -1354,6 +1368,70 @@ int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n
                     const uint64_t *q_lists, uint32_t n_query, uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes,
                     const rk_screen_opts *opts, uint64_t *off_out /* n_query + 1 */, rk_screen_rec **recs_out, uint64_t *n_recs,
                     uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out);
+
+/* ---- the screen with abundances ------------------------------------------------------------------ */
+/* rk_screen_abund_rows: rk_screen_rows for COUNTED query sketches (rk_sketches_has_counts; RK_ERR_UNSUPPORTED without counts, nothing
+ * written).  The rule does not change: off_out, *recs_out, *n_recs, matched_out, n_cand_out and claimed_out are byte for byte those of
+ * rk_screen_rows for the same index, queries and options.  With m(h) >= 1 the count of hash h in its query, every record gets a parallel
+ * record (*abund_out)[i] (the library's, rk_free_host; NULL when there is no record):
+ *   occ_common  the sum of m(h) over S n R_ref          med_common  the LOWER median of m(h) over S n R_ref
+ *   occ_won     the sum of m(h) over the hashes ref claims   med_won  the lower median over the claimed hashes, 0 when won == 0
+ * The lower median of n values is the one of 0-based rank (n - 1) / 2 in ascending order.  occ_out (host, 3 Q entries; only those of the
+ * selected rows are written): occ_out[3 q] = the sum of m over the whole sketch q, [3 q + 1] over its matched hashes, [3 q + 2] over its
+ * claimed hashes.  Everything is integers; the result is unique as that of rk_screen_rows is, and row shards concatenate.
+ * On the device the batches, the counter rows, the winner pass, the count, the scan and the write are those of rk_screen_rows (the count
+ * and the write kernel in a second instantiation: the one read-back of a batch also brings every row's records and the sum of their
+ * common, the write also leaves, in the dead won row, the record of every cell + 1 and gives every record a segment of exactly `common`
+ * values).  Then, per sub-range of the batch's rows whose values fit RK_SCREEN_VALUE_BYTES (default: the batch budget; at least one
+ * row), nothing read back in between: the fill kernel -- the tiles, the look-up and the three walks of the winner pass; it finds the
+ * winner of a hash again (one more walk of a list that is in cache, instead of 4 bytes per query hash and another instantiation of
+ * the winner kernel) and hands m(h) to every holder with a record, the winner's at seg + front++, the others' at seg + common - 1 -
+ * back++ (relaxed agent-scope adds on two cursors per record), so a segment holds its claimed values in [0, won) -- and the select
+ * kernels: a segment of up to rank_max values is ranked by one wave in registers, one of up to wave_sel_max by one wave with a radix
+ * select (four rounds of a pair of 256-bin LDS histograms: the claimed part and the whole together), a longer one by a workgroup.
+ * Nothing is sorted, no kernel waits for another workgroup, every store is a plain vector store.
+ * RK_SCREEN_DEVICE=0 answers inside the call as export + rk_screen_abund_lists, with the same bytes; stats->path says which leg ran.
+ * The refusals and the empty cases are those of rk_screen_rows; abund_out and occ_out (Q > 0) must not be NULL. */
+#define RK_MS_SCREEN_ABUND 18   /* rk_screen_abund_rows: the counts of the first batch through the last select kernel; 0 on the host leg */
+typedef struct rk_screen_abund {
+    uint64_t occ_common;     /* the sum of m(h) over S n R_ref */
+    uint64_t occ_won;        /* the sum of m(h) over the hashes ref claims */
+    uint32_t med_common;     /* the lower median of m(h) over S n R_ref */
+    uint32_t med_won;        /* the lower median over the claimed hashes; 0 when won == 0 */
+} rk_screen_abund;           /* 24 bytes */
+typedef struct rk_screen_abund_stats {
+    uint64_t records, candidates, matched, claimed;   /* these 120 bytes: rk_screen_stats, field by field */
+    uint64_t postings_walked;
+    uint64_t adds;
+    uint64_t lane_lists, wave_lists, block_lists;
+    uint64_t rows_per_batch;
+    uint32_t path;
+    uint32_t rows;
+    uint32_t batches;
+    uint32_t launches;
+    uint32_t read_backs;
+    uint32_t lane_max, wave_max, tile_hashes, threads;
+    uint32_t pad_;
+    uint64_t values;         /* the sum of common over the records: the values handed out */
+    uint64_t value_bytes;    /* the budget of the values of one sub-range (device leg) */
+    uint64_t rank_segs, wave_segs, block_segs;   /* records by who selects their medians (the host leg: by the class of their length) */
+    uint32_t value_passes;   /* fill passes: the sub-ranges of all batches (device leg) */
+    uint32_t rank_max, wave_sel_max, chunk;   /* a wave ranks up to rank_max values in registers, selects up to wave_sel_max by radix; a
+                                                 workgroup takes longer segments, `chunk` values per step (every path fills them) */
+} rk_screen_abund_stats;     /* 176 bytes */
+int rk_screen_abund_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out /* host, Q + 1 */,
+                         rk_screen_rec **recs_out, rk_screen_abund **abund_out, uint64_t *n_recs, uint32_t *matched_out /* host, Q */,
+                         uint32_t *n_cand_out /* host, Q */, uint32_t *claimed_out /* host, Q */, uint64_t *occ_out /* host, 3 Q */,
+                         rk_screen_abund_stats *stats /* optional */);
+/* Host only, no context: rk_screen_lists with q_counts parallel to q_lists (the count of the query hash that hit that list, >= 1) and
+ * query_occ (n_query: the sum of the counts of the whole sketch, which only fills occ_out[3 q]).  RK_ERR_ARG: what rk_screen_lists
+ * refuses, abund_out or occ_out (n_query > 0) NULL, q_counts NULL when a query hits a list, query_occ NULL when n_query > 0, a count of
+ * 0.  Nothing is written on a refusal. */
+int rk_screen_abund_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off /* n_query + 1 */,
+                          const uint64_t *q_lists, const uint32_t *q_counts, uint32_t n_query, uint32_t n_ref, const uint32_t *ref_sizes,
+                          const uint32_t *query_sizes, const uint64_t *query_occ, const rk_screen_opts *opts, uint64_t *off_out /* n_query + 1 */,
+                          rk_screen_rec **recs_out, rk_screen_abund **abund_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out,
+                          uint32_t *claimed_out, uint64_t *occ_out /* 3 n_query */);
 
 /* one output line, "%s\t%s\t%d|%d|%d\t%f\t%f\n" (src/dist.cpp:233 / :642) */
 int rk_format_hit(char *buf, size_t cap, const char *name_a, const char *name_b,

@@ -35,6 +35,7 @@ EXPORTS = [
     "rk_medoid_rows", "rk_medoid_hits", "rk_medoid_merge", "rk_medoid_pick", "rk_assign_rows", "rk_assign_hits",
     "rk_group_sketches", "rk_group_lists", "rk_gather_rows", "rk_gather_lists", "rk_sketches_mask", "rk_mask_lists",
     "rk_lca_rows", "rk_lca_lists", "rk_lca_call", "rk_screen_rows", "rk_screen_lists",
+    "rk_screen_abund_rows", "rk_screen_abund_lists", "rk_sketches_mask_counts", "rk_mask_lists_counts",
 ]
 
 # the words of rk_index_build_plan (RK_PLAN_*) and rk_index_build_report (RK_REPORT_*), in order
@@ -63,6 +64,9 @@ LCA_CALLED_DTYPE = np.dtype([("taxon", "<u4"), ("candidate", "<u4"), ("clade", "
 MS_SCREEN = 17              # RK_MS_SCREEN: the timed span of rk_screen_rows (Context.last_ms)
 # rk_screen_rec: one record per candidate of rk_screen_rows / rk_screen_lists that claims at least min_won hashes
 SCREEN_REC_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("common", "<u4"), ("won", "<u4"), ("size_ref", "<u4"), ("size_query", "<u4")])
+MS_SCREEN_ABUND = 18        # RK_MS_SCREEN_ABUND: the timed span of rk_screen_abund_rows (Context.last_ms)
+# rk_screen_abund: one record per record of rk_screen_abund_rows / rk_screen_abund_lists, parallel to the screen records
+SCREEN_ABUND_DTYPE = np.dtype([("occ_common", "<u8"), ("occ_won", "<u8"), ("med_common", "<u4"), ("med_won", "<u4")])
 # rk_gather_pick: one record per pick of rk_gather_rows / rk_gather_lists
 GATHER_PICK_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("rank", "<u4"), ("common", "<u4"), ("fresh", "<u4"), ("left", "<u4"),
                               ("size_ref", "<u4"), ("size_query", "<u4")])
@@ -197,6 +201,13 @@ class ScreenStats(C.Structure):
                 ("adds", C.c_uint64), ("lane_lists", C.c_uint64), ("wave_lists", C.c_uint64), ("block_lists", C.c_uint64), ("rows_per_batch", C.c_uint64),
                 ("path", C.c_uint32), ("rows", C.c_uint32), ("batches", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32),
                 ("lane_max", C.c_uint32), ("wave_max", C.c_uint32), ("tile_hashes", C.c_uint32), ("threads", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class ScreenAbundStats(C.Structure):
+    """rk_screen_abund_stats: what one rk_screen_abund_rows call did -- the fields of ScreenStats, then the values"""
+    _fields_ = ScreenStats._fields_ + [("values", C.c_uint64), ("value_bytes", C.c_uint64), ("rank_segs", C.c_uint64), ("wave_segs", C.c_uint64),
+                                       ("block_segs", C.c_uint64), ("value_passes", C.c_uint32), ("rank_max", C.c_uint32), ("wave_sel_max", C.c_uint32),
+                                       ("chunk", C.c_uint32)]
 
 
 class MaskRule(C.Structure):
@@ -869,6 +880,32 @@ class Context:
                                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(st)))
         return (off, _take_array(recs, n.value, SCREEN_REC_DTYPE)) + tuple(out) + (_stats_dict(st),)
 
+    def screen_abund_rows(self, index, queries, min_common=1, min_won=0, row_first=0, row_step=1, row_block=0, out=None):
+        """screen_rows for counted query sketches (rk_screen_abund_rows): (off, recs, abund, matched, n_cand, claimed, occ, stats) -- off,
+        recs, matched, n_cand and claimed are those of screen_rows; abund (SCREEN_ABUND_DTYPE), parallel to recs: the sum and the lower
+        median of the counts of the query's hashes over what the record shares (occ_common, med_common) and over what it claims
+        (occ_won, med_won; 0 when it claims nothing); occ (uint64, Q x 3): the sums of the counts over the whole sketch, over its
+        matched and over its claimed hashes.  Only the entries of the selected query rows are written: `out` (matched, n_cand,
+        claimed, occ as returned) lets row shards write into one set; their records concatenate"""
+        q = queries.count if queries is not None else 0
+        if out is None:
+            out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(3)) + (np.zeros((q, 3), dtype=np.uint64),)
+        elif (len(out) != 4 or any(not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.shape == (q,) and a.flags.c_contiguous and a.flags.writeable)
+                                   for a in out[:3])
+              or not (isinstance(out[3], np.ndarray) and out[3].dtype == np.uint64 and out[3].shape == (q, 3) and out[3].flags.c_contiguous
+                      and out[3].flags.writeable)):
+            raise ValueError("out needs (matched, n_cand, claimed, occ): writable contiguous uint32 arrays of one entry per query and a uint64 array of three")
+        o = ScreenOpts(int(min_common), int(min_won), int(row_first), int(row_step), int(row_block))
+        off = np.zeros(q + 1, dtype=np.uint64)
+        recs, abund, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        st = ScreenAbundStats()
+        L = lib()
+        L.rk_screen_abund_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScreenOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScreenAbundStats)]
+        self.check(L.rk_screen_abund_rows(self._h, index._h, queries._h if queries is not None else None, C.byref(o), _ptr(off), C.byref(recs), C.byref(abund),
+                                          C.byref(n), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), C.byref(st)))
+        return (off, _take_array(recs, n.value, SCREEN_REC_DTYPE), _take_array(abund, n.value, SCREEN_ABUND_DTYPE)) + tuple(out) + (_stats_dict(st),)
+
     def lca_rows(self, index, queries, taxa, parent, row_first=0, row_step=1, row_block=0, out=None):
         """the tally of per-hash lowest common ancestors of each query sketch (rk_lca_rows): (off, counts, matched, unlabelled, stats) --
         parent (uint32, one entry per node of the taxonomy, the root names itself), taxa (uint32, one node or LCA_NONE per reference in
@@ -911,6 +948,19 @@ class Context:
         L.rk_sketches_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MaskRule), C.POINTER(C.c_void_p), C.POINTER(MaskStats)]
         self.check(L.rk_sketches_mask(self._h, queries._h if queries is not None else None, index._h if index is not None else None, C.byref(r),
                                       C.byref(h), C.byref(st)))
+        return (Sketches(self, h) if h.value else None), _stats_dict(st)
+
+    def sketches_mask_counts(self, queries, index, min_refs=0, max_refs=0):
+        """sketches_mask for counted query sketches (rk_sketches_mask_counts): (sketches, stats) -- the same hashes, offsets and stats;
+        the result carries counts: every survivor keeps its count (Sketches.download_counts).  RkError (RK_ERR_UNSUPPORTED) for queries
+        without counts"""
+        r = MaskRule(int(min_refs), int(max_refs))
+        h = C.c_void_p()
+        st = MaskStats()
+        L = lib()
+        L.rk_sketches_mask_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MaskRule), C.POINTER(C.c_void_p), C.POINTER(MaskStats)]
+        self.check(L.rk_sketches_mask_counts(self._h, queries._h if queries is not None else None, index._h if index is not None else None, C.byref(r),
+                                             C.byref(h), C.byref(st)))
         return (Sketches(self, h) if h.value else None), _stats_dict(st)
 
     def dist_rows_dev(self, index, triangle, metric, kmer_size, max_dist, hits_dev_ptr, hits_cap,
@@ -1384,6 +1434,44 @@ def screen_lists(postings, counts, q_off, q_lists, n_ref, ref_sizes, query_sizes
     return (off, _take_array(recs, n.value, SCREEN_REC_DTYPE)) + out
 
 
+def screen_abund_lists(postings, counts, q_off, q_lists, q_counts, n_ref, ref_sizes, query_sizes, query_occ, min_common=1, min_won=0, row_first=0, row_step=1,
+                       row_block=0):
+    """the rule of Context.screen_abund_rows over exported posting lists (rk_screen_abund_lists, host only): (off, recs, abund, matched,
+    n_cand, claimed, occ) -- the arguments of screen_lists, q_counts parallel to q_lists (the count of the query hash that hit that
+    list, at least 1) and query_occ (the sum of the counts of every whole sketch: it only fills occ[:, 0])"""
+    postings = np.ascontiguousarray(postings, dtype=np.uint32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if int(counts.sum(dtype=np.uint64)) != len(postings):
+        raise ValueError("screen_abund_lists: the counts do not add up to the postings")
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    q_lists = np.ascontiguousarray(q_lists, dtype=np.uint64)
+    q_counts = np.ascontiguousarray(q_counts, dtype=np.uint32)
+    ref_sizes = np.ascontiguousarray(ref_sizes, dtype=np.uint32)
+    query_sizes = np.ascontiguousarray(query_sizes, dtype=np.uint32)
+    query_occ = np.ascontiguousarray(query_occ, dtype=np.uint64)
+    q = len(query_sizes)
+    if len(q_off) != q + 1 or len(ref_sizes) != int(n_ref) or (q and int(q_off[-1]) != len(q_lists)) or len(q_counts) != len(q_lists) or len(query_occ) != q:
+        raise ValueError("screen_abund_lists needs one size per reference, one size and one sum per query, q_off of one entry more than the queries, "
+                         "ending at len(q_lists), and one count per entry of q_lists")
+    o = ScreenOpts(int(min_common), int(min_won), int(row_first), int(row_step), int(row_block))
+    off = np.zeros(q + 1, dtype=np.uint64)
+    out = tuple(np.zeros(q, dtype=np.uint32) for _ in range(3))
+    occ = np.zeros((q, 3), dtype=np.uint64)
+    recs, abund, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    L = lib()
+    L.rk_screen_abund_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(ScreenOpts), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.rk_screen_abund_lists(_ptr(postings) if len(postings) else None, _ptr(counts) if len(counts) else None, C.c_uint64(len(counts)), _ptr(q_off),
+                                 _ptr(q_lists) if len(q_lists) else None, _ptr(q_counts) if len(q_counts) else None, C.c_uint32(q), C.c_uint32(n_ref),
+                                 _ptr(ref_sizes) if n_ref else None, _ptr(query_sizes) if q else None, _ptr(query_occ) if q else None, C.byref(o), _ptr(off),
+                                 C.byref(recs), C.byref(abund), C.byref(n), _ptr(out[0]) if q else None, _ptr(out[1]) if q else None, _ptr(out[2]) if q else None,
+                                 _ptr(occ) if q else None)
+    if rc:
+        raise RkError(rc, "rk_screen_abund_lists: what rk_screen_lists refuses, or a count of 0")
+    return (off, _take_array(recs, n.value, SCREEN_REC_DTYPE), _take_array(abund, n.value, SCREEN_ABUND_DTYPE)) + out + (occ,)
+
+
 def lca_lists(postings, counts, q_off, q_lists, taxa, parent, row_first=0, row_step=1, row_block=0):
     """the rule of Context.lca_rows over exported posting lists (rk_lca_lists, host only): (off, counts, matched, unlabelled, stats) --
     the lists back to back in `postings` with their lengths in `counts` (Index.export_lists / export64), reference ids in any order
@@ -1473,6 +1561,34 @@ def mask_lists(q_hashes, q_off, list_hashes, counts, min_refs=0, max_refs=0):
     if rc:
         raise RkError(rc, "rk_mask_lists: min_refs above max_refs, offsets that do not ascend from 0, or list hashes that do not strictly ascend")
     return _take_array(h, int(off[-1]), q_hashes.dtype), off, _stats_dict(st)
+
+
+def mask_lists_counts(q_hashes, q_counts, q_off, list_hashes, counts, min_refs=0, max_refs=0):
+    """mask_lists with the counts of the query hashes (rk_mask_lists_counts, host only): (hashes, kept counts, off, stats) -- q_counts
+    parallel to q_hashes; every survivor keeps its count"""
+    q_hashes = np.ascontiguousarray(q_hashes)
+    if q_hashes.dtype not in (np.uint32, np.uint64):
+        raise ValueError("mask_lists_counts needs uint32 or uint64 query hashes")
+    q_counts = np.ascontiguousarray(q_counts, dtype=np.uint32)
+    list_hashes = np.ascontiguousarray(list_hashes, dtype=q_hashes.dtype)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    if len(q_off) < 1 or len(counts) != len(list_hashes) or int(q_off[-1]) > len(q_hashes) or len(q_counts) != len(q_hashes):
+        raise ValueError("mask_lists_counts needs one count per list hash, one per query hash, and offsets that end within the query hashes")
+    q = len(q_off) - 1
+    r = MaskRule(int(min_refs), int(max_refs))
+    off = np.zeros(q + 1, dtype=np.uint64)
+    h, c = C.c_void_p(), C.c_void_p()
+    st = MaskStats()
+    L = lib()
+    L.rk_mask_lists_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MaskRule),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(MaskStats)]
+    rc = L.rk_mask_lists_counts(_ptr(q_hashes) if len(q_hashes) else None, _ptr(q_counts) if len(q_counts) else None, int(q_hashes.dtype == np.uint64),
+                                _ptr(q_off), C.c_uint32(q), _ptr(list_hashes) if len(counts) else None, _ptr(counts) if len(counts) else None,
+                                C.c_uint64(len(counts)), C.byref(r), C.byref(h), C.byref(c), _ptr(off), C.byref(st))
+    if rc:
+        raise RkError(rc, "rk_mask_lists_counts: min_refs above max_refs, offsets that do not ascend from 0, or list hashes that do not strictly ascend")
+    return _take_array(h, int(off[-1]), q_hashes.dtype), _take_array(c, int(off[-1]), np.uint32), off, _stats_dict(st)
 
 
 def medoid_merge(a, b, n, metric):

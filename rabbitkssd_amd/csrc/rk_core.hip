@@ -330,7 +330,7 @@ void rk_ctx_pool_stats(rk_ctx *ctx, uint64_t out[4])
     out[3] = ctx->driver_frees;
 }
 
-double rk_ctx_last_ms(const rk_ctx *ctx, int which) { return ctx && which >= 0 && which < 18 ? ctx->last_ms[which] : 0.0; }
+double rk_ctx_last_ms(const rk_ctx *ctx, int which) { return ctx && which >= 0 && which < 19 ? ctx->last_ms[which] : 0.0; }
 
 void rk_ctx_trim(rk_ctx *ctx)
 {

@@ -49,7 +49,7 @@ struct rk_ctx {
                                // object load) costs more than they save on one call
     bool timing = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double last_ms[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // RK_MS_* (include/rabbitkssd.h)
+    double last_ms[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // RK_MS_* (include/rabbitkssd.h)
     rk_sketch_plan sketch_plan = {};   // rk_sketch_last_plan: what the last sketch pass did
     bool sketch_plan_set = false;
     // developer switches (environment), read once at context creation

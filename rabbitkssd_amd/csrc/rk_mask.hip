@@ -15,6 +15,7 @@
 //             those workgroups.  tile_prefix() adds the two;
 //   scatter   k_mask_scatter: a tile's 32 keep words once per wave (their popcounts scanned across lanes), then every survivor to
 //             tile prefix + survivors before it in the tile.  Order is preserved; no atomics;
+//             k_mask_scatter<Hash, true> (rk_sketches_mask_counts): the survivor's count goes to the same place of the result's counts;
 //   offsets   k_mask_offsets: one lane per offset entry, off_out[g] = the survivors before element off_in[g], from the tile prefix and
 //             the keep words of one tile.  No segmented scan; empty sketches fall out by themselves.
 //
@@ -61,6 +62,8 @@ struct MaskArgs {
     void *out_hashes;                  // Hash[kept]
     uint64_t *off_out;                 // u64[n + 1]
     Counters *cnt;
+    const uint32_t *q_counts;          // u32[total]: rk_sketches_mask_counts only
+    uint32_t *out_counts;              // u32[kept]
 };
 
 __device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int delta)
@@ -170,7 +173,8 @@ __global__ void __launch_bounds__(64) k_mask_scan_blocks(MaskArgs a, uint32_t n_
     }
 }
 
-template <class Hash> __global__ void __launch_bounds__(kMaskThreads) k_mask_scatter(MaskArgs a)
+// COUNTS: a survivor's count goes along (rk_sketches_mask_counts)
+template <class Hash, bool COUNTS> __global__ void __launch_bounds__(kMaskThreads) k_mask_scatter(MaskArgs a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long tile = blockIdx.x;
@@ -195,7 +199,11 @@ template <class Hash> __global__ void __launch_bounds__(kMaskThreads) k_mask_sca
         const unsigned long long m = shfl_u64(word, w);
         const uint32_t before = (uint32_t)__shfl((int)word_before, w);
         // (a set bit names an element below total: k_mask_flag set it; its place lies below the sum of all tile counts)
-        if (m >> lane & 1ULL) out[first + before + (uint32_t)__popcll(m & lanes_below(lane))] = q[base + 64 * t + lane];
+        if (m >> lane & 1ULL) {
+            const unsigned long long at = first + before + (uint32_t)__popcll(m & lanes_below(lane));
+            out[at] = q[base + 64 * t + lane];
+            if constexpr (COUNTS) a.out_counts[at] = a.q_counts[base + 64 * t + lane];
+        }
     }
 }
 
@@ -238,9 +246,11 @@ void fill_geometry(rk_mask_stats *st, uint64_t hashes)
 }
 
 // the survivors of every query in its own order; off[n_query + 1]; counts what rk_mask_stats counts
+// (q_counts with kept_counts: the count of every survivor goes along)
 template <class Hash>
 void mask_lists(const Hash *q, const uint64_t *q_off, uint32_t n_query, const Hash *list_hashes, const uint32_t *counts, uint64_t n_lists,
-                const rk_mask_rule *rule, std::vector<Hash> *kept, uint64_t *off, rk_mask_stats *st)
+                const rk_mask_rule *rule, std::vector<Hash> *kept, uint64_t *off, rk_mask_stats *st, const uint32_t *q_counts = nullptr,
+                std::vector<uint32_t> *kept_counts = nullptr)
 {
     kept->clear();
     off[0] = 0;
@@ -249,7 +259,10 @@ void mask_lists(const Hash *q, const uint64_t *q_off, uint32_t n_query, const Ha
             const Hash *at = std::lower_bound(list_hashes, list_hashes + n_lists, q[j]);
             const uint32_t c = at != list_hashes + n_lists && *at == q[j] ? counts[at - list_hashes] : 0u;
             st->matched += c > 0;
-            if (c >= rule->min_refs && c <= rule->max_refs) kept->push_back(q[j]);
+            if (c >= rule->min_refs && c <= rule->max_refs) {
+                kept->push_back(q[j]);
+                if (kept_counts) kept_counts->push_back(q_counts[j]);
+            }
         }
         off[i + 1] = kept->size();
         st->emptied += q_off[i + 1] > q_off[i] && off[i + 1] == off[i];
@@ -258,9 +271,13 @@ void mask_lists(const Hash *q, const uint64_t *q_off, uint32_t n_query, const Ha
 }
 
 // RK_MASK_DEVICE=0: download + export + the rule on the host + rk_sketches_from_host(64)
-template <class Hash> int mask_on_host(rk_ctx *ctx, const rk_sketches *qs, const rk_index *idx, const rk_mask_rule *rule, rk_mask_stats *st, rk_sketches **out)
+// (with_counts: + rk_sketches_download_counts, the result by rk_sketches_from_host_counts)
+template <class Hash>
+int mask_on_host(rk_ctx *ctx, const rk_sketches *qs, const rk_index *idx, const rk_mask_rule *rule, bool with_counts, rk_mask_stats *st, rk_sketches **out)
 {
     std::vector<Hash> q(qs->total), hashes(idx->U), kept;
+    std::vector<uint32_t> qc((size_t)(with_counts ? qs->total : 0)), kc;
+    if (with_counts) RK_TRY(rk_sketches_download_counts(qs, qc.data()));
     std::vector<uint32_t> postings(idx->H), counts(idx->U);
     std::vector<uint64_t> off((size_t)qs->n + 1);
     if constexpr (sizeof(Hash) == 8) {
@@ -271,12 +288,14 @@ template <class Hash> int mask_on_host(rk_ctx *ctx, const rk_sketches *qs, const
         if (idx->U) RK_TRY(rk_index_export_lists(idx, postings.data(), hashes.data(), counts.data()));
     }
     // (a hash at or beyond 2^hash_bits is none of the exported hashes: the index holds none)
-    mask_lists(q.data(), qs->h_off.data(), qs->n, hashes.data(), counts.data(), idx->U, rule, &kept, off.data(), st);
+    mask_lists(q.data(), qs->h_off.data(), qs->n, hashes.data(), counts.data(), idx->U, rule, &kept, off.data(), st, with_counts ? qc.data() : nullptr,
+               with_counts ? &kc : nullptr);
+    if (with_counts) return rk_sketches_from_host_counts(ctx, kept.data(), sizeof(Hash) == 8, kc.data(), off.data(), qs->n, out);
     if constexpr (sizeof(Hash) == 8) return rk_sketches_from_host64(ctx, kept.data(), off.data(), qs->n, out);
     else return rk_sketches_from_host(ctx, kept.data(), off.data(), qs->n, out);
 }
 
-int mask_on_device(rk_ctx *ctx, const rk_sketches *qs, const rk_index *idx, const rk_mask_rule *rule, rk_mask_stats *st, rk_sketches **out)
+int mask_on_device(rk_ctx *ctx, const rk_sketches *qs, const rk_index *idx, const rk_mask_rule *rule, bool with_counts, rk_mask_stats *st, rk_sketches **out)
 {
     const uint32_t n = qs->n;
     const uint64_t total = qs->total, tiles = st->tiles;
@@ -339,7 +358,13 @@ int mask_on_device(rk_ctx *ctx, const rk_sketches *qs, const rk_index *idx, cons
         Hash *&hashes = hashes_of(s, ht);
         RK_TRY(pool_array(ctx, &hashes, total + 1));
         a.out_hashes = hashes;
-        if (tiles) hipLaunchKernelGGL(k_mask_scatter<Hash>, dim3((unsigned)tiles), dim3(kMaskThreads), 0, stream, a);
+        if (with_counts) {
+            RK_TRY(pool_array(ctx, &s->d_counts, total + 1));
+            a.q_counts = qs->d_counts;
+            a.out_counts = s->d_counts;
+        }
+        const auto scatter = with_counts ? k_mask_scatter<Hash, true> : k_mask_scatter<Hash, false>;
+        if (tiles) hipLaunchKernelGGL(scatter, dim3((unsigned)tiles), dim3(kMaskThreads), 0, stream, a);
         hipLaunchKernelGGL(k_mask_offsets<Hash>, dim3(blocks_for((uint64_t)n + 1, kMaskThreads)), dim3(kMaskThreads), 0, stream, a);
         RK_HIP(ctx, hipGetLastError());
         return RK_OK;
@@ -377,9 +402,11 @@ template <class Hash> bool strictly_ascending(const Hash *h, uint64_t n)
     return true;
 }
 
+// (counts_out with q_counts: rk_mask_lists_counts)
 template <class Hash>
 int mask_lists_call(const void *q_hashes, const uint64_t *q_off, uint32_t n_query, const void *list_hashes, const uint32_t *counts, uint64_t n_lists,
-                    const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out, rk_mask_stats *stats)
+                    const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out, rk_mask_stats *stats, const uint32_t *q_counts = nullptr,
+                    uint32_t **counts_out = nullptr)
 {
     if (!strictly_ascending((const Hash *)list_hashes, n_lists)) return RK_ERR_ARG;
     rk_mask_stats st;
@@ -388,15 +415,27 @@ int mask_lists_call(const void *q_hashes, const uint64_t *q_off, uint32_t n_quer
     st.path = 2;
     std::vector<Hash> kept;
     std::vector<uint64_t> off((size_t)n_query + 1);
-    mask_lists((const Hash *)q_hashes, q_off, n_query, (const Hash *)list_hashes, counts, n_lists, rule, &kept, off.data(), &st);
+    std::vector<uint32_t> kept_counts;
+    mask_lists((const Hash *)q_hashes, q_off, n_query, (const Hash *)list_hashes, counts, n_lists, rule, &kept, off.data(), &st, q_counts,
+               counts_out ? &kept_counts : nullptr);
     void *h = nullptr;
+    uint32_t *c = nullptr;
     if (!kept.empty()) {
         h = malloc(kept.size() * sizeof(Hash));
         if (!h) return RK_ERR_NOMEM;
         memcpy(h, kept.data(), kept.size() * sizeof(Hash));
+        if (counts_out) {
+            c = (uint32_t *)malloc(kept.size() * 4);
+            if (!c) {
+                free(h);
+                return RK_ERR_NOMEM;
+            }
+            memcpy(c, kept_counts.data(), kept.size() * 4);
+        }
     }
     memcpy(off_out, off.data(), off.size() * 8);
     *hashes_out = h;
+    if (counts_out) *counts_out = c;
     if (stats) *stats = st;
     return RK_OK;
 }
@@ -405,8 +444,10 @@ int mask_lists_call(const void *q_hashes, const uint64_t *q_off, uint32_t n_quer
 
 extern "C" {
 
-int rk_mask_lists(const void *q_hashes, int wide, const uint64_t *q_off, uint32_t n_query, const void *list_hashes, const uint32_t *counts, uint64_t n_lists,
-                  const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out, rk_mask_stats *stats)
+// rk_mask_lists (counts_out == null) and rk_mask_lists_counts
+static int mask_lists_entry(const void *q_hashes, const uint32_t *q_counts, int wide, const uint64_t *q_off, uint32_t n_query, const void *list_hashes,
+                            const uint32_t *counts, uint64_t n_lists, const rk_mask_rule *rule, void **hashes_out, uint32_t **counts_out, uint64_t *off_out,
+                            rk_mask_stats *stats)
 {
     if (!q_off || !rule || !hashes_out || !off_out) return RK_ERR_ARG;
     if (rule->min_refs > rule->max_refs) return RK_ERR_ARG;
@@ -414,15 +455,45 @@ int rk_mask_lists(const void *q_hashes, int wide, const uint64_t *q_off, uint32_
     if (q_off[0] != 0) return RK_ERR_ARG;
     for (uint32_t i = 0; i < n_query; i++)
         if (q_off[i + 1] < q_off[i]) return RK_ERR_ARG;
-    if (q_off[n_query] && !q_hashes) return RK_ERR_ARG;
-    return wide ? mask_lists_call<uint64_t>(q_hashes, q_off, n_query, list_hashes, counts, n_lists, rule, hashes_out, off_out, stats)
-                : mask_lists_call<uint32_t>(q_hashes, q_off, n_query, list_hashes, counts, n_lists, rule, hashes_out, off_out, stats);
+    if (q_off[n_query] && (!q_hashes || (counts_out && !q_counts))) return RK_ERR_ARG;
+    return wide ? mask_lists_call<uint64_t>(q_hashes, q_off, n_query, list_hashes, counts, n_lists, rule, hashes_out, off_out, stats, q_counts, counts_out)
+                : mask_lists_call<uint32_t>(q_hashes, q_off, n_query, list_hashes, counts, n_lists, rule, hashes_out, off_out, stats, q_counts, counts_out);
 }
+
+int rk_mask_lists(const void *q_hashes, int wide, const uint64_t *q_off, uint32_t n_query, const void *list_hashes, const uint32_t *counts, uint64_t n_lists,
+                  const rk_mask_rule *rule, void **hashes_out, uint64_t *off_out, rk_mask_stats *stats)
+{
+    return mask_lists_entry(q_hashes, nullptr, wide, q_off, n_query, list_hashes, counts, n_lists, rule, hashes_out, nullptr, off_out, stats);
+}
+
+int rk_mask_lists_counts(const void *q_hashes, const uint32_t *q_counts, int wide, const uint64_t *q_off, uint32_t n_query, const void *list_hashes,
+                         const uint32_t *counts, uint64_t n_lists, const rk_mask_rule *rule, void **hashes_out, uint32_t **counts_out, uint64_t *off_out,
+                         rk_mask_stats *stats)
+{
+    if (!counts_out) return RK_ERR_ARG;
+    return mask_lists_entry(q_hashes, q_counts, wide, q_off, n_query, list_hashes, counts, n_lists, rule, hashes_out, counts_out, off_out, stats);
+}
+
+static int sketches_mask(rk_ctx *ctx, const rk_sketches *queries, const rk_index *idx, const rk_mask_rule *rule, bool with_counts, rk_sketches **out,
+                         rk_mask_stats *stats);
 
 int rk_sketches_mask(rk_ctx *ctx, const rk_sketches *queries, const rk_index *idx, const rk_mask_rule *rule, rk_sketches **out, rk_mask_stats *stats)
 {
+    return sketches_mask(ctx, queries, idx, rule, false, out, stats);
+}
+
+int rk_sketches_mask_counts(rk_ctx *ctx, const rk_sketches *queries, const rk_index *idx, const rk_mask_rule *rule, rk_sketches **out, rk_mask_stats *stats)
+{
+    return sketches_mask(ctx, queries, idx, rule, true, out, stats);
+}
+
+// rk_sketches_mask, and with_counts rk_sketches_mask_counts: every survivor keeps its count
+static int sketches_mask(rk_ctx *ctx, const rk_sketches *queries, const rk_index *idx, const rk_mask_rule *rule, bool with_counts, rk_sketches **out,
+                         rk_mask_stats *stats)
+{
     if (!ctx || !queries || !idx || !rule || !out) return RK_ERR_ARG;
-    const char *const who = "rk_sketches_mask";
+    const char *const who = with_counts ? "rk_sketches_mask_counts" : "rk_sketches_mask";
+    if (with_counts && !queries->d_counts) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: the query sketches carry no counts (rk_sketches_has_counts)", who);
     if (rule->min_refs > rule->max_refs) return rk_fail(ctx, RK_ERR_ARG, "%s: min_refs is above max_refs", who);
     if (queries->wide != idx->wide) return rk_fail(ctx, RK_ERR_ARG, "query sketches and index use different hash widths");
     if (!idx->d_postings || !idx->d_upos || idx->n_shards > 1)
@@ -436,10 +507,11 @@ int rk_sketches_mask(rk_ctx *ctx, const rk_sketches *queries, const rk_index *id
         fill_geometry(&st, queries->total);
         if (rk_switched_off("RK_MASK_DEVICE")) {
             st.path = 2;
-            RK_TRY(queries->wide ? mask_on_host<uint64_t>(ctx, queries, idx, rule, &st, &s) : mask_on_host<uint32_t>(ctx, queries, idx, rule, &st, &s));
+            RK_TRY(queries->wide ? mask_on_host<uint64_t>(ctx, queries, idx, rule, with_counts, &st, &s)
+                                 : mask_on_host<uint32_t>(ctx, queries, idx, rule, with_counts, &st, &s));
         } else {
             st.path = 1;
-            RK_TRY(mask_on_device(ctx, queries, idx, rule, &st, &s));
+            RK_TRY(mask_on_device(ctx, queries, idx, rule, with_counts, &st, &s));
         }
     }
     *out = s;

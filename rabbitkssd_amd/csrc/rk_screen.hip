@@ -23,11 +23,16 @@
 //            ascending caller's index without atomics and without a sort;
 //   result   off[Q + 1] by k_query_scan over all rows; ONE copy to the host: 8 (Q + 1) + 12 Q + 24 records bytes.
 //
+// rk_screen_abund_rows (counted queries: per record the sum and the lower median of the counts over what it shares and over what it claims)
+// runs the same batches with the count and the write kernel in their ABUND instantiation, then the fill and select kernels of
+// rk_screen_abund.inc per sub-range of rows; rk_screen_abund_lists is screen_core with q_counts.  DESIGN.md 4.20.
+//
 // Memory scope: every array is written by one kernel and read by a later one on the same stream.  INSIDE a launch the only communication
 // between workgroups is relaxed agent-scope atomic adds -- the +1 on the won rows, matched[] and the statistics, none of which is read
 // before the launch is over -- and LDS between barriers.  No loop waits for another workgroup: any grid works.  DESIGN.md 4.18.
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -272,16 +277,31 @@ struct RowArgs {   // a batch of nb rows: slot s of the batch is query row row_o
     rk_screen_rec *recs;
     const uint32_t *sizes;                     // per caller's reference index
     const uint64_t *q_off;
+    // ABUND only (rk_screen_abund.inc): per slot the records of the row, the sum and the largest of their common, for the batch's one read-back;
+    // per slot where the row's values begin; the won rows once more, as the map; per record where its values begin
+    unsigned long long *row_recs, *row_vals, *row_longest;
+    const unsigned long long *val_off;
+    uint32_t *map;
+    unsigned long long *seg;
 };
 
-// One workgroup per row: the candidates, the records and the sum of won
-__global__ void __launch_bounds__(kScreenThreads) k_screen_count(RowArgs a)
+// One workgroup per row: the candidates, the records and the sum of won; ABUND: also the sum and the largest of common over the records
+template <bool ABUND> __global__ void __launch_bounds__(kScreenThreads) k_screen_count(RowArgs a)
 {
     __shared__ uint32_t s_cand, s_rec, s_claimed;
+    [[maybe_unused]] __shared__ unsigned long long s_vals;
+    [[maybe_unused]] __shared__ uint32_t s_longest;
+    [[maybe_unused]] unsigned long long vals = 0;
+    [[maybe_unused]] uint32_t longest = 0;
     const uint32_t s = blockIdx.x, tid = threadIdx.x;
     const int32_t *cnt = a.cnt + (size_t)s * a.n_ref;
     const uint32_t *won = a.won + (size_t)s * a.n_ref;
     if (tid == 0) s_cand = s_rec = s_claimed = 0;
+    if constexpr (ABUND)
+        if (tid == 0) {
+            s_vals = 0;
+            s_longest = 0;
+        }
     __syncthreads();
     uint32_t n_cand = 0, n_rec = 0, claimed = 0;
     for (uint32_t c = tid; c < a.n_ref; c += kScreenThreads) {
@@ -290,32 +310,55 @@ __global__ void __launch_bounds__(kScreenThreads) k_screen_count(RowArgs a)
         n_cand += cand;
         n_rec += cand && w >= a.min_won;
         claimed += w;
+        if constexpr (ABUND)
+            if (cand && w >= a.min_won) {
+                vals += (uint32_t)cnt[c];
+                longest = max(longest, (uint32_t)cnt[c]);
+            }
     }
     if (n_cand) atomicAdd(&s_cand, n_cand);
     if (n_rec) atomicAdd(&s_rec, n_rec);
     if (claimed) atomicAdd(&s_claimed, claimed);
+    if constexpr (ABUND)
+        if (vals) {
+            atomicAdd(&s_vals, vals);
+            atomicMax(&s_longest, longest);
+        }
     __syncthreads();
     if (tid == 0) {
         const uint32_t row = a.row_of[s];
         a.n_cand_q[row] = s_cand;
         a.nrec_q[row] = s_rec;
         a.claimed_q[row] = s_claimed;
+        if constexpr (ABUND) {
+            a.row_recs[s] = s_rec;
+            a.row_vals[s] = s_vals;
+            a.row_longest[s] = s_longest;
+        }
     }
 }
 
 // One workgroup per row, the row in chunks of the block size: the records at rec_off[s] + the records of the cells before, in the
-// order of the cells
-__global__ void __launch_bounds__(kScreenThreads) k_screen_write(RowArgs a)
+// order of the cells.  ABUND: also map[cell] = the record of the cell + 1 (0: none) over the won row, which nobody reads again, and
+// seg[record] = val_off[s] + the common of the row's records before it
+template <bool ABUND> __global__ void __launch_bounds__(kScreenThreads) k_screen_write(RowArgs a)
 {
     __shared__ uint32_t s_cnt[kWaves];
+    [[maybe_unused]] __shared__ unsigned long long s_val[kWaves];
     const uint32_t s = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
     const int32_t *cnt = a.cnt + (size_t)s * a.n_ref;
     const uint32_t *won = a.won + (size_t)s * a.n_ref;
     const unsigned long long beg = a.rec_off[s], room = a.rec_off[s + 1] - beg;
-    if (!room) return;   // (uniform)
+    if (!room) {   // (uniform)
+        if constexpr (ABUND)
+            for (uint32_t c = tid; c < a.n_ref; c += kScreenThreads) a.map[(size_t)s * a.n_ref + c] = 0;
+        return;
+    }
     const uint32_t row = a.row_of[s], size_query = (uint32_t)(a.q_off[row + 1] - a.q_off[row]);
     unsigned long long run = 0;
+    [[maybe_unused]] unsigned long long vrun = 0, vincl = 0;
+    if constexpr (ABUND) vrun = a.val_off[s];
     for (uint32_t c0 = 0; c0 < a.n_ref; c0 += kScreenThreads) {   // (uniform)
         const uint32_t c = c0 + tid;
         uint32_t common = 0, wn = 0;
@@ -327,6 +370,15 @@ __global__ void __launch_bounds__(kScreenThreads) k_screen_write(RowArgs a)
         }
         const unsigned long long m = __ballot(keep);
         if (lane == 0) s_cnt[w] = (uint32_t)__popcll(m);
+        if constexpr (ABUND) {   // the common of the kept cells up to and with this lane's
+            vincl = keep ? common : 0u;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned long long x = shfl_u64(vincl, (lane - o) & 63);
+                if (lane >= o) vincl += x;
+            }
+            if (lane == 63) s_val[w] = vincl;
+        }
         __syncthreads();
         uint32_t before = 0, all = 0;
 #pragma unroll
@@ -336,10 +388,23 @@ __global__ void __launch_bounds__(kScreenThreads) k_screen_write(RowArgs a)
         }
         const unsigned long long at = run + before + (uint32_t)__popcll(m & lanes_below(lane));
         if (keep && at < room) a.recs[beg + at] = rk_screen_rec{row, c, common, wn, a.sizes[c], size_query};
+        if constexpr (ABUND) {
+            unsigned long long vbefore = 0, vall = 0;
+#pragma unroll
+            for (int k = 0; k < kWaves; k++) {
+                if (k < w) vbefore += s_val[k];
+                vall += s_val[k];
+            }
+            if (keep && at < room) a.seg[beg + at] = vrun + vbefore + vincl - common;
+            if (c < a.n_ref) a.map[(size_t)s * a.n_ref + c] = keep && at < room ? (uint32_t)(beg + at + 1) : 0u;
+            vrun += vall;
+        }
         run += all;
         __syncthreads();   // (s_cnt is rewritten by the next chunk)
     }
 }
+
+#include "rk_screen_abund.inc"
 
 // ---- host: the rule, exactly ------------------------------------------------------------------------------------------------
 struct HostResult {
@@ -347,15 +412,39 @@ struct HostResult {
     std::vector<uint64_t> off;                          // Q + 1
     std::vector<uint32_t> matched, n_cand, claimed;     // Q (unselected rows: 0)
     uint64_t walked = 0, lane_lists = 0, wave_lists = 0, block_lists = 0;
+    // with q_counts only: one per record; per row the sums of the counts over the matched and over the claimed hashes at 3 q + 1, 3 q + 2
+    std::vector<rk_screen_abund> abund;
+    std::vector<uint64_t> occ;
+    uint64_t values = 0, rank_segs = 0, wave_segs = 0, block_segs = 0;
 };
+
+// the sum and the lower median of v[0 .. n), n > 0 (v is reordered)
+void sum_and_median(uint32_t *v, size_t n, uint64_t *sum, uint32_t *med)
+{
+    uint64_t s = 0;
+    for (size_t i = 0; i < n; i++) s += v[i];
+    std::nth_element(v, v + (n - 1) / 2, v + n);
+    *sum = s;
+    *med = v[(n - 1) / 2];
+}
 
 // lists: list u is post[pos[u] .. pos[u + 1]), strictly ascending reference ids below n_ref.  The winner of a list is found by scanning
 // its candidates with the comparator -- no ranking of the row, unlike tests/_screen_ref.py's second statement.
 // RK_ERR_ARG (strict only): a reference of a selected row shares more hashes than its size.
-int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off, const uint64_t *q_lists, uint32_t Q, uint32_t n_ref, const uint32_t *ref_sizes,
-                const uint32_t *query_sizes, const rk_screen_opts *o, const RowSel &sel, bool strict, HostResult *out)
+// q_counts (parallel to q_lists; null: the plain screen): the abundance records, as rk_screen_abund.inc lays them out -- every holder with
+// a record takes the count of the hash, the winner's from the front of its segment, everybody else's from the back.
+int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off, const uint64_t *q_lists, const uint32_t *q_counts, uint32_t Q, uint32_t n_ref,
+                const uint32_t *ref_sizes, const uint32_t *query_sizes, const rk_screen_opts *o, const RowSel &sel, bool strict, HostResult *out)
 {
     std::vector<uint32_t> common(n_ref, 0), won(n_ref, 0), touched, n_rec(Q, 0);
+    std::vector<uint32_t> winner, vals, front, back;
+    std::vector<uint64_t> seg;
+    if (q_counts) {
+        out->occ.assign((size_t)3 * Q, 0);
+        seg.assign(n_ref, 0);
+        front.assign(n_ref, 0);
+        back.assign(n_ref, 0);
+    }
     out->matched.assign(Q, 0);
     out->n_cand.assign(Q, 0);
     out->claimed.assign(Q, 0);
@@ -378,6 +467,7 @@ int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off
         for (const uint32_t r : touched) bad = bad || (strict && common[r] > ref_sizes[r]);
         if (bad) return RK_ERR_ARG;
         uint32_t claimed = 0;
+        if (q_counts) winner.assign(nl, UINT32_MAX);
         for (uint64_t k = 0; k < nl; k++) {
             Key best{0, 0, 0};
             for (uint64_t i = pos[lists[k]]; i < pos[lists[k] + 1]; i++) {
@@ -388,9 +478,30 @@ int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off
             if (best.c) {
                 won[best.r]++;
                 claimed++;
+                if (q_counts) {
+                    winner[k] = best.r;
+                    out->occ[(size_t)3 * q + 2] += q_counts[q_off[q] + k];
+                }
             }
+            if (q_counts && pos[lists[k] + 1] > pos[lists[k]]) out->occ[(size_t)3 * q + 1] += q_counts[q_off[q] + k];
         }
         std::sort(touched.begin(), touched.end());
+        if (q_counts) {   // the segments of the records, then the values
+            uint64_t room = 0;
+            for (const uint32_t r : touched)
+                if (common[r] >= o->min_common && won[r] >= o->min_won) {
+                    seg[r] = room;
+                    room += common[r];
+                }
+            vals.assign(room, 0);
+            for (uint64_t k = 0; k < nl; k++)
+                for (uint64_t i = pos[lists[k]]; i < pos[lists[k] + 1]; i++) {
+                    const uint32_t r = post[i];
+                    if (common[r] < o->min_common || won[r] < o->min_won) continue;
+                    vals[seg[r] + (winner[k] == r ? front[r]++ : common[r] - 1 - back[r]++)] = q_counts[q_off[q] + k];
+                }
+            out->values += room;
+        }
         uint32_t n_cand = 0;
         for (const uint32_t r : touched) {
             if (common[r] >= o->min_common) {
@@ -398,7 +509,17 @@ int screen_core(const uint32_t *post, const uint64_t *pos, const uint64_t *q_off
                 if (won[r] >= o->min_won) {
                     out->recs.push_back(rk_screen_rec{q, r, common[r], won[r], ref_sizes[r], query_sizes[q]});
                     n_rec[q]++;
+                    if (q_counts) {
+                        rk_screen_abund ab{0, 0, 0, 0};
+                        if (won[r]) sum_and_median(vals.data() + seg[r], won[r], &ab.occ_won, &ab.med_won);
+                        sum_and_median(vals.data() + seg[r], common[r], &ab.occ_common, &ab.med_common);
+                        out->abund.push_back(ab);
+                        if (common[r] <= kRankMax) out->rank_segs++;
+                        else if (common[r] <= kWaveSelMax) out->wave_segs++;
+                        else out->block_segs++;
+                    }
                 }
+                if (q_counts) front[r] = back[r] = 0;
             }
             common[r] = won[r] = 0;
         }
@@ -434,7 +555,8 @@ unsigned long long env_number(const char *name, unsigned long long otherwise)
 }
 
 // RK_SCREEN_DEVICE=0: export + the lists of the selected queries' hashes (a binary search each) + the rule on the host
-template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_screen_opts *o, const RowSel &sel, HostResult *out)
+// (abund: the counts of the queries go along, rk_screen_abund_rows)
+template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_screen_opts *o, const RowSel &sel, bool abund, HostResult *out)
 {
     const uint32_t N = idx->n_ref, Q = qs->n;
     std::vector<uint32_t> postings(idx->H), counts(idx->U), ref_sizes(N), query_sizes(Q);
@@ -454,7 +576,9 @@ template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const
         RK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (uint32_t i = 0; i < N; i++) ref_sizes[orig[i] < N ? orig[i] : i] = sizes[i];
     }
-    std::vector<uint64_t> l_off((size_t)Q + 1, 0), l;
+    std::vector<uint64_t> l_off((size_t)Q + 1, 0), l, whole((size_t)(abund ? Q : 0), 0);
+    std::vector<uint32_t> qc((size_t)(abund ? qs->total : 0)), lc;
+    if (abund) RK_TRY(rk_sketches_download_counts(qs, qc.data()));
     size_t next = 0;
     for (uint32_t q = 0; q < Q; q++) {
         query_sizes[q] = (uint32_t)(qoff[q + 1] - qoff[q]);
@@ -462,7 +586,11 @@ template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const
             next++;
             for (uint64_t j = qoff[q]; j < qoff[q + 1]; j++) {
                 const auto it = std::lower_bound(hashes.begin(), hashes.end(), qh[j]);
-                if (it != hashes.end() && *it == qh[j]) l.push_back((uint64_t)(it - hashes.begin()));
+                if (it != hashes.end() && *it == qh[j]) {
+                    l.push_back((uint64_t)(it - hashes.begin()));
+                    if (abund) lc.push_back(qc[j]);
+                }
+                if (abund) whole[q] += qc[j];
             }
         }
         l_off[q + 1] = l.size();
@@ -472,7 +600,11 @@ template <class Hash> int screen_on_host(rk_ctx *ctx, const rk_index *idx, const
     const uint32_t *post = nullptr;
     if (prepare_lists(postings.data(), counts.data(), idx->U, N, &pos, &fixed, &post))
         return rk_fail(ctx, RK_ERR_HIP, "rk_screen_rows: an exported posting names a genome beyond their number (internal error)");
-    return screen_core(post, pos.data(), l_off.data(), l.data(), Q, N, ref_sizes.data(), query_sizes.data(), o, sel, false, out);
+    static const uint32_t none = 0;   // (abund without a hit: q_counts must not be null)
+    RK_TRY(screen_core(post, pos.data(), l_off.data(), l.data(), abund ? (lc.empty() ? &none : lc.data()) : nullptr, Q, N, ref_sizes.data(), query_sizes.data(), o, sel,
+                       false, out));
+    for (uint32_t q = 0; abund && q < Q; q++) out->occ[(size_t)3 * q] = whole[q];
+    return RK_OK;
 }
 
 struct DeviceResult {
@@ -480,13 +612,23 @@ struct DeviceResult {
     uint64_t n_recs = 0;
 };
 
-int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_screen_opts *o, const RowSel &sel, rk_screen_stats *st, DeviceResult *res)
+constexpr unsigned long long kSelectRecs = 1ULL << 30;   // the records one launch of a select kernel takes
+
+struct AbundDevice {   // what rk_screen_abund_rows adds to the device leg
+    std::vector<unsigned char> block;   // rk_screen_abund[n_recs] | u64 occ[3 Q] | AbundCounters
+    uint64_t values = 0, value_bytes = 0;
+    uint32_t passes = 0;
+};
+
+// ab != null: rk_screen_abund_rows (the queries carry counts)
+int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, const rk_screen_opts *o, const RowSel &sel, rk_screen_stats *st, DeviceResult *res,
+                     AbundDevice *ab)
 {
     const uint32_t N = idx->n_ref, Q = qs->n;
     const uint64_t n_sel = sel.rows.size();
     RK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    const TimedSpan span{ctx, RK_MS_SCREEN};
+    const TimedSpan span{ctx, ab ? RK_MS_SCREEN_ABUND : RK_MS_SCREEN};
     const bool combine = !rk_switched_off("RK_SCREEN_COMBINE");
     RK_TRY(rk_index_ensure_dir(ctx, const_cast<rk_index *>(idx), stream));
     rk_dist_opts dopts;   // the row shard for rk_distq_counts; nothing of a distance is evaluated
@@ -522,11 +664,39 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
 
     // device bytes of one row of a batch: its counter row and its won row
     const uint64_t row_bytes = (uint64_t)N * 8 + 16;
-    const uint64_t rows_per_batch = std::max<uint64_t>(1, std::min<uint64_t>(n_sel, env_number("RK_SCREEN_BATCH_BYTES", 1ULL << 30) / row_bytes));
+    const uint64_t batch_bytes = env_number("RK_SCREEN_BATCH_BYTES", 1ULL << 30);
+    uint64_t rows_per_batch = std::max<uint64_t>(1, std::min<uint64_t>(n_sel, batch_bytes / row_bytes));
+    if (ab) rows_per_batch = std::min<uint64_t>(rows_per_batch, std::max<uint64_t>(1, 0xFFFFFFFEULL / N));   // a record of a batch + 1 fits 32 bits
     st->rows_per_batch = rows_per_batch;
     RK_HIP(ctx, counts.alloc(rows_per_batch * N));
     RK_HIP(ctx, won.alloc(rows_per_batch * N));
     RK_HIP(ctx, rec_off.alloc(rows_per_batch + 1));
+    // ab: the counters of a batch, the records of its rows and the sums of their common in ONE block: one read-back
+    Counters *cnt = cnt_dev.p;
+    DevBuf<unsigned char> home_dev(ctx);
+    DevBuf<unsigned long long> val_off(ctx), occ_dev(ctx);
+    DevBuf<AbundCounters> abc_dev(ctx);
+    std::vector<unsigned char> home_host;
+    std::vector<std::vector<unsigned long long>> uploads;   // pageable sources of copies: alive until the last synchronisation
+    const size_t home_bytes = sizeof(Counters) + (ab ? (size_t)24 * rows_per_batch : 0);
+    if (ab) {
+        RK_HIP(ctx, home_dev.alloc(home_bytes));
+        cnt = (Counters *)home_dev.p;
+        home_host.resize(home_bytes);
+        RK_HIP(ctx, val_off.alloc(rows_per_batch));
+        RK_HIP(ctx, occ_dev.alloc((size_t)3 * Q));
+        RK_HIP(ctx, abc_dev.alloc(1));
+        RK_HIP(ctx, hipMemsetAsync(occ_dev.p, 0, (size_t)24 * Q, stream));
+        RK_HIP(ctx, hipMemsetAsync(abc_dev.p, 0, sizeof(AbundCounters), stream));
+        ab->value_bytes = env_number("RK_SCREEN_VALUE_BYTES", batch_bytes);
+    }
+    unsigned long long *const row_recs = ab ? (unsigned long long *)(home_dev.p + sizeof(Counters)) : nullptr, *const row_vals = ab ? row_recs + rows_per_batch : nullptr,
+                       *const row_longest = ab ? row_vals + rows_per_batch : nullptr;
+    struct TakenAbund {   // the abundance records of one batch, as `taken` below
+        rk_ctx *ctx;
+        std::vector<std::pair<rk_screen_abund *, uint64_t>> parts;
+        ~TakenAbund() { for (auto &p : parts) rk_pool_free(ctx, p.first); }
+    } taken_abund{ctx, {}};
 
     struct Taken {   // the records of one batch, in order, until the result is put together
         rk_ctx *ctx;
@@ -542,7 +712,7 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         if (tiles > 0x7FFFFFFFULL) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "rk_screen_rows: more than 2^31 tiles of query hashes in one batch");
         RK_TRY(rk_distq_counts(ctx, idx, qs, &dopts, (uint32_t)s0, nb, counts.p, stream));
         RK_HIP(ctx, hipMemsetAsync(won.p, 0, (size_t)nb * N * 4, stream));
-        RK_HIP(ctx, hipMemsetAsync(cnt_dev.p, 0, sizeof(Counters), stream));
+        RK_HIP(ctx, hipMemsetAsync(cnt, 0, home_bytes, stream));
         if (tiles && idx->U) {
             WinArgs w;
             memset(&w, 0, sizeof w);
@@ -564,7 +734,7 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
             w.lane_max = st->lane_max;
             w.wave_max = st->wave_max;
             w.matched_q = per_q.p + Q;
-            w.c = cnt_dev.p;
+            w.c = cnt;
             const auto win = qs->wide ? (combine ? k_screen_win<uint64_t, true> : k_screen_win<uint64_t, false>)
                                       : (combine ? k_screen_win<uint32_t, true> : k_screen_win<uint32_t, false>);
             hipLaunchKernelGGL(win, dim3((unsigned)tiles), dim3(kScreenThreads), 0, stream, w);
@@ -585,12 +755,22 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         a.rec_off = rec_off.p;
         a.sizes = sizes.p;
         a.q_off = qs->d_off;
-        hipLaunchKernelGGL(k_screen_count, dim3(nb), dim3(kScreenThreads), 0, stream, a);
-        hipLaunchKernelGGL(k_query_scan<kScreenThreads>, dim3(1), dim3(kScreenThreads), 0, stream, a.nrec_q, a.row_of, nb, 0u, rec_off.p, &cnt_dev.p->rec_total);
+        a.row_recs = row_recs;
+        a.row_vals = row_vals;
+        a.row_longest = row_longest;
+        a.val_off = val_off.p;
+        a.map = won.p;
+        hipLaunchKernelGGL(ab ? k_screen_count<true> : k_screen_count<false>, dim3(nb), dim3(kScreenThreads), 0, stream, a);
+        hipLaunchKernelGGL(k_query_scan<kScreenThreads>, dim3(1), dim3(kScreenThreads), 0, stream, a.nrec_q, a.row_of, nb, 0u, rec_off.p, &cnt->rec_total);
         RK_HIP(ctx, hipGetLastError());
         st->launches += 2;
         Counters home;
-        RK_TRY(rk_read_back(ctx, &home, cnt_dev.p, sizeof home, stream));   // the room of the records
+        if (ab) {
+            RK_TRY(rk_read_back(ctx, home_host.data(), cnt, home_bytes, stream));   // the room of the records and of the values, row by row
+            memcpy(&home, home_host.data(), sizeof home);
+        } else {
+            RK_TRY(rk_read_back(ctx, &home, cnt, sizeof home, stream));   // the room of the records
+        }
         st->read_backs++;
         if (home.rec_total > (unsigned long long)nb * N) return rk_fail(ctx, RK_ERR_HIP, "rk_screen_rows: more records than cells (internal error)");
         st->postings_walked += home.walked;
@@ -603,10 +783,130 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
             if (!part) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu records on the device", home.rec_total);
             taken.parts.emplace_back(part, home.rec_total);
             a.recs = part;
-            hipLaunchKernelGGL(k_screen_write, dim3(nb), dim3(kScreenThreads), 0, stream, a);
+            if (!ab) {
+                hipLaunchKernelGGL(k_screen_write<false>, dim3(nb), dim3(kScreenThreads), 0, stream, a);
+                RK_HIP(ctx, hipGetLastError());
+                st->launches++;
+            }
+            total_recs += home.rec_total;
+        }
+        if (!ab) continue;
+        // ---- the abundances of the batch (rk_screen_abund.inc) ----
+        const unsigned long long *recs_h = (const unsigned long long *)(home_host.data() + sizeof(Counters)), *vals_h = recs_h + rows_per_batch,
+                                 *longest_h = vals_h + rows_per_batch;
+        // the sub-ranges of rows whose values fit the budget, at least one row each; val_off[s]: the values of its sub-range before row s
+        std::vector<unsigned long long> voff(nb), rec_before((size_t)nb + 1, 0);
+        std::vector<uint32_t> cut{0};   // sub-range k: slots cut[k] .. cut[k + 1]
+        unsigned long long run = 0, most = 0, batch_vals = 0;
+        for (uint32_t s = 0; s < nb; s++) {
+            if (s > cut.back() && (run + vals_h[s]) * 4 > ab->value_bytes) {
+                cut.push_back(s);
+                run = 0;
+            }
+            voff[s] = run;
+            run += vals_h[s];
+            most = std::max(most, run);
+            batch_vals += vals_h[s];
+            rec_before[s + 1] = rec_before[s] + recs_h[s];
+        }
+        cut.push_back(nb);
+        if (rec_before[nb] != home.rec_total) return rk_fail(ctx, RK_ERR_HIP, "rk_screen_abund_rows: the records of the rows do not add up (internal error)");
+        ab->values += batch_vals;
+        uploads.push_back(std::move(voff));
+        RK_HIP(ctx, hipMemcpyAsync(val_off.p, uploads.back().data(), (size_t)nb * 8, hipMemcpyHostToDevice, stream));
+        // (of this batch only: they go back to the pool at the end of the iteration while the kernels that use them may still be queued --
+        // safe because everything of this call is on ctx->stream, which orders any reuse of the memory behind them, as DevBuf requires)
+        DevBuf<unsigned long long> seg(ctx);
+        DevBuf<uint32_t> cur(ctx), vals(ctx);
+        RK_HIP(ctx, seg.alloc(home.rec_total));
+        RK_HIP(ctx, cur.alloc(2 * home.rec_total));
+        RK_HIP(ctx, vals.alloc(most));
+        if (home.rec_total) RK_HIP(ctx, hipMemsetAsync(cur.p, 0, (size_t)8 * home.rec_total, stream));
+        rk_screen_abund *ab_part = nullptr;
+        if (home.rec_total) {
+            ab_part = static_cast<rk_screen_abund *>(rk_pool_alloc(ctx, home.rec_total * sizeof(rk_screen_abund)));
+            if (!ab_part) return rk_fail(ctx, RK_ERR_NOMEM, "cannot allocate %llu abundance records on the device", home.rec_total);
+            taken_abund.parts.emplace_back(ab_part, home.rec_total);
+            RK_HIP(ctx, hipMemsetAsync(ab_part, 0, home.rec_total * sizeof(rk_screen_abund), stream));
+            a.seg = seg.p;
+            hipLaunchKernelGGL(k_screen_write<true>, dim3(nb), dim3(kScreenThreads), 0, stream, a);
             RK_HIP(ctx, hipGetLastError());
             st->launches++;
-            total_recs += home.rec_total;
+        } else {
+            RK_HIP(ctx, hipMemsetAsync(won.p, 0, (size_t)nb * N * 4, stream));   // no cell has a record
+        }
+        for (size_t k = 0; k + 1 < cut.size(); k++) {
+            const uint32_t sa = cut[k], sb = cut[k + 1];
+            const uint64_t sub_hashes = hoff[s0 + sb] - hoff[s0 + sa], sub_tiles = (sub_hashes + kTileHashes - 1) / kTileHashes;
+            const unsigned long long sub_recs = rec_before[sb] - rec_before[sa];
+            ab->passes++;
+            if (sub_tiles) {
+                FillArgs f;
+                memset(&f, 0, sizeof f);
+                f.q_hashes = qs->wide ? (const void *)qs->d_hashes64 : (const void *)qs->d_hashes;
+                f.q_counts = qs->d_counts;
+                f.q_off = qs->d_off;
+                f.row_of = row_of.p + s0 + sa;
+                f.hoff = hoff_dev.p + s0 + sa;
+                f.nb = sb - sa;
+                f.n_hashes = sub_hashes;
+                f.ix = index_lookup_of(idx);
+                f.postings = idx->d_postings;
+                f.upos = idx->d_upos;
+                f.orig = idx->relabeled ? idx->d_orig : nullptr;
+                f.sizes_internal = idx->d_sizes;
+                f.cnt = counts.p + (size_t)sa * N;
+                f.map = won.p + (size_t)sa * N;
+                f.n_ref = N;
+                f.min_common = o->min_common;
+                f.lane_max = st->lane_max;
+                f.wave_max = st->wave_max;
+                f.seg = seg.p;
+                f.cur = cur.p;
+                f.vals = vals.p;
+                f.vals_cap = std::max<unsigned long long>(1, most);
+                f.occ_q = occ_dev.p;
+                f.c = abc_dev.p;
+                hipLaunchKernelGGL(qs->wide ? k_screen_fill<uint64_t> : k_screen_fill<uint32_t>, dim3((unsigned)sub_tiles), dim3(kScreenThreads), 0, stream, f);
+                RK_HIP(ctx, hipGetLastError());
+                st->launches++;
+            }
+            if (sub_recs) {
+                SelArgs g;
+                memset(&g, 0, sizeof g);
+                g.recs = a.recs;
+                g.seg = seg.p;
+                g.vals = vals.p;
+                g.vals_cap = std::max<unsigned long long>(1, most);
+                g.out = ab_part;
+                g.wave_sel_max = kWaveSelMax;
+                g.c = abc_dev.p;
+                // a launch takes at most kSelectRecs records: no grid beyond 2^30 workgroups, however many records a sub-range has
+                const auto select = [&](unsigned long long first, unsigned long long end, bool by_block) {
+                    for (unsigned long long at = first; at < end; at += kSelectRecs) {
+                        g.rec_first = at;
+                        g.rec_end = std::min(end, at + kSelectRecs);
+                        const unsigned long long n = g.rec_end - g.rec_first;
+                        if (by_block) hipLaunchKernelGGL(k_screen_select_block, dim3((unsigned)n), dim3(kScreenThreads), 0, stream, g);
+                        else hipLaunchKernelGGL(k_screen_select_wave, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kScreenThreads), 0, stream, g);
+                        st->launches++;
+                    }
+                };
+                select(rec_before[sa], rec_before[sb], false);
+                // the workgroup's select only over the rows that have a record for it (the read-back brought every row's longest segment):
+                // one launch per run of such rows, a workgroup per record of the run -- those of its shorter records return at once
+                for (uint32_t s = sa; s < sb;) {
+                    if (longest_h[s] <= kWaveSelMax) {
+                        s++;
+                        continue;
+                    }
+                    uint32_t e = s + 1;
+                    while (e < sb && longest_h[e] > kWaveSelMax) e++;
+                    select(rec_before[s], rec_before[e], true);
+                    s = e;
+                }
+                RK_HIP(ctx, hipGetLastError());
+            }
         }
     }
     // the result in one block, one copy
@@ -614,7 +914,7 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
     DevBuf<unsigned char> block(ctx);
     RK_HIP(ctx, block.alloc(bytes));
     hipLaunchKernelGGL(k_query_scan<kScreenThreads>, dim3(1), dim3(kScreenThreads), 0, stream, per_q.p + 3 * (size_t)Q, (const uint32_t *)nullptr, Q, 0u,
-                       (unsigned long long *)block.p, &cnt_dev.p->all_total);
+                       (unsigned long long *)block.p, &cnt->all_total);
     RK_HIP(ctx, hipGetLastError());
     st->launches++;
     if (Q) RK_HIP(ctx, hipMemcpyAsync(block.p + ((size_t)Q + 1) * 8, per_q.p + Q, (size_t)4 * Q, hipMemcpyDeviceToDevice, stream));              // matched
@@ -625,24 +925,42 @@ int screen_on_device(rk_ctx *ctx, const rk_index *idx, const rk_sketches *qs, co
         RK_HIP(ctx, hipMemcpyAsync(block.p + at, p.first, p.second * sizeof(rk_screen_rec), hipMemcpyDeviceToDevice, stream));
         at += p.second * sizeof(rk_screen_rec);
     }
+    DevBuf<unsigned char> ab_block(ctx);
+    const size_t ab_bytes = total_recs * sizeof(rk_screen_abund) + (size_t)24 * Q + sizeof(AbundCounters);
+    if (ab) {   // the abundance records, the sums of the rows and the classes in a block of their own
+        RK_HIP(ctx, ab_block.alloc(ab_bytes));
+        size_t to = 0;
+        for (const auto &p : taken_abund.parts) {
+            RK_HIP(ctx, hipMemcpyAsync(ab_block.p + to, p.first, p.second * sizeof(rk_screen_abund), hipMemcpyDeviceToDevice, stream));
+            to += p.second * sizeof(rk_screen_abund);
+        }
+        if (Q) RK_HIP(ctx, hipMemcpyAsync(ab_block.p + to, occ_dev.p, (size_t)24 * Q, hipMemcpyDeviceToDevice, stream));
+        RK_HIP(ctx, hipMemcpyAsync(ab_block.p + to + (size_t)24 * Q, abc_dev.p, sizeof(AbundCounters), hipMemcpyDeviceToDevice, stream));
+    }
     RK_HIP(ctx, span.end());
     res->block.resize(bytes);
     RK_HIP(ctx, hipMemcpyAsync(res->block.data(), block.p, bytes, hipMemcpyDeviceToHost, stream));
+    if (ab) {
+        ab->block.resize(ab_bytes);
+        RK_HIP(ctx, hipMemcpyAsync(ab->block.data(), ab_block.p, ab_bytes, hipMemcpyDeviceToHost, stream));
+    }
     RK_HIP(ctx, hipStreamSynchronize(stream));
     span.read();
     res->n_recs = total_recs;
+    if (ab) {
+        AbundCounters c;
+        memcpy(&c, ab->block.data() + total_recs * sizeof(rk_screen_abund) + (size_t)24 * Q, sizeof c);
+        if (c.errors) return rk_fail(ctx, RK_ERR_HIP, "rk_screen_abund_rows: %llu values outside their segments (internal error)", c.errors);
+    }
     const uint64_t *off = (const uint64_t *)res->block.data();
     if (off[0] != 0 || off[Q] != total_recs) return rk_fail(ctx, RK_ERR_HIP, "rk_screen_rows: the offsets of the rows do not span the records (internal error)");
     return RK_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off, const uint64_t *q_lists, uint32_t n_query,
-                    uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes, const rk_screen_opts *opts, uint64_t *off_out,
-                    rk_screen_rec **recs_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out)
+// what rk_screen_lists and rk_screen_abund_lists refuse alike
+int check_lists_args(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off, const uint64_t *q_lists, uint32_t n_query, uint32_t n_ref,
+                     const uint32_t *ref_sizes, const uint32_t *query_sizes, const rk_screen_opts *opts, const uint64_t *off_out, rk_screen_rec *const *recs_out,
+                     const uint64_t *n_recs, const uint32_t *matched_out, const uint32_t *n_cand_out, const uint32_t *claimed_out)
 {
     if (!q_off || !opts || !off_out || !recs_out || !n_recs) return RK_ERR_ARG;
     if (n_query && (!query_sizes || !matched_out || !n_cand_out || !claimed_out)) return RK_ERR_ARG;
@@ -661,22 +979,56 @@ int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n
     uint64_t total = 0;
     for (uint64_t u = 0; u < n_lists; u++) total += counts[u];
     if (total && !postings) return RK_ERR_ARG;
-    std::vector<uint64_t> pos;
-    std::vector<uint32_t> fixed;
-    const uint32_t *post = nullptr;
-    if (int rc = prepare_lists(postings, counts, n_lists, n_ref, &pos, &fixed, &post)) return rc;
-    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, n_query);
-    HostResult r;
-    if (int rc = screen_core(post, pos.data(), q_off, q_lists, n_query, n_ref, ref_sizes, query_sizes, opts, sel, true, &r)) return rc;
-    return hand_out(view(r), sel, n_query, off_out, recs_out, n_recs, {matched_out, n_cand_out, claimed_out});
+    return RK_OK;
 }
 
-int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out, rk_screen_rec **recs_out,
-                   uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out, rk_screen_stats *stats)
+// hand_out with the abundance records in memory of their own and the sums of the selected rows; RK_ERR_NOMEM leaves everything untouched
+int hand_out_abund(const Result &r, const RowSel &sel, uint32_t Q, uint64_t *off_out, rk_screen_rec **recs_out, rk_screen_abund **abund_out,
+                   uint64_t *n_recs, uint32_t *const (&per_row_out)[3], const rk_screen_abund *abund, const uint64_t *occ, uint64_t *occ_out)
 {
+    rk_screen_abund *p = nullptr;
+    if (r.n_recs) {
+        p = (rk_screen_abund *)malloc(r.n_recs * sizeof(rk_screen_abund));
+        if (!p) return RK_ERR_NOMEM;
+        memcpy(p, abund, r.n_recs * sizeof(rk_screen_abund));
+    }
+    if (hand_out(r, sel, Q, off_out, recs_out, n_recs, per_row_out)) {
+        free(p);
+        return RK_ERR_NOMEM;
+    }
+    for (const uint32_t q : sel.rows)
+        for (int k = 0; k < 3; k++) occ_out[(size_t)3 * q + k] = occ ? occ[(size_t)3 * q + k] : 0;
+    *abund_out = p;
+    return RK_OK;
+}
+
+// the sums of the counts of the selected sketches at occ[3 q] (the rest 0), from a download: when nothing else runs
+int whole_sums(rk_ctx *, const rk_sketches *qs, const RowSel &sel, std::vector<uint64_t> *occ)
+{
+    std::vector<uint32_t> c(qs->total);
+    RK_TRY(rk_sketches_download_counts(qs, c.data()));
+    occ->assign((size_t)3 * qs->n, 0);
+    for (const uint32_t q : sel.rows)
+        for (uint64_t j = qs->h_off[q]; j < qs->h_off[q + 1]; j++) (*occ)[(size_t)3 * q] += c[j];
+    return RK_OK;
+}
+
+// rk_screen_rows (abund_out == null) and rk_screen_abund_rows.  *full (written on success only) begins with the fields of rk_screen_stats;
+// what follows them stays 0 for the plain screen.
+int screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out, rk_screen_rec **recs_out,
+                rk_screen_abund **abund_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out, uint64_t *occ_out,
+                rk_screen_abund_stats *full)
+{
+    static_assert(offsetof(rk_screen_abund_stats, values) == sizeof(rk_screen_stats), "rk_screen_abund_stats begins with rk_screen_stats");
+    rk_screen_abund_stats more;   // what rk_screen_abund_stats adds
+    memset(&more, 0, sizeof more);
+    rk_screen_abund_stats *const ast = &more;
     if (!ctx || !idx || !queries || !opts || !off_out || !recs_out || !n_recs) return RK_ERR_ARG;
-    const char *const who = "rk_screen_rows";
+    const bool abund = abund_out != nullptr;
+    const char *const who = abund ? "rk_screen_abund_rows" : "rk_screen_rows";
     const uint32_t N = idx->n_ref, Q = queries->n;
+    if (abund && Q && !occ_out) return rk_fail(ctx, RK_ERR_ARG, "%s: occ_out is null", who);
+    if (abund && !queries->d_counts) return rk_fail(ctx, RK_ERR_UNSUPPORTED, "%s: the query sketches carry no counts (rk_sketches_has_counts)", who);
     if (Q && (!matched_out || !n_cand_out || !claimed_out)) return rk_fail(ctx, RK_ERR_ARG, "%s: matched_out, n_cand_out or claimed_out is null", who);
     if (!opts->min_common) return rk_fail(ctx, RK_ERR_ARG, "%s: min_common must be at least 1", who);
     if (queries->wide != idx->wide) return rk_fail(ctx, RK_ERR_ARG, "query sketches and index use different hash widths");
@@ -689,9 +1041,10 @@ int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
     rk_screen_stats st;
     memset(&st, 0, sizeof st);
     fill_constants(&st);
-    const TimedSpan span{ctx, RK_MS_SCREEN};
+    const TimedSpan span{ctx, abund ? RK_MS_SCREEN_ABUND : RK_MS_SCREEN};
     span.clear();
     const RowSel sel(opts->row_first, opts->row_step, opts->row_block, Q);
+    AbundDevice ab;
     st.rows = (uint32_t)sel.rows.size();
     uint32_t *const outs[3] = {matched_out, n_cand_out, claimed_out};
     HostResult host;
@@ -700,7 +1053,7 @@ int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
     const bool runs = N && !sel.rows.empty();   // (else every row is empty: r stays without offsets)
     if (runs && rk_switched_off("RK_SCREEN_DEVICE")) {
         st.path = 2;
-        RK_TRY(idx->wide ? screen_on_host<uint64_t>(ctx, idx, queries, opts, sel, &host) : screen_on_host<uint32_t>(ctx, idx, queries, opts, sel, &host));
+        RK_TRY(idx->wide ? screen_on_host<uint64_t>(ctx, idx, queries, opts, sel, abund, &host) : screen_on_host<uint32_t>(ctx, idx, queries, opts, sel, abund, &host));
         r = view(host);
         st.postings_walked = host.walked;
         st.lane_lists = host.lane_lists;
@@ -710,17 +1063,114 @@ int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries,
         st.rows_per_batch = sel.rows.size();
     } else if (runs) {
         st.path = 1;
-        RK_TRY(screen_on_device(ctx, idx, queries, opts, sel, &st, &dev));
+        RK_TRY(screen_on_device(ctx, idx, queries, opts, sel, &st, &dev, abund ? &ab : nullptr));
         r = Result::from_block(dev.block.data(), Q, dev.n_recs);
     }
-    if (hand_out(r, sel, Q, off_out, recs_out, n_recs, outs)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+    if (abund) {
+        const rk_screen_abund *recs_ab = nullptr;
+        const uint64_t *occ = nullptr;
+        ast->rank_max = kRankMax;
+        ast->wave_sel_max = kWaveSelMax;
+        ast->chunk = kScreenThreads;
+        if (st.path == 2) {
+            recs_ab = host.abund.data();
+            occ = host.occ.data();
+            ast->values = host.values;
+            ast->rank_segs = host.rank_segs;
+            ast->wave_segs = host.wave_segs;
+            ast->block_segs = host.block_segs;
+        } else if (st.path == 1) {
+            recs_ab = (const rk_screen_abund *)ab.block.data();
+            occ = (const uint64_t *)(ab.block.data() + dev.n_recs * sizeof(rk_screen_abund));
+            AbundCounters c;
+            memcpy(&c, ab.block.data() + dev.n_recs * sizeof(rk_screen_abund) + (size_t)24 * Q, sizeof c);
+            ast->values = ab.values;
+            ast->value_bytes = ab.value_bytes;
+            ast->value_passes = ab.passes;
+            ast->rank_segs = c.rank_segs;
+            ast->wave_segs = c.wave_segs;
+            ast->block_segs = c.block_segs;
+        }
+        if (st.path == 0 && Q && !N) {   // an index without genomes: the sums of the whole sketches are still the queries'
+            RK_TRY(whole_sums(ctx, queries, sel, &host.occ));
+            occ = host.occ.data();
+        }
+        if (hand_out_abund(r, sel, Q, off_out, recs_out, abund_out, n_recs, outs, recs_ab, occ, occ_out)) return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+    } else if (hand_out(r, sel, Q, off_out, recs_out, n_recs, outs)) {
+        return rk_fail(ctx, RK_ERR_NOMEM, "%s: out of host memory", who);
+    }
     st.records = r.n_recs;
     for (const uint32_t q : sel.rows) {
         st.matched += matched_out[q];
         st.candidates += n_cand_out[q];
         st.claimed += claimed_out[q];
     }
-    if (stats) *stats = st;
+    memcpy(&more, &st, sizeof st);
+    *full = more;
+    return RK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rk_screen_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off, const uint64_t *q_lists, uint32_t n_query,
+                    uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes, const rk_screen_opts *opts, uint64_t *off_out,
+                    rk_screen_rec **recs_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out)
+{
+    if (int rc = check_lists_args(postings, counts, n_lists, q_off, q_lists, n_query, n_ref, ref_sizes, query_sizes, opts, off_out, recs_out, n_recs, matched_out,
+                                  n_cand_out, claimed_out))
+        return rc;
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> fixed;
+    const uint32_t *post = nullptr;
+    if (int rc = prepare_lists(postings, counts, n_lists, n_ref, &pos, &fixed, &post)) return rc;
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, n_query);
+    HostResult r;
+    if (int rc = screen_core(post, pos.data(), q_off, q_lists, nullptr, n_query, n_ref, ref_sizes, query_sizes, opts, sel, true, &r)) return rc;
+    return hand_out(view(r), sel, n_query, off_out, recs_out, n_recs, {matched_out, n_cand_out, claimed_out});
+}
+
+int rk_screen_abund_lists(const uint32_t *postings, const uint32_t *counts, uint64_t n_lists, const uint64_t *q_off, const uint64_t *q_lists, const uint32_t *q_counts,
+                          uint32_t n_query, uint32_t n_ref, const uint32_t *ref_sizes, const uint32_t *query_sizes, const uint64_t *query_occ, const rk_screen_opts *opts,
+                          uint64_t *off_out, rk_screen_rec **recs_out, rk_screen_abund **abund_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out,
+                          uint32_t *claimed_out, uint64_t *occ_out)
+{
+    if (int rc = check_lists_args(postings, counts, n_lists, q_off, q_lists, n_query, n_ref, ref_sizes, query_sizes, opts, off_out, recs_out, n_recs, matched_out,
+                                  n_cand_out, claimed_out))
+        return rc;
+    if (!abund_out || (n_query && (!occ_out || !query_occ)) || (q_off[n_query] && !q_counts)) return RK_ERR_ARG;
+    for (uint64_t j = 0; j < q_off[n_query]; j++)
+        if (!q_counts[j]) return RK_ERR_ARG;
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> fixed;
+    const uint32_t *post = nullptr;
+    if (int rc = prepare_lists(postings, counts, n_lists, n_ref, &pos, &fixed, &post)) return rc;
+    const RowSel sel(opts->row_first, opts->row_step, opts->row_block, n_query);
+    HostResult r;
+    static const uint32_t none = 0;   // (no query hits a list: q_counts may be null)
+    if (int rc = screen_core(post, pos.data(), q_off, q_lists, q_counts ? q_counts : &none, n_query, n_ref, ref_sizes, query_sizes, opts, sel, true, &r)) return rc;
+    for (const uint32_t q : sel.rows) r.occ[(size_t)3 * q] = query_occ[q];
+    return hand_out_abund(view(r), sel, n_query, off_out, recs_out, abund_out, n_recs, {matched_out, n_cand_out, claimed_out}, r.abund.data(), r.occ.data(), occ_out);
+}
+
+int rk_screen_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out, rk_screen_rec **recs_out,
+                   uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out, rk_screen_stats *stats)
+{
+    rk_screen_abund_stats full;
+    RK_TRY(screen_rows(ctx, idx, queries, opts, off_out, recs_out, nullptr, n_recs, matched_out, n_cand_out, claimed_out, nullptr, &full));
+    if (stats) memcpy(stats, &full, sizeof *stats);
+    return RK_OK;
+}
+
+int rk_screen_abund_rows(rk_ctx *ctx, const rk_index *idx, const rk_sketches *queries, const rk_screen_opts *opts, uint64_t *off_out, rk_screen_rec **recs_out,
+                         rk_screen_abund **abund_out, uint64_t *n_recs, uint32_t *matched_out, uint32_t *n_cand_out, uint32_t *claimed_out, uint64_t *occ_out,
+                         rk_screen_abund_stats *stats)
+{
+    if (!abund_out) return RK_ERR_ARG;
+    rk_screen_abund_stats full;
+    RK_TRY(screen_rows(ctx, idx, queries, opts, off_out, recs_out, abund_out, n_recs, matched_out, n_cand_out, claimed_out, occ_out, &full));
+    if (stats) *stats = full;
     return RK_OK;
 }
 

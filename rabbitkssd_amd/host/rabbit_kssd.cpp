@@ -502,6 +502,43 @@ static rk_sketches *upload(Gpu &gpu, const SketchSet &s)
     return sk;
 }
 
+// the sketches of s with their counts (s.counts, read_abund) on the device: a counted sketch ascends, so every sketch goes up with its
+// (hash, count) pairs in ascending hash order, whatever order the file had
+static rk_sketches *upload_counted(Gpu &gpu, const SketchSet &s)
+{
+    const uint64_t total = s.total();
+    vector<uint32_t> counts(total);
+    vector<uint64_t> hashes(total), order;
+    for (size_t g = 0; g < s.size(); g++) {
+        order.resize(s.off[g + 1] - s.off[g]);
+        for (uint64_t i = 0; i < order.size(); i++) order[i] = s.off[g] + i;
+        auto hash_at = [&](uint64_t i) { return s.wide() ? s.hashes64[i] : (uint64_t)s.hashes[i]; };
+        std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return hash_at(x) < hash_at(y); });
+        for (uint64_t i = 0; i < order.size(); i++) {
+            hashes[s.off[g] + i] = hash_at(order[i]);
+            counts[s.off[g] + i] = s.counts[order[i]];
+        }
+    }
+    vector<uint32_t> narrow;
+    if (!s.wide()) narrow.assign(hashes.begin(), hashes.end());
+    rk_sketches *sk = nullptr;
+    gpu.check(rk_sketches_from_host_counts(gpu.ctx, s.wide() ? (const void *)hashes.data() : (const void *)narrow.data(), s.wide() ? 1 : 0, counts.data(), s.off.data(),
+                                           (uint32_t)s.size(), &sk), "rk_sketches_from_host_counts");
+    return sk;
+}
+
+// -q of `screen --abund` / `mask --abund` is a .sketch file (checked before anything is read or sketched), with its side-car, or a message
+static void need_sketch_queries(const Args &a, const char *who)
+{
+    if (a.has("abund") && !is_sketch_file(a.str("q", "")))
+        die("%s --abund needs -q x.sketch with its x.sketch.abund (sketch --abund writes both), not a list of sequence files", who);
+}
+static void need_counted_queries(const char *who, const string &qry_path, SketchSet &qry)
+{
+    string err;
+    if (!read_abund(abund_path(qry_path), qry, err)) die("%s --abund needs the occurrence counts of the queries, %s.abund (sketch --abund writes it): %s", who, qry_path.c_str(), err.c_str());
+}
+
 // builds the index on the GPU and, when asked, writes <sketch>.dict/.index (transSketches,
 // src/sketch.cpp:894-1021)
 static rk_index *build_index(Gpu &gpu, const SketchSet &s, const string &sketch_path, bool write_files)
@@ -1747,13 +1784,15 @@ static int cmd_assign(const Args &a)
 
 // the sketches of `qry` on the device with only the hashes that between rule.min_refs and rule.max_refs sketches of `ref` hold
 // (rk_sketches_mask); NULL without a query sketch.  The index of `ref` is built for the call, and written next to ref_path when asked.
+// counted: the queries go up with qry.counts and every survivor keeps its count (rk_sketches_mask_counts).
 static rk_sketches *masked_queries(GpuSet &set, const SketchSet &ref, const string &ref_path, bool write_files, const SketchSet &qry, const rk_mask_rule &rule,
-                                   rk_mask_stats *stats)
+                                   rk_mask_stats *stats, bool counted = false)
 {
     vector<rk_index *> idx(1, nullptr);
     build_everywhere(set, ref, ref_path, write_files, idx);
-    rk_sketches *qs = upload(set[0], qry), *out = nullptr;
-    set[0].check(rk_sketches_mask(set[0].ctx, qs, idx[0], &rule, &out, stats), "rk_sketches_mask");
+    rk_sketches *qs = counted ? upload_counted(set[0], qry) : upload(set[0], qry), *out = nullptr;
+    if (counted) set[0].check(rk_sketches_mask_counts(set[0].ctx, qs, idx[0], &rule, &out, stats), "rk_sketches_mask_counts");
+    else set[0].check(rk_sketches_mask(set[0].ctx, qs, idx[0], &rule, &out, stats), "rk_sketches_mask");
     rk_sketches_free(qs);
     rk_index_free(idx[0]);
     return out;
@@ -1769,6 +1808,7 @@ static int cmd_mask(const Args &a)
     if (a.has("keep") && (a.has("min-refs") || a.has("max-refs"))) die("command_mask(), --keep and --min-refs / --max-refs exclude each other");
     const string keep = a.str("keep", "absent");
     if (keep != "absent" && keep != "present") die("command_mask(), --keep must be absent or present");
+    need_sketch_queries(a, "mask");
     rk_mask_rule rule{0, 0};
     if (keep == "present") rule = rk_mask_rule{1, 0xFFFFFFFFu};
     if (a.has("min-refs") || a.has("max-refs")) {
@@ -1805,11 +1845,13 @@ static int cmd_mask(const Args &a)
     if (qry.info.id != ref.info.id)
         die("command_mask(), the sketch infos between reference and query files are not match\n"
             "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    const bool abund = a.has("abund");   // --abund: the counts of the queries go along, into out.sketch.abund
+    if (abund) need_counted_queries("mask", qry_path, qry);
     // the .dict/.index pair next to the reference is (re)written only if missing, as dist does
     const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
     if (getenv("RK_TIMING")) rk_ctx_set_timing(set[0].ctx, 1);
     rk_mask_stats stats;
-    rk_sketches *kept = masked_queries(set, ref, ref_path, missing, qry, rule, &stats);
+    rk_sketches *kept = masked_queries(set, ref, ref_path, missing, qry, rule, &stats, abund);
     stamp("queries masked");
     SketchSet out;
     out.info = qry.info;
@@ -1823,10 +1865,15 @@ static int cmd_mask(const Args &a)
             out.hashes.resize(rk_sketches_total(kept));
             set[0].check(rk_sketches_download(kept, out.hashes.data(), out.off.data()), "rk_sketches_download");
         }
+        if (abund) {
+            out.counts.resize(rk_sketches_total(kept));
+            set[0].check(rk_sketches_download_counts(kept, out.counts.data()), "rk_sketches_download_counts");
+        }
         rk_sketches_free(kept);
     }
     string err;
     if (!save_sketches(a.str("o", ""), out, err)) die("%s", err.c_str());
+    if (abund && !save_abund(abund_path(a.str("o", "")), out, err)) die("%s", err.c_str());
     if (getenv("RK_TIMING"))
         fprintf(stderr, "[timing] %zu queries against %zu references: %llu of %llu hashes kept (%llu have a posting list), %u sketches emptied, %llu tiles, %u scan block(s), "
                         "path %u, %.3f ms on the device\n", qry.size(), ref.size(), (unsigned long long)stats.kept, (unsigned long long)stats.hashes,
@@ -1930,6 +1977,7 @@ static int cmd_screen(const Args &a)
     if (a.num("gpus", 1) != 1) die("command_screen(), screen runs on one GPU (--gpus 1)");
     if (a.has("min-common") && a.num("min-common", 1) < 1) die("command_screen(), --min-common must be >= 1");
     if (a.has("min-won") && a.num("min-won", 0) < 0) die("command_screen(), --min-won must be >= 0 (0: every candidate)");
+    need_sketch_queries(a, "screen");
     const string out = a.str("o", "result.out");
     const int threads = a.num("t", (int)std::thread::hardware_concurrency());
     GpuSet set(a.num("device", 0), 1, false);
@@ -1952,6 +2000,8 @@ static int cmd_screen(const Args &a)
     if (qry.info.id != ref.info.id)
         die("command_screen(), the sketch infos between reference and query files are not match\n"
             "try to use the same shuffle file to generate sketches of the reference and query datasets");
+    const bool abund = a.has("abund");   // --abund: four more columns per line, three more per line of --summary (rk_screen_abund_rows)
+    if (abund) need_counted_queries("screen", qry_path, qry);
     const size_t N = ref.size(), Q = qry.size();
     const bool missing = !exist_file(ref_path + ".index") || !exist_file(ref_path + ".dict");
     vector<rk_index *> idx(1, nullptr);
@@ -1962,8 +2012,11 @@ static int cmd_screen(const Args &a)
     vector<uint64_t> off(Q + 1, 0);
     vector<uint32_t> matched(Q ? Q : 1, 0), n_cand(Q ? Q : 1, 0), claimed(Q ? Q : 1, 0);
     rk_screen_rec *recs = nullptr;
+    rk_screen_abund *abunds = nullptr;
+    vector<uint64_t> occ(abund ? 3 * Q + 1 : 1, 0);
     uint64_t n_recs = 0;
     rk_screen_stats stats;
+    rk_screen_abund_stats abund_stats;
     rk_sketches *qs = nullptr;
     vector<uint64_t> q_off = qry.off;   // the sizes of the queries as they are screened
     if (a.has("sub")) {
@@ -1973,12 +2026,18 @@ static int cmd_screen(const Args &a)
         string err;
         if (!read_sketches(host_path, host, err)) die("readSketches(), %s", err.c_str());
         if (host.info.id != qry.info.id) die("command_screen(), the sketch infos between the --sub sketches and the query sketches are not same");
-        qs = masked_queries(set, host, host_path, false, qry, rk_mask_rule{0, 0}, nullptr);
+        qs = masked_queries(set, host, host_path, false, qry, rk_mask_rule{0, 0}, nullptr, abund);
         if (qs) set[0].check(rk_sketches_download(qs, nullptr, q_off.data()), "rk_sketches_download");
         stamp("queries masked");
     }
-    if (!qs) qs = upload(set[0], qry);
-    set[0].check(rk_screen_rows(set[0].ctx, idx[0], qs, &o, off.data(), &recs, &n_recs, matched.data(), n_cand.data(), claimed.data(), &stats), "rk_screen_rows");
+    if (!qs) qs = abund ? upload_counted(set[0], qry) : upload(set[0], qry);
+    if (abund) {
+        set[0].check(rk_screen_abund_rows(set[0].ctx, idx[0], qs, &o, off.data(), &recs, &abunds, &n_recs, matched.data(), n_cand.data(), claimed.data(), occ.data(),
+                                          &abund_stats), "rk_screen_abund_rows");
+        memcpy(&stats, &abund_stats, sizeof stats);   // (rk_screen_abund_stats begins with rk_screen_stats)
+    } else {
+        set[0].check(rk_screen_rows(set[0].ctx, idx[0], qs, &o, off.data(), &recs, &n_recs, matched.data(), n_cand.data(), claimed.data(), &stats), "rk_screen_rows");
+    }
     rk_sketches_free(qs);
     stamp("queries screened");
     const double inv_k = 1.0 / (double)(2 * ref.info.half_k);   // the k-mer length, as dist reads it
@@ -1986,16 +2045,24 @@ static int cmd_screen(const Args &a)
     if (!fp) die("cannot write %s", out.c_str());
     for (uint64_t k = 0; k < n_recs; k++) {
         const rk_screen_rec &p = recs[k];
-        fprintf(fp, "%s\t%s\t%u\t%u\t%u\t%.6f\t%.6f\n", qry.names[p.query].c_str(), ref.names[p.ref].c_str(), p.common, p.size_ref, p.won,
+        fprintf(fp, "%s\t%s\t%u\t%u\t%u\t%.6f\t%.6f", qry.names[p.query].c_str(), ref.names[p.ref].c_str(), p.common, p.size_ref, p.won,
                 pow((double)p.common / (double)p.size_ref, inv_k), p.won ? pow((double)p.won / (double)p.size_ref, inv_k) : 0.0);
+        if (abund)   // the lower median and the mean count over what the record shares, then over what it claims
+            fprintf(fp, "\t%u\t%.3f\t%u\t%.3f", abunds[k].med_common, (double)abunds[k].occ_common / (double)p.common, abunds[k].med_won,
+                    p.won ? (double)abunds[k].occ_won / (double)p.won : 0.0);
+        fputc('\n', fp);
     }
     fclose(fp);
     if (a.has("summary")) {
         FILE *sp = fopen(a.str("summary", "").c_str(), "w");
         if (!sp) die("cannot write %s", a.str("summary", "").c_str());
-        for (size_t q = 0; q < Q; q++)
-            fprintf(sp, "%s\t%llu\t%u\t%u\t%u\t%llu\n", qry.names[q].c_str(), (unsigned long long)(q_off[q + 1] - q_off[q]), matched[q], n_cand[q], claimed[q],
+        for (size_t q = 0; q < Q; q++) {
+            fprintf(sp, "%s\t%llu\t%u\t%u\t%u\t%llu", qry.names[q].c_str(), (unsigned long long)(q_off[q + 1] - q_off[q]), matched[q], n_cand[q], claimed[q],
                     (unsigned long long)(off[q + 1] - off[q]));
+            if (abund)   // the sums of the counts over the whole sketch, over its matched and over its claimed hashes
+                fprintf(sp, "\t%llu\t%llu\t%llu", (unsigned long long)occ[3 * q], (unsigned long long)occ[3 * q + 1], (unsigned long long)occ[3 * q + 2]);
+            fputc('\n', sp);
+        }
         fclose(sp);
     }
     if (getenv("RK_TIMING"))
@@ -2004,8 +2071,9 @@ static int cmd_screen(const Args &a)
                 Q, N, (unsigned long long)stats.records, (unsigned long long)stats.candidates, (unsigned long long)stats.claimed, (unsigned long long)stats.matched,
                 (unsigned long long)stats.postings_walked, (unsigned long long)stats.lane_lists, (unsigned long long)stats.wave_lists,
                 (unsigned long long)stats.block_lists, (unsigned long long)stats.adds, stats.batches, stats.launches, stats.read_backs, stats.path,
-                rk_ctx_last_ms(set[0].ctx, RK_MS_SCREEN));
+                rk_ctx_last_ms(set[0].ctx, abund ? RK_MS_SCREEN_ABUND : RK_MS_SCREEN));
     rk_free_host(recs);
+    rk_free_host(abunds);
     SelfJoin::leave();
 }
 
@@ -2540,14 +2608,14 @@ static int usage()
             "  assign -r ref.sketch|list -q qry.sketch|list -D maxDist [-M 0|1] (--labels FILE | --by cluster|greedy|dbscan -m minPts) -o out [--novel FILE] [--gpus G] [--device N]   (placement of the queries into the clustered references: per query the cluster of its nearest labelled reference within -D, that reference's dist line, the query's references of that cluster, labelled and all within -D, and the runner-up cluster with its distance; - when novel; -D below 1.0; the labels from --labels -- one line per reference, an integer below their number or - -- or from --by on the same index (default cluster; dbscan needs -m and leaves non-core references unlabelled; greedy and dbscan on the first GPU); --novel: the names of the unplaced queries)\n"
             "  group -i in.sketch|genomes.list (--labels FILE | --by cluster|greedy|dbscan [-D 0.05] [-M 0|1] [-m 5]) [--pan | --core | --share P/Q] [--min-count C] [--only] -o out.sketch [--map FILE] [--device N]   (one sketch per cluster: --pan, the default, the union of its members' sketches; --core the hashes every member holds; --share P/Q those at least P of Q of its members hold; --min-count C: at least C members hold it; --only: no genome outside the cluster holds it -- its markers; the labels as medoid takes them; out.sketch: one sketch per cluster by ascending label, named after its first member; --map: per cluster its number, label, genomes, hashes kept and name; one GPU)\n"
             "  gather -r ref.sketch|list -q qry.sketch|list [--min-new 1] [--max-picks 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references explain each query, greedily: per round the reference that holds most of the query's hashes no earlier pick held, ties to the earlier reference, until a pick would add fewer than --min-new hashes or --max-picks are made; one line per pick: query, reference, rank, common|size_ref|size_query, fresh, fresh / size_query, common / size_ref; --summary: per query its name, size, hashes some reference holds, hashes the picks explain, references sharing at least --min-new hashes, picks; --sub: the queries first lose every hash a sketch of host.sketch holds, on the device -- the cover of what sub would write; one GPU)\n"
-            "  screen  -r ref.sketch|list -q qry.sketch|list [--min-common 1] [--min-won 0] [--sub host.sketch] -o out [--summary FILE] [--device N]   (which references are contained in each query, every shared hash credited to one of them -- mash screen -w in one pass: among the references that share at least --min-common hashes with the query a hash goes to the one with the larger common / size, compared exactly, then to the larger, then to the earlier one; one line per reference that keeps at least --min-won hashes: query, reference, common, size_ref, won, identity = (common / size_ref)^(1/K) and identity_won = (won / size_ref)^(1/K) for the sketches' k-mer length K; --summary: per query its name, size, hashes some reference holds, candidates, hashes claimed, records; --sub as in gather; Mash's p-value and median multiplicity are not offered: Kssd sketches carry no multiplicities; one GPU)\n"
+            "  screen  -r ref.sketch|list -q qry.sketch|list [--min-common 1] [--min-won 0] [--sub host.sketch] [--abund] -o out [--summary FILE] [--device N]   (which references are contained in each query, every shared hash credited to one of them -- mash screen -w in one pass: among the references that share at least --min-common hashes with the query a hash goes to the one with the larger common / size, compared exactly, then to the larger, then to the earlier one; one line per reference that keeps at least --min-won hashes: query, reference, common, size_ref, won, identity = (common / size_ref)^(1/K) and identity_won = (won / size_ref)^(1/K) for the sketches' k-mer length K; --summary: per query its name, size, hashes some reference holds, candidates, hashes claimed, records; --sub as in gather; --abund, for -q x.sketch with x.sketch.abund: four more columns, the lower median and the mean of the counts of the query's hashes over what the record shares, then over what it claims -- Mash's median multiplicity --, and three more in --summary: the sums of the counts over the whole sketch, its matched and its claimed hashes; the counts survive --sub; Mash's p-value is not offered; one GPU)\n"
             "  dist    -r ref.sketch|list -q qry.sketch|list -o out [-D maxDist] [-N n] [-M 0|1] [--device N] [--gpus G]\n"
             "  abund   -i in.sketch [-o out] [--bins 64]   |   abund -i in.sketch --min-count N [--max-count M] -o out.sketch   (the occurrence counts of a counted sketch, in.sketch.abund as sketch --abund writes it: per genome a line name, distinct hashes, occurrences, largest count, lower median, then count<TAB>hashes per non-empty bin below --bins and >=bins for the rest; with --min-count / --max-count the sketches reduced to the hashes whose count lies in [N, M], emptied genomes kept, and out.sketch.abund; host only)\n"
             "  info    -i in.sketch -o out [-F]\n"
             "  merge   -i sketches.list -o out.sketch\n"
             "  union   -i in.sketch -o out.sketch\n"
             "  sub     --rs ref.sketch --qs qry.sketch -o out.sketch\n"
-            "  mask    -r ref.sketch|list -q qry.sketch|list [--keep absent|present | --min-refs A --max-refs B] -o out.sketch [--device N]   (the query sketches with only the hashes that at least A and at most B reference sketches hold, hashes ascending: --keep absent, the default, is A = B = 0 -- the sketches sub writes, computed on the device; --keep present is A = 1 without B -- the intersection; --max-refs B alone drops the hashes more than B references hold, --min-refs A alone keeps those at least A hold; one GPU)\n"
+            "  mask    -r ref.sketch|list -q qry.sketch|list [--keep absent|present | --min-refs A --max-refs B] [--abund] -o out.sketch [--device N]   (the query sketches with only the hashes that at least A and at most B reference sketches hold, hashes ascending: --keep absent, the default, is A = B = 0 -- the sketches sub writes, computed on the device; --keep present is A = 1 without B -- the intersection; --max-refs B alone drops the hashes more than B references hold, --min-refs A alone keeps those at least A hold; one GPU; --abund, for -q x.sketch with x.sketch.abund: every surviving hash keeps its count, in out.sketch.abund)\n"
             "  lca     -r ref.sketch|list -q qry.sketch|list --taxonomy FILE --taxa FILE [--min-count 1] [--confidence P/Q] [--of labelled|sketch] -o out [--summary FILE] [-L file.shuf] [--device N]   (every query classified by the lowest common ancestors of its hashes: a hash of the references carries the LCA of the taxa of the references that hold it, a query is the tally of those; --taxonomy: one line per node, id<TAB>parent id[<TAB>name], the root names itself; --taxa: one line per reference, an id of the taxonomy or -; the call is the LCA of the taxa with the highest root-to-node sum among those with at least --min-count hashes, moved towards the root until its clade holds P/Q of the hashes that carry a taxon, or with --of sketch of the whole sketch; one line per query: name, called id or -, its name, candidate id, clade, retained, matched, unlabelled, sketch size; --summary: per query and taxon its id, name, hashes and clade; one GPU)\n"
             "  convert -i kssd_dir -o out[.sketch] [-q]   |   convert --reverse -i in.sketch -o kssd_dir\n";
     return 1;
@@ -2615,8 +2683,8 @@ int main(int argc, char **argv)
     if (sub == "assign") { cerr << "-----run the subcommand: assign" << endl; return leave(cmd_assign(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "group") { cerr << "-----run the subcommand: group" << endl; return leave(cmd_group(parse_args(argc, argv, 2, alias, {"pan", "core", "only"}))); }   // (--core is a flag here, a file of mreach)
     if (sub == "gather") { cerr << "-----run the subcommand: gather" << endl; return leave(cmd_gather(parse_args(argc, argv, 2, alias, {}))); }
-    if (sub == "screen") { cerr << "-----run the subcommand: screen" << endl; return leave(cmd_screen(parse_args(argc, argv, 2, alias, {}))); }
-    if (sub == "mask") { cerr << "-----run the subcommand: mask" << endl; return leave(cmd_mask(parse_args(argc, argv, 2, alias, {}))); }
+    if (sub == "screen") { cerr << "-----run the subcommand: screen" << endl; return leave(cmd_screen(parse_args(argc, argv, 2, alias, {"abund"}))); }
+    if (sub == "mask") { cerr << "-----run the subcommand: mask" << endl; return leave(cmd_mask(parse_args(argc, argv, 2, alias, {"abund"}))); }
     if (sub == "lca") { cerr << "-----run the subcommand: lca" << endl; return leave(cmd_lca(parse_args(argc, argv, 2, alias, {}))); }
     if (sub == "dist") { cerr << "-----run the subcommand: dist" << endl; return leave(cmd_dist(parse_args(argc, argv, 2, alias, {"same-device"}))); }
     if (sub == "abund") { cerr << "-----run the subcommand: abund" << endl; return cmd_abund(parse_args(argc, argv, 2, alias, {})); }

@@ -25,6 +25,8 @@ extern "C" int rk_sketches_download(const rk_sketches *, uint32_t *, uint64_t *)
 extern "C" int rk_sketches_download64(const rk_sketches *, uint64_t *, uint64_t *) { return -1; }
 extern "C" int rk_sketches_from_host(rk_ctx *, const uint32_t *, const uint64_t *, uint32_t, rk_sketches **) { return -1; }
 extern "C" int rk_sketches_from_host64(rk_ctx *, const uint64_t *, const uint64_t *, uint32_t, rk_sketches **) { return -1; }
+extern "C" int rk_sketches_download_counts(const rk_sketches *, uint32_t *) { return -1; }
+extern "C" int rk_sketches_from_host_counts(rk_ctx *, const void *, int, const uint32_t *, const uint64_t *, uint32_t, rk_sketches **) { return -1; }
 extern "C" void rk_sketches_free(rk_sketches *) {}
 extern "C" void rk_free_host(void *p) { free(p); }
 

@@ -29,6 +29,7 @@ extern "C" int rk_index_export_lists(const rk_index *, uint32_t *, uint32_t *, u
 extern "C" int rk_index_export64(const rk_index *, uint32_t *, uint64_t *, uint32_t *) { return -1; }
 extern "C" int rk_sketches_download(const rk_sketches *, uint32_t *, uint64_t *) { return -1; }
 extern "C" int rk_sketches_download64(const rk_sketches *, uint64_t *, uint64_t *) { return -1; }
+extern "C" int rk_sketches_download_counts(const rk_sketches *, uint32_t *) { return -1; }
 extern "C" int rk_index_order(const rk_index *, uint32_t *) { return -1; }
 extern "C" void rk_free_host(void *p) { free(p); }
 
